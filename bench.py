@@ -2,6 +2,8 @@
 """Headline benchmark: 1080p I-frames/s of the MPEG-1 I-frame hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: starts torch.distributed.run itself, as a child process)
+    python bench.py ... --dump-outputs DIR                (also writes the last timed step's output as DIR/<name>.npy)
+    python bench.py ... --full                            (also the legs below that take runs of their own)
 
 A step = one pass of the hot path over one batch of synthetic frames that are already resident in
 HBM (BASELINE.json configs[2]: 300 x 1920x1080, FULL region, quality factor 12): RGB in, contiguous
@@ -11,6 +13,10 @@ step k on the main stream, the exchange of step k-1's bitstreams on a side strea
 grouped send/recv to rank 0 over RCCL; --gather host: every rank copies its bitstream into its slice
 of one pinned host buffer), one host wait per step on eight pinned bytes per rank, nothing allocated
 inside the loop.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line; `ms_per_step`
+is the wall time of one timed step.  `sustained`, `config4`, `host_delivery` and `cpu_baseline` are measured only with
+--full (each can then still be switched off on its own: --sustained-s 0, --no-config4, --deliver none, --no-cpu-baseline).
 
 The line's `roofline` prices the dominant kernel (k_encode_tiles for 3-channel input, k_encode_dense otherwise; --path
 forces one) against HBM with its time from HIP events recorded on the launch stream inside the library (per launch:
@@ -364,6 +370,38 @@ def config4_leg(torch, Mpeg1Encoder, gpu_index, qf, seed, frames=300, warm=12, s
         enc.close()
 
 
+DUMP_HEAD_BYTES = 4 << 20      # the first 4 MiB of the stream, byte for byte
+DUMP_SAMPLE_BYTES = 1 << 21    # plus 2 Mi bytes at fixed, seeded positions over the whole stream
+
+
+def dump_outputs(dirname, stream, sizes, meta):
+    """What the caller of the timed path receives from its last step, as float64 / float32 .npy files (about 40 MB at most):
+      meta            [total bytes, status bits]
+      frame_sizes     bytes of every frame record (this rank's frames)
+      frame_sums      per frame record: sum of its bytes, and sum of byte x (1 + position in the record): every byte counts
+      stream_head     the first DUMP_HEAD_BYTES bytes of the stream (values 0..255)
+      stream_sample   the stream at DUMP_SAMPLE_BYTES positions drawn from [0, total) by a fixed seed, and those positions
+    stream = the uint8 stream (frame records back to back), sizes = int64 record sizes, meta = (total, status)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    data = stream.cpu().numpy() if hasattr(stream, "cpu") else np.asarray(stream)
+    data = np.ascontiguousarray(data, np.uint8)
+    sizes = np.asarray(sizes.cpu().numpy() if hasattr(sizes, "cpu") else sizes, np.int64)
+    total = int(data.size)
+    np.save(os.path.join(dirname, "meta.npy"), np.asarray(meta, np.float64))
+    np.save(os.path.join(dirname, "frame_sizes.npy"), sizes.astype(np.float64))
+    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]]) if sizes.size else np.zeros(0, np.int64)
+    sums = np.zeros((sizes.size, 2), np.float64)
+    for i, (s, k) in enumerate(zip(starts, sizes)):
+        rec = data[s:s + k].astype(np.int64)
+        sums[i] = (rec.sum(), (rec * np.arange(1, rec.size + 1, dtype=np.int64)).sum())
+    np.save(os.path.join(dirname, "frame_sums.npy"), sums)
+    np.save(os.path.join(dirname, "stream_head.npy"), data[:DUMP_HEAD_BYTES].astype(np.float32))
+    pos = np.sort(np.random.default_rng(504).integers(0, max(total, 1), DUMP_SAMPLE_BYTES)) if total else np.zeros(0, np.int64)
+    np.save(os.path.join(dirname, "stream_sample.npy"), data[pos].astype(np.float32))
+    np.save(os.path.join(dirname, "stream_sample_positions.npy"), pos.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -378,7 +416,7 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=80.0,
                     help="keep the GPU busy re-generating the synthetic input for this long before the warm-up steps, so "
                          "that short runs are not timed inside the clock ramp (0 = off); reported as clock_settle_ms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` leg")
     ap.add_argument("--host-path", action="store_true", help="also time the host-buffer (PCIe inclusive) entry point")
     ap.add_argument("--pipeline", action="store_true",
                     help="N=1: overlap each batch's layout + gather with the next batch's encode (m1v_set_pipelined); "
@@ -390,7 +428,7 @@ def main():
                     help="N>1: how the per-rank bitstreams reach one place.  xgmi = grouped send/recv to rank 0 (RCCL); "
                          "host = every rank copies its blob into its slice of one pinned host buffer shared by the ranks")
     ap.add_argument("--deliver", default="host", choices=["none", "host"],
-                    help="N=1: after the headline run, time the same steps with every batch's frame records delivered to pinned host "
+                    help="N=1, --full: after the headline run, time the same steps with every batch's frame records delivered to pinned host "
                          "memory (device-to-host copy of batch k on a side stream under the encode of batch k+1); reported as the "
                          "`host_delivery` sub-record, never as `value`")
     ap.add_argument("--path", default="auto", choices=["auto", "tiles", "runs"],
@@ -398,16 +436,25 @@ def main():
     ap.add_argument("--cli", action="store_true",
                     help="instead of the headline run: time the folder-of-JPEGs CLI path end to end (SURVEY 8f.1/8f.2)")
     ap.add_argument("--sustained-s", type=float, default=2.5,
-                    help="N=1: length of the second, sustained leg (back-to-back steps with socket power and shader clock sampled by a "
+                    help="N=1, --full: length of the second, sustained leg (back-to-back steps with socket power and shader clock sampled by a "
                          "child rocm-smi poller); 0 = off.  Reported as `sustained`, never as `value`")
-    ap.add_argument("--no-config4", action="store_true", help="N=1: skip the 300 x 3840x2160 leg (BASELINE config 4, `config4`)")
+    ap.add_argument("--no-config4", action="store_true", help="N=1, --full: skip the 300 x 3840x2160 leg (BASELINE config 4, `config4`)")
     ap.add_argument("--cli-reference-frames", type=int, default=6)
     ap.add_argument("--cli-repeats", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline run, also the legs that take runs of their own: `sustained`, `config4`, "
+                         "`host_delivery`, `cpu_baseline` (off in a plain run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy (float32/float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cli:
         if args.frames == 300:
             args.frames = 128
         return cli_bench(args)
+    if not args.full:      # a plain run: the headline steps and nothing else
+        args.sustained_s, args.no_config4, args.no_cpu_baseline, args.deliver = 0.0, True, True, "none"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started the way the driver starts it (python bench.py --gpus N ...): the ranks run as a child process group, this
@@ -544,6 +591,17 @@ def main():
 
     total_bytes, status = (int(x) for x in meta.cpu())
     assert (status & 0xFFFFFFFF) == 0, f"device status {status:#x}"
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step's product: one GPU = its output buffer; N > 1 = the stream gathered on rank 0
+        if distributed:
+            last_total, last_status = sum(int(c) for c in pipe.last_counts), status
+            stream = pipe.result()
+        else:
+            b_last = (step_no - 1) % len(outs)
+            last_total, last_status = (int(x) for x in metas[b_last].cpu())
+            stream = outs[b_last][:last_total]
+        dump_outputs(args.dump_outputs, stream, sizes[:n], (last_total, last_status))
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3

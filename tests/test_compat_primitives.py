@@ -104,11 +104,12 @@ def test_block_chain_matches_the_oracle(lib, orc):
 
 @pytest.mark.reference
 def test_reference_main_object_links_and_matches(ref, lib, tmp_path):
-    """main.o built from the reference's main.c AND the reference's header (the driver is inside main.o and needs
+    """main.o built from the reference's main.c AND the reference's header by `make -C oracle _ref` (the driver is inside main.o and needs
     the fine-grained symbols) + this library == the reference's own binary, byte for byte (.mpeg and .bit)."""
     from PIL import Image
-    obj, exe = tmp_path / "main_ref.o", tmp_path / "legacy_encoder"
-    subprocess.run(["gcc", "-g", "-w", "-I/root/reference/include", "-c", "/root/reference/main.c", "-o", str(obj)], check=True)
+    obj, exe = os.path.join(ROOT, "oracle", "_ref", "main_ref.o"), tmp_path / "legacy_encoder"   # `make -C oracle _ref`
+    if not os.path.exists(obj):
+        pytest.skip("oracle/_ref/main_ref.o not built (reference sources absent)")
     und = subprocess.run(["nm", "-u", str(obj)], capture_output=True, text=True).stdout
     needed = {l.split()[-1] for l in und.splitlines() if "GLIBC" not in l and " U " in l}
     assert "fast_DCT" in needed and "mpeg_encode_procedure" not in needed

@@ -260,19 +260,17 @@ def test_driver_300_frames_hour_wrap(ref, orc, tmp_path):
 
 
 def test_driver_sample_images(ref, orc, tmp_path):
-    """The reference's own sample data (images.zip: 30 JPEGs 400x600, 3 distinct)."""
-    import zipfile
-    z = "/root/reference/images.zip"
-    if not os.path.exists(z):
-        pytest.skip("images.zip absent")
+    """The reference's own sample data (images.zip: 30 JPEGs 400x600, 3 distinct).  tests/golden/reference_images.npz holds
+    the three distinct files (jpg_0..jpg_2); the archive's other 27 entries are byte-identical copies, k_1.jpg .. k_9.jpg of
+    k.jpg, and are written back under the same names."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_images.npz"))
     d = tmp_path / "sample"
     (d / "bit").mkdir(parents=True)
-    with zipfile.ZipFile(z) as zf:
-        members = [m for m in zf.namelist() if m.lower().endswith((".jpg", ".jpeg")) and "__MACOSX" not in m]
-        for m in members:
-            target = d / "images" / os.path.basename(m)
-            target.parent.mkdir(exist_ok=True)
-            target.write_bytes(zf.read(m))
+    (d / "images").mkdir()
+    for k in range(3):
+        jpg = z[f"jpg_{k}"].tobytes()
+        for name in [f"{k}.jpg"] + [f"{k}_{i}.jpg" for i in range(1, 10)]:
+            (d / "images" / name).write_bytes(jpg)
     _check_folder(ref, orc, d, 12)
 
 

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() { # tag, frames kept, bench args...
   local tag=$1 keep=$2; shift 2
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$tag -o r -- python3 $ROOT/bench.py --no-cpu-baseline --deliver none "$@" > $OUT/r03_${tag}_bench_under_rocprof.json 2> $OUT/prof_$tag.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$tag -o r -- python3 $ROOT/bench.py --full --no-cpu-baseline --deliver none "$@" > $OUT/r03_${tag}_bench_under_rocprof.json 2> $OUT/prof_$tag.err
   python3 $ROOT/tools/rocpd_stats.py $(ls $OUT/prof_$tag/*results.db $OUT/prof_$tag/*/*results.db 2>/dev/null | head -1) --last $keep > $OUT/r03_${tag}_kernel_stats_timed.csv
   rm -rf $OUT/prof_$tag
 }
@@ -34,9 +34,9 @@ stats 4k 60 --width 3840 --height 2160 --steps 60 --warmup 20
 stats 4k_runs 60 --width 3840 --height 2160 --steps 60 --warmup 20 --path runs
 echo "== plain bench"
 cd $ROOT
-python3 bench.py > $OUT/r03_1080p_bench.json 2> /dev/null
-python3 bench.py --path runs --no-cpu-baseline > $OUT/r03_1080p_runs_bench.json 2> /dev/null
-python3 bench.py --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 > $OUT/r03_4k_bench.json 2> /dev/null
-python3 bench.py --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 --path runs > $OUT/r03_4k_runs_bench.json 2> /dev/null
+python3 bench.py --full > $OUT/r03_1080p_bench.json 2> /dev/null
+python3 bench.py --full --path runs --no-cpu-baseline > $OUT/r03_1080p_runs_bench.json 2> /dev/null
+python3 bench.py --full --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 > $OUT/r03_4k_bench.json 2> /dev/null
+python3 bench.py --full --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 --path runs > $OUT/r03_4k_runs_bench.json 2> /dev/null
 head -6 $OUT/r03_1080p_kernel_stats_timed.csv $OUT/r03_4k_kernel_stats_timed.csv
 cat $OUT/r03_1080p_bench.json | cut -c1-600

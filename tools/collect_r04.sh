@@ -37,11 +37,11 @@ stats 1080p 200
 stats 4k 60 --width 3840 --height 2160 --steps 60 --warmup 20
 echo "== plain bench"
 cd $ROOT
-python3 bench.py > $OUT/r04_1080p_bench.json 2> /dev/null
-python3 bench.py --path runs --no-cpu-baseline --no-config4 > $OUT/r04_1080p_runs_bench.json 2> /dev/null
-python3 bench.py --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 > $OUT/r04_4k_bench.json 2> /dev/null
+python3 bench.py --full > $OUT/r04_1080p_bench.json 2> /dev/null
+python3 bench.py --full --path runs --no-cpu-baseline --no-config4 > $OUT/r04_1080p_runs_bench.json 2> /dev/null
+python3 bench.py --full --no-cpu-baseline --width 3840 --height 2160 --steps 60 --warmup 20 > $OUT/r04_4k_bench.json 2> /dev/null
 echo "== the bench as the driver runs it"
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+for i in 1 2 3; do python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; s=d.get('sustained') or {}
 print('driver-style run $i: fps', round(d['value']), 'ms_per_step', d['ms_per_step'], 'kernel_ms', r.get('kernel_ms'), 'frac', r['frac'], 'step_frac', r['step_frac'], '| sustained fps', s.get('value'), 'power', s.get('power'), '| config4 frac', (d.get('config4') or {}).get('frac'), 'step_frac', (d.get('config4') or {}).get('step_frac'))"; done > $OUT/r04_bench_driver_style.txt
