@@ -1526,6 +1526,7 @@ struct m1v_encoder {
         unsigned turn;
         hipEvent_t enc_done, gather_done;
         bool gather_pending;
+        bool poisoned;          // a call that took a counter set returned an error: neither set is known to be clear
     } batch[2];
     unsigned long long *d_stamps;
     // device-side staging of the host-buffer entry points, kept between calls
@@ -1633,6 +1634,12 @@ static hipError_t plan_malloc(void **p, size_t bytes) {
     if (g_fail_alloc_in > 0 && --g_fail_alloc_in == 0) return hipErrorOutOfMemory;
     return hipMalloc(p, bytes);
 }
+static int g_fail_encode_at = 0; // test hook (m1v_debug_fail_encode): the stage at which the next encode returns M1V_E_HIP
+static int fail_encode_at(int stage) {
+    if (g_fail_encode_at != stage) return M1V_OK;
+    g_fail_encode_at = 0;
+    return fail(M1V_E_HIP, "injected failure (m1v_debug_fail_encode)%s");
+}
 static int configure_path(m1v_encoder *e) {
     const int dense_T = e->forced_T;
     const Geometry &g = e->g;
@@ -1666,6 +1673,9 @@ static int configure_path(m1v_encoder *e) {
         // run kernels' (512 words per 256 blocks at quality <= 25) + the segments' word alignment and slice headers
         plan.image_words = e->lds_words > 0 ? e->lds_words : (e->qf <= 25 ? 400 : (e->qf <= 50 ? 784 : (e->qf <= 76 ? 1552 : 3088)));
         plan.image_words = (plan.image_words + 3) & ~3; // cleared 16 bytes per lane
+        // (the same budget m1v_encode_device checks before each launch: an image that cannot launch is refused here)
+        if ((size_t)kTileFixedWords * 4 + 2 * (size_t)plan.luma_region + plan.chroma_region + (size_t)plan.image_words * 4 > 160 * 1024)
+            return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
         plan.slot_bytes = (uint32_t)((((size_t)plan.image_words * 4 + 127) & ~(size_t)127) | 128);
         const size_t runs = (size_t)e->max_frames * plan.tiles_per_frame;
         plan.arena_slots = (uint32_t)(e->reserve_worst ? runs : (runs / 256 > 32 ? runs / 256 : (runs < 32 ? runs : 32)));
@@ -1685,6 +1695,11 @@ static int configure_path(m1v_encoder *e) {
         // blocks needs ~150 words at quality 12 on noise; scale the default with the quantiser (finer quantisers emit
         // more bits per block).  The compact scratch slot of a run is exactly that image.
         plan.image_words = e->lds_words > 0 ? e->lds_words : (e->qf <= 25 ? 512 : (e->qf <= 50 ? 1024 : (e->qf <= 76 ? 2048 : 4096)));
+        {
+            const size_t zero_iters = ((size_t)plan.image_words + T - 1) / T, stride = e->narrow ? kStageStride8 : kStageStride16;
+            if (((size_t)(T / kWave) * kVlcWords + 32 + stride * T + zero_iters * T) * 4 > 160 * 1024)
+                return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
+        }
         // + 128: an odd number of 128-byte lines, so that the slots (of which only the first third is written at quality
         // 12) do not all start on the same few memory channels (a power-of-two stride measured 3 % slower)
         plan.slot_bytes = (uint32_t)((((size_t)plan.image_words * 4 + 127) & ~(size_t)127) | 128);
@@ -1798,6 +1813,7 @@ static int configure_path(m1v_encoder *e) {
             bt.ctr[0] = f.ctr[0];
             bt.ctr[1] = f.ctr[1];
             bt.turn = 0;
+            bt.poisoned = false;
             bt.enc_done = f.enc_done;
             bt.gather_done = f.gather_done;
         }
@@ -2026,8 +2042,13 @@ int m1v_flush(m1v_encoder *e, void *stream) {
     HIP_TRY(hipSetDevice(e->device));
     // The mark stays set: a later m1v_encode_device on ANOTHER stream must still wait for this set's gather before its
     // encode kernel overwrites the scratch (waiting for an event that has completed costs nothing).
-    for (m1v_encoder::Batch &bt : e->batch)
+    for (m1v_encoder::Batch &bt : e->batch) {
+        if (e->pipelined && bt.poisoned) { // a failed call may have left an assembly on the internal stream without its event
+            HIP_TRY(hipEventRecord(bt.gather_done, e->side));
+            bt.gather_pending = true;
+        }
         if (bt.gather_pending) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, bt.gather_done, 0));
+    }
     return M1V_OK;
 }
 
@@ -2074,6 +2095,12 @@ void m1v_debug_fail_alloc(int nth) {
     // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
     const char *on = getenv("EC504_DEBUG_HOOKS");
     g_fail_alloc_in = (on && on[0] == '1' && nth > 0) ? nth : 0;
+}
+
+void m1v_debug_fail_encode(int stage) {
+    // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
+    const char *on = getenv("EC504_DEBUG_HOOKS");
+    g_fail_encode_at = (on && on[0] == '1' && stage >= 1 && stage <= 3) ? stage : 0;
 }
 
 #if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
@@ -2152,7 +2179,7 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                       uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                       uint32_t *d_status, void *stream) {
-    if (!e || !d_rgb || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (!e || (!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));
@@ -2160,6 +2187,23 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
     hipStream_t gs = e->pipelined ? e->side : st;   // stream of the layout + gather kernels
     if (e->pipelined && bt.gather_pending)           // this set's previous gather must have drained its scratch
         HIP_TRY(hipStreamWaitEvent(st, bt.gather_done, 0));
+    if (bt.poisoned) {
+        // The last call on this Batch failed after it took a counter set: its kernels may have added to one set and left
+        // the other uncleared.  Behind everything already queued on the internal stream (the failed call's layout and
+        // assembly, whose completion event may never have been recorded), clear both sets in full.
+        if (e->pipelined) {
+            HIP_TRY(hipEventRecord(bt.gather_done, gs));
+            HIP_TRY(hipStreamWaitEvent(st, bt.gather_done, 0));
+        }
+        const size_t nslots = (size_t)e->max_frames * e->g.n_strips;
+        for (m1v_encoder::Counters &c : bt.ctr) {
+            HIP_TRY(hipMemsetAsync(c.strip_ctr, 0, nslots * 8, st));
+            HIP_TRY(hipMemsetAsync(c.frame_bytes, 0, (size_t)e->max_frames * 8, st));
+            HIP_TRY(hipMemsetAsync(c.words, 0, 4 * sizeof(uint32_t), st));
+            c.dirty_frames = 0;
+        }
+        bt.poisoned = false;
+    }
     if (n_frames == 0) {
         if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
         if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, 4, st));
@@ -2172,6 +2216,12 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
     // the counters this batch adds to, and the set the next batch of this Batch will use (k_assemble clears it)
     m1v_encoder::Counters &cur = bt.ctr[bt.turn & 1u], &nxt = bt.ctr[(bt.turn + 1u) & 1u];
     bt.turn++;
+    // From here on an error return leaves the counters half used: the next call on this Batch clears them first.
+    struct PoisonOnReturn {
+        bool *flag;
+        ~PoisonOnReturn() { if (flag) *flag = true; }
+    } poison{&bt.poisoned};
+    if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
     if (e->tiles) {
         TileArgs a;
         a.g = g;
@@ -2308,6 +2358,7 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
             HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
         }
     }
+    if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
     // ---- frame offsets, strip offsets, concatenation, headers, sizes, status: one launch (m1v_assemble.h) ----
     {
         AssembleArgs ga;
@@ -2350,10 +2401,12 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
             hipLaunchKernelGGL(k_assemble<false>, grid, dim3(kAsmThreads), lds, gs, ga);
         HIP_TRY(hipGetLastError());
     }
+    if (fail_encode_at(3) != M1V_OK) return M1V_E_HIP;
     if (e->pipelined) {
         HIP_TRY(hipEventRecord(bt.gather_done, gs));
         bt.gather_pending = true;
     }
+    poison.flag = nullptr;
     return M1V_OK;
 }
 
@@ -2473,7 +2526,10 @@ int m1v_delivery_step(m1v_delivery *d, const uint8_t *d_rgb, int n_frames, int f
     }
     const int rc = m1v_encode_device(e, d_rgb, n_frames, first_frame_index, d->d_out[b], d->cap, (uint64_t *)d->d_sizes[b],
                                      (uint64_t *)d->d_meta[b], reinterpret_cast<uint32_t *>(d->d_meta[b] + 1), st);
-    if (rc != M1V_OK) return rc;
+    if (rc != M1V_OK) { // slot b holds no batch: the next step uses it again, the pending batch in the other slot is untouched
+        d->step_no--;
+        return rc;
+    }
     if (e->pipelined) HIP_TRY(m1v_flush(e, st) == M1V_OK ? hipSuccess : hipErrorUnknown);
     HIP_TRY(hipEventRecord(d->encoded[b], st));
     d->args[b].rgb = d_rgb;

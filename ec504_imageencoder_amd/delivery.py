@@ -37,8 +37,7 @@ class HostDelivery:
         self.delivered = [None, None]
         self.last = None            # (slot, total bytes) of the newest batch on its way / delivered
         self.bytes_delivered = 0
-        self._keep = [None, None]   # the input of the batch in each slot: must outlive the start of its copy
-        self._step = 0
+        self._keep = []             # inputs of the batches whose copy may not have started: must outlive that start
 
     def close(self):
         if self._h:
@@ -70,11 +69,12 @@ class HostDelivery:
 
     def step(self, rgb, first_frame_index=0):
         """Encode `rgb` (device-resident) on the current stream; the batch before it starts travelling behind it."""
-        slot_in = self._step & 1
-        self._step += 1
-        self._keep[slot_in] = rgb
+        self._keep.append(rgb)
         n = int(rgb.shape[0])
-        self._started(_ffi.lib().m1v_delivery_step(self._h, _ptr(rgb), n, int(first_frame_index), _stream()))
+        slot = _ffi.lib().m1v_delivery_step(self._h, _ptr(rgb), n, int(first_frame_index), _stream())
+        if slot >= 0:               # this batch is pending, the one before it has started travelling (a failed step keeps all)
+            del self._keep[:-1]
+        self._started(slot)
 
     def fence(self):
         import torch

@@ -109,10 +109,14 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
                       uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                       uint32_t *d_status, void *stream);
 
-/* Pipelined mode (off by default).  When on, m1v_encode_device launches only the encode kernel on `stream`;
- * the layout scans and the gather into d_out run on an internal stream, so the NEXT batch's encode kernel
- * (launched on `stream`) overlaps them.  d_out / d_frame_sizes / d_total / d_status of a batch are complete
- * once work enqueued behind m1v_flush(enc, s) on stream s has started; callers double-buffer d_out.  The
+/* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
+ * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
+ * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.
+ *
+ * Pipelined mode (off by default).  When on, m1v_encode_device launches only the encode kernel on `stream`;
+ * the run layout (run kernels) and the assembly into d_out (k_assemble) run on an internal stream, so the NEXT
+ * batch's encode kernel (launched on `stream`) overlaps them.  d_out / d_frame_sizes / d_total / d_status of a batch
+ * are complete once work enqueued behind m1v_flush(enc, s) on stream s has started; callers double-buffer d_out.  The
  * internal scratch is double-buffered, so at most two batches are in flight. */
 int m1v_set_pipelined(m1v_encoder *enc, int enable);
 /* Makes `stream` wait for every gather still pending on the internal stream.  An encoder in pipelined mode is meant to
@@ -210,6 +214,11 @@ int m1v_path_in_use(const m1v_encoder *enc); /* 1 = tiles, 0 = runs */
  * the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
  * M1V_E_HIP and leaves the encoder exactly as it was.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
 void m1v_debug_fail_alloc(int nth);
+/* Test hook: the next m1v_encode_device that reaches `stage` returns M1V_E_HIP there, as a failed HIP call would: 1 = after
+ * the internal counter set is chosen, before the encode kernel; 2 = after the encode kernel (and the run layout), before
+ * the assembly; 3 = after the assembly, before the pipelined completion event.  One-shot; 0 = off.  Host side only: it
+ * launches nothing and touches no device memory.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
+void m1v_debug_fail_encode(int stage);
 /* Test hook: force how the RUN kernel loads its pixels (forcing a mode selects the run path): -1 = automatic (by width,
  * channel count and pointer alignment), 0 = byte loads (valid everywhere), 2 = 28-byte loads + funnel shift (3 channels,
  * 4-byte aligned buffer).  A mode that is not valid for the buffer at hand is ignored.  Lets tests compare the load paths

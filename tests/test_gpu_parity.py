@@ -876,6 +876,16 @@ def test_fuzz_slice(torch_cuda, orc):
     assert cases >= 40 and skipped < cases // 2
 
 
+def test_sequence_fuzz_slice(torch_cuda, orc):
+    """A seeded slice of the sequence mode of tests/fuzz_parity.py (hand-run soak: fuzz_parity.py SECONDS SEED seq): one
+    encoder per case through 4..12 random steps (batch sizes 0..max_frames, pipelined on / off, forced path, LDS image,
+    reservation, run length and input mode, injected encode failures), every encode against the oracle."""
+    import fuzz_parity
+    cases, encodes, skipped, fails = fuzz_parity.run_sequences(budget=60.0, seed=20261016, max_cases=80, verbose=False)
+    assert not fails, fails[:5]
+    assert cases >= 30 and encodes >= 200 and skipped < encodes // 4, (cases, encodes, skipped)
+
+
 def test_scratch_is_compact_and_overflow_is_handled(torch_cuda, orc):
     """Round 1 reserved a worst-case slot (28 KiB) per run of 256 blocks: 1.6 GB for 34 MB of payload.  Now a run owns a
     compact slot and only runs that outgrow the LDS image take a worst-case slot from an overflow arena:
