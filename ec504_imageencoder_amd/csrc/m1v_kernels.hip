@@ -135,6 +135,8 @@ struct EncodeArgs {
     Geometry g;
     const uint8_t *rgb;
     const Tables *tab;
+    const float *rq_all;        // quantiser of every quality (see frame_rq_t)
+    const uint32_t *qsel;       // [frame]: where the frame's quantiser lies in rq_all
     uint8_t *scratch;           // [frame][strip][strip_cap]
     uint2 *seg;                 // [frame][strip]: (bits of the strip, where it starts in scratch: 4-byte words) — one segment per strip
     unsigned long long *strip_ctr;   // [frame][strip]: bits of the strip
@@ -249,6 +251,16 @@ __device__ __forceinline__ float component_raw(uint32_t r, uint32_t g, uint32_t 
 }
 
 #define M1V_CONST_AS __attribute__((address_space(4)))
+
+// Per-frame quality.  rq_all holds Tables::rq_t of every quality factor, [quality - 1][64] (m1v_create; the entry of the
+// encoder's own quality is bit-identical to its Tables::rq_t), and qsel[frame] is the offset in floats of the frame's entry:
+// the encoder's own quality for every frame on the plain path, the caller's per-frame choice (k_frame_quality) otherwise.
+// The frame is workgroup-uniform, so the selection is ONE scalar load per workgroup, in front of the table's own scalar
+// loads; no branch, no vector load.
+__device__ __forceinline__ const float *frame_rq_t(const float *rq_all, const uint32_t *qsel, int frame) {
+    const M1V_CONST_AS uint32_t *sel = reinterpret_cast<const M1V_CONST_AS uint32_t *>(reinterpret_cast<uintptr_t>(qsel));
+    return rq_all + sel[frame];
+}
 
 
 // The tile kernels run their fp32 arithmetic rounded TOWARD MINUS INFINITY: fdct_row_f<float, true> takes two floors of
@@ -900,7 +912,7 @@ __global__ __launch_bounds__(kWave) void k_encode_strips(EncodeArgs a) {
     uint32_t *blk = stage + tid * kStageStride16;
     if (valid) {
         uint32_t lds_addr;
-        dc = block_to_stage<FAST ? 1 : 0, false>(g, fbase, src, raw, a.tab->rq_t, blk, lds_addr);
+        dc = block_to_stage<FAST ? 1 : 0, false>(g, fbase, src, raw, frame_rq_t(a.rq_all, a.qsel, frame), blk, lds_addr);
         nz = (stage_nonzero_mask<false>(blk, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
     }
     auto fetch = [&](int p) -> int { return fetch_level<false>(blk, p); };
@@ -963,6 +975,8 @@ struct DenseArgs {
     Geometry g;
     const uint8_t *rgb;
     const Tables *tab;
+    const float *rq_all;    // quantiser of every quality (see frame_rq_t)
+    const uint32_t *qsel;   // [frame]: where the frame's quantiser lies in rq_all
     uint8_t *scratch;       // [frame][run][slot_bytes] compact slots (a run whose image fits the LDS image), then the overflow
                             // arena: arena_slots x run_cap, handed out by an atomic counter to the runs that build in global memory
     uint32_t *run_meta;     // [frame][run][4]: bits of segment 0, bits of segment 1, first word of segment 1, where the run's
@@ -1054,7 +1068,7 @@ void k_encode_dense(DenseArgs a) {
     uint32_t *blk = stage + tid * kStride;
     if (valid) {
         uint32_t lds_addr;
-        dc = block_to_stage<FAST, STAGE8, RowT>(g, fbase, src, raw, a.tab->rq_t, blk, lds_addr);
+        dc = block_to_stage<FAST, STAGE8, RowT>(g, fbase, src, raw, frame_rq_t(a.rq_all, a.qsel, frame), blk, lds_addr);
         nz = (stage_nonzero_mask<STAGE8>(blk, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
     }
     // No barrier here: pass 1 below reads only the lane's own staged levels and the wave's own copy of the VLC table.
@@ -1225,6 +1239,83 @@ __global__ __launch_bounds__(256) void k_dense_frame_layout(DenseGeom d, int seg
 }
 
 #include "m1v_tiles.h"
+
+// ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
+constexpr int kMaxCandidates = 8;
+struct QualityArgs {
+    const uint8_t *quality;                  // [frame] the caller's qualities, or null
+    int uniform;                             // the quality of every frame when `quality` and `probe_sizes` are null
+    int max_q;                               // the encoder's quality factor (1..100): the largest valid entry
+    // budget: probe_sizes[k * stride + frame] = record bytes of the frame at cand[k] (strictly increasing)
+    const unsigned long long *probe_sizes;
+    int stride, n_cand;
+    uint8_t cand[kMaxCandidates];
+    const unsigned long long *budget;        // [frame] per-frame budgets, or null: max_bytes for every frame
+    unsigned long long max_bytes;
+    const uint32_t *probe_status;            // [n_cand] status words of the probes
+    int n_frames;
+    uint32_t *qsel;                          // out: [frame] offset of the frame's entry in rq_all
+    uint8_t *chosen;                         // out (budget, may be null): [frame] the quality picked
+    uint32_t *status;                        // the batch's status word (M1V_STATUS_QUALITY, M1V_STATUS_OVER_BUDGET, ...)
+};
+
+// One lane per frame: the frame's quality -> its offset in rq_all.  An entry outside 1..max_q sets M1V_STATUS_QUALITY and
+// encodes at max_q (every plan of the encoder holds there; the batch's output is undefined, as with the other status bits).
+// Budget form: the largest candidate whose probed record fits the frame's budget, else the smallest and
+// M1V_STATUS_OVER_BUDGET; a probe that ran out of overflow scratch (sizes undefined) passes M1V_STATUS_SCRATCH on.
+__global__ __launch_bounds__(256) void k_frame_quality(QualityArgs a) {
+    const int f = (int)(blockIdx.x * 256 + threadIdx.x);
+    uint32_t bits = 0;
+    if (f == 0 && a.probe_sizes)
+        for (int k = 0; k < a.n_cand; k++) bits |= a.probe_status[k] & (uint32_t)M1V_STATUS_SCRATCH;
+    if (f < a.n_frames) {
+        int q;
+        if (a.probe_sizes) {
+            const unsigned long long cap = a.budget ? a.budget[f] : a.max_bytes;
+            int pick = -1;
+            for (int k = 0; k < a.n_cand; k++)
+                if (a.probe_sizes[(size_t)k * a.stride + f] <= cap) pick = k;
+            if (pick < 0) bits |= (uint32_t)M1V_STATUS_OVER_BUDGET;
+            q = a.cand[pick < 0 ? 0 : pick];
+            if (a.chosen) a.chosen[f] = (uint8_t)q;
+        } else {
+            q = a.quality ? (int)a.quality[f] : a.uniform;
+        }
+        if (q < 1 || q > a.max_q) {
+            bits |= (uint32_t)M1V_STATUS_QUALITY;
+            q = a.max_q;
+        }
+        a.qsel[f] = (uint32_t)(q - 1) * 64u;
+    }
+    if (bits) atomicOr(a.status, bits);
+}
+
+// The probe's place of k_assemble (one workgroup per frame): each record's size (its strips' bytes + 48 bytes of headers and
+// trailer, what k_assemble derives) and the status word, and the same counter hand-over — the set the next call adds into is
+// cleared for the frames this launch reaches (the host clears the rest).  Nothing is assembled, nothing written to d_out.
+struct SizesArgs {
+    int n_frames, n_strips, next_frames;
+    const unsigned long long *frame_bytes;
+    const uint32_t *enc_words;
+    unsigned long long *next_strip_ctr, *next_frame_bytes;
+    uint32_t *next_words;
+    unsigned long long *out_sizes; // may be null
+    uint32_t *out_status;
+};
+__global__ __launch_bounds__(256) void k_frame_sizes(SizesArgs a) {
+    const int f = blockIdx.x;
+    if (f < a.next_frames)
+        for (int s = threadIdx.x; s < a.n_strips; s += 256) a.next_strip_ctr[(size_t)f * a.n_strips + s] = 0ull;
+    if (threadIdx.x == 0) {
+        if (a.out_sizes) a.out_sizes[f] = 48ull + a.frame_bytes[f];
+        if (f < a.next_frames) a.next_frame_bytes[f] = 0ull;
+        if (f == a.n_frames - 1) {
+            *a.out_status = a.enc_words[0];
+            a.next_words[0] = 0u;
+            a.next_words[2] = 0u;
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // partial pipelines
@@ -1506,6 +1597,14 @@ struct m1v_encoder {
     size_t meta_bytes, seg_bytes; // sizes of run_meta and seg in effect
     int segs;               // segments per strip: tile rows (tiles), or the most runs a strip can touch (run kernels)
     Tables *d_tab;
+    // Per-frame quality (frame_rq_t): Tables::rq_t of every quality [100][64]; the selection of the plain path (the encoder's
+    // own quality, [max_frames]); the selection k_frame_quality writes; the budget call's probes ([kMaxCandidates][max_frames]
+    // sizes, kMaxCandidates status words) and its choice when the caller does not want it
+    float *d_rq_all;
+    uint32_t *d_qsel_own, *d_qsel;
+    unsigned long long *d_probe_sizes;
+    uint32_t *d_probe_status;
+    uint8_t *d_chosen;
     // What k_assemble needs to know about the output (configure_path): strips per workgroup, lanes per segment, LDS image
     int asm_group, asm_lanes_log2, asm_img_words;
     // What an encode kernel adds to and k_assemble reads.  Two sets per Batch, taken in turns: the assemble kernel of call j clears
@@ -1901,6 +2000,11 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     e->prof = false;
     e->ev_used = 0;
     e->d_stamps = nullptr;
+    e->d_rq_all = nullptr;
+    e->d_qsel_own = e->d_qsel = nullptr;
+    e->d_probe_sizes = nullptr;
+    e->d_probe_status = nullptr;
+    e->d_chosen = nullptr;
 
     Tables *t = new Tables();
     int q[64];
@@ -1920,6 +2024,29 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
 
     hipError_t err = hipMalloc(&e->d_tab, sizeof(Tables));
     if (err == hipSuccess) err = hipMemcpy(e->d_tab, t, sizeof(Tables), hipMemcpyHostToDevice);
+    {
+        // per-frame quality: the transposed reciprocal table of every quality, built as Tables::rq_t is
+        std::vector<float> all(100 * 64);
+        for (int qf = 1; qf <= 100; qf++) {
+            int qq[64];
+            scaled_matrix(qf, qq);
+            for (int u = 0; u < 8; u++)
+                for (int i = 0; i < 8; i++)
+                    all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)((1.0 / qq[u * 8 + i]) * (1.0 + 1.0 / 1048576.0));
+        }
+        const int own = std::min(std::max(quality_factor, 1), 100);
+        if (memcmp(&all[(size_t)(own - 1) * 64], t->rq_t, sizeof t->rq_t) != 0) err = hipErrorUnknown; // (cannot happen)
+        const std::vector<uint32_t> sel((size_t)max_frames, (uint32_t)(own - 1) * 64u);
+        if (err == hipSuccess) err = hipMalloc(&e->d_rq_all, all.size() * sizeof(float));
+        if (err == hipSuccess) err = hipMemcpy(e->d_rq_all, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMalloc(&e->d_qsel_own, sel.size() * sizeof(uint32_t));
+        if (err == hipSuccess) err = hipMemcpy(e->d_qsel_own, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMalloc(&e->d_qsel, sel.size() * sizeof(uint32_t));
+        if (err == hipSuccess) err = hipMemcpy(e->d_qsel, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
+        if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
+        if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
+    }
     delete t;
 #if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
     if (err == hipSuccess) err = hipMalloc(&e->d_stamps, (32 + 8 * 65536) * 8); // [32] phase sums, then a timeline of 8 stamps per workgroup
@@ -1948,6 +2075,12 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipSetDevice(e->device);
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     (void)hipFree(e->d_tab);
+    (void)hipFree(e->d_rq_all);
+    (void)hipFree(e->d_qsel_own);
+    (void)hipFree(e->d_qsel);
+    (void)hipFree(e->d_probe_sizes);
+    (void)hipFree(e->d_probe_status);
+    (void)hipFree(e->d_chosen);
     for (m1v_encoder::Batch &bt : e->batch) {
         (void)hipFree(bt.scratch);
         (void)hipFree(bt.run_meta);
@@ -2176,10 +2309,15 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
     return e->fast_ok && ((uintptr_t)d_rgb & 3) == 0;
 }
 
-int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                      uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
-                      uint32_t *d_status, void *stream) {
-    if (!e || (!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
+static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
+
+// One batch through the encode kernel of the encoder's path.  qa == null: every frame at the encoder's own quality (the plain
+// path); otherwise k_frame_quality first writes the per-frame selection (into the batch's status word) from qa.  probe: the
+// counter hand-over ends in k_frame_sizes instead of k_assemble (record sizes and status only; d_out is not touched).
+static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, QualityArgs *qa, bool probe,
+                        uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status,
+                        void *stream) {
+    if (!e || (!d_rgb && n_frames > 0) || (!d_out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));
@@ -2222,11 +2360,23 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
         ~PoisonOnReturn() { if (flag) *flag = true; }
     } poison{&bt.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
+    const uint32_t *qsel = e->d_qsel_own;
+    if (qa) {
+        qa->max_q = encoder_quality(e);
+        qa->n_frames = n_frames;
+        qa->qsel = e->d_qsel;
+        qa->status = cur.words;
+        hipLaunchKernelGGL(k_frame_quality, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, *qa);
+        HIP_TRY(hipGetLastError());
+        qsel = e->d_qsel;
+    }
     if (e->tiles) {
         TileArgs a;
         a.g = g;
         a.rgb = d_rgb;
         a.tab = e->d_tab;
+        a.rq_all = e->d_rq_all;
+        a.qsel = qsel;
         a.scratch = bt.scratch;
         a.seg = bt.seg;
         a.strip_ctr = cur.strip_ctr;
@@ -2271,6 +2421,8 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
         a.g = g;
         a.rgb = d_rgb;
         a.tab = e->d_tab;
+        a.rq_all = e->d_rq_all;
+        a.qsel = qsel;
         a.scratch = bt.scratch;
         a.run_meta = bt.run_meta;
         a.status = cur.words;
@@ -2335,6 +2487,8 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
         a.g = g;
         a.rgb = d_rgb;
         a.tab = e->d_tab;
+        a.rq_all = e->d_rq_all;
+        a.qsel = qsel;
         a.scratch = bt.scratch;
         a.seg = bt.seg;
         a.strip_ctr = cur.strip_ctr;
@@ -2359,8 +2513,30 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
         }
     }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
-    // ---- frame offsets, strip offsets, concatenation, headers, sizes, status: one launch (m1v_assemble.h) ----
-    {
+    if (probe) {
+        // ---- record sizes and status only, with k_assemble's counter hand-over ----
+        SizesArgs sa;
+        sa.n_frames = n_frames;
+        sa.n_strips = g.n_strips;
+        sa.frame_bytes = cur.frame_bytes;
+        sa.enc_words = cur.words;
+        sa.next_strip_ctr = nxt.strip_ctr;
+        sa.next_frame_bytes = nxt.frame_bytes;
+        sa.next_words = nxt.words;
+        if (nxt.dirty_frames > n_frames) { // as below
+            HIP_TRY(hipMemsetAsync(nxt.strip_ctr, 0, (size_t)nxt.dirty_frames * g.n_strips * 8, gs));
+            HIP_TRY(hipMemsetAsync(nxt.frame_bytes, 0, (size_t)nxt.dirty_frames * 8, gs));
+            nxt.dirty_frames = 0;
+        }
+        sa.next_frames = nxt.dirty_frames;
+        nxt.dirty_frames = 0;
+        cur.dirty_frames = n_frames;
+        sa.out_sizes = (unsigned long long *)d_frame_sizes;
+        sa.out_status = d_status ? d_status : cur.words + 1;
+        hipLaunchKernelGGL(k_frame_sizes, dim3((unsigned)n_frames), dim3(256), 0, gs, sa);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // ---- frame offsets, strip offsets, concatenation, headers, sizes, status: one launch (m1v_assemble.h) ----
         AssembleArgs ga;
         ga.n_frames = n_frames;
         ga.n_strips = g.n_strips;
@@ -2408,6 +2584,68 @@ int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int fi
     }
     poison.flag = nullptr;
     return M1V_OK;
+}
+
+int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                      uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                      uint32_t *d_status, void *stream) {
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status,
+                        stream);
+}
+
+int m1v_encode_quality_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                              uint64_t *d_total, uint32_t *d_status, void *stream) {
+    QualityArgs qa = {};
+    qa.quality = d_quality;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, d_quality ? &qa : nullptr, false, d_out, out_cap, d_frame_sizes,
+                        d_total, d_status, stream);
+}
+
+int m1v_frame_sizes_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *d_quality,
+                           uint64_t *d_frame_sizes, uint32_t *d_status, void *stream) {
+    QualityArgs qa = {};
+    qa.quality = d_quality;
+    return encode_batch(e, d_rgb, n_frames, 0, d_quality ? &qa : nullptr, true, nullptr, 0, d_frame_sizes, nullptr, d_status,
+                        stream);
+}
+
+int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                             const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
+                             const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
+                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                             uint32_t *d_status, void *stream) {
+    if (!e || !candidates) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
+    for (int k = 0; k < n_candidates; k++)
+        if (candidates[k] < 1 || candidates[k] > encoder_quality(e) || (k > 0 && candidates[k] <= candidates[k - 1]))
+            return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    // 1. the record size of every frame at every candidate (each probe is a complete call: its own counter hand-over)
+    for (int k = 0; k < n_candidates; k++) {
+        QualityArgs qa = {};
+        qa.uniform = candidates[k];
+        const int rc = encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, true, nullptr, 0,
+                                    (uint64_t *)(e->d_probe_sizes + (size_t)k * e->max_frames), nullptr, e->d_probe_status + k, stream);
+        if (rc != M1V_OK) return rc;
+    }
+    // (pipelined: the probes' sizes are written on the internal stream)
+    if (e->pipelined) {
+        const int rc = m1v_flush(e, stream);
+        if (rc != M1V_OK) return rc;
+    }
+    // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
+    QualityArgs qa = {};
+    qa.probe_sizes = e->d_probe_sizes;
+    qa.stride = e->max_frames;
+    qa.n_cand = n_candidates;
+    for (int k = 0; k < n_candidates; k++) qa.cand[k] = candidates[k];
+    qa.budget = (const unsigned long long *)d_max_frame_bytes;
+    qa.max_bytes = max_frame_bytes;
+    qa.probe_status = e->d_probe_status;
+    qa.chosen = d_chosen ? d_chosen : e->d_chosen;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

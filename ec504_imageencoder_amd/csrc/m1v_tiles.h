@@ -38,6 +38,8 @@ struct TileArgs {
     Geometry g;
     const uint8_t *rgb;
     const Tables *tab;
+    const float *rq_all;    // quantiser of every quality (frame_rq_t)
+    const uint32_t *qsel;   // [frame]: where the frame's quantiser lies in rq_all
     uint8_t *scratch;       // [frame][tile][slot_bytes] compact slots, then the overflow arena (as the run kernels)
     uint2 *seg;             // [frame][tile row][strip]: bits of the segment, where it starts (4-byte words from `scratch`)
     unsigned long long *strip_ctr;   // [frame][strip]: every tile adds (1 << 40 | its segment's bits) with ONE returning atomic: the tile
@@ -326,7 +328,7 @@ void k_encode_tiles(TileArgs a) {
             for (int k = tid; k < (a.lds_words >> 2); k += kTileThreads) image4[k] = make_uint4(0u, 0u, 0u, 0u);
         },
         rows);
-    const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(a.tab->rq_t));
+    const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(frame_rq_t(a.rq_all, a.qsel, frame)));
     // The lane's place in the tile, derived again behind the pixel stage (from an opaque copy of the lane id: five values
     // less to carry through the stage, whose register budget decides the waves per SIMD)
     int j, m, blk;

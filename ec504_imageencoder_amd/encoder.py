@@ -7,6 +7,7 @@ records out, both as torch CUDA tensors.  torch is plumbing here (device memory,
 arithmetic happens in libencoder.so's HIP kernels.
 """
 import ctypes as C
+import numbers
 
 from . import _ffi
 
@@ -61,26 +62,121 @@ class Mpeg1Encoder:
             pass
 
     # ---- the hot path -------------------------------------------------------------------------
-    def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None):
+    def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
         """rgb: uint8 CUDA tensor [n, H, W, C] (contiguous).  Asynchronous on torch's current stream.
+        quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
+        CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
         meta int64[2] = (total bytes, status bits)."""
         import torch
         n = rgb.shape[0]
-        assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
-        assert rgb.numel() == n * self.frame_bytes_in
+        self._check_input(rgb)
         if out is None:
             out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
         if sizes is None:
             sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
         if meta is None:
             meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
-        rc = _ffi.lib().m1v_encode_device(self._h, _ptr(rgb), n, int(first_frame_index), _ptr(out), out.numel(),
-                                          _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8),
-                                          _stream())
+        if quality is None:
+            rc = _ffi.lib().m1v_encode_device(self._h, _ptr(rgb), n, int(first_frame_index), _ptr(out), out.numel(),
+                                              _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8),
+                                              _stream())
+            where = "m1v_encode_device"
+        else:
+            q = self._quality_tensor(quality, n, rgb.device)
+            rc = _ffi.lib().m1v_encode_quality_device(self._h, _ptr(rgb), n, int(first_frame_index), _ptr(q), _ptr(out),
+                                                      out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()),
+                                                      C.c_void_p(meta.data_ptr() + 8), _stream())
+            where = "m1v_encode_quality_device"
         if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_encode_device")
+            raise EncoderError(rc, where)
         return out, sizes, meta
+
+    def _check_input(self, rgb):
+        import torch
+        assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+        assert rgb.numel() == rgb.shape[0] * self.frame_bytes_in
+
+    @staticmethod
+    def _quality_tensor(quality, n, device):
+        """One uint8 quality per frame, on the device (the library validates the values)."""
+        import torch
+        if isinstance(quality, torch.Tensor):
+            assert quality.is_cuda and quality.dtype == torch.uint8 and quality.numel() == n, "quality: CUDA uint8, one per frame"
+            return quality.contiguous()
+        q = [int(x) for x in quality]
+        assert len(q) == n, "quality: one entry per frame"
+        if any(x < 0 or x > 255 for x in q):
+            raise EncoderError(_ffi.E_ARG, "quality: entries must fit uint8")
+        return torch.tensor(q if q else [0], dtype=torch.uint8).to(device, non_blocking=False)
+
+    def frame_sizes(self, rgb, quality=None, status=None):
+        """The exact record size of every frame at `quality` (as in encode(); None = the encoder's quality factor), without
+        assembling or writing any output: int64 CUDA tensor [n].  Asynchronous on torch's current stream (in pipelined mode
+        complete behind flush()).  status: optional CUDA int32 tensor [1] that receives the status bits."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        sizes = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
+        q = self._quality_tensor(quality, n, rgb.device) if quality is not None else None
+        rc = _ffi.lib().m1v_frame_sizes_device(self._h, _ptr(rgb), n, _ptr(q), _ptr(sizes), _ptr(status), _stream())
+        if rc != _ffi.OK:
+            raise EncoderError(rc, "m1v_frame_sizes_device")
+        return sizes[:n]
+
+    def encode_to_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
+        """Synchronous: every frame at the largest of `candidates` (1..8 qualities, strictly increasing, each <= quality_factor)
+        whose record fits its budget, else at the smallest.  max_frame_bytes: one budget for every frame, or one per frame
+        (a sequence or a CUDA int64 tensor).  Returns (bytes, sizes, chosen, over_budget_frames)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        cands = [int(c) for c in candidates]
+        if not 1 <= len(cands) <= _ffi.MAX_CANDIDATES or any(c < 1 or c > 255 for c in cands):
+            raise EncoderError(_ffi.E_ARG, "encode_to_budget: 1 to 8 candidate qualities")
+        cand_buf = (C.c_uint8 * len(cands))(*cands)
+        if isinstance(max_frame_bytes, torch.Tensor):
+            assert max_frame_bytes.is_cuda and max_frame_bytes.dtype == torch.int64 and max_frame_bytes.numel() == n
+            budget, d_budget = 0, max_frame_bytes.contiguous()
+        elif isinstance(max_frame_bytes, numbers.Integral):
+            budget, d_budget = max_frame_bytes, None
+        else:
+            b = [int(x) for x in max_frame_bytes]
+            assert len(b) == n, "max_frame_bytes: one entry per frame"
+            budget, d_budget = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        out = None
+        for attempt in range(3):
+            if out is None:
+                out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
+            sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
+            meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
+            rc = _ffi.lib().m1v_encode_budget_device(self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cands), budget,
+                                                     _ptr(d_budget), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes),
+                                                     C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream())
+            if rc != _ffi.OK:
+                raise EncoderError(rc, "m1v_encode_budget_device")
+            self.flush()
+            torch.cuda.synchronize(rgb.device)
+            total, status = (int(x) for x in meta.cpu())
+            status &= 0xFFFFFFFF
+            if status & _ffi.STATUS_UNENCODABLE:
+                raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
+            if status & _ffi.STATUS_QUALITY:
+                raise EncoderError(_ffi.E_ARG, "encode_to_budget: a quality outside 1 .. quality_factor")
+            if not status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
+                break
+            if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
+                self.reserve_scratch(True)
+            if status & _ffi.STATUS_NOSPACE:
+                out = torch.empty(self.frame_bound * max(n, 1), dtype=torch.uint8, device=rgb.device)
+        else:
+            raise EncoderError(_ffi.E_NOSPACE if status & _ffi.STATUS_NOSPACE else _ffi.E_SCRATCH, "encode_to_budget")
+        sizes_l = [int(s) for s in sizes[:n].cpu()]
+        chosen_l = [int(c) for c in chosen[:n].cpu()]
+        budgets = [budget] * n if d_budget is None else [int(x) for x in d_budget[:n].cpu()]
+        over = [f for f in range(n) if sizes_l[f] > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
+        return out[:total].cpu().numpy().tobytes(), sizes_l, chosen_l, over
 
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.
@@ -102,34 +198,38 @@ class Mpeg1Encoder:
         # `out` of frame_bound * n bytes.  NOSPACE is reported through the status word.
         return int(min(self.frame_bound, self.frame_bytes_in // 2 + 4096) * max(n, 1))
 
-    def encode_to_bytes(self, rgb, first_frame_index=0):
-        """Synchronous convenience: returns (bytes, [sizes])."""
+    def encode_to_bytes(self, rgb, first_frame_index=0, quality=None):
+        """Synchronous convenience: returns (bytes, [sizes]).  quality: as in encode()."""
         import torch
-        out, sizes, meta = self.encode(rgb, first_frame_index)
+        if quality is not None:     # one upload, reused by a retry
+            quality = self._quality_tensor(quality, rgb.shape[0], rgb.device)
+        out, sizes, meta = self.encode(rgb, first_frame_index, quality=quality)
         self.flush()
         torch.cuda.synchronize(rgb.device)
         total, status = (int(x) for x in meta.cpu())
         status &= 0xFFFFFFFF
         if status & _ffi.STATUS_UNENCODABLE:
             raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
+        if status & _ffi.STATUS_QUALITY:
+            raise EncoderError(_ffi.E_ARG, "encode: a quality outside 1 .. quality_factor")
         if status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
             if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
                 self.reserve_scratch(True)
             if status & _ffi.STATUS_NOSPACE:
                 out = torch.empty(self.frame_bound * rgb.shape[0], dtype=torch.uint8, device=rgb.device)
-            return self._retry_bytes(rgb, first_frame_index, out)
+            return self._retry_bytes(rgb, first_frame_index, out, quality)
         return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:rgb.shape[0]].cpu()]
 
-    def _retry_bytes(self, rgb, first_frame_index, out):
+    def _retry_bytes(self, rgb, first_frame_index, out, quality=None):
         import torch
-        out, sizes, meta = self.encode(rgb, first_frame_index, out=out)
+        out, sizes, meta = self.encode(rgb, first_frame_index, out=out, quality=quality)
         self.flush()
         torch.cuda.synchronize(rgb.device)
         total, status = (int(x) for x in meta.cpu())
         status &= 0xFFFFFFFF
         if status & _ffi.STATUS_NOSPACE:            # scratch was the first obstacle, the output buffer is the second
             out = torch.empty(self.frame_bound * rgb.shape[0], dtype=torch.uint8, device=rgb.device)
-            out, sizes, meta = self.encode(rgb, first_frame_index, out=out)
+            out, sizes, meta = self.encode(rgb, first_frame_index, out=out, quality=quality)
             self.flush()
             torch.cuda.synchronize(rgb.device)
             total, status = (int(x) for x in meta.cpu())

@@ -17,6 +17,8 @@
  *       and the 4 trailing bytes (encoder.h:456-458).
  *   m1v_encode_planes_host     one frame-loop iteration per frame, complete: the frame record AND the planes that
  *                              write_to_bitstream (image_processing.c:753, called at encoder.h:461-465) stores
+ *   m1v_encode_quality_device / m1v_frame_sizes_device / m1v_encode_budget_device
+ *                              no reference counterpart (one quality per run there): per-frame quality, size probe, budget
  *   m1v_set_pipelined / m1v_flush   no reference counterpart: overlap of one batch's gather with the next encode
  *   m1v_warm_up, m1v_alloc_host/_free_host   no reference counterpart: runtime start-up off the critical path, pinned buffers
  *   m1v_coefficients_device    fast_DCT + quantization + zigzag_scanning only (BASELINE config 2)
@@ -65,13 +67,17 @@ enum {
 
 /* bits of the device status word (m1v_encode_device's d_status) */
 enum { M1V_STATUS_UNENCODABLE = 1u, M1V_STATUS_NOSPACE = 2u, M1V_STATUS_SCRATCH = 4u };
+/* M1V_STATUS_QUALITY: a per-frame quality outside 1 .. the encoder's quality factor (output of the batch undefined);
+ * M1V_STATUS_OVER_BUDGET: m1v_encode_budget_device found no candidate that fits some frame's budget (output valid) */
+enum { M1V_STATUS_QUALITY = 8u, M1V_STATUS_OVER_BUDGET = 16u };
 
 typedef struct m1v_encoder m1v_encoder;
 
 int m1v_device_count(void);
 const char *m1v_last_error(void); /* thread-local, never NULL */
 
-/* One encoder = one device, one picture geometry, one quality factor.  max_frames bounds the batch
+/* One encoder = one device, one picture geometry, one quality factor (the finest a frame of it can have: see
+ * m1v_encode_quality_device).  max_frames bounds the batch
  * a single m1v_encode_* call may carry (scratch is sized for it). */
 int m1v_create(m1v_encoder **out, int device, int width, int height, int channels,
                int quality_factor, int mode, int max_frames);
@@ -108,6 +114,37 @@ size_t m1v_file_prolog(uint8_t out[27]);
 int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                       uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                       uint32_t *d_status, void *stream);
+
+/* Per-frame quality factors and frame-size budgets.  A frame record depends only on the frame's pixels, its global index and
+ * its quality factor, so every frame of a batch may have its own.  Contract: 1 <= q[f] <= the encoder's quality factor
+ * (clamped to 1..100); every plan the encoder made for its own quality stays valid for coarser ones.  An entry of 0 or above
+ * that bound sets M1V_STATUS_QUALITY in d_status, and the batch's output is undefined.  All three are calls like
+ * m1v_encode_device (asynchronous on `stream`, same counter hand-over, pipelined mode included) and may be interleaved with it.
+ *
+ * m1v_encode_quality_device   m1v_encode_device with frame f at quality d_quality[f] (uint8[n_frames] on the device; NULL =
+ *                             the encoder's quality for every frame, the plain call).
+ * m1v_frame_sizes_device      the exact record size each frame would have at d_quality (NULL = the encoder's quality) into
+ *                             d_frame_sizes, and the status bits of the encode into d_status; assembles nothing and writes
+ *                             nothing else (no output buffer).  Costs the encode kernel of a plain call.
+ * m1v_encode_budget_device    fit each frame into a byte budget with no host wait: probes the record size of every frame at each
+ *                             of the n_candidates qualities in `candidates` (a HOST array, 1 <= K <= 8, strictly increasing, each
+ *                             <= the encoder's quality), picks per frame the LARGEST candidate whose record fits the frame's
+ *                             budget (the whole record, as d_frame_sizes counts it), or the smallest candidate and
+ *                             M1V_STATUS_OVER_BUDGET when none fits, then encodes once at the picked qualities.  The budget of
+ *                             frame f is d_max_frame_bytes[f] (uint64[n_frames] on the device) or, when that is NULL,
+ *                             max_frame_bytes.  d_chosen (uint8[n_frames] on the device, may be NULL) receives the picks.
+ *                             Costs K + 1 encode kernels.  A probe that exhausts the overflow scratch reports M1V_STATUS_SCRATCH.
+ * Argument errors (bad candidates, n_frames > max_frames, null pointers) return M1V_E_ARG. */
+int m1v_encode_quality_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                              uint64_t *d_total, uint32_t *d_status, void *stream);
+int m1v_frame_sizes_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const uint8_t *d_quality,
+                           uint64_t *d_frame_sizes, uint32_t *d_status, void *stream);
+int m1v_encode_budget_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                             const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
+                             const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
+                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                             uint32_t *d_status, void *stream);
 
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
