@@ -1458,7 +1458,7 @@ __global__ __launch_bounds__(256) void k_synth(uint8_t *rgb, unsigned long long 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side of the C-ABI
+// host side: the plan of an encoder and the launches of a batch from it (the C-ABI itself: m1v_runtime.h)
 // ------------------------------------------------------------------------------------------------
 thread_local char g_err[512] = "";
 
@@ -1472,226 +1472,100 @@ int fail(int code, const char *fmt, const char *detail = "") {
         if (e_ != hipSuccess) return fail(M1V_E_HIP, #expr ": %s", hipGetErrorString(e_));         \
     } while (0)
 
-// scaled quantiser matrix, image_processing.c:314-343 (float scale factor, double division,
-// round half away from zero, floor of 1)
-void scaled_matrix(int qf, int q[64]) {
-    static const unsigned char base[64] = {
-        8,  16, 19, 22, 26, 27, 29, 34, 16, 16, 22, 24, 27, 29, 34, 37, 19, 22, 26, 27, 29, 34,
-        34, 38, 22, 22, 26, 27, 29, 34, 37, 40, 22, 26, 27, 29, 32, 35, 40, 48, 26, 27, 29, 32,
-        35, 40, 48, 58, 26, 27, 29, 34, 38, 46, 56, 69, 27, 29, 35, 38, 46, 56, 69, 83};
-    if (qf < 1) qf = 1;
-    if (qf > 100) qf = 100;
-    float sf = qf < 50 ? (float)(5000.0 / qf) : (float)(200.0 - 2 * qf);
-    for (int k = 0; k < 64; k++) {
-        float prod = (float)base[k] * sf;
-        int v = (int)round((double)prod / 100.0);
-        q[k] = v < 1 ? 1 : v;
-    }
-}
-
-// The VLC table of the kernels (layout: kVlc*).  Run/level code words without sign bit as the reference stores them
-// (vlc.c:176-288), in its order, with its offset index (vlc.c:172-174); the reference's indexing rule (vlc.c:329-339)
-// reads row r = run - 1 at |level| - 1, so in row 0 entry idx codes level idx + 2 — except idx 0, which the rule
-// replaces by the special "11" and which is therefore stored that way here.  DC size codes: vlc.c:121-144.
-void build_vlc_table(uint32_t t[kVlcWords]) {
-    static const unsigned char row_len[32] = {39, 18, 5, 4, 3, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2,
-                                              2,  1,  1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-    static const unsigned char code[110] = {
-        0x04, 0x05, 0x06, 0x26, 0x21, 0x0a, 0x1d, 0x18, 0x13, 0x10, 0x1a, 0x19, 0x18, 0x17, 0x1f, 0x1e,
-        0x1d, 0x1c, 0x1b, 0x1a, 0x19, 0x18, 0x17, 0x16, 0x15, 0x14, 0x13, 0x12, 0x11, 0x10, 0x18, 0x17,
-        0x16, 0x15, 0x14, 0x13, 0x12, 0x11, 0x10, 0x03, 0x06, 0x25, 0x0c, 0x1b, 0x16, 0x15, 0x1f, 0x1e,
-        0x1d, 0x1c, 0x1b, 0x1a, 0x19, 0x13, 0x12, 0x11, 0x10, 0x05, 0x04, 0x0b, 0x14, 0x14, 0x07, 0x24,
-        0x1c, 0x13, 0x06, 0x0f, 0x12, 0x07, 0x09, 0x12, 0x05, 0x1e, 0x14, 0x04, 0x15, 0x07, 0x11, 0x05,
-        0x11, 0x27, 0x10, 0x23, 0x1a, 0x22, 0x19, 0x20, 0x18, 0x0e, 0x17, 0x0d, 0x16, 0x08, 0x15, 0x1f,
-        0x1a, 0x19, 0x17, 0x16, 0x1f, 0x1e, 0x1d, 0x1c, 0x1b, 0x1f, 0x1e, 0x1d, 0x1c, 0x1b};
-    static const unsigned char bits[110] = {
-        4,  5,  7,  8,  8,  10, 12, 12, 12, 12, 13, 13, 13, 13, 14, 14, 14, 14, 14, 14, 14, 14,
-        14, 14, 14, 14, 14, 14, 14, 14, 15, 15, 15, 15, 15, 15, 15, 15, 15, 3,  6,  8,  10, 12,
-        13, 13, 15, 15, 15, 15, 15, 15, 15, 16, 16, 16, 16, 4,  7,  10, 12, 13, 5,  8,  12, 13,
-        5,  10, 12, 6,  10, 13, 6,  12, 16, 6,  12, 7,  12, 7,  13, 8,  13, 8,  16, 8,  16, 8,
-        16, 10, 16, 10, 16, 10, 15, 12, 12, 12, 12, 12, 13, 13, 13, 13, 13, 16, 16, 16, 16, 16};
-    memset(t, 0, kVlcWords * sizeof(uint32_t));
-    int first = 0;
-    for (int r = 0; r < kAcRows; r++) {
-        t[kVlcRowInfo + r] = (uint32_t)first | ((uint32_t)row_len[r] << 8);
-        first += row_len[r];
-    }
-    for (int e = 0; e < 110; e++) t[kVlcEntries + e] = ((uint32_t)bits[e] << 16) | code[e];
-    t[kVlcEntries] = (2u << 16) | 0x3u; // run 1, |level| 1 -> "11" (vlc.c:329-334 with first == 0)
-    static const unsigned char lc[9] = {0x4, 0x0, 0x1, 0x5, 0x6, 0xE, 0x1E, 0x3E, 0x7E};
-    static const unsigned char lb[9] = {3, 2, 2, 3, 3, 4, 5, 6, 7};
-    static const unsigned char cc[9] = {0x0, 0x1, 0x2, 0x6, 0xE, 0x1E, 0x3E, 0x7E, 0xFE};
-    static const unsigned char cb[9] = {2, 2, 2, 3, 4, 5, 6, 7, 8};
-    for (int i = 0; i < 9; i++) {
-        t[kVlcDcLuma + i] = ((uint32_t)lb[i] << 16) | lc[i];
-        t[kVlcDcChroma + i] = ((uint32_t)cb[i] << 16) | cc[i];
-    }
-}
-
-void put_timestamp(uint8_t *o, uint8_t prefix, uint32_t v) { // mpeg1_enc.c:59-64, :67-71
-    o[0] = (uint8_t)(prefix | ((v & 0xe0000000u) >> 28));
-    o[1] = (uint8_t)((v & 0x1fe00000u) >> 21);
-    o[2] = (uint8_t)(0x01 | ((v & 0x001fc000u) >> 13));
-    o[3] = (uint8_t)((v & 0x00003fc0u) >> 6);
-    o[4] = (uint8_t)(0x01 | ((v & 0x0000003fu) << 1));
-}
-
-// PKT(16) SEQ(12) GOP(8) PIC(8) of the frame whose uint8 `hour` is given (encoder.h:37-63,186-230)
-void build_frame_header(uint8_t h[44], int W, int H, int hour) {
-    memset(h, 0, 44);
-    h[2] = 0x01; h[3] = 0xe0;                                  // packet, stream id 0 (mpeg1_enc.c:47-77)
-    uint32_t ts = (uint32_t)(1 + 3600 * hour);
-    ts = (uint32_t)((double)ts * 1.2);
-    ts += 0xbeef;
-    put_timestamp(h + 6, 0x31, ts);
-    ts -= 0xbeef;
-    put_timestamp(h + 11, 0x11, ts);
-    uint8_t *s = h + 16;                                       // sequence (mpeg1_enc.c:81-94)
-    unsigned w = (unsigned)W & 0xffu, hh = (unsigned)H & 0xffu; // uint8_t width/height, encoder.h:186-187
-    s[2] = 0x01; s[3] = 0xb3;
-    s[4] = (uint8_t)((w & 0xff0) >> 4);
-    s[5] = (uint8_t)(((w & 0xf) << 4) | ((hh & 0xf00) >> 8));
-    s[6] = (uint8_t)(hh & 0xff);
-    s[7] = 0x14; s[8] = 0xff; s[9] = 0xff; s[10] = 0xe0; s[11] = 0x18;
-    uint8_t *g = h + 28;                                       // GOP (mpeg1_enc.c:103-113)
-    g[2] = 0x01; g[3] = 0xb8;
-    g[4] = (uint8_t)((hour & 0x1f) << 2);
-    g[5] = 0x08; g[6] = 0x00; g[7] = 0x40;
-    uint8_t *p = h + 36;                                       // picture (mpeg1_enc.c:120-129)
-    p[2] = 0x01; p[3] = 0x00; p[4] = 0x00; p[5] = 0x0f; p[6] = 0xff; p[7] = 0xf8;
-}
-
 } // namespace
 
-struct m1v_encoder {
-    int device;
-    Geometry g;
-    int qf, mode, max_frames;
-    int threads;       // workgroup size of k_encode_strips
-    int lds_words;
-    bool dense;        // blocks per strip >= 64: k_encode_dense, else one workgroup per strip
-    bool narrow;       // no AC level can reach +-128: one byte per staged level
-    int dense_T, runs_per_frame;
-    uint32_t run_cap;       // worst-case bytes of one run = one slot of the overflow arena
-    uint32_t slot_bytes;    // compact slot of a run (what the LDS image can hold)
+#ifndef M1V_TILE_RING
+#define M1V_TILE_RING 2
+#endif
+
+// Which encode kernel serves a batch.  Tiles (k_encode_tiles, m1v_tiles.h): 3-channel pictures, any width and alignment — the
+// default.  Runs: k_encode_dense (4-channel pictures, and whatever the test hooks force: m1v_debug_set_path, a forced input mode, a
+// forced run length), or k_encode_strips where a strip has fewer than 64 blocks.
+enum class Producer { tiles, dense, strips };
+
+// What the encoder's settings decide (plan_for): the producer kernel, its launch shape, the layout of its scratch, k_assemble's shape.
+struct Plan {
+    Producer producer;
+    int block;              // workgroup size of the producer (dense: the run length T)
+    size_t lds_bytes;       // its dynamic LDS
+    int units;              // its workgroups per frame: tiles, runs or strips
+    int image_words;        // LDS image of a unit's bits
+    int zero_iters;         // dense: passes of the run's lanes over that image to clear it
+    int tile_cols, tile_rows;
+    uint32_t luma_region, chroma_region; // tiles: LDS bytes of a wave's ring / staging region
+    uint32_t run_cap;       // worst-case bytes of one unit = one slot of the overflow arena
+    uint32_t slot_bytes;    // compact slot of a unit (what the LDS image can hold)
     uint32_t arena_slots;
     size_t arena_off;
-    int image_words;        // capacity of the dense kernel's LDS image in effect
-    bool reserve_worst;     // overflow arena sized for every run (m1v_reserve_scratch, or a forced tiny LDS image)
-    size_t scratch_bytes;   // per batch state
-    bool pipelined;         // layout + gather of batch k on `side` while batch k+1 encodes on the caller's stream
-    unsigned calls;
-    hipStream_t side;
-    bool fast_ok;      // geometry allows the 4-byte-aligned 24-byte row loads
-    int forced_mode;   // test hook (m1v_debug_set_input_mode): -1 = pick by geometry and alignment
-    // Which encode kernel serves a batch.  Tiles (k_encode_tiles, m1v_tiles.h): 3-channel pictures, any width and
-    // alignment — the default.  Runs (k_encode_dense / k_encode_strips): 4-channel pictures, and whatever the test
-    // hooks force (m1v_debug_set_path, a forced input mode, a forced run length).
-    int forced_path;   // -1 = by geometry, 0 = runs, 1 = tiles
-    int forced_T;      // run length forced by m1v_debug_set_dense_threads (0 = default)
-    bool tiles;        // the path configure_path set up
-    int tile_cols, tile_rows, tiles_per_frame, tile_ring;
-    uint32_t luma_region, chroma_region; // LDS bytes of a wave's ring / staging region
-    uint32_t *d_tile_order;  // tile-row processing order of the tile kernel (tile_row_order_for), [tile_rows]
-    int tile_order_rows;     // for how many tile rows d_tile_order was built
-    size_t meta_bytes, seg_bytes; // sizes of run_meta and seg in effect
+    size_t scratch_bytes, meta_bytes, seg_bytes; // per batch state (meta: run metadata, dense only)
     int segs;               // segments per strip: tile rows (tiles), or the most runs a strip can touch (run kernels)
-    Tables *d_tab;
+    int asm_group, asm_lanes_log2; // k_assemble: strips per workgroup, lanes per segment
+};
+
+struct m1v_encoder {
+    int device = 0;
+    Geometry g = {};
+    int qf = 0, mode = 0, max_frames = 0;
+    bool dense = false;     // blocks per strip >= 64: k_encode_dense, else one workgroup per strip
+    bool narrow = false;    // no AC level can reach +-128: one byte per staged level
+    bool fast_ok = false;   // geometry allows the 4-byte-aligned 24-byte row loads
+    // settings that plan_for reads (m1v_reserve_scratch, m1v_set_pipelined and the m1v_debug_set_* hooks change them)
+    int lds_words = 0;          // forced LDS image, 0 = default of the kernel in use
+    bool reserve_worst = false; // overflow arena sized for every run (m1v_reserve_scratch, or a forced tiny LDS image)
+    int forced_mode = -1;       // m1v_debug_set_input_mode: -1 = pick by geometry and alignment
+    int forced_path = -1;       // m1v_debug_set_path: -1 = by geometry, 0 = runs, 1 = tiles
+    int forced_T = 0;           // run length forced by m1v_debug_set_dense_threads (0 = default)
+    bool pipelined = false;     // layout + gather of batch k on `side` while batch k+1 encodes on the caller's stream
+    Plan plan = {};             // the plan configure_path set up
+    unsigned calls = 0;
+    hipStream_t side = nullptr;
+    uint32_t *d_tile_order = nullptr; // tile-row processing order of the tile kernel (tile_row_order_for), [tile_rows]
+    int tile_order_rows = 0;          // for how many tile rows d_tile_order was built
+    Tables *d_tab = nullptr;
     // Per-frame quality (frame_rq_t): Tables::rq_t of every quality [100][64]; the selection of the plain path (the encoder's
     // own quality, [max_frames]); the selection k_frame_quality writes; the budget call's probes ([kMaxCandidates][max_frames]
     // sizes, kMaxCandidates status words) and its choice when the caller does not want it
-    float *d_rq_all;
-    uint32_t *d_qsel_own, *d_qsel;
-    unsigned long long *d_probe_sizes;
-    uint32_t *d_probe_status;
-    uint8_t *d_chosen;
-    // What k_assemble needs to know about the output (configure_path): strips per workgroup, lanes per segment, LDS image
-    int asm_group, asm_lanes_log2, asm_img_words;
+    float *d_rq_all = nullptr;
+    uint32_t *d_qsel_own = nullptr, *d_qsel = nullptr;
+    unsigned long long *d_probe_sizes = nullptr;
+    uint32_t *d_probe_status = nullptr;
+    uint8_t *d_chosen = nullptr;
     // What an encode kernel adds to and k_assemble reads.  Two sets per Batch, taken in turns: the assemble kernel of call j clears
     // the set call j + 1 will add to (the one call j - 1 used), so no launch and no memset stands between two batches.
     struct Counters {
-        unsigned long long *strip_ctr;   // [frame][strip] bits of the strip (tile kernel: + arrivals << 40)
-        unsigned long long *frame_bytes; // [frame] bytes of the frame's strips
-        uint32_t *words;                 // [0] status bits of the encode kernel, [1] sink for callers without a status word, [2] arena counter
-        int dirty_frames;                // frames of the set's last batch that nobody has cleared yet
+        unsigned long long *strip_ctr = nullptr;   // [frame][strip] bits of the strip (tile kernel: + arrivals << 40)
+        unsigned long long *frame_bytes = nullptr; // [frame] bytes of the frame's strips
+        uint32_t *words = nullptr;                 // [0] status bits of the encode kernel, [1] sink for callers without a status word, [2] arena counter
+        int dirty_frames = 0;                      // frames of the set's last batch that nobody has cleared yet
     };
     // Everything one batch owns between its encode kernel and the end of its assembly.  Two sets, so that in
     // pipelined mode batch k+1 can encode while batch k is still being assembled.
     struct Batch {
-        uint8_t *scratch;
-        uint32_t *run_meta;     // run kernels: [frame][run][4]
-        uint2 *seg;             // [frame][segment][strip] (bits, where): what a strip is concatenated from
+        uint8_t *scratch = nullptr;
+        uint32_t *run_meta = nullptr; // run kernels: [frame][run][4]
+        uint2 *seg = nullptr;         // [frame][segment][strip] (bits, where): what a strip is concatenated from
+        size_t scratch_bytes = 0, meta_bytes = 0, seg_bytes = 0; // sizes of the three above
         Counters ctr[2];
-        unsigned turn;
-        hipEvent_t enc_done, gather_done;
-        bool gather_pending;
-        bool poisoned;          // a call that took a counter set returned an error: neither set is known to be clear
+        unsigned turn = 0;
+        hipEvent_t enc_done = nullptr, gather_done = nullptr;
+        bool gather_pending = false;
+        bool poisoned = false;        // a call that took a counter set returned an error: neither set is known to be clear
     } batch[2];
-    unsigned long long *d_stamps;
+    unsigned long long *d_stamps = nullptr;
     // device-side staging of the host-buffer entry points, kept between calls
     struct HostPath {
-        uint8_t *d_in, *d_out, *d_planes;
-        unsigned long long *d_meta;
-        size_t in_cap, out_cap, planes_cap, meta_cap;
-        hipStream_t copy_in, work; // upload stream; convert/encode/download stream
-        hipEvent_t uploaded[2];
+        uint8_t *d_in = nullptr, *d_out = nullptr, *d_planes = nullptr;
+        unsigned long long *d_meta = nullptr;
+        size_t in_cap = 0, out_cap = 0, planes_cap = 0, meta_cap = 0;
+        hipStream_t copy_in = nullptr, work = nullptr; // upload stream; convert/encode/download stream
+        hipEvent_t uploaded[2] = {};
     } hp;
     // profiling
-    bool prof;
+    bool prof = false;
     std::vector<hipEvent_t> ev;
-    size_t ev_used;
+    size_t ev_used = 0;
 };
 
-template <typename T>
-static hipError_t ensure_device(T **p, size_t *cap, size_t need) {
-    if (need <= *cap) return hipSuccess;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    hipError_t err = hipMalloc(p, need);
-    if (err == hipSuccess) *cap = need;
-    return err;
-}
-
-extern "C" {
-
-const char *m1v_last_error(void) { return g_err; }
-
-int m1v_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int m1v_warm_up(int device) {
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipFree(nullptr)); // creates the context
-    hipFuncAttributes attr;    // loads this library's code object for the device
-    HIP_TRY(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&k_assemble<false>)));
-    return M1V_OK;
-}
-
-size_t m1v_file_prolog(uint8_t out[27]) {
-    static const uint8_t pack[9] = {0x00, 0x00, 0x01, 0xba, 0x21, 0x00, 0x01, 0x00, 0x01};
-    memcpy(out, pack, 9);
-    uint32_t rate = (2202035u & 0x3fffffu) | 0x400000u; // mpeg1_enc.c:14-16
-    rate = (rate << 1) | 1u;
-    out[9] = (uint8_t)(rate >> 16); out[10] = (uint8_t)(rate >> 8); out[11] = (uint8_t)rate;
-    uint8_t *s = out + 12;                                 // mpeg1_enc.c:24-44, packet_num 0xe6
-    s[0] = 0; s[1] = 0; s[2] = 1; s[3] = 0xbb; s[4] = 0; s[5] = 9;
-    s[6] = (uint8_t)(rate >> 16); s[7] = (uint8_t)(rate >> 8); s[8] = (uint8_t)rate;
-    s[9] = 0; s[10] = 0x21; s[11] = 0xff; s[12] = 0xe0; s[13] = 0xe0; s[14] = 0xe6;
-    return 27;
-}
-
-// Chooses the encode kernel and its geometry and (re)allocates its scratch.  e->forced_T: run length of the run kernels
-// (0 = default: 256 blocks = 4 waves, one per SIMD, so that 5 workgroups of 96-VGPR waves share a CU; or the largest
-// multiple of 64 that the strip holds when it has fewer than 256 blocks).
-// New buffers are allocated FIRST and swapped in, together with the geometry they belong to, only when every allocation
-// has succeeded: a failed call (the worst-case arena of m1v_reserve_scratch is large) leaves the encoder as it was.
-#ifndef M1V_TILE_RING
-#define M1V_TILE_RING 2
-#endif
 // The order in which a frame's tile rows are processed.  Tile row R (macroblock rows 4R..4R+3) reads its luma from picture
 // rows [64R, 64R+64) and — the chroma quirk, encoder.h:347-348 — its chroma from rows [16R, 16R+16), i.e. from one quarter of
 // the luma region of tile row R/4.  Every byte of the top quarter of the picture is therefore read twice, once as luma and once
@@ -1728,582 +1602,108 @@ static void tile_row_order_for(int tile_rows, std::vector<uint32_t> &order) {
     order = Arrange{tile_rows, size}.run(0);
 }
 
-static int g_fail_alloc_in = 0; // test hook (m1v_debug_fail_alloc): the n-th allocation of configure_path from now fails
-static hipError_t plan_malloc(void **p, size_t bytes) {
-    if (g_fail_alloc_in > 0 && --g_fail_alloc_in == 0) return hipErrorOutOfMemory;
-    return hipMalloc(p, bytes);
-}
-static int g_fail_encode_at = 0; // test hook (m1v_debug_fail_encode): the stage at which the next encode returns M1V_E_HIP
-static int fail_encode_at(int stage) {
-    if (g_fail_encode_at != stage) return M1V_OK;
-    g_fail_encode_at = 0;
-    return fail(M1V_E_HIP, "injected failure (m1v_debug_fail_encode)%s");
-}
-static int configure_path(m1v_encoder *e) {
-    const int dense_T = e->forced_T;
-    const Geometry &g = e->g;
+// The plan of an encoder: a pure function of its geometry, its quality and its settings; M1V_E_ARG for settings that cannot
+// launch.  e.forced_T: run length of the run kernels (0 = default: 256 blocks = 4 waves, one per SIMD, so that 5 workgroups of
+// 96-VGPR waves share a CU; or the largest multiple of 64 that the strip holds when it has fewer than 256 blocks).
+static int plan_for(const m1v_encoder &e, Plan &out) {
+    const Geometry &g = e.g;
     const int bps = g.n_mbrows * 6;
-    struct {
-        bool tiles;
-        int tile_cols, tile_rows, tiles_per_frame, tile_ring;
-        uint32_t luma_region, chroma_region;
-        int dense_T, runs_per_frame;
-        uint32_t run_cap, slot_bytes, arena_slots;
-        size_t arena_off;
-        int image_words;
-    } plan = {};
+    const size_t stride = e.narrow ? kStageStride8 : kStageStride16;
+    Plan p = {};
     // Tiles for every 3-channel picture: 1.3-4x faster than the run kernel where that cannot use its aligned 24-byte row loads
     // (widths that are not a multiple of 8, buffers off a 4-byte boundary), 1 % faster at 4K (the order of the tile rows keeps
     // the chroma re-reads in L2, tile_row_order_for), and 0.5-1 % faster per step on aligned 1080p in a sustained run
     // (profiles/r03_ab_history.txt).  The run kernel serves 4-channel input and the m1v_debug_set_* hooks.
-    plan.tiles = g.C == 3 && e->forced_path != 0 && e->forced_mode < 0 && !(e->forced_path < 0 && dense_T > 0);
-    size_t need, meta = 0, segb = 0;
-    int segs = 0; // segments per strip
-    if (plan.tiles) {
-        plan.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
-        plan.tile_rows = (g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
-        plan.tiles_per_frame = plan.tile_cols * plan.tile_rows;
-        plan.tile_ring = M1V_TILE_RING;
-        const uint32_t stage = (uint32_t)(kWave * (e->narrow ? kStageStride8 : kStageStride16) * 4);
-        plan.luma_region = plan.chroma_region = (std::max<uint32_t>((uint32_t)plan.tile_ring * kTileSlot, stage) + 15u) & ~15u;
+    if (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0)) {
+        p.producer = Producer::tiles;
+        p.block = kTileThreads;
+        p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
+        p.tile_rows = (g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
+        p.units = p.tile_cols * p.tile_rows;
+        const uint32_t stage = (uint32_t)(kWave * stride * 4);
+        p.luma_region = p.chroma_region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, stage) + 15u) & ~15u;
         // worst case of a tile: 8 word-aligned segments of 24 blocks of <= 886 + 2 bits, 8 slice headers, slack
-        plan.run_cap = (uint32_t)(((((size_t)kTileThreads * (kMaxBlockBits + 2) + kTileStrips * (38 + 32) + 64 + 7) / 8) + 32 + 15) & ~(size_t)15);
+        p.run_cap = (uint32_t)(((((size_t)kTileThreads * (kMaxBlockBits + 2) + kTileStrips * (38 + 32) + 64 + 7) / 8) + 32 + 15) & ~(size_t)15);
         // LDS image of the tile's bits (192 blocks: ~115 words at quality 12 on noise), scaled with the quantiser like the
         // run kernels' (512 words per 256 blocks at quality <= 25) + the segments' word alignment and slice headers
-        plan.image_words = e->lds_words > 0 ? e->lds_words : (e->qf <= 25 ? 400 : (e->qf <= 50 ? 784 : (e->qf <= 76 ? 1552 : 3088)));
-        plan.image_words = (plan.image_words + 3) & ~3; // cleared 16 bytes per lane
-        // (the same budget m1v_encode_device checks before each launch: an image that cannot launch is refused here)
-        if ((size_t)kTileFixedWords * 4 + 2 * (size_t)plan.luma_region + plan.chroma_region + (size_t)plan.image_words * 4 > 160 * 1024)
-            return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
-        plan.slot_bytes = (uint32_t)((((size_t)plan.image_words * 4 + 127) & ~(size_t)127) | 128);
-        const size_t runs = (size_t)e->max_frames * plan.tiles_per_frame;
-        plan.arena_slots = (uint32_t)(e->reserve_worst ? runs : (runs / 256 > 32 ? runs / 256 : (runs < 32 ? runs : 32)));
-        plan.arena_off = runs * plan.slot_bytes;
-        need = plan.arena_off + (size_t)plan.arena_slots * plan.run_cap;
-        if ((need >> 2) >= (1ull << 32)) return fail(M1V_E_ARG, "scratch beyond 16 GiB: lower max_frames%s");
-        segs = plan.tile_rows;
-    } else if (e->dense) {
-        int T = dense_T > 0 ? dense_T : (bps >= 256 ? 256 : (bps / kWave) * kWave);
+        p.image_words = e.lds_words > 0 ? e.lds_words : (e.qf <= 25 ? 400 : (e.qf <= 50 ? 784 : (e.qf <= 76 ? 1552 : 3088)));
+        p.image_words = (p.image_words + 3) & ~3; // cleared 16 bytes per lane
+        p.lds_bytes = (size_t)kTileFixedWords * 4 + 2 * (size_t)p.luma_region + p.chroma_region + (size_t)p.image_words * 4;
+        p.segs = p.tile_rows;
+    } else if (e.dense) {
+        const int T = e.forced_T > 0 ? e.forced_T : (bps >= 256 ? 256 : (bps / kWave) * kWave);
         if (T < kWave || T > 384 || T % kWave || T > bps) return fail(M1V_E_ARG, "bad dense run length%s");
-        plan.dense_T = T;
-        int nb = g.n_strips * bps;
-        plan.runs_per_frame = (nb + T - 1) / T;
+        p.producer = Producer::dense;
+        p.block = T;
+        p.units = (g.n_strips * bps + T - 1) / T;
         // worst case of a run: two word-aligned segments of at most T blocks of <= 886 + 2 bits, two slice headers, slack
-        plan.run_cap = (uint32_t)(((((size_t)T * (kMaxBlockBits + 2) + 2 * 38 + 3 * 32 + 7) / 8) + 32 + 15) & ~(size_t)15);
+        p.run_cap = (uint32_t)(((((size_t)T * (kMaxBlockBits + 2) + 2 * 38 + 3 * 32 + 7) / 8) + 32 + 15) & ~(size_t)15);
         // LDS image of the run's bits: zeroing it costs time, outgrowing it the slow global-atomics path.  A run of 256
         // blocks needs ~150 words at quality 12 on noise; scale the default with the quantiser (finer quantisers emit
         // more bits per block).  The compact scratch slot of a run is exactly that image.
-        plan.image_words = e->lds_words > 0 ? e->lds_words : (e->qf <= 25 ? 512 : (e->qf <= 50 ? 1024 : (e->qf <= 76 ? 2048 : 4096)));
-        {
-            const size_t zero_iters = ((size_t)plan.image_words + T - 1) / T, stride = e->narrow ? kStageStride8 : kStageStride16;
-            if (((size_t)(T / kWave) * kVlcWords + 32 + stride * T + zero_iters * T) * 4 > 160 * 1024)
-                return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
-        }
+        p.image_words = e.lds_words > 0 ? e.lds_words : (e.qf <= 25 ? 512 : (e.qf <= 50 ? 1024 : (e.qf <= 76 ? 2048 : 4096)));
+        const size_t zero_iters = ((size_t)p.image_words + T - 1) / T;
+        p.zero_iters = (int)zero_iters; // (small whenever the LDS check below passes)
+        p.lds_bytes = ((size_t)(T / kWave) * kVlcWords + 32 + stride * T + zero_iters * T) * 4;
+        p.meta_bytes = (size_t)e.max_frames * p.units * 4 * sizeof(uint32_t);
+        p.segs = (bps + T - 1) / T + 1; // the most runs whose blocks one strip can hold
+    } else {
+        p.producer = Producer::strips;
+        p.block = kWave;
+        p.units = g.n_strips;
+        p.image_words = e.lds_words > 0 ? e.lds_words : kDefaultLdsWords;
+        p.lds_bytes = ((size_t)kVlcWords + 32 + (size_t)kStageStride16 * kWave + (size_t)p.image_words) * 4;
+        p.scratch_bytes = (size_t)e.max_frames * g.n_strips * g.strip_cap;
+        p.segs = 1; // a strip is one piece
+    }
+    if (p.lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
+    if (p.producer != Producer::strips) {
+        // Scratch: one compact slot per unit + an overflow arena of worst-case slots for the units whose image outgrows LDS
+        // (handed out by an atomic counter).  By default the arena holds 1/256 of the units (quality 12 noise needs none);
+        // m1v_reserve_scratch(enc, 1) sizes it for all of them — what every run had in round 1, 47x the payload.
         // + 128: an odd number of 128-byte lines, so that the slots (of which only the first third is written at quality
         // 12) do not all start on the same few memory channels (a power-of-two stride measured 3 % slower)
-        plan.slot_bytes = (uint32_t)((((size_t)plan.image_words * 4 + 127) & ~(size_t)127) | 128);
-        // Scratch: one compact slot per run + an overflow arena of worst-case slots for the runs whose image outgrows LDS
-        // (handed out by an atomic counter).  By default the arena holds 1/256 of the runs (quality 12 noise needs none);
-        // m1v_reserve_scratch(enc, 1) sizes it for all of them — what every run had in round 1, 47x the payload.
-        const size_t runs = (size_t)e->max_frames * plan.runs_per_frame;
-        plan.arena_slots = (uint32_t)(e->reserve_worst ? runs : (runs / 256 > 32 ? runs / 256 : (runs < 32 ? runs : 32)));
-        plan.arena_off = runs * plan.slot_bytes;
-        need = plan.arena_off + (size_t)plan.arena_slots * plan.run_cap;
-        if ((need >> 2) >= (1ull << 32)) return fail(M1V_E_ARG, "scratch beyond 16 GiB: lower max_frames%s");
-        meta = runs * 4 * sizeof(uint32_t);
-        segs = (bps + T - 1) / T + 1; // the most runs whose blocks one strip can hold
-    } else {
-        need = (size_t)e->max_frames * g.n_strips * g.strip_cap;
-        if ((need >> 2) >= (1ull << 32)) return fail(M1V_E_ARG, "scratch beyond 16 GiB: lower max_frames%s");
-        segs = 1; // a strip is one piece
+        const size_t units = (size_t)e.max_frames * p.units;
+        p.slot_bytes = (uint32_t)((((size_t)p.image_words * 4 + 127) & ~(size_t)127) | 128);
+        p.arena_slots = (uint32_t)(e.reserve_worst ? units : (units / 256 > 32 ? units / 256 : (units < 32 ? units : 32)));
+        p.arena_off = units * p.slot_bytes;
+        p.scratch_bytes = p.arena_off + (size_t)p.arena_slots * p.run_cap;
     }
+    if ((p.scratch_bytes >> 2) >= (1ull << 32)) return fail(M1V_E_ARG, "scratch beyond 16 GiB: lower max_frames%s");
+    p.seg_bytes = (size_t)e.max_frames * g.n_strips * p.segs * sizeof(uint2);
     // k_assemble (m1v_assemble.h): strips per workgroup so that a group's bytes fit its 14-KiB LDS image (eight workgroups per CU) in one pass on noise at
     // this quality (19 bits per block at quality 12; anything larger takes more passes), a power of two (the eight
     // strips of a tile column share their scratch lines); lanes per segment (four words each) ~ the words a segment holds.
-    int asm_group, asm_lanes_log2;
-    {
-        const int qscale = e->qf <= 25 ? 1 : (e->qf <= 50 ? 2 : (e->qf <= 76 ? 4 : 8));
-        const size_t bpb = 22u * (size_t)qscale;
-        const size_t strip_est = (38 + (size_t)g.n_mbrows * (2 + 6 * bpb)) / 8 + 1;
-        asm_group = 1;
-        while (asm_group < kAsmMaxGroup && (size_t)(2 * asm_group) * strip_est * 5 / 4 <= kAsmImageBytes && 2 * asm_group <= g.n_strips) asm_group *= 2;
-        const size_t seg_blocks = plan.tiles ? (size_t)kTileSegBlocks : (e->dense ? (size_t)plan.dense_T : (size_t)bps);
-        const size_t seg_words = seg_blocks * bpb / 32;
-        asm_lanes_log2 = 1; // four words per lane: enough lanes for 1.6 x the expected words, at most one DPP row
-        while (asm_lanes_log2 < 4 && ((size_t)4 << asm_lanes_log2) * 5 < seg_words * 8) asm_lanes_log2++;
-    }
-    const int sets = e->pipelined ? 2 : 1;
-    segb = (size_t)e->max_frames * g.n_strips * segs * sizeof(uint2);
-    // ---- allocate EVERYTHING the new plan needs first (every device allocation through plan_malloc: the fault-injection hook
-    //      reaches all of them); nothing of the encoder is touched until all of it is there ----
-    struct Fresh {
-        uint8_t *scratch;
-        void *meta, *seg;
-        bool new_scratch, new_meta, new_seg, new_fixed;
-        m1v_encoder::Counters ctr[2];
-        hipEvent_t enc_done, gather_done;
-    } fresh[2] = {};
-    uint32_t *fresh_order = nullptr;
-    const bool new_order = plan.tiles && e->tile_order_rows != plan.tile_rows;
-    const size_t nslots = (size_t)e->max_frames * g.n_strips;
-    bool ok = true;
-    for (int i = 0; i < sets && ok; i++) {
-        const m1v_encoder::Batch &bt = e->batch[i];
-        Fresh &f = fresh[i];
-        f.new_scratch = need != e->scratch_bytes || !bt.scratch;
-        f.new_meta = meta != 0 && (meta != e->meta_bytes || !bt.run_meta);
-        f.new_seg = segb != 0 && (segb != e->seg_bytes || !bt.seg);
-        f.new_fixed = !bt.enc_done;
-        if (f.new_scratch) ok = plan_malloc((void **)&f.scratch, need) == hipSuccess;
-        if (ok && f.new_meta) ok = plan_malloc(&f.meta, meta) == hipSuccess;
-        if (ok && f.new_seg) ok = plan_malloc(&f.seg, segb) == hipSuccess;
-        if (ok && f.new_fixed) {
-            for (m1v_encoder::Counters &c : f.ctr) {
-                ok = ok && plan_malloc((void **)&c.strip_ctr, nslots * 8) == hipSuccess && hipMemset(c.strip_ctr, 0, nslots * 8) == hipSuccess;
-                ok = ok && plan_malloc((void **)&c.frame_bytes, (size_t)e->max_frames * 8) == hipSuccess &&
-                     hipMemset(c.frame_bytes, 0, (size_t)e->max_frames * 8) == hipSuccess;
-                ok = ok && plan_malloc((void **)&c.words, 4 * sizeof(uint32_t)) == hipSuccess && hipMemset(c.words, 0, 4 * sizeof(uint32_t)) == hipSuccess;
-                c.dirty_frames = 0;
-            }
-            ok = ok && hipEventCreateWithFlags(&f.gather_done, hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&f.enc_done, hipEventDisableTiming) == hipSuccess;
-        }
-    }
-    if (ok && new_order) {
-        std::vector<uint32_t> order;
-        tile_row_order_for(plan.tile_rows, order);
-        ok = plan_malloc((void **)&fresh_order, order.size() * sizeof(uint32_t)) == hipSuccess &&
-             hipMemcpy(fresh_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) {
-        for (Fresh &f : fresh) {
-            (void)hipFree(f.scratch);
-            (void)hipFree(f.meta);
-            (void)hipFree(f.seg);
-            for (m1v_encoder::Counters &c : f.ctr) {
-                (void)hipFree(c.strip_ctr);
-                (void)hipFree(c.frame_bytes);
-                (void)hipFree(c.words);
-            }
-            if (f.enc_done) (void)hipEventDestroy(f.enc_done);
-            if (f.gather_done) (void)hipEventDestroy(f.gather_done);
-        }
-        (void)hipFree(fresh_order);
-        (void)hipGetLastError();
-        return fail(M1V_E_HIP, "allocation failed (the encoder keeps its previous configuration)%s");
-    }
-    // ---- commit ----
-    for (int i = 0; i < sets; i++) {
-        m1v_encoder::Batch &bt = e->batch[i];
-        Fresh &f = fresh[i];
-        if (f.new_scratch) {
-            (void)hipFree(bt.scratch);
-            bt.scratch = f.scratch;
-        }
-        if (f.new_meta) {
-            (void)hipFree(bt.run_meta);
-            bt.run_meta = (uint32_t *)f.meta;
-        }
-        if (f.new_seg) {
-            (void)hipFree(bt.seg);
-            bt.seg = (uint2 *)f.seg;
-        }
-        if (f.new_fixed) {
-            bt.ctr[0] = f.ctr[0];
-            bt.ctr[1] = f.ctr[1];
-            bt.turn = 0;
-            bt.poisoned = false;
-            bt.enc_done = f.enc_done;
-            bt.gather_done = f.gather_done;
-        }
-    }
-    if (new_order) {
-        (void)hipFree(e->d_tile_order);
-        e->d_tile_order = fresh_order;
-        e->tile_order_rows = plan.tile_rows;
-    }
-    e->tiles = plan.tiles;
-    e->tile_cols = plan.tile_cols; e->tile_rows = plan.tile_rows; e->tiles_per_frame = plan.tiles_per_frame;
-    e->tile_ring = plan.tile_ring;
-    e->luma_region = plan.luma_region; e->chroma_region = plan.chroma_region;
-    e->dense_T = plan.dense_T; e->runs_per_frame = plan.runs_per_frame;
-    e->run_cap = plan.run_cap; e->image_words = plan.image_words; e->slot_bytes = plan.slot_bytes;
-    e->arena_slots = plan.arena_slots; e->arena_off = plan.arena_off;
-    e->scratch_bytes = need;
-    e->meta_bytes = meta ? meta : e->meta_bytes; // (a path without run metadata keeps the other path's array and its size)
-    e->seg_bytes = segb ? segb : e->seg_bytes;
-    e->segs = segs;
-    e->asm_group = asm_group;
-    e->asm_lanes_log2 = asm_lanes_log2;
-    e->asm_img_words = kAsmImageBytes / 4;
+    const int qscale = e.qf <= 25 ? 1 : (e.qf <= 50 ? 2 : (e.qf <= 76 ? 4 : 8));
+    const size_t bpb = 22u * (size_t)qscale;
+    const size_t strip_est = (38 + (size_t)g.n_mbrows * (2 + 6 * bpb)) / 8 + 1;
+    p.asm_group = 1;
+    while (p.asm_group < kAsmMaxGroup && (size_t)(2 * p.asm_group) * strip_est * 5 / 4 <= kAsmImageBytes && 2 * p.asm_group <= g.n_strips) p.asm_group *= 2;
+    const size_t seg_blocks = p.producer == Producer::tiles ? (size_t)kTileSegBlocks : (size_t)(p.producer == Producer::dense ? p.block : bps);
+    const size_t seg_words = seg_blocks * bpb / 32;
+    p.asm_lanes_log2 = 1; // four words per lane: enough lanes for 1.6 x the expected words, at most one DPP row
+    while (p.asm_lanes_log2 < 4 && ((size_t)4 << p.asm_lanes_log2) * 5 < seg_words * 8) p.asm_lanes_log2++;
+    out = p;
     return M1V_OK;
 }
 
-int m1v_create(m1v_encoder **out, int device, int width, int height, int channels,
-               int quality_factor, int mode, int max_frames) {
-    if (!out) return fail(M1V_E_ARG, "null out%s");
-    *out = nullptr;
-    if (width <= 0 || height <= 0 || channels < 3 || channels > 4 || max_frames <= 0)
-        return fail(M1V_E_ARG, "bad geometry%s");
-    if (mode != M1V_MODE_STRICT && mode != M1V_MODE_FULL) return fail(M1V_E_ARG, "bad mode%s");
-    int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96;
-    int ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
-    if (xe > width || ye > height)
-        return fail(M1V_E_ARG, "picture smaller than the 96x144 region the reference encodes%s");
-    if (xe == 0 || ye == 0) return fail(M1V_E_ARG, "picture smaller than one macroblock%s");
-    if ((unsigned long long)width * height * channels >= (1ull << 32))
-        return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
-    int n = m1v_device_count();
-    if (n <= 0) return fail(M1V_E_NODEVICE, "no HIP device%s");
-    if (device < 0 || device >= n) return fail(M1V_E_ARG, "device index out of range%s");
-    HIP_TRY(hipSetDevice(device));
+// Every instantiation of the producer kernels, [producer][input mode][narrow staging]: the launch picks from it (producer_kernel)
+// and m1v_create raises the dynamic LDS limit of each.  Input modes of the pixel loads (load_block_rows): 1 = aligned rows, 2 = any
+// row offset in an aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The tile kernel takes any input in
+// one mode; the strip kernel has modes 0 and 1 and stages every level wide.
+static const void *const kProducerKernels[3][4][2] = {
+    {{(const void *)&k_encode_tiles<false, M1V_TILE_RING>, (const void *)&k_encode_tiles<true, M1V_TILE_RING>}},
+    {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
+     {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
+     {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
+     {(const void *)&k_encode_dense<3, false>, (const void *)&k_encode_dense<3, true>}},
+    {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
+     {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
 
-    m1v_encoder *e = new m1v_encoder();
-    e->device = device;
-    e->qf = quality_factor;
-    e->mode = mode;
-    e->max_frames = max_frames;
-    Geometry &g = e->g;
-    g.W = width; g.H = height; g.C = channels;
-    g.n_strips = xe / 16; g.n_mbrows = ye / 16;
-    g.half_w = width / 2;
-    g.frame_bytes = (unsigned long long)width * height * channels;
-    unsigned long long strip_bits = 38ull + (unsigned long long)g.n_mbrows * (2 + 6 * kMaxBlockBits);
-    g.strip_cap = (uint32_t)((((strip_bits + 7) / 8) + 16 + 15) & ~15ull);
-    int bps = g.n_mbrows * 6;
-    e->threads = kWave;               // strip-per-workgroup kernel: only used when bps < 64
-    e->lds_words = 0;                 // 0 = default of the kernel in use
-    e->dense = bps >= kWave;
-    e->dense_T = 0;
-    e->scratch_bytes = 0;
-    e->reserve_worst = false;
-    e->pipelined = false;
-    e->calls = 0;
-    e->side = nullptr;
-    memset(e->batch, 0, sizeof e->batch);
-    memset(&e->hp, 0, sizeof e->hp);
-    e->fast_ok = channels == 3 && (width % 8) == 0;
-    e->forced_mode = -1;
-    e->forced_path = -1;
-    e->forced_T = 0;
-    e->tiles = false;
-    e->tile_cols = e->tile_rows = e->tiles_per_frame = e->tile_ring = 0;
-    e->luma_region = e->chroma_region = 0;
-    e->meta_bytes = e->seg_bytes = 0;
-    e->segs = 0;
-    e->d_tile_order = nullptr;
-    e->tile_order_rows = 0;
-    e->runs_per_frame = 0;
-    e->run_cap = e->slot_bytes = e->arena_slots = 0;
-    e->arena_off = 0;
-    e->image_words = 0;
-    e->prof = false;
-    e->ev_used = 0;
-    e->d_stamps = nullptr;
-    e->d_rq_all = nullptr;
-    e->d_qsel_own = e->d_qsel = nullptr;
-    e->d_probe_sizes = nullptr;
-    e->d_probe_status = nullptr;
-    e->d_chosen = nullptr;
-
-    Tables *t = new Tables();
-    int q[64];
-    scaled_matrix(quality_factor, q);
-    for (int k = 0; k < 64; k++) t->rq[k] = (float)((1.0 / q[k]) * (1.0 + 1.0 / 1048576.0));
-    for (int u = 0; u < 8; u++)
-        for (int i = 0; i < 8; i++) t->rq_t[i * 8 + u] = t->rq[u * 8 + i];
-    // One byte per staged level is exact iff no AC level can reach +-128.  |AC coefficient| of the
-    // reference's FDCT on u8 pixels is at most 1022 (127.5 * 8 + the +2 rounding bias, reached at (0,4), (4,0),
-    // (4,4); tests/test_host_tables.py::test_fdct_output_range), so 128 * (smallest AC divisor) >= 1024
-    // suffices: quality factors <= 76.
-    int min_ac = q[1];
-    for (int k = 1; k < 64; k++) min_ac = q[k] < min_ac ? q[k] : min_ac;
-    e->narrow = min_ac >= 8;
-    build_vlc_table(t->vlc);
-    for (int h = 0; h < 256; h++) build_frame_header(t->hdr[h], width, height, h);
-
-    hipError_t err = hipMalloc(&e->d_tab, sizeof(Tables));
-    if (err == hipSuccess) err = hipMemcpy(e->d_tab, t, sizeof(Tables), hipMemcpyHostToDevice);
-    {
-        // per-frame quality: the transposed reciprocal table of every quality, built as Tables::rq_t is
-        std::vector<float> all(100 * 64);
-        for (int qf = 1; qf <= 100; qf++) {
-            int qq[64];
-            scaled_matrix(qf, qq);
-            for (int u = 0; u < 8; u++)
-                for (int i = 0; i < 8; i++)
-                    all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)((1.0 / qq[u * 8 + i]) * (1.0 + 1.0 / 1048576.0));
-        }
-        const int own = std::min(std::max(quality_factor, 1), 100);
-        if (memcmp(&all[(size_t)(own - 1) * 64], t->rq_t, sizeof t->rq_t) != 0) err = hipErrorUnknown; // (cannot happen)
-        const std::vector<uint32_t> sel((size_t)max_frames, (uint32_t)(own - 1) * 64u);
-        if (err == hipSuccess) err = hipMalloc(&e->d_rq_all, all.size() * sizeof(float));
-        if (err == hipSuccess) err = hipMemcpy(e->d_rq_all, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMalloc(&e->d_qsel_own, sel.size() * sizeof(uint32_t));
-        if (err == hipSuccess) err = hipMemcpy(e->d_qsel_own, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMalloc(&e->d_qsel, sel.size() * sizeof(uint32_t));
-        if (err == hipSuccess) err = hipMemcpy(e->d_qsel, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
-        if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
-        if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
-    }
-    delete t;
-#if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
-    if (err == hipSuccess) err = hipMalloc(&e->d_stamps, (32 + 8 * 65536) * 8); // [32] phase sums, then a timeline of 8 stamps per workgroup
-    if (err == hipSuccess) err = hipMemset(e->d_stamps, 0, (32 + 8 * 65536) * 8);
-#endif
-    if (err == hipSuccess) err = configure_path(e) == M1V_OK ? hipSuccess : hipErrorOutOfMemory;
-    const void *kernels[] = {(const void *)&k_encode_dense<1, true>, (const void *)&k_encode_dense<1, false>,
-                             (const void *)&k_encode_dense<2, true>, (const void *)&k_encode_dense<2, false>,
-                             (const void *)&k_encode_dense<3, true>, (const void *)&k_encode_dense<3, false>,
-                             (const void *)&k_encode_dense<0, true>, (const void *)&k_encode_dense<0, false>,
-                             (const void *)&k_encode_strips<true>,       (const void *)&k_encode_strips<false>,
-                             (const void *)&k_encode_tiles<true, M1V_TILE_RING>, (const void *)&k_encode_tiles<false, M1V_TILE_RING>};
-    for (const void *kf : kernels)
-        if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) {
-        fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
-        m1v_destroy(e);
-        return M1V_E_HIP;
-    }
-    *out = e;
-    return M1V_OK;
-}
-
-void m1v_destroy(m1v_encoder *e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
-    (void)hipFree(e->d_tab);
-    (void)hipFree(e->d_rq_all);
-    (void)hipFree(e->d_qsel_own);
-    (void)hipFree(e->d_qsel);
-    (void)hipFree(e->d_probe_sizes);
-    (void)hipFree(e->d_probe_status);
-    (void)hipFree(e->d_chosen);
-    for (m1v_encoder::Batch &bt : e->batch) {
-        (void)hipFree(bt.scratch);
-        (void)hipFree(bt.run_meta);
-        (void)hipFree(bt.seg);
-        for (m1v_encoder::Counters &c : bt.ctr) {
-            (void)hipFree(c.strip_ctr);
-            (void)hipFree(c.frame_bytes);
-            (void)hipFree(c.words);
-        }
-        if (bt.enc_done) (void)hipEventDestroy(bt.enc_done);
-        if (bt.gather_done) (void)hipEventDestroy(bt.gather_done);
-    }
-    if (e->side) (void)hipStreamDestroy(e->side);
-    (void)hipFree(e->hp.d_in);
-    (void)hipFree(e->hp.d_out);
-    (void)hipFree(e->hp.d_planes);
-    (void)hipFree(e->hp.d_meta);
-    if (e->hp.copy_in) (void)hipStreamDestroy(e->hp.copy_in);
-    if (e->hp.work) (void)hipStreamDestroy(e->hp.work);
-    for (hipEvent_t ev : e->hp.uploaded)
-        if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(e->d_stamps);
-    (void)hipFree(e->d_tile_order);
-    delete e;
-}
-
-int m1v_strips(const m1v_encoder *e) { return e ? e->g.n_strips : 0; }
-int m1v_mb_rows(const m1v_encoder *e) { return e ? e->g.n_mbrows : 0; }
-size_t m1v_frame_bytes_in(const m1v_encoder *e) { return e ? (size_t)e->g.frame_bytes : 0; }
-
-size_t m1v_frame_bound_for(int width, int height, int mode) {
-    const int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96, ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
-    if (width <= 0 || height <= 0 || xe <= 0 || ye <= 0 || xe > width || ye > height) return 0;
-    const size_t strip_bits = 38 + (size_t)(ye / 16) * (2 + 6 * kMaxBlockBits);
-    return 44 + (size_t)(xe / 16) * ((strip_bits + 7) / 8) + 4;
-}
-
-size_t m1v_frame_bound(const m1v_encoder *e) {
-    if (!e) return 0;
-    size_t strip_bits = 38 + (size_t)e->g.n_mbrows * (2 + 6 * kMaxBlockBits);
-    return 44 + (size_t)e->g.n_strips * ((strip_bits + 7) / 8) + 4;
-}
-
-int m1v_debug_set_lds_words(m1v_encoder *e, int words) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    const int before = e->lds_words;
-    e->lds_words = words > 0 ? (words < 4 ? 4 : words) : 0;
-    if (!e->dense && !e->tiles) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int rc = configure_path(e); // (a small forced image sends many runs to the overflow arena: M1V_STATUS_SCRATCH)
-    if (rc != M1V_OK) e->lds_words = before;
-    return rc;
-}
-
-int m1v_reserve_scratch(m1v_encoder *e, int worst_case) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (!e->dense && !e->tiles) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const bool before = e->reserve_worst;
-    e->reserve_worst = worst_case != 0;
-    const int rc = configure_path(e);
-    if (rc != M1V_OK) e->reserve_worst = before; // the previous arena is still in place
-    return rc;
-}
-
-size_t m1v_scratch_bytes(const m1v_encoder *e) { return e ? e->scratch_bytes * (e->pipelined ? 2 : 1) : 0; }
-
-int m1v_set_pipelined(m1v_encoder *e, int enable) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    for (m1v_encoder::Batch &bt : e->batch) bt.gather_pending = false;
-    const bool before = e->pipelined;
-    e->pipelined = enable != 0;
-    e->calls = 0;
-    if (e->pipelined && !e->side) {
-        // highest priority: the few memory-bound workgroups of layout + gather should take the first slots the (much longer,
-        // arithmetic-bound) encode kernel of the next batch frees, not queue behind its whole grid
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, greatest));
-    }
-    const int rc = configure_path(e);
-    if (rc != M1V_OK) e->pipelined = before; // the second set of buffers could not be allocated: stay as we were
-    return rc;
-}
-
-int m1v_flush(m1v_encoder *e, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    HIP_TRY(hipSetDevice(e->device));
-    // The mark stays set: a later m1v_encode_device on ANOTHER stream must still wait for this set's gather before its
-    // encode kernel overwrites the scratch (waiting for an event that has completed costs nothing).
-    for (m1v_encoder::Batch &bt : e->batch) {
-        if (e->pipelined && bt.poisoned) { // a failed call may have left an assembly on the internal stream without its event
-            HIP_TRY(hipEventRecord(bt.gather_done, e->side));
-            bt.gather_pending = true;
-        }
-        if (bt.gather_pending) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, bt.gather_done, 0));
-    }
-    return M1V_OK;
-}
-
-int m1v_debug_set_input_mode(m1v_encoder *e, int mode) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (mode != -1 && mode != 0 && mode != 2) return fail(M1V_E_ARG, "input mode must be -1 (auto), 0 (byte loads) or 2 (funnel)%s");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int before = e->forced_mode;
-    e->forced_mode = mode; // an input mode is a property of the run kernels: forcing one selects them
-    const int rc = configure_path(e);
-    if (rc != M1V_OK) e->forced_mode = before;
-    return rc;
-}
-
-int m1v_debug_set_dense_threads(m1v_encoder *e, int threads) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (!e->dense) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int before = e->forced_T;
-    e->forced_T = threads > 0 ? threads : 0; // a run length is a property of the run kernels: forcing one selects them
-    const int rc = configure_path(e);
-    if (rc != M1V_OK) e->forced_T = before;
-    return rc;
-}
-
-int m1v_debug_set_path(m1v_encoder *e, int path) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (path < -1 || path > 1) return fail(M1V_E_ARG, "path must be -1 (by geometry), 0 (runs) or 1 (tiles)%s");
-    if (path == 1 && e->g.C != 3) return fail(M1V_E_ARG, "the tile kernel takes 3-channel pictures%s");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int before = e->forced_path;
-    e->forced_path = path;
-    const int rc = configure_path(e);
-    if (rc != M1V_OK) e->forced_path = before;
-    return rc;
-}
-
-int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->tiles ? 1 : 0) : -1; }
-
-void m1v_debug_fail_alloc(int nth) {
-    // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
-    const char *on = getenv("EC504_DEBUG_HOOKS");
-    g_fail_alloc_in = (on && on[0] == '1' && nth > 0) ? nth : 0;
-}
-
-void m1v_debug_fail_encode(int stage) {
-    // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
-    const char *on = getenv("EC504_DEBUG_HOOKS");
-    g_fail_encode_at = (on && on[0] == '1' && stage >= 1 && stage <= 3) ? stage : 0;
-}
-
-#if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
-// diagnostic builds only: read and clear the per-phase cycle sums
-int m1v_debug_read_stamps(m1v_encoder *e, unsigned long long out[32]) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, e->d_stamps, 32 * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(e->d_stamps, 0, 32 * 8));
-    return M1V_OK;
-}
-// diagnostic builds only: the per-workgroup timeline of the last k_assemble launch (8 stamps each)
-int m1v_debug_read_timeline(m1v_encoder *e, unsigned long long *out, int workgroups) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, e->d_stamps + 32, (size_t)(workgroups > 65536 ? 65536 : workgroups) * 64, hipMemcpyDeviceToHost));
-    return M1V_OK;
-}
-#endif
-
-int m1v_profile_enable(m1v_encoder *e, int enable) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    e->prof = enable != 0;
-    e->ev_used = 0;
-    return M1V_OK;
-}
-
-int m1v_profile_read(m1v_encoder *e, int *launches, double *total_ms) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    HIP_TRY(hipSetDevice(e->device));
-    double sum = 0;
-    int n = 0;
-    for (size_t i = 0; i + 1 < e->ev_used; i += 2) {
-        HIP_TRY(hipEventSynchronize(e->ev[i + 1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ev[i], e->ev[i + 1]));
-        sum += ms;
-        n++;
-    }
-    e->ev_used = 0;
-    if (launches) *launches = n;
-    if (total_ms) *total_ms = sum;
-    return M1V_OK;
-}
-
-int m1v_profile_read_times(m1v_encoder *e, float *ms, int cap, int *launches) {
-    if (!e || (cap > 0 && !ms)) return fail(M1V_E_ARG, "bad argument%s");
-    HIP_TRY(hipSetDevice(e->device));
-    int n = 0;
-    for (size_t i = 0; i + 1 < e->ev_used; i += 2) {
-        HIP_TRY(hipEventSynchronize(e->ev[i + 1]));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, e->ev[i], e->ev[i + 1]));
-        if (n < cap) ms[n] = t;
-        n++;
-    }
-    e->ev_used = 0;
-    if (launches) *launches = n;
-    return M1V_OK;
-}
-
-static int profile_event(m1v_encoder *e, hipStream_t st) {
-    if (e->ev_used == e->ev.size()) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        e->ev.push_back(ev);
-    }
-    HIP_TRY(hipEventRecord(e->ev[e->ev_used++], st));
-    return M1V_OK;
-}
+// defined in m1v_runtime.h
+static int profile_event(m1v_encoder *e, hipStream_t st);
+static int fail_encode_at(int stage);
+static hipError_t counters_clear(const m1v_encoder *e, m1v_encoder::Counters &c, hipStream_t st);
 
 static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
     return e->fast_ok && ((uintptr_t)d_rgb & 3) == 0;
@@ -2311,7 +1711,55 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 
 static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
 
-// One batch through the encode kernel of the encoder's path.  qa == null: every frame at the encoder's own quality (the plain
+static const void *producer_kernel(const m1v_encoder *e, const uint8_t *d_rgb) {
+    const bool aligned4 = ((uintptr_t)d_rgb & 3) == 0, fast = fast_path(e, d_rgb);
+    int mode = 0;
+    if (e->plan.producer == Producer::strips) {
+        mode = fast ? 1 : 0;
+    } else if (e->plan.producer == Producer::dense) {
+        mode = fast ? 1 : (aligned4 && e->g.C == 3 ? 2 : (aligned4 && e->g.C == 4 ? 3 : 0));
+        if (e->forced_mode == 0 || (e->forced_mode == 2 && mode == 1)) mode = e->forced_mode; // only modes that are valid here
+    }
+    return kProducerKernels[(int)e->plan.producer][mode][e->narrow ? 1 : 0];
+}
+
+// The plan's producer kernel over n_frames, with profile events around it; in pipelined mode the layout + gather stream gs
+// then waits for it.
+template <typename Args>
+static int launch_producer(m1v_encoder *e, m1v_encoder::Batch &bt, const void *kernel, int n_frames, Args &a, hipStream_t st,
+                           hipStream_t gs) {
+    const Plan &p = e->plan;
+    void *args[] = {&a};
+    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((size_t)n_frames * p.units)), dim3((unsigned)p.block), args, p.lds_bytes, st);
+    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
+    HIP_TRY(hipGetLastError());
+    if (e->pipelined) {
+        HIP_TRY(hipEventRecord(bt.enc_done, st));
+        HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
+    }
+    return M1V_OK;
+}
+
+// The counter hand-over of a batch's last kernel (k_assemble or k_frame_sizes): it clears the first next_frames frames of the set
+// the next batch on this Batch adds to.  What a longer batch than this one left there beyond n_frames is cleared here, on gs.
+template <typename Args>
+static int hand_over(Args &a, m1v_encoder::Counters &cur, m1v_encoder::Counters &nxt, int n_frames, int n_strips, hipStream_t gs) {
+    a.next_strip_ctr = nxt.strip_ctr;
+    a.next_frame_bytes = nxt.frame_bytes;
+    a.next_words = nxt.words;
+    if (nxt.dirty_frames > n_frames) {
+        HIP_TRY(hipMemsetAsync(nxt.strip_ctr, 0, (size_t)nxt.dirty_frames * n_strips * 8, gs));
+        HIP_TRY(hipMemsetAsync(nxt.frame_bytes, 0, (size_t)nxt.dirty_frames * 8, gs));
+        nxt.dirty_frames = 0;
+    }
+    a.next_frames = nxt.dirty_frames;
+    nxt.dirty_frames = 0;
+    cur.dirty_frames = n_frames;
+    return M1V_OK;
+}
+
+// One batch through the encode kernel of the encoder's plan.  qa == null: every frame at the encoder's own quality (the plain
 // path); otherwise k_frame_quality first writes the per-frame selection (into the batch's status word) from qa.  probe: the
 // counter hand-over ends in k_frame_sizes instead of k_assemble (record sizes and status only; d_out is not touched).
 static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, QualityArgs *qa, bool probe,
@@ -2333,13 +1781,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
             HIP_TRY(hipEventRecord(bt.gather_done, gs));
             HIP_TRY(hipStreamWaitEvent(st, bt.gather_done, 0));
         }
-        const size_t nslots = (size_t)e->max_frames * e->g.n_strips;
-        for (m1v_encoder::Counters &c : bt.ctr) {
-            HIP_TRY(hipMemsetAsync(c.strip_ctr, 0, nslots * 8, st));
-            HIP_TRY(hipMemsetAsync(c.frame_bytes, 0, (size_t)e->max_frames * 8, st));
-            HIP_TRY(hipMemsetAsync(c.words, 0, 4 * sizeof(uint32_t), st));
-            c.dirty_frames = 0;
-        }
+        for (m1v_encoder::Counters &c : bt.ctr) HIP_TRY(counters_clear(e, c, st));
         bt.poisoned = false;
     }
     if (n_frames == 0) {
@@ -2348,8 +1790,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         return M1V_OK;
     }
     const Geometry &g = e->g;
-    const bool fast = fast_path(e, d_rgb);
-    if (!bt.scratch || !bt.seg || (!e->tiles && e->dense && !bt.run_meta))
+    const Plan &p = e->plan;
+    if (!bt.scratch || !bt.seg || (p.producer == Producer::dense && !bt.run_meta))
         return fail(M1V_E_HIP, "the encoder has no scratch (an earlier allocation failed)%s");
     // the counters this batch adds to, and the set the next batch of this Batch will use (k_assemble clears it)
     m1v_encoder::Counters &cur = bt.ctr[bt.turn & 1u], &nxt = bt.ctr[(bt.turn + 1u) & 1u];
@@ -2370,7 +1812,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         HIP_TRY(hipGetLastError());
         qsel = e->d_qsel;
     }
-    if (e->tiles) {
+    const void *kernel = producer_kernel(e, d_rgb);
+    if (p.producer == Producer::tiles) {
         TileArgs a;
         a.g = g;
         a.rgb = d_rgb;
@@ -2382,41 +1825,26 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.strip_ctr = cur.strip_ctr;
         a.frame_bytes = cur.frame_bytes;
         a.arena_next = cur.words + 2;
-        a.slot_bytes = e->slot_bytes;
-        a.arena_slots = e->arena_slots;
-        a.arena_off = e->arena_off;
+        a.slot_bytes = p.slot_bytes;
+        a.arena_slots = p.arena_slots;
+        a.arena_off = p.arena_off;
         a.status = cur.words;
         a.n_frames = n_frames;
-        a.tile_cols = e->tile_cols;
-        a.tile_rows = e->tile_rows;
-        a.tiles_per_frame = e->tiles_per_frame;
-        {
-            const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)e->tiles_per_frame;
-            a.div_group = div_magic(8u * (uint32_t)e->tiles_per_frame, units);
-            a.div_frame = div_magic((uint32_t)e->tiles_per_frame, units);
-            a.div_cols = div_magic((uint32_t)e->tile_cols, (unsigned long long)e->tiles_per_frame);
-        }
+        a.tile_cols = p.tile_cols;
+        a.tile_rows = p.tile_rows;
+        a.tiles_per_frame = p.units;
+        const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.units;
+        a.div_group = div_magic(8u * (uint32_t)p.units, units);
+        a.div_frame = div_magic((uint32_t)p.units, units);
+        a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.units);
         a.tile_row_order = e->d_tile_order;
-        a.lds_words = e->image_words;
-        a.run_cap = e->run_cap;
-        a.luma_region = e->luma_region;
-        a.chroma_region = e->chroma_region;
+        a.lds_words = p.image_words;
+        a.run_cap = p.run_cap;
+        a.luma_region = p.luma_region;
+        a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        const size_t lds = (size_t)kTileFixedWords * 4 + 2 * (size_t)a.luma_region + a.chroma_region + (size_t)a.lds_words * 4;
-        if (lds > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded%s");
-        dim3 grid((unsigned)((size_t)n_frames * e->tiles_per_frame)), block((unsigned)kTileThreads);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        if (e->narrow)
-            hipLaunchKernelGGL((k_encode_tiles<true, M1V_TILE_RING>), grid, block, lds, st, a);
-        else
-            hipLaunchKernelGGL((k_encode_tiles<false, M1V_TILE_RING>), grid, block, lds, st, a);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        HIP_TRY(hipGetLastError());
-        if (e->pipelined) {
-            HIP_TRY(hipEventRecord(bt.enc_done, st));
-            HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
-        }
-    } else if (e->dense) {
+        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
+    } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
         a.rgb = d_rgb;
@@ -2427,59 +1855,24 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.run_meta = bt.run_meta;
         a.status = cur.words;
         a.n_frames = n_frames;
-        a.threads = e->dense_T;
-        a.runs_per_frame = e->runs_per_frame;
-        // LDS image of the run's bits: zeroing it is ~3 % of the kernel per KiB-word, outgrowing it costs the
-        // slow global-atomics path.  A run of 256 blocks needs ~230 words at quality 12 on noise; scale the
-        // default with the quantiser (finer quantisers emit more bits per block).
-        a.lds_words = e->image_words;
-        a.run_cap = e->run_cap;
-        a.slot_bytes = e->slot_bytes;
-        a.arena_slots = e->arena_slots;
-        a.arena_off = e->arena_off;
+        a.threads = p.block;
+        a.runs_per_frame = p.units;
+        a.lds_words = p.image_words;
+        a.run_cap = p.run_cap;
+        a.slot_bytes = p.slot_bytes;
+        a.arena_slots = p.arena_slots;
+        a.arena_off = p.arena_off;
         a.arena_next = cur.words + 2;
         a.stamps = e->d_stamps;
-        const int stride = e->narrow ? kStageStride8 : kStageStride16;
-        a.zero_iters = (a.lds_words + e->dense_T - 1) / e->dense_T;
-        size_t lds = (size_t)((e->dense_T / kWave) * kVlcWords + 32 + stride * e->dense_T + a.zero_iters * e->dense_T) * 4;
-        if (lds > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded%s");
-        dim3 grid((unsigned)((size_t)n_frames * e->runs_per_frame)), block((unsigned)e->dense_T);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        // input mode of the pixel loads (see load_block_rows): 1 = aligned rows, 2 = any row offset in an aligned
-        // buffer (3 channels), 0 = byte loads
-        const bool aligned4 = ((uintptr_t)d_rgb & 3) == 0;
-        int mode = fast ? 1 : (aligned4 && g.C == 3 ? 2 : (aligned4 && g.C == 4 ? 3 : 0));
-        if (e->forced_mode == 0 || (e->forced_mode == 2 && mode == 1)) mode = e->forced_mode; // only modes that are valid here
-        if (mode == 1 && e->narrow)
-            hipLaunchKernelGGL((k_encode_dense<1, true>), grid, block, lds, st, a);
-        else if (mode == 1)
-            hipLaunchKernelGGL((k_encode_dense<1, false>), grid, block, lds, st, a);
-        else if (mode == 2 && e->narrow)
-            hipLaunchKernelGGL((k_encode_dense<2, true>), grid, block, lds, st, a);
-        else if (mode == 2)
-            hipLaunchKernelGGL((k_encode_dense<2, false>), grid, block, lds, st, a);
-        else if (mode == 3 && e->narrow)
-            hipLaunchKernelGGL((k_encode_dense<3, true>), grid, block, lds, st, a);
-        else if (mode == 3)
-            hipLaunchKernelGGL((k_encode_dense<3, false>), grid, block, lds, st, a);
-        else if (e->narrow)
-            hipLaunchKernelGGL((k_encode_dense<0, true>), grid, block, lds, st, a);
-        else
-            hipLaunchKernelGGL((k_encode_dense<0, false>), grid, block, lds, st, a);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        HIP_TRY(hipGetLastError());
-        if (e->pipelined) {
-            HIP_TRY(hipEventRecord(bt.enc_done, st));
-            HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
-        }
-
+        a.zero_iters = p.zero_iters;
+        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
         DenseGeom d;
         d.n_frames = n_frames;
         d.n_strips = g.n_strips;
         d.bps = g.n_mbrows * 6;
-        d.T = e->dense_T;
-        d.runs_per_frame = e->runs_per_frame;
-        hipLaunchKernelGGL(k_dense_frame_layout, dim3(n_frames), dim3(256), 0, gs, d, e->segs, bt.run_meta, bt.seg, cur.strip_ctr,
+        d.T = p.block;
+        d.runs_per_frame = p.units;
+        hipLaunchKernelGGL(k_dense_frame_layout, dim3(n_frames), dim3(256), 0, gs, d, p.segs, bt.run_meta, bt.seg, cur.strip_ctr,
                            cur.frame_bytes);
         HIP_TRY(hipGetLastError());
     } else {
@@ -2495,22 +1888,10 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.frame_bytes = cur.frame_bytes;
         a.status = cur.words;
         a.n_frames = n_frames;
-        a.threads = e->threads;
-        a.lds_words = e->lds_words > 0 ? e->lds_words : kDefaultLdsWords;
+        a.threads = p.block;
+        a.lds_words = p.image_words;
         a.stamps = e->d_stamps;
-        size_t lds = (size_t)(kVlcWords + 32 + kStageStride16 * e->threads + a.lds_words) * 4;
-        dim3 grid((unsigned)((size_t)n_frames * g.n_strips)), block((unsigned)e->threads);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        if (fast)
-            hipLaunchKernelGGL(k_encode_strips<true>, grid, block, lds, st, a);
-        else
-            hipLaunchKernelGGL(k_encode_strips<false>, grid, block, lds, st, a);
-        if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-        HIP_TRY(hipGetLastError());
-        if (e->pipelined) {
-            HIP_TRY(hipEventRecord(bt.enc_done, st));
-            HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
-        }
+        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
     }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
     if (probe) {
@@ -2520,17 +1901,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         sa.n_strips = g.n_strips;
         sa.frame_bytes = cur.frame_bytes;
         sa.enc_words = cur.words;
-        sa.next_strip_ctr = nxt.strip_ctr;
-        sa.next_frame_bytes = nxt.frame_bytes;
-        sa.next_words = nxt.words;
-        if (nxt.dirty_frames > n_frames) { // as below
-            HIP_TRY(hipMemsetAsync(nxt.strip_ctr, 0, (size_t)nxt.dirty_frames * g.n_strips * 8, gs));
-            HIP_TRY(hipMemsetAsync(nxt.frame_bytes, 0, (size_t)nxt.dirty_frames * 8, gs));
-            nxt.dirty_frames = 0;
-        }
-        sa.next_frames = nxt.dirty_frames;
-        nxt.dirty_frames = 0;
-        cur.dirty_frames = n_frames;
+        if (const int rc = hand_over(sa, cur, nxt, n_frames, g.n_strips, gs)) return rc;
         sa.out_sizes = (unsigned long long *)d_frame_sizes;
         sa.out_status = d_status ? d_status : cur.words + 1;
         hipLaunchKernelGGL(k_frame_sizes, dim3((unsigned)n_frames), dim3(256), 0, gs, sa);
@@ -2540,27 +1911,17 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         AssembleArgs ga;
         ga.n_frames = n_frames;
         ga.n_strips = g.n_strips;
-        ga.segs = e->segs;
-        ga.group = e->asm_group;
-        ga.lanes_log2 = e->asm_lanes_log2;
-        ga.img_words = e->asm_img_words;
-        ga.div_segs = div_magic((uint32_t)e->segs, (unsigned long long)e->asm_group * (unsigned long long)e->segs);
+        ga.segs = p.segs;
+        ga.group = p.asm_group;
+        ga.lanes_log2 = p.asm_lanes_log2;
+        ga.img_words = kAsmImageBytes / 4;
+        ga.div_segs = div_magic((uint32_t)p.segs, (unsigned long long)p.asm_group * (unsigned long long)p.segs);
         ga.scratch = bt.scratch;
         ga.seg = bt.seg;
         ga.strip_ctr = cur.strip_ctr;
         ga.frame_bytes = cur.frame_bytes;
         ga.enc_words = cur.words;
-        ga.next_strip_ctr = nxt.strip_ctr;
-        ga.next_frame_bytes = nxt.frame_bytes;
-        ga.next_words = nxt.words;
-        if (nxt.dirty_frames > n_frames) { // a longer batch than this one used that set last: clear what this launch does not reach
-            HIP_TRY(hipMemsetAsync(nxt.strip_ctr, 0, (size_t)nxt.dirty_frames * g.n_strips * 8, gs));
-            HIP_TRY(hipMemsetAsync(nxt.frame_bytes, 0, (size_t)nxt.dirty_frames * 8, gs));
-            nxt.dirty_frames = 0;
-        }
-        ga.next_frames = nxt.dirty_frames;
-        nxt.dirty_frames = 0;
-        cur.dirty_frames = n_frames;
+        if (const int rc = hand_over(ga, cur, nxt, n_frames, g.n_strips, gs)) return rc;
         ga.tab = e->d_tab;
         ga.out = d_out;
         ga.out_cap = out_cap;
@@ -2569,9 +1930,9 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         ga.out_status = d_status ? d_status : cur.words + 1;
         ga.first_index = first_frame_index;
         ga.stamps = e->d_stamps;
-        const dim3 grid((unsigned)((g.n_strips + e->asm_group - 1) / e->asm_group), (unsigned)n_frames);
-        const size_t lds = (size_t)(e->asm_img_words + kAsmFixedWords) * sizeof(uint32_t);
-        if (e->scratch_bytes >= (1ull << 32))
+        const dim3 grid((unsigned)((g.n_strips + p.asm_group - 1) / p.asm_group), (unsigned)n_frames);
+        const size_t lds = (size_t)(kAsmImageBytes / 4 + kAsmFixedWords) * sizeof(uint32_t);
+        if (p.scratch_bytes >= (1ull << 32))
             hipLaunchKernelGGL(k_assemble<true>, grid, dim3(kAsmThreads), lds, gs, ga);
         else
             hipLaunchKernelGGL(k_assemble<false>, grid, dim3(kAsmThreads), lds, gs, ga);
@@ -2586,430 +1947,5 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     return M1V_OK;
 }
 
-int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                      uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
-                      uint32_t *d_status, void *stream) {
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status,
-                        stream);
-}
-
-int m1v_encode_quality_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
-                              uint64_t *d_total, uint32_t *d_status, void *stream) {
-    QualityArgs qa = {};
-    qa.quality = d_quality;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, d_quality ? &qa : nullptr, false, d_out, out_cap, d_frame_sizes,
-                        d_total, d_status, stream);
-}
-
-int m1v_frame_sizes_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *d_quality,
-                           uint64_t *d_frame_sizes, uint32_t *d_status, void *stream) {
-    QualityArgs qa = {};
-    qa.quality = d_quality;
-    return encode_batch(e, d_rgb, n_frames, 0, d_quality ? &qa : nullptr, true, nullptr, 0, d_frame_sizes, nullptr, d_status,
-                        stream);
-}
-
-int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                             const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
-                             const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
-                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
-                             uint32_t *d_status, void *stream) {
-    if (!e || !candidates) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
-    for (int k = 0; k < n_candidates; k++)
-        if (candidates[k] < 1 || candidates[k] > encoder_quality(e) || (k > 0 && candidates[k] <= candidates[k - 1]))
-            return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
-    // 1. the record size of every frame at every candidate (each probe is a complete call: its own counter hand-over)
-    for (int k = 0; k < n_candidates; k++) {
-        QualityArgs qa = {};
-        qa.uniform = candidates[k];
-        const int rc = encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, true, nullptr, 0,
-                                    (uint64_t *)(e->d_probe_sizes + (size_t)k * e->max_frames), nullptr, e->d_probe_status + k, stream);
-        if (rc != M1V_OK) return rc;
-    }
-    // (pipelined: the probes' sizes are written on the internal stream)
-    if (e->pipelined) {
-        const int rc = m1v_flush(e, stream);
-        if (rc != M1V_OK) return rc;
-    }
-    // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
-    QualityArgs qa = {};
-    qa.probe_sizes = e->d_probe_sizes;
-    qa.stride = e->max_frames;
-    qa.n_cand = n_candidates;
-    for (int k = 0; k < n_candidates; k++) qa.cand[k] = candidates[k];
-    qa.budget = (const unsigned long long *)d_max_frame_bytes;
-    qa.max_bytes = max_frame_bytes;
-    qa.probe_status = e->d_probe_status;
-    qa.chosen = d_chosen ? d_chosen : e->d_chosen;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
-}
-
-// ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------
-struct m1v_delivery {
-    m1v_encoder *e;
-    int device; // (the encoder may be destroyed before the delivery object is)
-    size_t cap;
-    int max_frames;
-    uint8_t *d_out[2], *h_out[2];
-    unsigned long long *d_meta[2], *h_meta[2];   // [0] total bytes, [1] status word (low 32 bits)
-    unsigned long long *d_sizes[2], *h_sizes[2];
-    hipStream_t side;
-    hipEvent_t encoded[2], counted[2], delivered[2];
-    bool in_flight[2];                            // delivered[b] has been recorded and not yet been waited for by an encode
-    struct {
-        const uint8_t *rgb;
-        int n, first;
-    } args[2];
-    int pending;                                  // slot whose batch is encoded (or encoding) and not yet on its way, or -1
-    unsigned step_no;
-};
-
-static int delivery_start(m1v_delivery *d, int b) { // the copy of slot b's batch, behind its encode
-    m1v_encoder *e = d->e;
-    HIP_TRY(hipStreamWaitEvent(d->side, d->encoded[b], 0));
-    HIP_TRY(hipMemcpyAsync(d->h_meta[b], d->d_meta[b], 16, hipMemcpyDeviceToHost, d->side));
-    HIP_TRY(hipEventRecord(d->counted[b], d->side));
-    HIP_TRY(hipEventSynchronize(d->counted[b])); // the step's only host wait: the next encode is already queued
-    unsigned long long total = d->h_meta[b][0];
-    uint32_t status = (uint32_t)d->h_meta[b][1];
-    if (status == M1V_STATUS_SCRATCH) { // recoverable: the worst case reserved (waits for the device), the same frames again
-        int rc = m1v_reserve_scratch(e, 1);
-        if (rc != M1V_OK) return rc;
-        rc = m1v_encode_device(e, d->args[b].rgb, d->args[b].n, d->args[b].first, d->d_out[b], d->cap, (uint64_t *)d->d_sizes[b],
-                               (uint64_t *)d->d_meta[b], reinterpret_cast<uint32_t *>(d->d_meta[b] + 1), d->side);
-        if (rc != M1V_OK) return rc;
-        if (e->pipelined) HIP_TRY(hipStreamWaitEvent(d->side, e->batch[(e->calls - 1u) & 1u].gather_done, 0));
-        HIP_TRY(hipMemcpyAsync(d->h_meta[b], d->d_meta[b], 16, hipMemcpyDeviceToHost, d->side));
-        HIP_TRY(hipStreamSynchronize(d->side));
-        total = d->h_meta[b][0];
-        status = (uint32_t)d->h_meta[b][1];
-    }
-    if (status & M1V_STATUS_UNENCODABLE) return fail(M1V_E_UNENCODABLE, "a level of 256 or more: the reference cannot code this batch%s");
-    if (status & M1V_STATUS_NOSPACE) return fail(M1V_E_NOSPACE, "the delivery's output buffers are too small for this batch%s");
-    if (status) return fail(M1V_E_SCRATCH, "the batch ran out of scratch twice%s");
-    if (total > d->cap) return fail(M1V_E_NOSPACE, "the delivery's output buffers are too small for this batch%s");
-    HIP_TRY(hipMemcpyAsync(d->h_out[b], d->d_out[b], total, hipMemcpyDeviceToHost, d->side));
-    HIP_TRY(hipMemcpyAsync(d->h_sizes[b], d->d_sizes[b], (size_t)d->args[b].n * 8, hipMemcpyDeviceToHost, d->side));
-    HIP_TRY(hipEventRecord(d->delivered[b], d->side));
-    d->in_flight[b] = true;
-    return b;
-}
-
-int m1v_delivery_create(m1v_encoder *e, size_t out_cap, m1v_delivery **out) {
-    if (!e || !out) return fail(M1V_E_ARG, "null pointer%s");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(e->device));
-    m1v_delivery *d = new m1v_delivery();
-    memset(d, 0, sizeof *d);
-    d->e = e;
-    d->device = e->device;
-    d->max_frames = e->max_frames;
-    d->cap = out_cap ? out_cap : (size_t)e->max_frames * m1v_frame_bound(e);
-    d->pending = -1;
-    hipError_t err = hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking);
-    for (int b = 0; b < 2; b++) {
-        if (err == hipSuccess) err = hipMalloc(&d->d_out[b], d->cap);
-        if (err == hipSuccess) err = hipMalloc(&d->d_meta[b], 16);
-        if (err == hipSuccess) err = hipMemset(d->d_meta[b], 0, 16);
-        if (err == hipSuccess) err = hipMalloc(&d->d_sizes[b], (size_t)e->max_frames * 8);
-        if (err == hipSuccess) err = hipHostMalloc(&d->h_out[b], d->cap, hipHostMallocDefault);
-        if (err == hipSuccess) err = hipHostMalloc(&d->h_meta[b], 16, hipHostMallocDefault);
-        if (err == hipSuccess) err = hipHostMalloc(&d->h_sizes[b], (size_t)e->max_frames * 8, hipHostMallocDefault);
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->encoded[b], hipEventDisableTiming);
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->counted[b], hipEventDisableTiming);
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->delivered[b], hipEventDisableTiming);
-    }
-    if (err != hipSuccess) {
-        fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
-        m1v_delivery_destroy(d);
-        return M1V_E_HIP;
-    }
-    *out = d;
-    return M1V_OK;
-}
-
-void m1v_delivery_destroy(m1v_delivery *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    if (d->side) (void)hipStreamSynchronize(d->side);
-    for (int b = 0; b < 2; b++) {
-        (void)hipFree(d->d_out[b]);
-        (void)hipFree(d->d_meta[b]);
-        (void)hipFree(d->d_sizes[b]);
-        (void)hipHostFree(d->h_out[b]);
-        (void)hipHostFree(d->h_meta[b]);
-        (void)hipHostFree(d->h_sizes[b]);
-        if (d->encoded[b]) (void)hipEventDestroy(d->encoded[b]);
-        if (d->counted[b]) (void)hipEventDestroy(d->counted[b]);
-        if (d->delivered[b]) (void)hipEventDestroy(d->delivered[b]);
-    }
-    if (d->side) (void)hipStreamDestroy(d->side);
-    delete d;
-}
-
-int m1v_delivery_step(m1v_delivery *d, const uint8_t *d_rgb, int n_frames, int first_frame_index, void *stream) {
-    if (!d || !d_rgb) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_frames <= 0 || n_frames > d->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    m1v_encoder *e = d->e;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(e->device));
-    const int b = (int)(d->step_no++ & 1u);
-    if (d->in_flight[b]) { // slot b's previous batch has left for the host before its buffers are written again
-        HIP_TRY(hipStreamWaitEvent(st, d->delivered[b], 0));
-        d->in_flight[b] = false;
-    }
-    const int rc = m1v_encode_device(e, d_rgb, n_frames, first_frame_index, d->d_out[b], d->cap, (uint64_t *)d->d_sizes[b],
-                                     (uint64_t *)d->d_meta[b], reinterpret_cast<uint32_t *>(d->d_meta[b] + 1), st);
-    if (rc != M1V_OK) { // slot b holds no batch: the next step uses it again, the pending batch in the other slot is untouched
-        d->step_no--;
-        return rc;
-    }
-    if (e->pipelined) HIP_TRY(m1v_flush(e, st) == M1V_OK ? hipSuccess : hipErrorUnknown);
-    HIP_TRY(hipEventRecord(d->encoded[b], st));
-    d->args[b].rgb = d_rgb;
-    d->args[b].n = n_frames;
-    d->args[b].first = first_frame_index;
-    const int before = d->pending;
-    d->pending = b;
-    return before >= 0 ? delivery_start(d, before) : (int)M1V_DELIVERY_NONE;
-}
-
-int m1v_delivery_flush(m1v_delivery *d) {
-    if (!d) return fail(M1V_E_ARG, "null pointer%s");
-    HIP_TRY(hipSetDevice(d->e->device));
-    const int before = d->pending;
-    d->pending = -1;
-    return before >= 0 ? delivery_start(d, before) : (int)M1V_DELIVERY_NONE;
-}
-
-uint64_t m1v_delivery_bytes(const m1v_delivery *d, int slot) { return d && slot >= 0 && slot <= 1 ? d->h_meta[slot][0] : 0; }
-
-int m1v_delivery_wait(m1v_delivery *d, int slot, const uint8_t **host, uint64_t *bytes, const uint64_t **frame_sizes) {
-    if (!d || slot < 0 || slot > 1) return fail(M1V_E_ARG, "bad slot%s");
-    HIP_TRY(hipSetDevice(d->device));
-    HIP_TRY(hipEventSynchronize(d->delivered[slot]));
-    if (host) *host = d->h_out[slot];
-    if (bytes) *bytes = d->h_meta[slot][0];
-    if (frame_sizes) *frame_sizes = (const uint64_t *)d->h_sizes[slot];
-    return M1V_OK;
-}
-
-/* Pinned host memory for callers of the host-buffer entry points: H2D/D2H copies from it run at the PCIe
- * rate instead of being staged by the runtime. */
-void *m1v_alloc_host(size_t bytes) {
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-    return p;
-}
-void *m1v_alloc_device(size_t bytes) {
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return p;
-}
-void m1v_free_device(void *p) { (void)hipFree(p); }
-void m1v_free_host(void *p) {
-    if (p) (void)hipHostFree(p);
-}
-
-long m1v_encode_planes_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first_frame_index,
-                            uint8_t *out, size_t out_cap, uint64_t *frame_sizes, uint8_t *planes) {
-    if (!e || !rgb || !out) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    if (n_frames == 0) return 0;
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t frame_in = (size_t)e->g.frame_bytes, frame_planes = (size_t)e->g.W * e->g.H * 3;
-    size_t in_bytes = frame_in * n_frames;
-    size_t bound = m1v_frame_bound(e) * (size_t)n_frames;
-    size_t dcap = out_cap < bound ? out_cap : bound;
-    m1v_encoder::HostPath &hp = e->hp;
-    HIP_TRY(ensure_device(&hp.d_in, &hp.in_cap, in_bytes));
-    HIP_TRY(ensure_device(&hp.d_out, &hp.out_cap, dcap));
-    HIP_TRY(ensure_device(&hp.d_meta, &hp.meta_cap, (size_t)(n_frames + 2) * 8)); // [n] sizes, total, status
-    if (planes) HIP_TRY(ensure_device(&hp.d_planes, &hp.planes_cap, frame_planes * n_frames));
-    if (!hp.copy_in) { // all or nothing: a half-built set must not survive into the next call
-        hipError_t err = hipStreamCreateWithFlags(&hp.copy_in, hipStreamNonBlocking);
-        if (err == hipSuccess) err = hipStreamCreateWithFlags(&hp.work, hipStreamNonBlocking);
-        for (hipEvent_t &ev : hp.uploaded)
-            if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (err != hipSuccess) {
-            if (hp.copy_in) (void)hipStreamDestroy(hp.copy_in);
-            if (hp.work) (void)hipStreamDestroy(hp.work);
-            for (hipEvent_t &ev : hp.uploaded) {
-                if (ev) (void)hipEventDestroy(ev);
-                ev = nullptr;
-            }
-            hp.copy_in = hp.work = nullptr;
-            return fail(M1V_E_HIP, "stream creation failed: %s", hipGetErrorString(err));
-        }
-    }
-    // From here on copies to and from the caller's buffers are in flight: every error return first waits for both
-    // streams, so that the caller may free (or reuse) rgb / planes / out as soon as this function has returned.
-    auto drained = [&](int rc) {
-        (void)hipStreamSynchronize(hp.copy_in);
-        (void)hipStreamSynchronize(hp.work);
-        return rc;
-    };
-#define HIP_TRY_DRAIN(expr)                                                                        \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return drained(fail(M1V_E_HIP, #expr ": %s", hipGetErrorString(e_))); \
-    } while (0)
-    // copy_in: H2D half A, H2D half B.   work: [planes A -> host] while B uploads, [planes B -> host], encode all.
-    const int half[3] = {0, planes && n_frames > 1 ? n_frames / 2 : n_frames, n_frames};
-    for (int h = 0; h < 2; h++) {
-        int f0 = half[h], nf = half[h + 1] - half[h];
-        if (nf == 0) continue;
-        HIP_TRY_DRAIN(hipMemcpyAsync(hp.d_in + frame_in * f0, rgb + frame_in * f0, frame_in * nf, hipMemcpyHostToDevice, hp.copy_in));
-        HIP_TRY_DRAIN(hipEventRecord(hp.uploaded[h], hp.copy_in));
-        HIP_TRY_DRAIN(hipStreamWaitEvent(hp.work, hp.uploaded[h], 0));
-        if (planes) {
-            int rc = m1v_convert_device(e, hp.d_in + frame_in * f0, nf, hp.d_planes + frame_planes * f0, hp.work);
-            if (rc != M1V_OK) return drained(rc);
-            HIP_TRY_DRAIN(hipMemcpyAsync(planes + frame_planes * f0, hp.d_planes + frame_planes * f0, frame_planes * nf,
-                                   hipMemcpyDeviceToHost, hp.work));
-        }
-    }
-    std::vector<unsigned long long> meta((size_t)n_frames + 2);
-    uint32_t status = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        int r = m1v_encode_device(e, hp.d_in, n_frames, first_frame_index, hp.d_out, dcap, (uint64_t *)hp.d_meta,
-                                  (uint64_t *)(hp.d_meta + n_frames), (uint32_t *)(hp.d_meta + n_frames + 1), hp.work);
-        if (r != M1V_OK) return drained(r);
-        if (m1v_flush(e, hp.work) != M1V_OK) return drained(M1V_E_HIP);
-        HIP_TRY_DRAIN(hipMemcpyAsync(meta.data(), hp.d_meta, meta.size() * 8, hipMemcpyDeviceToHost, hp.work));
-        HIP_TRY_DRAIN(hipStreamSynchronize(hp.work));
-        status = (uint32_t)meta[(size_t)n_frames + 1];
-        if (!(status & M1V_STATUS_SCRATCH) || attempt == 1) break;
-        // more runs outgrew their compact scratch slot than the overflow arena holds: reserve the worst case, encode again
-        int rr = m1v_reserve_scratch(e, 1);
-        if (rr != M1V_OK) return drained(rr);
-    }
-    if (status & M1V_STATUS_SCRATCH) return drained(fail(M1V_E_SCRATCH, "scratch exhausted%s"));
-    unsigned long long total = meta[n_frames];
-    if (status & M1V_STATUS_UNENCODABLE)
-        return fail(M1V_E_UNENCODABLE, "an AC level has |level| >= 256 (the reference crashes here)%s");
-    if ((status & M1V_STATUS_NOSPACE) || total > out_cap) return fail(M1V_E_NOSPACE, "output buffer too small%s");
-    HIP_TRY_DRAIN(hipMemcpy(out, hp.d_out, total, hipMemcpyDeviceToHost));
-    if (frame_sizes)
-        for (int f = 0; f < n_frames; f++) frame_sizes[f] = meta[f];
-    return (long)total;
-#undef HIP_TRY_DRAIN
-}
-
-long m1v_encode_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first_frame_index,
-                     uint8_t *out, size_t out_cap, uint64_t *frame_sizes) {
-    return m1v_encode_planes_host(e, rgb, n_frames, first_frame_index, out, out_cap, frame_sizes, nullptr);
-}
-
-int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int16_t *d_coeffs,
-                            void *stream) {
-    if (!e || !d_rgb || !d_coeffs || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
-    if (n_frames == 0) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    CoefArgs a;
-    a.g = e->g;
-    a.rgb = d_rgb;
-    a.tab = e->d_tab;
-    a.out = d_coeffs;
-    a.n_frames = n_frames;
-    if (e->g.C == 3 && e->forced_mode < 0 && e->forced_path != 0) { // tiles (any width, any alignment); the run-shaped kernel serves 4 channels
-        CoefTileArgs t;
-        t.g = e->g;
-        t.rgb = d_rgb;
-        t.tab = e->d_tab;
-        t.out = d_coeffs;
-        t.n_frames = n_frames;
-        t.tile_cols = (e->g.n_strips + kTileStrips - 1) / kTileStrips;
-        t.tile_rows = (e->g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
-        t.tiles_per_frame = t.tile_cols * t.tile_rows;
-        t.region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * kCoefStride * 4)) + 15u) & ~15u;
-        hipLaunchKernelGGL((k_coefficient_tiles<M1V_TILE_RING>), dim3((unsigned)((size_t)n_frames * t.tiles_per_frame)),
-                           dim3(kTileThreads), 3 * (size_t)t.region, (hipStream_t)stream, t);
-        HIP_TRY(hipGetLastError());
-        return M1V_OK;
-    }
-    int bps = e->g.n_mbrows * 6;
-    dim3 grid((bps + 255) / 256, e->g.n_strips, n_frames);
-    if (fast_path(e, d_rgb))
-        hipLaunchKernelGGL(k_coefficients<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_coefficients<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
-}
-
-int m1v_convert_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, uint8_t *d_planes,
-                       void *stream) {
-    if (!e || !d_rgb || !d_planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
-    if (n_frames == 0) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    unsigned long long npx = (unsigned long long)e->g.W * e->g.H;
-    unsigned long long total = npx * n_frames;
-    if (npx % 4 == 0 && (((uintptr_t)d_rgb | (uintptr_t)d_planes) & 3) == 0) { // four pixels per lane, dword loads and stores
-        total /= 4;
-        unsigned blocks = (unsigned)((total + 255) / 256 > 131072 ? 131072 : (total + 255) / 256);
-        if (e->g.C == 3)
-            hipLaunchKernelGGL(k_convert4<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_rgb,
-                               npx / 4, n_frames, (uint32_t *)d_planes);
-        else
-            hipLaunchKernelGGL(k_convert4<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_rgb,
-                               npx / 4, n_frames, (uint32_t *)d_planes);
-        HIP_TRY(hipGetLastError());
-        return M1V_OK;
-    }
-    unsigned blocks = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_convert, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rgb, e->g.C, npx,
-                       n_frames, d_planes);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
-}
-
-int m1v_convert_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, uint8_t *planes) {
-    if (!e || !rgb || !planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
-    if (n_frames == 0) return M1V_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    size_t in_bytes = (size_t)e->g.frame_bytes * n_frames;
-    size_t out_bytes = (size_t)e->g.W * e->g.H * 3 * n_frames;
-    m1v_encoder::HostPath &hp = e->hp;
-    HIP_TRY(ensure_device(&hp.d_in, &hp.in_cap, in_bytes));
-    HIP_TRY(ensure_device(&hp.d_planes, &hp.planes_cap, out_bytes));
-    HIP_TRY(hipMemcpy(hp.d_in, rgb, in_bytes, hipMemcpyHostToDevice));
-    int rc = m1v_convert_device(e, hp.d_in, n_frames, hp.d_planes, nullptr);
-    if (rc != M1V_OK) return rc;
-    HIP_TRY(hipMemcpy(planes, hp.d_planes, out_bytes, hipMemcpyDeviceToHost));
-    return M1V_OK;
-}
-
-int m1v_subsample_device(m1v_encoder *e, const uint8_t *d_cb, const uint8_t *d_cr, uint8_t *d_cb_sub,
-                         uint8_t *d_cr_sub, void *stream) {
-    if (!e || !d_cb || !d_cr || !d_cb_sub || !d_cr_sub) return fail(M1V_E_ARG, "bad argument%s");
-    if ((e->g.W | e->g.H) & 1) return fail(M1V_E_ARG, "odd dimensions: the reference reads out of bounds%s");
-    HIP_TRY(hipSetDevice(e->device));
-    int n = (e->g.W / 2) * (e->g.H / 2);
-    hipLaunchKernelGGL(k_subsample, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_cb, d_cr,
-                       e->g.W, e->g.H, d_cb_sub, d_cr_sub);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
-}
-
-int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint64_t seed,
-                     uint64_t first_frame_index, void *stream) {
-    if (!d_rgb || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
-    if (n_frames == 0 || bytes_per_frame == 0) return M1V_OK;
-    unsigned long long total = ((bytes_per_frame + 7) / 8) * (unsigned long long)n_frames;
-    unsigned blocks = (unsigned)((total + 255) / 256 > 262144 ? 262144 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_synth, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rgb,
-                       (unsigned long long)bytes_per_frame, n_frames, (unsigned long long)seed,
-                       (unsigned long long)first_frame_index);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
-}
-
-} // extern "C"
+// the C-ABI: object lifetime, buffers, the entry points, delivery, the host path, profiling, debug hooks
+#include "m1v_runtime.h"

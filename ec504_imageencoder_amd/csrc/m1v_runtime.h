@@ -1,0 +1,973 @@
+// ec504_imageencoder_amd/csrc/m1v_runtime.h — the C-ABI of include/mpeg1_hip.h around the plan and the launches of
+// m1v_kernels.hip: object lifetime, buffer allocation, counters, streams and events, the quality and budget entry points,
+// delivery, the host path, profiling and the debug hooks.  Not standalone: included once, at the end of m1v_kernels.hip.
+
+namespace {
+
+// scaled quantiser matrix, image_processing.c:314-343 (float scale factor, double division,
+// round half away from zero, floor of 1)
+void scaled_matrix(int qf, int q[64]) {
+    static const unsigned char base[64] = {
+        8,  16, 19, 22, 26, 27, 29, 34, 16, 16, 22, 24, 27, 29, 34, 37, 19, 22, 26, 27, 29, 34,
+        34, 38, 22, 22, 26, 27, 29, 34, 37, 40, 22, 26, 27, 29, 32, 35, 40, 48, 26, 27, 29, 32,
+        35, 40, 48, 58, 26, 27, 29, 34, 38, 46, 56, 69, 27, 29, 35, 38, 46, 56, 69, 83};
+    if (qf < 1) qf = 1;
+    if (qf > 100) qf = 100;
+    float sf = qf < 50 ? (float)(5000.0 / qf) : (float)(200.0 - 2 * qf);
+    for (int k = 0; k < 64; k++) {
+        float prod = (float)base[k] * sf;
+        int v = (int)round((double)prod / 100.0);
+        q[k] = v < 1 ? 1 : v;
+    }
+}
+
+// The VLC table of the kernels (layout: kVlc*).  Run/level code words without sign bit as the reference stores them
+// (vlc.c:176-288), in its order, with its offset index (vlc.c:172-174); the reference's indexing rule (vlc.c:329-339)
+// reads row r = run - 1 at |level| - 1, so in row 0 entry idx codes level idx + 2 — except idx 0, which the rule
+// replaces by the special "11" and which is therefore stored that way here.  DC size codes: vlc.c:121-144.
+void build_vlc_table(uint32_t t[kVlcWords]) {
+    static const unsigned char row_len[32] = {39, 18, 5, 4, 3, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2,
+                                              2,  1,  1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+    static const unsigned char code[110] = {
+        0x04, 0x05, 0x06, 0x26, 0x21, 0x0a, 0x1d, 0x18, 0x13, 0x10, 0x1a, 0x19, 0x18, 0x17, 0x1f, 0x1e,
+        0x1d, 0x1c, 0x1b, 0x1a, 0x19, 0x18, 0x17, 0x16, 0x15, 0x14, 0x13, 0x12, 0x11, 0x10, 0x18, 0x17,
+        0x16, 0x15, 0x14, 0x13, 0x12, 0x11, 0x10, 0x03, 0x06, 0x25, 0x0c, 0x1b, 0x16, 0x15, 0x1f, 0x1e,
+        0x1d, 0x1c, 0x1b, 0x1a, 0x19, 0x13, 0x12, 0x11, 0x10, 0x05, 0x04, 0x0b, 0x14, 0x14, 0x07, 0x24,
+        0x1c, 0x13, 0x06, 0x0f, 0x12, 0x07, 0x09, 0x12, 0x05, 0x1e, 0x14, 0x04, 0x15, 0x07, 0x11, 0x05,
+        0x11, 0x27, 0x10, 0x23, 0x1a, 0x22, 0x19, 0x20, 0x18, 0x0e, 0x17, 0x0d, 0x16, 0x08, 0x15, 0x1f,
+        0x1a, 0x19, 0x17, 0x16, 0x1f, 0x1e, 0x1d, 0x1c, 0x1b, 0x1f, 0x1e, 0x1d, 0x1c, 0x1b};
+    static const unsigned char bits[110] = {
+        4,  5,  7,  8,  8,  10, 12, 12, 12, 12, 13, 13, 13, 13, 14, 14, 14, 14, 14, 14, 14, 14,
+        14, 14, 14, 14, 14, 14, 14, 14, 15, 15, 15, 15, 15, 15, 15, 15, 15, 3,  6,  8,  10, 12,
+        13, 13, 15, 15, 15, 15, 15, 15, 15, 16, 16, 16, 16, 4,  7,  10, 12, 13, 5,  8,  12, 13,
+        5,  10, 12, 6,  10, 13, 6,  12, 16, 6,  12, 7,  12, 7,  13, 8,  13, 8,  16, 8,  16, 8,
+        16, 10, 16, 10, 16, 10, 15, 12, 12, 12, 12, 12, 13, 13, 13, 13, 13, 16, 16, 16, 16, 16};
+    memset(t, 0, kVlcWords * sizeof(uint32_t));
+    int first = 0;
+    for (int r = 0; r < kAcRows; r++) {
+        t[kVlcRowInfo + r] = (uint32_t)first | ((uint32_t)row_len[r] << 8);
+        first += row_len[r];
+    }
+    for (int e = 0; e < 110; e++) t[kVlcEntries + e] = ((uint32_t)bits[e] << 16) | code[e];
+    t[kVlcEntries] = (2u << 16) | 0x3u; // run 1, |level| 1 -> "11" (vlc.c:329-334 with first == 0)
+    static const unsigned char lc[9] = {0x4, 0x0, 0x1, 0x5, 0x6, 0xE, 0x1E, 0x3E, 0x7E};
+    static const unsigned char lb[9] = {3, 2, 2, 3, 3, 4, 5, 6, 7};
+    static const unsigned char cc[9] = {0x0, 0x1, 0x2, 0x6, 0xE, 0x1E, 0x3E, 0x7E, 0xFE};
+    static const unsigned char cb[9] = {2, 2, 2, 3, 4, 5, 6, 7, 8};
+    for (int i = 0; i < 9; i++) {
+        t[kVlcDcLuma + i] = ((uint32_t)lb[i] << 16) | lc[i];
+        t[kVlcDcChroma + i] = ((uint32_t)cb[i] << 16) | cc[i];
+    }
+}
+
+void put_timestamp(uint8_t *o, uint8_t prefix, uint32_t v) { // mpeg1_enc.c:59-64, :67-71
+    o[0] = (uint8_t)(prefix | ((v & 0xe0000000u) >> 28));
+    o[1] = (uint8_t)((v & 0x1fe00000u) >> 21);
+    o[2] = (uint8_t)(0x01 | ((v & 0x001fc000u) >> 13));
+    o[3] = (uint8_t)((v & 0x00003fc0u) >> 6);
+    o[4] = (uint8_t)(0x01 | ((v & 0x0000003fu) << 1));
+}
+
+// PKT(16) SEQ(12) GOP(8) PIC(8) of the frame whose uint8 `hour` is given (encoder.h:37-63,186-230)
+void build_frame_header(uint8_t h[44], int W, int H, int hour) {
+    memset(h, 0, 44);
+    h[2] = 0x01; h[3] = 0xe0;                                  // packet, stream id 0 (mpeg1_enc.c:47-77)
+    uint32_t ts = (uint32_t)(1 + 3600 * hour);
+    ts = (uint32_t)((double)ts * 1.2);
+    ts += 0xbeef;
+    put_timestamp(h + 6, 0x31, ts);
+    ts -= 0xbeef;
+    put_timestamp(h + 11, 0x11, ts);
+    uint8_t *s = h + 16;                                       // sequence (mpeg1_enc.c:81-94)
+    unsigned w = (unsigned)W & 0xffu, hh = (unsigned)H & 0xffu; // uint8_t width/height, encoder.h:186-187
+    s[2] = 0x01; s[3] = 0xb3;
+    s[4] = (uint8_t)((w & 0xff0) >> 4);
+    s[5] = (uint8_t)(((w & 0xf) << 4) | ((hh & 0xf00) >> 8));
+    s[6] = (uint8_t)(hh & 0xff);
+    s[7] = 0x14; s[8] = 0xff; s[9] = 0xff; s[10] = 0xe0; s[11] = 0x18;
+    uint8_t *g = h + 28;                                       // GOP (mpeg1_enc.c:103-113)
+    g[2] = 0x01; g[3] = 0xb8;
+    g[4] = (uint8_t)((hour & 0x1f) << 2);
+    g[5] = 0x08; g[6] = 0x00; g[7] = 0x40;
+    uint8_t *p = h + 36;                                       // picture (mpeg1_enc.c:120-129)
+    p[2] = 0x01; p[3] = 0x00; p[4] = 0x00; p[5] = 0x0f; p[6] = 0xff; p[7] = 0xf8;
+}
+
+} // namespace
+
+template <typename T>
+static hipError_t ensure_device(T **p, size_t *cap, size_t need) {
+    if (need <= *cap) return hipSuccess;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    hipError_t err = hipMalloc(p, need);
+    if (err == hipSuccess) *cap = need;
+    return err;
+}
+
+static int g_fail_alloc_in = 0; // test hook (m1v_debug_fail_alloc): the n-th allocation of configure_path from now fails
+template <typename T>
+static hipError_t plan_malloc(T **p, size_t bytes) {
+    if (g_fail_alloc_in > 0 && --g_fail_alloc_in == 0) return hipErrorOutOfMemory;
+    return hipMalloc(p, bytes);
+}
+static int g_fail_encode_at = 0; // test hook (m1v_debug_fail_encode): the stage at which the next encode returns M1V_E_HIP
+static int fail_encode_at(int stage) {
+    if (g_fail_encode_at != stage) return M1V_OK;
+    g_fail_encode_at = 0;
+    return fail(M1V_E_HIP, "injected failure (m1v_debug_fail_encode)%s");
+}
+
+// A counter set: cleared in full on a stream; allocated (through plan_malloc) and cleared before the allocation returns; freed.
+static hipError_t counters_clear(const m1v_encoder *e, m1v_encoder::Counters &c, hipStream_t st) {
+    c.dirty_frames = 0;
+    hipError_t err = hipMemsetAsync(c.strip_ctr, 0, (size_t)e->max_frames * e->g.n_strips * 8, st);
+    if (err == hipSuccess) err = hipMemsetAsync(c.frame_bytes, 0, (size_t)e->max_frames * 8, st);
+    if (err == hipSuccess) err = hipMemsetAsync(c.words, 0, 4 * sizeof(uint32_t), st);
+    return err;
+}
+static bool counters_alloc(const m1v_encoder *e, m1v_encoder::Counters &c) {
+    return plan_malloc(&c.strip_ctr, (size_t)e->max_frames * e->g.n_strips * 8) == hipSuccess &&
+           plan_malloc(&c.frame_bytes, (size_t)e->max_frames * 8) == hipSuccess && plan_malloc(&c.words, 4 * sizeof(uint32_t)) == hipSuccess &&
+           counters_clear(e, c, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+}
+static void counters_free(m1v_encoder::Counters &c) {
+    (void)hipFree(c.strip_ctr);
+    (void)hipFree(c.frame_bytes);
+    (void)hipFree(c.words);
+}
+
+static void batch_free(m1v_encoder::Batch &bt) {
+    (void)hipFree(bt.scratch);
+    (void)hipFree(bt.run_meta);
+    (void)hipFree(bt.seg);
+    for (m1v_encoder::Counters &c : bt.ctr) counters_free(c);
+    if (bt.enc_done) (void)hipEventDestroy(bt.enc_done);
+    if (bt.gather_done) (void)hipEventDestroy(bt.gather_done);
+}
+
+static int profile_event(m1v_encoder *e, hipStream_t st) {
+    if (e->ev_used == e->ev.size()) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        e->ev.push_back(ev);
+    }
+    HIP_TRY(hipEventRecord(e->ev[e->ev_used++], st));
+    return M1V_OK;
+}
+
+// The launches profiled since the last read: their count, their sum and the first `cap` of their times; forgets them.
+static int profile_times(m1v_encoder *e, float *ms, int cap, int *launches, double *total_ms) {
+    HIP_TRY(hipSetDevice(e->device));
+    double sum = 0;
+    int n = 0;
+    for (size_t i = 0; i + 1 < e->ev_used; i += 2) {
+        HIP_TRY(hipEventSynchronize(e->ev[i + 1]));
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, e->ev[i], e->ev[i + 1]));
+        if (n < cap) ms[n] = t;
+        sum += t;
+        n++;
+    }
+    e->ev_used = 0;
+    if (launches) *launches = n;
+    if (total_ms) *total_ms = sum;
+    return M1V_OK;
+}
+
+// Makes the encoder's plan (plan_for) and (re)allocates what it needs.  New buffers are allocated FIRST and swapped in, together
+// with the plan they belong to, only when every allocation has succeeded: a failed call (the worst-case arena of
+// m1v_reserve_scratch is large) leaves the encoder as it was.  Every device allocation goes through plan_malloc: the
+// fault-injection hook reaches all of them.
+static int configure_path(m1v_encoder *e) {
+    Plan p;
+    if (const int rc = plan_for(*e, p)) return rc;
+    const int sets = e->pipelined ? 2 : 1;
+    struct Fresh {
+        m1v_encoder::Batch b;
+        bool new_scratch, new_meta, new_seg, new_fixed;
+    } fresh[2] = {};
+    uint32_t *fresh_order = nullptr;
+    const bool new_order = p.producer == Producer::tiles && e->tile_order_rows != p.tile_rows;
+    bool ok = true;
+    for (int i = 0; i < sets && ok; i++) {
+        const m1v_encoder::Batch &bt = e->batch[i];
+        Fresh &f = fresh[i];
+        f.new_scratch = p.scratch_bytes != bt.scratch_bytes || !bt.scratch;
+        f.new_meta = p.meta_bytes != 0 && (p.meta_bytes != bt.meta_bytes || !bt.run_meta); // (tiles and strips keep the array)
+        f.new_seg = p.seg_bytes != bt.seg_bytes || !bt.seg;
+        f.new_fixed = !bt.enc_done;
+        if (f.new_scratch) ok = plan_malloc(&f.b.scratch, p.scratch_bytes) == hipSuccess;
+        if (ok && f.new_meta) ok = plan_malloc(&f.b.run_meta, p.meta_bytes) == hipSuccess;
+        if (ok && f.new_seg) ok = plan_malloc(&f.b.seg, p.seg_bytes) == hipSuccess;
+        if (ok && f.new_fixed) {
+            for (m1v_encoder::Counters &c : f.b.ctr) ok = ok && counters_alloc(e, c);
+            ok = ok && hipEventCreateWithFlags(&f.b.gather_done, hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipEventCreateWithFlags(&f.b.enc_done, hipEventDisableTiming) == hipSuccess;
+        }
+    }
+    if (ok && new_order) {
+        std::vector<uint32_t> order;
+        tile_row_order_for(p.tile_rows, order);
+        ok = plan_malloc(&fresh_order, order.size() * sizeof(uint32_t)) == hipSuccess &&
+             hipMemcpy(fresh_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (!ok) {
+        for (Fresh &f : fresh) batch_free(f.b);
+        (void)hipFree(fresh_order);
+        (void)hipGetLastError();
+        return fail(M1V_E_HIP, "allocation failed (the encoder keeps its previous configuration)%s");
+    }
+    // ---- commit ----
+    for (int i = 0; i < sets; i++) {
+        m1v_encoder::Batch &bt = e->batch[i];
+        Fresh &f = fresh[i];
+        if (f.new_scratch) {
+            (void)hipFree(bt.scratch);
+            bt.scratch = f.b.scratch;
+            bt.scratch_bytes = p.scratch_bytes;
+        }
+        if (f.new_meta) {
+            (void)hipFree(bt.run_meta);
+            bt.run_meta = f.b.run_meta;
+            bt.meta_bytes = p.meta_bytes;
+        }
+        if (f.new_seg) {
+            (void)hipFree(bt.seg);
+            bt.seg = f.b.seg;
+            bt.seg_bytes = p.seg_bytes;
+        }
+        if (f.new_fixed) {
+            bt.ctr[0] = f.b.ctr[0];
+            bt.ctr[1] = f.b.ctr[1];
+            bt.turn = 0;
+            bt.poisoned = false;
+            bt.enc_done = f.b.enc_done;
+            bt.gather_done = f.b.gather_done;
+        }
+    }
+    if (new_order) {
+        (void)hipFree(e->d_tile_order);
+        e->d_tile_order = fresh_order;
+        e->tile_order_rows = p.tile_rows;
+    }
+    e->plan = p;
+    return M1V_OK;
+}
+
+// A setting that changes the plan: set behind everything queued on the device, and put back when the new plan cannot be set up
+template <typename T>
+static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const T before = e->*field;
+    e->*field = value;
+    const int rc = configure_path(e);
+    if (rc != M1V_OK) e->*field = before;
+    return rc;
+}
+
+extern "C" {
+
+const char *m1v_last_error(void) { return g_err; }
+
+int m1v_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int m1v_warm_up(int device) {
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipFree(nullptr)); // creates the context
+    hipFuncAttributes attr;    // loads this library's code object for the device
+    HIP_TRY(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&k_assemble<false>)));
+    return M1V_OK;
+}
+
+size_t m1v_file_prolog(uint8_t out[27]) {
+    static const uint8_t pack[9] = {0x00, 0x00, 0x01, 0xba, 0x21, 0x00, 0x01, 0x00, 0x01};
+    memcpy(out, pack, 9);
+    uint32_t rate = (2202035u & 0x3fffffu) | 0x400000u; // mpeg1_enc.c:14-16
+    rate = (rate << 1) | 1u;
+    out[9] = (uint8_t)(rate >> 16); out[10] = (uint8_t)(rate >> 8); out[11] = (uint8_t)rate;
+    uint8_t *s = out + 12;                                 // mpeg1_enc.c:24-44, packet_num 0xe6
+    s[0] = 0; s[1] = 0; s[2] = 1; s[3] = 0xbb; s[4] = 0; s[5] = 9;
+    s[6] = (uint8_t)(rate >> 16); s[7] = (uint8_t)(rate >> 8); s[8] = (uint8_t)rate;
+    s[9] = 0; s[10] = 0x21; s[11] = 0xff; s[12] = 0xe0; s[13] = 0xe0; s[14] = 0xe6;
+    return 27;
+}
+
+int m1v_create(m1v_encoder **out, int device, int width, int height, int channels,
+               int quality_factor, int mode, int max_frames) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    *out = nullptr;
+    if (width <= 0 || height <= 0 || channels < 3 || channels > 4 || max_frames <= 0)
+        return fail(M1V_E_ARG, "bad geometry%s");
+    if (mode != M1V_MODE_STRICT && mode != M1V_MODE_FULL) return fail(M1V_E_ARG, "bad mode%s");
+    int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96;
+    int ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
+    if (xe > width || ye > height)
+        return fail(M1V_E_ARG, "picture smaller than the 96x144 region the reference encodes%s");
+    if (xe == 0 || ye == 0) return fail(M1V_E_ARG, "picture smaller than one macroblock%s");
+    if ((unsigned long long)width * height * channels >= (1ull << 32))
+        return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+    int n = m1v_device_count();
+    if (n <= 0) return fail(M1V_E_NODEVICE, "no HIP device%s");
+    if (device < 0 || device >= n) return fail(M1V_E_ARG, "device index out of range%s");
+    HIP_TRY(hipSetDevice(device));
+
+    m1v_encoder *e = new m1v_encoder();
+    e->device = device;
+    e->qf = quality_factor;
+    e->mode = mode;
+    e->max_frames = max_frames;
+    Geometry &g = e->g;
+    g.W = width; g.H = height; g.C = channels;
+    g.n_strips = xe / 16; g.n_mbrows = ye / 16;
+    g.half_w = width / 2;
+    g.frame_bytes = (unsigned long long)width * height * channels;
+    unsigned long long strip_bits = 38ull + (unsigned long long)g.n_mbrows * (2 + 6 * kMaxBlockBits);
+    g.strip_cap = (uint32_t)((((strip_bits + 7) / 8) + 16 + 15) & ~15ull);
+    e->dense = g.n_mbrows * 6 >= kWave;
+    e->fast_ok = channels == 3 && (width % 8) == 0;
+
+    // Per-frame quality: the transposed reciprocal table of every quality ([100][64], frame_rq_t); Tables::rq_t is the row of the
+    // encoder's own quality, Tables::rq that row in natural order
+    const int own = encoder_quality(e);
+    std::vector<float> rq_all(100 * 64);
+    int min_ac = 0;
+    for (int qf = 1; qf <= 100; qf++) {
+        int q[64];
+        scaled_matrix(qf, q);
+        for (int u = 0; u < 8; u++)
+            for (int i = 0; i < 8; i++)
+                rq_all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)((1.0 / q[u * 8 + i]) * (1.0 + 1.0 / 1048576.0));
+        if (qf == own) min_ac = *std::min_element(q + 1, q + 64);
+    }
+    // One byte per staged level is exact iff no AC level can reach +-128.  |AC coefficient| of the
+    // reference's FDCT on u8 pixels is at most 1022 (127.5 * 8 + the +2 rounding bias, reached at (0,4), (4,0),
+    // (4,4); tests/test_host_tables.py::test_fdct_output_range), so 128 * (smallest AC divisor) >= 1024
+    // suffices: quality factors <= 76.
+    e->narrow = min_ac >= 8;
+    Tables *t = new Tables();
+    const float *rq_t = &rq_all[(size_t)(own - 1) * 64];
+    memcpy(t->rq_t, rq_t, sizeof t->rq_t);
+    for (int u = 0; u < 8; u++)
+        for (int i = 0; i < 8; i++) t->rq[u * 8 + i] = rq_t[i * 8 + u];
+    build_vlc_table(t->vlc);
+    for (int h = 0; h < 256; h++) build_frame_header(t->hdr[h], width, height, h);
+    const std::vector<uint32_t> sel((size_t)max_frames, (uint32_t)(own - 1) * 64u);
+
+    hipError_t err = hipMalloc(&e->d_tab, sizeof(Tables));
+    if (err == hipSuccess) err = hipMemcpy(e->d_tab, t, sizeof(Tables), hipMemcpyHostToDevice);
+    delete t;
+    if (err == hipSuccess) err = hipMalloc(&e->d_rq_all, rq_all.size() * sizeof(float));
+    if (err == hipSuccess) err = hipMemcpy(e->d_rq_all, rq_all.data(), rq_all.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMalloc(&e->d_qsel_own, sel.size() * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMemcpy(e->d_qsel_own, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMalloc(&e->d_qsel, sel.size() * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMemcpy(e->d_qsel, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
+#if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
+    if (err == hipSuccess) err = hipMalloc(&e->d_stamps, (32 + 8 * 65536) * 8); // [32] phase sums, then a timeline of 8 stamps per workgroup
+    if (err == hipSuccess) err = hipMemset(e->d_stamps, 0, (32 + 8 * 65536) * 8);
+#endif
+    if (err == hipSuccess) err = configure_path(e) == M1V_OK ? hipSuccess : hipErrorOutOfMemory;
+    for (const auto &by_mode : kProducerKernels)
+        for (const auto &by_staging : by_mode)
+            for (const void *kf : by_staging)
+                if (err == hipSuccess && kf) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (err != hipSuccess) {
+        fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
+        m1v_destroy(e);
+        return M1V_E_HIP;
+    }
+    *out = e;
+    return M1V_OK;
+}
+
+void m1v_destroy(m1v_encoder *e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
+    (void)hipFree(e->d_tab);
+    (void)hipFree(e->d_rq_all);
+    (void)hipFree(e->d_qsel_own);
+    (void)hipFree(e->d_qsel);
+    (void)hipFree(e->d_probe_sizes);
+    (void)hipFree(e->d_probe_status);
+    (void)hipFree(e->d_chosen);
+    for (m1v_encoder::Batch &bt : e->batch) batch_free(bt);
+    if (e->side) (void)hipStreamDestroy(e->side);
+    (void)hipFree(e->hp.d_in);
+    (void)hipFree(e->hp.d_out);
+    (void)hipFree(e->hp.d_planes);
+    (void)hipFree(e->hp.d_meta);
+    if (e->hp.copy_in) (void)hipStreamDestroy(e->hp.copy_in);
+    if (e->hp.work) (void)hipStreamDestroy(e->hp.work);
+    for (hipEvent_t ev : e->hp.uploaded)
+        if (ev) (void)hipEventDestroy(ev);
+    (void)hipFree(e->d_stamps);
+    (void)hipFree(e->d_tile_order);
+    delete e;
+}
+
+int m1v_strips(const m1v_encoder *e) { return e ? e->g.n_strips : 0; }
+int m1v_mb_rows(const m1v_encoder *e) { return e ? e->g.n_mbrows : 0; }
+size_t m1v_frame_bytes_in(const m1v_encoder *e) { return e ? (size_t)e->g.frame_bytes : 0; }
+
+size_t m1v_frame_bound_for(int width, int height, int mode) {
+    const int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96, ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
+    if (width <= 0 || height <= 0 || xe <= 0 || ye <= 0 || xe > width || ye > height) return 0;
+    const size_t strip_bits = 38 + (size_t)(ye / 16) * (2 + 6 * kMaxBlockBits);
+    return 44 + (size_t)(xe / 16) * ((strip_bits + 7) / 8) + 4;
+}
+
+size_t m1v_frame_bound(const m1v_encoder *e) { return e ? m1v_frame_bound_for(e->g.W, e->g.H, e->mode) : 0; }
+
+int m1v_debug_set_lds_words(m1v_encoder *e, int words) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    // (a small forced image sends many units to the overflow arena: M1V_STATUS_SCRATCH)
+    return reconfigure(e, &m1v_encoder::lds_words, words > 0 ? (words < 4 ? 4 : words) : 0);
+}
+
+int m1v_reserve_scratch(m1v_encoder *e, int worst_case) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->plan.producer == Producer::strips) return M1V_OK;
+    return reconfigure(e, &m1v_encoder::reserve_worst, worst_case != 0); // (on failure the previous arena is still in place)
+}
+
+size_t m1v_scratch_bytes(const m1v_encoder *e) { return e ? e->plan.scratch_bytes * (e->pipelined ? 2 : 1) : 0; }
+
+int m1v_set_pipelined(m1v_encoder *e, int enable) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (m1v_encoder::Batch &bt : e->batch) bt.gather_pending = false;
+    e->calls = 0;
+    if (enable && !e->side) {
+        // highest priority: the few memory-bound workgroups of layout + gather should take the first slots the (much longer,
+        // arithmetic-bound) encode kernel of the next batch frees, not queue behind its whole grid
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, greatest));
+    }
+    // (when the second set of buffers cannot be allocated the encoder stays as it was)
+    return reconfigure(e, &m1v_encoder::pipelined, enable != 0);
+}
+
+int m1v_flush(m1v_encoder *e, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    HIP_TRY(hipSetDevice(e->device));
+    // The mark stays set: a later m1v_encode_device on ANOTHER stream must still wait for this set's gather before its
+    // encode kernel overwrites the scratch (waiting for an event that has completed costs nothing).
+    for (m1v_encoder::Batch &bt : e->batch) {
+        if (e->pipelined && bt.poisoned) { // a failed call may have left an assembly on the internal stream without its event
+            HIP_TRY(hipEventRecord(bt.gather_done, e->side));
+            bt.gather_pending = true;
+        }
+        if (bt.gather_pending) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, bt.gather_done, 0));
+    }
+    return M1V_OK;
+}
+
+int m1v_debug_set_input_mode(m1v_encoder *e, int mode) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (mode != -1 && mode != 0 && mode != 2) return fail(M1V_E_ARG, "input mode must be -1 (auto), 0 (byte loads) or 2 (funnel)%s");
+    return reconfigure(e, &m1v_encoder::forced_mode, mode); // an input mode is a property of the run kernels: forcing one selects them
+}
+
+int m1v_debug_set_dense_threads(m1v_encoder *e, int threads) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (!e->dense) return M1V_OK;
+    // a run length is a property of the run kernels: forcing one selects them
+    return reconfigure(e, &m1v_encoder::forced_T, threads > 0 ? threads : 0);
+}
+
+int m1v_debug_set_path(m1v_encoder *e, int path) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (path < -1 || path > 1) return fail(M1V_E_ARG, "path must be -1 (by geometry), 0 (runs) or 1 (tiles)%s");
+    if (path == 1 && e->g.C != 3) return fail(M1V_E_ARG, "the tile kernel takes 3-channel pictures%s");
+    return reconfigure(e, &m1v_encoder::forced_path, path);
+}
+
+int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }
+
+void m1v_debug_fail_alloc(int nth) {
+    // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
+    const char *on = getenv("EC504_DEBUG_HOOKS");
+    g_fail_alloc_in = (on && on[0] == '1' && nth > 0) ? nth : 0;
+}
+
+void m1v_debug_fail_encode(int stage) {
+    // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
+    const char *on = getenv("EC504_DEBUG_HOOKS");
+    g_fail_encode_at = (on && on[0] == '1' && stage >= 1 && stage <= 3) ? stage : 0;
+}
+
+#if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
+// diagnostic builds only: read and clear the per-phase cycle sums
+int m1v_debug_read_stamps(m1v_encoder *e, unsigned long long out[32]) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, e->d_stamps, 32 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(e->d_stamps, 0, 32 * 8));
+    return M1V_OK;
+}
+// diagnostic builds only: the per-workgroup timeline of the last k_assemble launch (8 stamps each)
+int m1v_debug_read_timeline(m1v_encoder *e, unsigned long long *out, int workgroups) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, e->d_stamps + 32, (size_t)(workgroups > 65536 ? 65536 : workgroups) * 64, hipMemcpyDeviceToHost));
+    return M1V_OK;
+}
+#endif
+
+int m1v_profile_enable(m1v_encoder *e, int enable) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    e->prof = enable != 0;
+    e->ev_used = 0;
+    return M1V_OK;
+}
+
+int m1v_profile_read(m1v_encoder *e, int *launches, double *total_ms) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    return profile_times(e, nullptr, 0, launches, total_ms);
+}
+
+int m1v_profile_read_times(m1v_encoder *e, float *ms, int cap, int *launches) {
+    if (!e || (cap > 0 && !ms)) return fail(M1V_E_ARG, "bad argument%s");
+    return profile_times(e, ms, cap, launches, nullptr);
+}
+
+int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                      uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                      uint32_t *d_status, void *stream) {
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status,
+                        stream);
+}
+
+int m1v_encode_quality_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                              uint64_t *d_total, uint32_t *d_status, void *stream) {
+    QualityArgs qa = {};
+    qa.quality = d_quality;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, d_quality ? &qa : nullptr, false, d_out, out_cap, d_frame_sizes,
+                        d_total, d_status, stream);
+}
+
+int m1v_frame_sizes_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *d_quality,
+                           uint64_t *d_frame_sizes, uint32_t *d_status, void *stream) {
+    QualityArgs qa = {};
+    qa.quality = d_quality;
+    return encode_batch(e, d_rgb, n_frames, 0, d_quality ? &qa : nullptr, true, nullptr, 0, d_frame_sizes, nullptr, d_status,
+                        stream);
+}
+
+int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                             const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
+                             const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
+                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                             uint32_t *d_status, void *stream) {
+    if (!e || !candidates) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
+    for (int k = 0; k < n_candidates; k++)
+        if (candidates[k] < 1 || candidates[k] > encoder_quality(e) || (k > 0 && candidates[k] <= candidates[k - 1]))
+            return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    // 1. the record size of every frame at every candidate (each probe is a complete call: its own counter hand-over)
+    for (int k = 0; k < n_candidates; k++) {
+        QualityArgs qa = {};
+        qa.uniform = candidates[k];
+        const int rc = encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, true, nullptr, 0,
+                                    (uint64_t *)(e->d_probe_sizes + (size_t)k * e->max_frames), nullptr, e->d_probe_status + k, stream);
+        if (rc != M1V_OK) return rc;
+    }
+    // (pipelined: the probes' sizes are written on the internal stream)
+    if (e->pipelined) {
+        const int rc = m1v_flush(e, stream);
+        if (rc != M1V_OK) return rc;
+    }
+    // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
+    QualityArgs qa = {};
+    qa.probe_sizes = e->d_probe_sizes;
+    qa.stride = e->max_frames;
+    qa.n_cand = n_candidates;
+    for (int k = 0; k < n_candidates; k++) qa.cand[k] = candidates[k];
+    qa.budget = (const unsigned long long *)d_max_frame_bytes;
+    qa.max_bytes = max_frame_bytes;
+    qa.probe_status = e->d_probe_status;
+    qa.chosen = d_chosen ? d_chosen : e->d_chosen;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+}
+
+// ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------
+struct m1v_delivery {
+    m1v_encoder *e;
+    int device; // (the encoder may be destroyed before the delivery object is)
+    size_t cap;
+    int max_frames;
+    uint8_t *d_out[2], *h_out[2];
+    unsigned long long *d_meta[2], *h_meta[2];   // [0] total bytes, [1] status word (low 32 bits)
+    unsigned long long *d_sizes[2], *h_sizes[2];
+    hipStream_t side;
+    hipEvent_t encoded[2], counted[2], delivered[2];
+    bool in_flight[2];                            // delivered[b] has been recorded and not yet been waited for by an encode
+    struct {
+        const uint8_t *rgb;
+        int n, first;
+    } args[2];
+    int pending;                                  // slot whose batch is encoded (or encoding) and not yet on its way, or -1
+    unsigned step_no;
+};
+
+static int delivery_start(m1v_delivery *d, int b) { // the copy of slot b's batch, behind its encode
+    m1v_encoder *e = d->e;
+    HIP_TRY(hipStreamWaitEvent(d->side, d->encoded[b], 0));
+    HIP_TRY(hipMemcpyAsync(d->h_meta[b], d->d_meta[b], 16, hipMemcpyDeviceToHost, d->side));
+    HIP_TRY(hipEventRecord(d->counted[b], d->side));
+    HIP_TRY(hipEventSynchronize(d->counted[b])); // the step's only host wait: the next encode is already queued
+    unsigned long long total = d->h_meta[b][0];
+    uint32_t status = (uint32_t)d->h_meta[b][1];
+    if (status == M1V_STATUS_SCRATCH) { // recoverable: the worst case reserved (waits for the device), the same frames again
+        int rc = m1v_reserve_scratch(e, 1);
+        if (rc != M1V_OK) return rc;
+        rc = m1v_encode_device(e, d->args[b].rgb, d->args[b].n, d->args[b].first, d->d_out[b], d->cap, (uint64_t *)d->d_sizes[b],
+                               (uint64_t *)d->d_meta[b], reinterpret_cast<uint32_t *>(d->d_meta[b] + 1), d->side);
+        if (rc != M1V_OK) return rc;
+        if (e->pipelined) HIP_TRY(hipStreamWaitEvent(d->side, e->batch[(e->calls - 1u) & 1u].gather_done, 0));
+        HIP_TRY(hipMemcpyAsync(d->h_meta[b], d->d_meta[b], 16, hipMemcpyDeviceToHost, d->side));
+        HIP_TRY(hipStreamSynchronize(d->side));
+        total = d->h_meta[b][0];
+        status = (uint32_t)d->h_meta[b][1];
+    }
+    if (status & M1V_STATUS_UNENCODABLE) return fail(M1V_E_UNENCODABLE, "a level of 256 or more: the reference cannot code this batch%s");
+    if (status & M1V_STATUS_NOSPACE) return fail(M1V_E_NOSPACE, "the delivery's output buffers are too small for this batch%s");
+    if (status) return fail(M1V_E_SCRATCH, "the batch ran out of scratch twice%s");
+    if (total > d->cap) return fail(M1V_E_NOSPACE, "the delivery's output buffers are too small for this batch%s");
+    HIP_TRY(hipMemcpyAsync(d->h_out[b], d->d_out[b], total, hipMemcpyDeviceToHost, d->side));
+    HIP_TRY(hipMemcpyAsync(d->h_sizes[b], d->d_sizes[b], (size_t)d->args[b].n * 8, hipMemcpyDeviceToHost, d->side));
+    HIP_TRY(hipEventRecord(d->delivered[b], d->side));
+    d->in_flight[b] = true;
+    return b;
+}
+
+int m1v_delivery_create(m1v_encoder *e, size_t out_cap, m1v_delivery **out) {
+    if (!e || !out) return fail(M1V_E_ARG, "null pointer%s");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(e->device));
+    m1v_delivery *d = new m1v_delivery();
+    memset(d, 0, sizeof *d);
+    d->e = e;
+    d->device = e->device;
+    d->max_frames = e->max_frames;
+    d->cap = out_cap ? out_cap : (size_t)e->max_frames * m1v_frame_bound(e);
+    d->pending = -1;
+    hipError_t err = hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking);
+    for (int b = 0; b < 2; b++) {
+        if (err == hipSuccess) err = hipMalloc(&d->d_out[b], d->cap);
+        if (err == hipSuccess) err = hipMalloc(&d->d_meta[b], 16);
+        if (err == hipSuccess) err = hipMemset(d->d_meta[b], 0, 16);
+        if (err == hipSuccess) err = hipMalloc(&d->d_sizes[b], (size_t)e->max_frames * 8);
+        if (err == hipSuccess) err = hipHostMalloc(&d->h_out[b], d->cap, hipHostMallocDefault);
+        if (err == hipSuccess) err = hipHostMalloc(&d->h_meta[b], 16, hipHostMallocDefault);
+        if (err == hipSuccess) err = hipHostMalloc(&d->h_sizes[b], (size_t)e->max_frames * 8, hipHostMallocDefault);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->encoded[b], hipEventDisableTiming);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->counted[b], hipEventDisableTiming);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&d->delivered[b], hipEventDisableTiming);
+    }
+    if (err != hipSuccess) {
+        fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
+        m1v_delivery_destroy(d);
+        return M1V_E_HIP;
+    }
+    *out = d;
+    return M1V_OK;
+}
+
+void m1v_delivery_destroy(m1v_delivery *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (d->side) (void)hipStreamSynchronize(d->side);
+    for (int b = 0; b < 2; b++) {
+        (void)hipFree(d->d_out[b]);
+        (void)hipFree(d->d_meta[b]);
+        (void)hipFree(d->d_sizes[b]);
+        (void)hipHostFree(d->h_out[b]);
+        (void)hipHostFree(d->h_meta[b]);
+        (void)hipHostFree(d->h_sizes[b]);
+        if (d->encoded[b]) (void)hipEventDestroy(d->encoded[b]);
+        if (d->counted[b]) (void)hipEventDestroy(d->counted[b]);
+        if (d->delivered[b]) (void)hipEventDestroy(d->delivered[b]);
+    }
+    if (d->side) (void)hipStreamDestroy(d->side);
+    delete d;
+}
+
+int m1v_delivery_step(m1v_delivery *d, const uint8_t *d_rgb, int n_frames, int first_frame_index, void *stream) {
+    if (!d || !d_rgb) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_frames <= 0 || n_frames > d->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    m1v_encoder *e = d->e;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(e->device));
+    const int b = (int)(d->step_no++ & 1u);
+    if (d->in_flight[b]) { // slot b's previous batch has left for the host before its buffers are written again
+        HIP_TRY(hipStreamWaitEvent(st, d->delivered[b], 0));
+        d->in_flight[b] = false;
+    }
+    const int rc = m1v_encode_device(e, d_rgb, n_frames, first_frame_index, d->d_out[b], d->cap, (uint64_t *)d->d_sizes[b],
+                                     (uint64_t *)d->d_meta[b], reinterpret_cast<uint32_t *>(d->d_meta[b] + 1), st);
+    if (rc != M1V_OK) { // slot b holds no batch: the next step uses it again, the pending batch in the other slot is untouched
+        d->step_no--;
+        return rc;
+    }
+    if (e->pipelined) HIP_TRY(m1v_flush(e, st) == M1V_OK ? hipSuccess : hipErrorUnknown);
+    HIP_TRY(hipEventRecord(d->encoded[b], st));
+    d->args[b].rgb = d_rgb;
+    d->args[b].n = n_frames;
+    d->args[b].first = first_frame_index;
+    const int before = d->pending;
+    d->pending = b;
+    return before >= 0 ? delivery_start(d, before) : (int)M1V_DELIVERY_NONE;
+}
+
+int m1v_delivery_flush(m1v_delivery *d) {
+    if (!d) return fail(M1V_E_ARG, "null pointer%s");
+    HIP_TRY(hipSetDevice(d->e->device));
+    const int before = d->pending;
+    d->pending = -1;
+    return before >= 0 ? delivery_start(d, before) : (int)M1V_DELIVERY_NONE;
+}
+
+uint64_t m1v_delivery_bytes(const m1v_delivery *d, int slot) { return d && slot >= 0 && slot <= 1 ? d->h_meta[slot][0] : 0; }
+
+int m1v_delivery_wait(m1v_delivery *d, int slot, const uint8_t **host, uint64_t *bytes, const uint64_t **frame_sizes) {
+    if (!d || slot < 0 || slot > 1) return fail(M1V_E_ARG, "bad slot%s");
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipEventSynchronize(d->delivered[slot]));
+    if (host) *host = d->h_out[slot];
+    if (bytes) *bytes = d->h_meta[slot][0];
+    if (frame_sizes) *frame_sizes = (const uint64_t *)d->h_sizes[slot];
+    return M1V_OK;
+}
+
+/* Pinned host memory for callers of the host-buffer entry points: H2D/D2H copies from it run at the PCIe
+ * rate instead of being staged by the runtime. */
+void *m1v_alloc_host(size_t bytes) {
+    void *p = nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+    return p;
+}
+void *m1v_alloc_device(size_t bytes) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return p;
+}
+void m1v_free_device(void *p) { (void)hipFree(p); }
+void m1v_free_host(void *p) {
+    if (p) (void)hipHostFree(p);
+}
+
+long m1v_encode_planes_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first_frame_index,
+                            uint8_t *out, size_t out_cap, uint64_t *frame_sizes, uint8_t *planes) {
+    if (!e || !rgb || !out) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (n_frames == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t frame_in = (size_t)e->g.frame_bytes, frame_planes = (size_t)e->g.W * e->g.H * 3;
+    size_t in_bytes = frame_in * n_frames;
+    size_t bound = m1v_frame_bound(e) * (size_t)n_frames;
+    size_t dcap = out_cap < bound ? out_cap : bound;
+    m1v_encoder::HostPath &hp = e->hp;
+    HIP_TRY(ensure_device(&hp.d_in, &hp.in_cap, in_bytes));
+    HIP_TRY(ensure_device(&hp.d_out, &hp.out_cap, dcap));
+    HIP_TRY(ensure_device(&hp.d_meta, &hp.meta_cap, (size_t)(n_frames + 2) * 8)); // [n] sizes, total, status
+    if (planes) HIP_TRY(ensure_device(&hp.d_planes, &hp.planes_cap, frame_planes * n_frames));
+    if (!hp.copy_in) { // all or nothing: a half-built set must not survive into the next call
+        hipError_t err = hipStreamCreateWithFlags(&hp.copy_in, hipStreamNonBlocking);
+        if (err == hipSuccess) err = hipStreamCreateWithFlags(&hp.work, hipStreamNonBlocking);
+        for (hipEvent_t &ev : hp.uploaded)
+            if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (err != hipSuccess) {
+            if (hp.copy_in) (void)hipStreamDestroy(hp.copy_in);
+            if (hp.work) (void)hipStreamDestroy(hp.work);
+            for (hipEvent_t &ev : hp.uploaded) {
+                if (ev) (void)hipEventDestroy(ev);
+                ev = nullptr;
+            }
+            hp.copy_in = hp.work = nullptr;
+            return fail(M1V_E_HIP, "stream creation failed: %s", hipGetErrorString(err));
+        }
+    }
+    // From here on copies to and from the caller's buffers are in flight: every error return first waits for both
+    // streams, so that the caller may free (or reuse) rgb / planes / out as soon as this function has returned.
+    auto drained = [&](int rc) {
+        (void)hipStreamSynchronize(hp.copy_in);
+        (void)hipStreamSynchronize(hp.work);
+        return rc;
+    };
+#define HIP_TRY_DRAIN(expr)                                                                        \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return drained(fail(M1V_E_HIP, #expr ": %s", hipGetErrorString(e_))); \
+    } while (0)
+    // copy_in: H2D half A, H2D half B.   work: [planes A -> host] while B uploads, [planes B -> host], encode all.
+    const int half[3] = {0, planes && n_frames > 1 ? n_frames / 2 : n_frames, n_frames};
+    for (int h = 0; h < 2; h++) {
+        int f0 = half[h], nf = half[h + 1] - half[h];
+        if (nf == 0) continue;
+        HIP_TRY_DRAIN(hipMemcpyAsync(hp.d_in + frame_in * f0, rgb + frame_in * f0, frame_in * nf, hipMemcpyHostToDevice, hp.copy_in));
+        HIP_TRY_DRAIN(hipEventRecord(hp.uploaded[h], hp.copy_in));
+        HIP_TRY_DRAIN(hipStreamWaitEvent(hp.work, hp.uploaded[h], 0));
+        if (planes) {
+            int rc = m1v_convert_device(e, hp.d_in + frame_in * f0, nf, hp.d_planes + frame_planes * f0, hp.work);
+            if (rc != M1V_OK) return drained(rc);
+            HIP_TRY_DRAIN(hipMemcpyAsync(planes + frame_planes * f0, hp.d_planes + frame_planes * f0, frame_planes * nf,
+                                   hipMemcpyDeviceToHost, hp.work));
+        }
+    }
+    std::vector<unsigned long long> meta((size_t)n_frames + 2);
+    uint32_t status = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        int r = m1v_encode_device(e, hp.d_in, n_frames, first_frame_index, hp.d_out, dcap, (uint64_t *)hp.d_meta,
+                                  (uint64_t *)(hp.d_meta + n_frames), (uint32_t *)(hp.d_meta + n_frames + 1), hp.work);
+        if (r != M1V_OK) return drained(r);
+        if (m1v_flush(e, hp.work) != M1V_OK) return drained(M1V_E_HIP);
+        HIP_TRY_DRAIN(hipMemcpyAsync(meta.data(), hp.d_meta, meta.size() * 8, hipMemcpyDeviceToHost, hp.work));
+        HIP_TRY_DRAIN(hipStreamSynchronize(hp.work));
+        status = (uint32_t)meta[(size_t)n_frames + 1];
+        if (!(status & M1V_STATUS_SCRATCH) || attempt == 1) break;
+        // more runs outgrew their compact scratch slot than the overflow arena holds: reserve the worst case, encode again
+        int rr = m1v_reserve_scratch(e, 1);
+        if (rr != M1V_OK) return drained(rr);
+    }
+    if (status & M1V_STATUS_SCRATCH) return drained(fail(M1V_E_SCRATCH, "scratch exhausted%s"));
+    unsigned long long total = meta[n_frames];
+    if (status & M1V_STATUS_UNENCODABLE)
+        return fail(M1V_E_UNENCODABLE, "an AC level has |level| >= 256 (the reference crashes here)%s");
+    if ((status & M1V_STATUS_NOSPACE) || total > out_cap) return fail(M1V_E_NOSPACE, "output buffer too small%s");
+    HIP_TRY_DRAIN(hipMemcpy(out, hp.d_out, total, hipMemcpyDeviceToHost));
+    if (frame_sizes)
+        for (int f = 0; f < n_frames; f++) frame_sizes[f] = meta[f];
+    return (long)total;
+#undef HIP_TRY_DRAIN
+}
+
+long m1v_encode_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first_frame_index,
+                     uint8_t *out, size_t out_cap, uint64_t *frame_sizes) {
+    return m1v_encode_planes_host(e, rgb, n_frames, first_frame_index, out, out_cap, frame_sizes, nullptr);
+}
+
+int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int16_t *d_coeffs,
+                            void *stream) {
+    if (!e || !d_rgb || !d_coeffs || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (n_frames == 0) return M1V_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    CoefArgs a;
+    a.g = e->g;
+    a.rgb = d_rgb;
+    a.tab = e->d_tab;
+    a.out = d_coeffs;
+    a.n_frames = n_frames;
+    if (e->g.C == 3 && e->forced_mode < 0 && e->forced_path != 0) { // tiles (any width, any alignment); the run-shaped kernel serves 4 channels
+        CoefTileArgs t;
+        t.g = e->g;
+        t.rgb = d_rgb;
+        t.tab = e->d_tab;
+        t.out = d_coeffs;
+        t.n_frames = n_frames;
+        t.tile_cols = (e->g.n_strips + kTileStrips - 1) / kTileStrips;
+        t.tile_rows = (e->g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
+        t.tiles_per_frame = t.tile_cols * t.tile_rows;
+        t.region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * kCoefStride * 4)) + 15u) & ~15u;
+        hipLaunchKernelGGL((k_coefficient_tiles<M1V_TILE_RING>), dim3((unsigned)((size_t)n_frames * t.tiles_per_frame)),
+                           dim3(kTileThreads), 3 * (size_t)t.region, (hipStream_t)stream, t);
+        HIP_TRY(hipGetLastError());
+        return M1V_OK;
+    }
+    int bps = e->g.n_mbrows * 6;
+    dim3 grid((bps + 255) / 256, e->g.n_strips, n_frames);
+    if (fast_path(e, d_rgb))
+        hipLaunchKernelGGL(k_coefficients<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(k_coefficients<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+int m1v_convert_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, uint8_t *d_planes,
+                       void *stream) {
+    if (!e || !d_rgb || !d_planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (n_frames == 0) return M1V_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    unsigned long long npx = (unsigned long long)e->g.W * e->g.H;
+    unsigned long long total = npx * n_frames;
+    if (npx % 4 == 0 && (((uintptr_t)d_rgb | (uintptr_t)d_planes) & 3) == 0) { // four pixels per lane, dword loads and stores
+        total /= 4;
+        unsigned blocks = (unsigned)((total + 255) / 256 > 131072 ? 131072 : (total + 255) / 256);
+        if (e->g.C == 3)
+            hipLaunchKernelGGL(k_convert4<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_rgb,
+                               npx / 4, n_frames, (uint32_t *)d_planes);
+        else
+            hipLaunchKernelGGL(k_convert4<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_rgb,
+                               npx / 4, n_frames, (uint32_t *)d_planes);
+        HIP_TRY(hipGetLastError());
+        return M1V_OK;
+    }
+    unsigned blocks = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
+    hipLaunchKernelGGL(k_convert, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rgb, e->g.C, npx,
+                       n_frames, d_planes);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+int m1v_convert_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, uint8_t *planes) {
+    if (!e || !rgb || !planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (n_frames == 0) return M1V_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    size_t in_bytes = (size_t)e->g.frame_bytes * n_frames;
+    size_t out_bytes = (size_t)e->g.W * e->g.H * 3 * n_frames;
+    m1v_encoder::HostPath &hp = e->hp;
+    HIP_TRY(ensure_device(&hp.d_in, &hp.in_cap, in_bytes));
+    HIP_TRY(ensure_device(&hp.d_planes, &hp.planes_cap, out_bytes));
+    HIP_TRY(hipMemcpy(hp.d_in, rgb, in_bytes, hipMemcpyHostToDevice));
+    int rc = m1v_convert_device(e, hp.d_in, n_frames, hp.d_planes, nullptr);
+    if (rc != M1V_OK) return rc;
+    HIP_TRY(hipMemcpy(planes, hp.d_planes, out_bytes, hipMemcpyDeviceToHost));
+    return M1V_OK;
+}
+
+int m1v_subsample_device(m1v_encoder *e, const uint8_t *d_cb, const uint8_t *d_cr, uint8_t *d_cb_sub,
+                         uint8_t *d_cr_sub, void *stream) {
+    if (!e || !d_cb || !d_cr || !d_cb_sub || !d_cr_sub) return fail(M1V_E_ARG, "bad argument%s");
+    if ((e->g.W | e->g.H) & 1) return fail(M1V_E_ARG, "odd dimensions: the reference reads out of bounds%s");
+    HIP_TRY(hipSetDevice(e->device));
+    int n = (e->g.W / 2) * (e->g.H / 2);
+    hipLaunchKernelGGL(k_subsample, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_cb, d_cr,
+                       e->g.W, e->g.H, d_cb_sub, d_cr_sub);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint64_t seed,
+                     uint64_t first_frame_index, void *stream) {
+    if (!d_rgb || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (n_frames == 0 || bytes_per_frame == 0) return M1V_OK;
+    unsigned long long total = ((bytes_per_frame + 7) / 8) * (unsigned long long)n_frames;
+    unsigned blocks = (unsigned)((total + 255) / 256 > 262144 ? 262144 : (total + 255) / 256);
+    hipLaunchKernelGGL(k_synth, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rgb,
+                       (unsigned long long)bytes_per_frame, n_frames, (unsigned long long)seed,
+                       (unsigned long long)first_frame_index);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+} // extern "C"

@@ -183,7 +183,7 @@ def test_failed_call_leaves_the_encoder_correct(torch_cuda, orc, producer, pipel
     enc.close()
 
 
-@pytest.mark.parametrize("producer", ["tiles", "runs"])
+@pytest.mark.parametrize("producer", ["tiles", "runs", "strips"])
 def test_oversized_lds_image_is_refused_when_set(torch_cuda, orc, producer):
     """A forced LDS image that cannot launch (41000 words: more than the 160 KiB of a workgroup) is refused by
     m1v_debug_set_lds_words itself (the budget the encode checks before each launch is checked when the image is set), and
