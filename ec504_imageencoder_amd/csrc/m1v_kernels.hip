@@ -1238,10 +1238,11 @@ __global__ __launch_bounds__(256) void k_dense_frame_layout(DenseGeom d, int seg
     if (threadIdx.x == 0) frame_bytes[f] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
+constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
+
 #include "m1v_tiles.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
-constexpr int kMaxCandidates = 8;
 struct QualityArgs {
     const uint8_t *quality;                  // [frame] the caller's qualities, or null
     int uniform;                             // the quality of every frame when `quality` and `probe_sizes` are null
@@ -1500,6 +1501,8 @@ struct Plan {
     size_t scratch_bytes, meta_bytes, seg_bytes; // per batch state (meta: run metadata, dense only)
     int segs;               // segments per strip: tile rows (tiles), or the most runs a strip can touch (run kernels)
     int asm_group, asm_lanes_log2; // k_assemble: strips per workgroup, lanes per segment
+    uint32_t table_region;  // tiles: k_size_table_tiles' LDS bytes of a wave's ring / staging region
+    size_t table_lds_bytes; //        and its dynamic LDS
 };
 
 struct m1v_encoder {
@@ -1530,6 +1533,14 @@ struct m1v_encoder {
     unsigned long long *d_probe_sizes = nullptr;
     uint32_t *d_probe_status = nullptr;
     uint8_t *d_chosen = nullptr;
+    int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
+    // The size table's counters (3-channel encoders): k_size_table_tiles adds, k_size_table_sizes reads and clears what it added.
+    struct TableCounters {
+        unsigned long long *strip_ctr = nullptr;   // [kMaxCandidates][max_frames][strip]
+        unsigned long long *frame_bytes = nullptr; // [kMaxCandidates][max_frames]
+        uint32_t *words = nullptr;                 // [kMaxCandidates] status words
+        bool poisoned = false;                     // a call returned an error after its probe may have added: clear in full
+    } table;
     // What an encode kernel adds to and k_assemble reads.  Two sets per Batch, taken in turns: the assemble kernel of call j clears
     // the set call j + 1 will add to (the one call j - 1 used), so no launch and no memset stands between two batches.
     struct Counters {
@@ -1630,6 +1641,10 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
         p.image_words = (p.image_words + 3) & ~3; // cleared 16 bytes per lane
         p.lds_bytes = (size_t)kTileFixedWords * 4 + 2 * (size_t)p.luma_region + p.chroma_region + (size_t)p.image_words * 4;
         p.segs = p.tile_rows;
+        // the size table: the ring, or the staged levels at the widest quality the encoder allows, per wave; no image
+        p.table_region = p.luma_region;
+        p.table_lds_bytes = (size_t)kTableFixedWords * 4 + 3 * (size_t)p.table_region;
+        if (p.table_lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the size table does not fit%s");
     } else if (e.dense) {
         const int T = e.forced_T > 0 ? e.forced_T : (bps >= 256 ? 256 : (bps / kWave) * kWave);
         if (T < kWave || T > 384 || T % kWave || T > bps) return fail(M1V_E_ARG, "bad dense run length%s");
@@ -1700,10 +1715,15 @@ static const void *const kProducerKernels[3][4][2] = {
     {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
      {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
 
+// The size-table kernel of the tile path, [narrow staging] (m1v_create raises their dynamic LDS limit)
+static const void *const kTableKernels[2] = {(const void *)&k_size_table_tiles<false, M1V_TILE_RING>,
+                                             (const void *)&k_size_table_tiles<true, M1V_TILE_RING>};
+
 // defined in m1v_runtime.h
 static int profile_event(m1v_encoder *e, hipStream_t st);
 static int fail_encode_at(int stage);
 static hipError_t counters_clear(const m1v_encoder *e, m1v_encoder::Counters &c, hipStream_t st);
+static hipError_t table_clear(const m1v_encoder *e, hipStream_t st);
 
 static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
     return e->fast_ok && ((uintptr_t)d_rgb & 3) == 0;
@@ -1943,6 +1963,70 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         HIP_TRY(hipEventRecord(bt.gather_done, gs));
         bt.gather_pending = true;
     }
+    poison.flag = nullptr;
+    return M1V_OK;
+}
+
+
+// The size table on the tile path: k_size_table_tiles, then k_size_table_sizes, both on the caller's stream (no Batch, no
+// scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
+// sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
+static int size_table_tiles(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
+                            unsigned long long *sizes, size_t stride, uint32_t *status, hipStream_t st) {
+    HIP_TRY(hipSetDevice(e->device));
+    m1v_encoder::TableCounters &tc = e->table;
+    const Plan &p = e->plan;
+    if (!tc.strip_ctr || p.producer != Producer::tiles) return fail(M1V_E_HIP, "the encoder has no size-table counters%s");
+    if (tc.poisoned) { // the last call failed after its probe kernel may have added: clear every counter first
+        HIP_TRY(table_clear(e, st));
+        tc.poisoned = false;
+    }
+    if (n_frames == 0) return M1V_OK;
+    struct PoisonOnReturn {
+        bool *flag;
+        ~PoisonOnReturn() { if (flag) *flag = true; }
+    } poison{&tc.poisoned};
+    if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
+    const Geometry &g = e->g;
+    TableArgs a;
+    a.g = g;
+    a.rgb = d_rgb;
+    a.tab = e->d_tab;
+    a.rq_all = e->d_rq_all;
+    for (int k = 0; k < kMaxCandidates; k++) a.qoff[k] = k < n_q ? (uint32_t)(qualities[k] - 1) * 64u : 0u;
+    a.n_q = n_q;
+    a.strip_ctr = tc.strip_ctr;
+    a.frame_bytes = tc.frame_bytes;
+    a.status = tc.words;
+    a.n_frames = n_frames;
+    a.tile_cols = p.tile_cols;
+    a.tile_rows = p.tile_rows;
+    a.tiles_per_frame = p.units;
+    const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.units;
+    a.div_group = div_magic(8u * (uint32_t)p.units, units);
+    a.div_frame = div_magic((uint32_t)p.units, units);
+    a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.units);
+    a.tile_row_order = e->d_tile_order;
+    a.region = p.table_region;
+    void *args[] = {&a};
+    const void *kernel = kTableKernels[qualities[n_q - 1] <= e->narrow_q ? 1 : 0];
+    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
+    (void)hipLaunchKernel(kernel, dim3((unsigned)units), dim3((unsigned)kTileThreads), args, p.table_lds_bytes, st);
+    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
+    HIP_TRY(hipGetLastError());
+    if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
+    TableSizesArgs sa;
+    sa.n_frames = n_frames;
+    sa.n_strips = g.n_strips;
+    sa.strip_ctr = tc.strip_ctr;
+    sa.frame_bytes = tc.frame_bytes;
+    sa.status = tc.words;
+    sa.out_sizes = sizes;
+    sa.stride = stride;
+    sa.out_status = status;
+    hipLaunchKernelGGL(k_size_table_sizes, dim3((unsigned)n_frames, (unsigned)n_q), dim3(256), 0, st, sa);
+    HIP_TRY(hipGetLastError());
+    if (fail_encode_at(3) != M1V_OK) return M1V_E_HIP;
     poison.flag = nullptr;
     return M1V_OK;
 }

@@ -138,6 +138,16 @@ static void counters_free(m1v_encoder::Counters &c) {
     (void)hipFree(c.words);
 }
 
+// The size table's counters, cleared in full on a stream
+static hipError_t table_clear(const m1v_encoder *e, hipStream_t st) {
+    const m1v_encoder::TableCounters &t = e->table;
+    const size_t kf = (size_t)kMaxCandidates * e->max_frames;
+    hipError_t err = hipMemsetAsync(t.strip_ctr, 0, kf * e->g.n_strips * 8, st);
+    if (err == hipSuccess) err = hipMemsetAsync(t.frame_bytes, 0, kf * 8, st);
+    if (err == hipSuccess) err = hipMemsetAsync(t.words, 0, kMaxCandidates * sizeof(uint32_t), st);
+    return err;
+}
+
 static void batch_free(m1v_encoder::Batch &bt) {
     (void)hipFree(bt.scratch);
     (void)hipFree(bt.run_meta);
@@ -344,7 +354,9 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
         for (int u = 0; u < 8; u++)
             for (int i = 0; i < 8; i++)
                 rq_all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)((1.0 / q[u * 8 + i]) * (1.0 + 1.0 / 1048576.0));
-        if (qf == own) min_ac = *std::min_element(q + 1, q + 64);
+        const int ac = *std::min_element(q + 1, q + 64);
+        if (qf == own) min_ac = ac;
+        if (ac >= 8) e->narrow_q = qf; // (the divisors shrink as the quality grows)
     }
     // One byte per staged level is exact iff no AC level can reach +-128.  |AC coefficient| of the
     // reference's FDCT on u8 pixels is at most 1022 (127.5 * 8 + the +2 rounding bias, reached at (0,4), (4,0),
@@ -372,6 +384,14 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
+    if (channels == 3) { // the size table's counters (tile path), clear
+        const size_t kf = (size_t)kMaxCandidates * max_frames;
+        if (err == hipSuccess) err = hipMalloc(&e->table.strip_ctr, kf * g.n_strips * 8);
+        if (err == hipSuccess) err = hipMalloc(&e->table.frame_bytes, kf * 8);
+        if (err == hipSuccess) err = hipMalloc(&e->table.words, kMaxCandidates * sizeof(uint32_t));
+        if (err == hipSuccess) err = table_clear(e, nullptr);
+        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+    }
 #if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
     if (err == hipSuccess) err = hipMalloc(&e->d_stamps, (32 + 8 * 65536) * 8); // [32] phase sums, then a timeline of 8 stamps per workgroup
     if (err == hipSuccess) err = hipMemset(e->d_stamps, 0, (32 + 8 * 65536) * 8);
@@ -381,6 +401,8 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
         for (const auto &by_staging : by_mode)
             for (const void *kf : by_staging)
                 if (err == hipSuccess && kf) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const void *kf : kTableKernels)
+        if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err != hipSuccess) {
         fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
         m1v_destroy(e);
@@ -401,6 +423,9 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipFree(e->d_probe_sizes);
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
+    (void)hipFree(e->table.strip_ctr);
+    (void)hipFree(e->table.frame_bytes);
+    (void)hipFree(e->table.words);
     for (m1v_encoder::Batch &bt : e->batch) batch_free(bt);
     if (e->side) (void)hipStreamDestroy(e->side);
     (void)hipFree(e->hp.d_in);
@@ -568,31 +593,56 @@ int m1v_frame_sizes_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, c
                         stream);
 }
 
+// A list of 1..8 strictly increasing qualities, each within 1 .. the encoder's quality factor
+static int check_qualities(const m1v_encoder *e, const uint8_t *q, int n) {
+    if (!q) return fail(M1V_E_ARG, "null pointer%s");
+    if (n < 1 || n > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
+    for (int k = 0; k < n; k++)
+        if (q[k] < 1 || q[k] > encoder_quality(e) || (k > 0 && q[k] <= q[k - 1]))
+            return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
+    return M1V_OK;
+}
+
+// sizes[k * stride + frame] and status[k] of every quality: one k_size_table_tiles pass on the tile path; on the run path one
+// probe call (m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that
+// every row is complete in stream order.
+static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
+                      unsigned long long *sizes, size_t stride, uint32_t *status, void *stream) {
+    if (e->plan.producer == Producer::tiles)
+        return size_table_tiles(e, d_rgb, n_frames, qualities, n_q, sizes, stride, status, (hipStream_t)stream);
+    for (int k = 0; k < n_q; k++) {
+        QualityArgs qa = {};
+        qa.uniform = qualities[k];
+        const int rc = encode_batch(e, d_rgb, n_frames, 0, &qa, true, nullptr, 0, (uint64_t *)(sizes + (size_t)k * stride), nullptr,
+                                    status ? status + k : nullptr, stream);
+        if (rc != M1V_OK) return rc;
+    }
+    // (pipelined: the probes' sizes are written on the internal stream)
+    return e->pipelined ? m1v_flush(e, stream) : M1V_OK;
+}
+
+int m1v_frame_size_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
+                                uint64_t *d_sizes, uint32_t *d_status, void *stream) {
+    if (!e || !d_sizes || (!d_rgb && n_frames > 0)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
+    if (const int rc = check_qualities(e, qualities, n_qualities)) return rc;
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (n_frames == 0) return M1V_OK;
+    return size_table(e, d_rgb, n_frames, qualities, n_qualities, (unsigned long long *)d_sizes, (size_t)n_frames, d_status, stream);
+}
+
 int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                              const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
                              const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
                              uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                              uint32_t *d_status, void *stream) {
-    if (!e || !candidates) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
-    for (int k = 0; k < n_candidates; k++)
-        if (candidates[k] < 1 || candidates[k] > encoder_quality(e) || (k > 0 && candidates[k] <= candidates[k - 1]))
-            return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
+    if (!e) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
-    // 1. the record size of every frame at every candidate (each probe is a complete call: its own counter hand-over)
-    for (int k = 0; k < n_candidates; k++) {
-        QualityArgs qa = {};
-        qa.uniform = candidates[k];
-        const int rc = encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, true, nullptr, 0,
-                                    (uint64_t *)(e->d_probe_sizes + (size_t)k * e->max_frames), nullptr, e->d_probe_status + k, stream);
-        if (rc != M1V_OK) return rc;
-    }
-    // (pipelined: the probes' sizes are written on the internal stream)
-    if (e->pipelined) {
-        const int rc = m1v_flush(e, stream);
-        if (rc != M1V_OK) return rc;
-    }
+    // 1. the record size of every frame at every candidate ([kMaxCandidates][max_frames])
+    if (const int rc = size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames,
+                                  e->d_probe_status, stream))
+        return rc;
     // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
     QualityArgs qa = {};
     qa.probe_sizes = e->d_probe_sizes;

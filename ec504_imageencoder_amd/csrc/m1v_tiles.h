@@ -167,8 +167,10 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
 
 // The front half of a tile wave (shared by k_encode_tiles and k_coefficient_tiles): brings the wave's 64 blocks in through
 // its LDS ring and leaves the 64 row-pass outputs of the lane's block in `rows`.  `ring` = LDS byte address of the wave's
-// region; wave 0, 1 = luma, wave 2 = chroma (see the head of this file); `first` / `meanwhile`: see below.
-template <int R, int KEEP, typename First, typename Meanwhile>
+// region; wave 0, 1 = luma, wave 2 = chroma (see the head of this file); `first` / `meanwhile`: see below.  DOWN: the row
+// pass takes its rounded-down form (the wave has switched MODE: pixel_stage_rounds_down); false = the integer form of the run
+// kernels, right in the default mode (k_size_table_tiles).
+template <int R, int KEEP, bool DOWN = true, typename First, typename Meanwhile>
 __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t *fbase, uint32_t ring, int wave, int lane, int s0,
                                                 int m0, int strips_here, int comp, First first, Meanwhile meanwhile,
                                                 RowStore<KEEP> &rows) {
@@ -256,7 +258,7 @@ __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t
         float px[8];
         convert_row<3, M1V_TILE_LEAN>(v, kf, px);
         float ro[8];
-        m1vf::fdct_row_f<float, true>(px, ro); // the wave rounds down: pixel_stage_rounds_down()
+        m1vf::fdct_row_f<float, DOWN>(px, ro); // DOWN: the wave rounds down, pixel_stage_rounds_down()
         rows.put(i, ro);
     }
 }
@@ -538,3 +540,178 @@ void k_coefficient_tiles(CoefTileArgs a) {
     }
 }
 
+
+// ---- the size table (m1v_frame_size_table_device): record sizes of every frame at up to 8 qualities in one pass ---------
+// The tile front half runs ONCE per block: colour, row pass, column pass.  The 64 coefficients then stay in registers, and
+// for each quality k the lane quantises them with that quality's table, stages the levels (the ring's bytes, as k_encode_tiles),
+// builds the non-zero mask and counts the block's bits with the pass 1 of k_encode_tiles (dc_header, emit_set,
+// block_bits_pass1).  No bits are placed: no pass 2, no LDS image, no compact slot, no overflow arena.  After one barrier lane
+// k * 8 + j of wave 0 sums segment j at quality k and adds it to strip_ctr with the arrival count of k_encode_tiles; the tile
+// that completes a strip adds its bytes to frame_bytes.  k_size_table_sizes turns those into sizes and clears them.
+// The wave stays in the default rounding mode: the row pass takes the integer form of the run kernels (fdct_row_f<float, false>).
+struct TableArgs {
+    Geometry g;
+    const uint8_t *rgb;
+    const Tables *tab;
+    const float *rq_all;                 // quantiser of every quality (frame_rq_t)
+    uint32_t qoff[kMaxCandidates];       // [k] where quality k's quantiser lies in rq_all
+    int n_q;
+    unsigned long long *strip_ctr;       // [k][frame][strip]: (arrivals << 40) | bits, as TileArgs::strip_ctr
+    unsigned long long *frame_bytes;     // [k][frame]: bytes of the frame's strips
+    uint32_t *status;                    // [k]: M1V_STATUS_UNENCODABLE
+    int n_frames, tile_cols, tile_rows, tiles_per_frame;
+    DivMagic div_group, div_frame, div_cols; // as TileArgs
+    const uint32_t *tile_row_order;
+    uint32_t region;                     // LDS bytes of a wave's ring / staging region
+};
+// LDS words in front of the per-wave regions: one VLC table per wave, the bit counts [quality][block in emission order]
+constexpr int kTableCnt = 3 * kVlcWords, kTableFixedWords = kTableCnt + kMaxCandidates * kTileThreads;
+
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void k_size_table_tiles(TableArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const Geometry &g = a.g;
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool chroma = wave == 2; // wave-uniform
+    constexpr int kStride = STAGE8 ? kStageStride8 : kStageStride16;
+    const uint32_t *vlc = lds + wave * kVlcWords;
+    uint32_t *cnt = lds + kTableCnt;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds;
+    const uint32_t region_off = (uint32_t)kTableFixedWords * 4u + (uint32_t)wave * a.region; // bytes from lds
+
+    // the tile and its place in the tile-row order: as k_encode_tiles
+    int frame, tile;
+    frame_unit_of(blockIdx.x, a.n_frames, a.div_group, a.div_frame, frame, tile);
+    const int tk = (int)udiv((uint32_t)tile, a.div_cols), tc = tile - tk * a.tile_cols;
+    const int tr = (int)a.tile_row_order[tk];
+    const int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
+    const uint8_t *fbase = a.rgb + (unsigned long long)frame * g.frame_bytes;
+    auto owner = [&](int ln, int &j, int &m, int &blk) {
+        if (!chroma) {
+            m = 2 * wave + (ln >> 5);
+            blk = ((ln >> 4) & 1) * 2 + (ln & 1);
+            j = (ln >> 1) & 7;
+        } else {
+            m = (ln >> 3) & 3;
+            blk = 4 + (ln >> 5);
+            j = ln & 7;
+        }
+    };
+    const int strips_here = min(kTileStrips, g.n_strips - s0); // >= 1
+    int comp;
+    {
+        int j_, m_, blk_;
+        owner(lane, j_, m_, blk_);
+        comp = blk_ < 4 ? 0 : blk_ - 3;
+    }
+
+    // ---- pixel stage, once: the wave's VLC table is requested in front of the rows ----
+    RowStore<8> rows;
+    tile_pixel_rows<R, 8, false>(
+        g, fbase, lds0 + region_off, wave, lane, s0, m0, strips_here, comp,
+        [&]() {
+#pragma unroll
+            for (int q = 0; q < kVlcWords / kWave; q++)
+                dma4((uint32_t)lane * 4u, lds0 + (uint32_t)(wave * kVlcWords + q * kWave) * 4u, a.tab->vlc + q * kWave);
+        },
+        [] {}, rows);
+    // ---- column pass, once: coef[u * 8 + i] = coefficient (row u, column i) ----
+    float coef[64];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        float c[8];
+        m1vf::fdct_col_f<float>(rows.get(0, i), rows.get(1, i), rows.get(2, i), rows.get(3, i), rows.get(4, i), rows.get(5, i),
+                                rows.get(6, i), rows.get(7, i), c, i == 0 ? RowStore<8>::kBias0 : 0.0f);
+#pragma unroll
+        for (int u = 0; u < 8; u++) coef[u * 8 + i] = c[u];
+    }
+    int j, m, blk;
+    {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        owner(ln, j, m, blk);
+    }
+    const bool valid = j < strips_here && m0 + m < g.n_mbrows;
+    const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
+    // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
+    const uint32_t *blkp = lds + region_off / 4u + lane * kStride;
+    auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
+
+    // ---- per quality: quantise, stage, mask, count (pass 1) ----
+    uint32_t bad_q = 0; // bit k: an unencodable level at quality k
+    for (int k = 0; k < a.n_q; k++) {
+        const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(a.rq_all + a.qoff[k]));
+        uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint32_t *)blkp;
+        // the staging stores (asm, chained through lds_addr) stay behind the previous quality's reads of the staged levels
+        asm volatile("" : "+v"(lds_addr) : : "memory");
+        int dc = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int q = quant(coef[u * 8 + i], rq_t[i * 8 + u]);
+                const int p = scan_pos(u * 8 + i);
+                if (p == 0) dc = q;
+                if (STAGE8)
+                    asm("ds_write_b8 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte8(p)));
+                else
+                    asm("ds_write_b16 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte16(p)));
+            }
+        }
+        const unsigned long long nz = (stage_nonzero_mask<STAGE8>(blkp, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
+        uint32_t hdr = 0, bad = 0;
+        int hlen = 0;
+        BlockBits bb = {0, 0};
+        dc_header(dc, blk < 4, blk, vlc, hdr, hlen);
+        block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
+        cnt[k * kTileThreads + e] = valid ? (uint32_t)bb.tot : 0u;
+        bad_q |= (valid && bad) ? 1u << k : 0u;
+    }
+    lds_barrier();
+
+    // ---- wave 0, lane k * 8 + j: segment j at quality k (24 consecutive counts), then the strip's arrival ----
+    if (wave == 0) {
+        const int k = lane >> 3, jj = lane & 7;
+        if (k < a.n_q && jj < strips_here) {
+            const uint4 *c4 = reinterpret_cast<const uint4 *>(cnt + k * kTileThreads + jj * kTileSegBlocks);
+            uint32_t bits = tr == 0 ? 38u : 0u; // the strip starts in this tile: slice header in front (mpeg1_blk.c:12-16)
+#pragma unroll
+            for (int t = 0; t < kTileSegBlocks / 4; t++) {
+                const uint4 v = c4[t];
+                bits += v.x + v.y + v.z + v.w;
+            }
+            const unsigned long long kf = (unsigned long long)k * (unsigned)a.n_frames + (unsigned)frame;
+            const unsigned long long before = atomicAdd(a.strip_ctr + kf * (unsigned)g.n_strips + (unsigned)(s0 + jj),
+                                                        (1ull << kCtrCountShift) | (unsigned long long)bits);
+            if ((uint32_t)(before >> kCtrCountShift) == (uint32_t)a.tile_rows - 1u)
+                atomicAdd(&a.frame_bytes[kf], ((before & kCtrBitsMask) + bits + 7ull) >> 3);
+        }
+    }
+    for (uint32_t b = bad_q; b; b &= b - 1u) atomicOr(&a.status[__builtin_ctz(b)], (uint32_t)M1V_STATUS_UNENCODABLE); // (rare)
+}
+
+// The size table's place of k_frame_sizes (one workgroup per frame and quality): the record size (48 bytes of headers and trailer
+// + the strips' bytes) into out_sizes[k * stride + frame], the status word of quality k into out_status[k], and every counter
+// the probe added to cleared for the next call.
+struct TableSizesArgs {
+    int n_frames, n_strips;
+    unsigned long long *strip_ctr, *frame_bytes; // [k][frame][strip], [k][frame]
+    uint32_t *status;                            // [k]
+    unsigned long long *out_sizes;
+    unsigned long long stride;
+    uint32_t *out_status;                        // [k], or null
+};
+__global__ __launch_bounds__(256) void k_size_table_sizes(TableSizesArgs a) {
+    const unsigned long long kf = (unsigned long long)blockIdx.y * (unsigned)a.n_frames + blockIdx.x;
+    for (int s = threadIdx.x; s < a.n_strips; s += 256) a.strip_ctr[kf * (unsigned)a.n_strips + s] = 0ull;
+    if (threadIdx.x == 0) {
+        a.out_sizes[blockIdx.y * a.stride + blockIdx.x] = 48ull + a.frame_bytes[kf];
+        a.frame_bytes[kf] = 0ull;
+        if (blockIdx.x == 0) {
+            if (a.out_status) a.out_status[blockIdx.y] = a.status[blockIdx.y];
+            a.status[blockIdx.y] = 0u;
+        }
+    }
+}

@@ -124,6 +124,26 @@ class Mpeg1Encoder:
             raise EncoderError(rc, "m1v_frame_sizes_device")
         return sizes[:n]
 
+    def frame_size_table(self, rgb, qualities, status=None):
+        """The exact record size of every frame at each of `qualities` (1..8, strictly increasing, each <= quality_factor):
+        int64 CUDA tensor [K, n], row k = frame_sizes(rgb, quality=[qualities[k]] * n).  One fused pass on the tile path.
+        Asynchronous on torch's current stream (complete in stream order, pipelined mode included).  status: optional CUDA
+        int32 tensor [K] that receives each quality's status bits (STATUS_UNENCODABLE: that row is undefined)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        qs = [int(q) for q in qualities]
+        if not 1 <= len(qs) <= _ffi.MAX_CANDIDATES or any(q < 1 or q > 255 for q in qs):
+            raise EncoderError(_ffi.E_ARG, "frame_size_table: 1 to 8 qualities")
+        if status is not None:
+            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= len(qs), "status: CUDA int32, one per quality"
+        q_buf = (C.c_uint8 * len(qs))(*qs)
+        sizes = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
+        rc = _ffi.lib().m1v_frame_size_table_device(self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(status), _stream())
+        if rc != _ffi.OK:
+            raise EncoderError(rc, "m1v_frame_size_table_device")
+        return sizes[:len(qs) * n].view(len(qs), n)
+
     def encode_to_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
         """Synchronous: every frame at the largest of `candidates` (1..8 qualities, strictly increasing, each <= quality_factor)
         whose record fits its budget, else at the smallest.  max_frame_bytes: one budget for every frame, or one per frame

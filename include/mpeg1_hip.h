@@ -133,8 +133,21 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
  *                             M1V_STATUS_OVER_BUDGET when none fits, then encodes once at the picked qualities.  The budget of
  *                             frame f is d_max_frame_bytes[f] (uint64[n_frames] on the device) or, when that is NULL,
  *                             max_frame_bytes.  d_chosen (uint8[n_frames] on the device, may be NULL) receives the picks.
- *                             Costs K + 1 encode kernels.  A probe that exhausts the overflow scratch reports M1V_STATUS_SCRATCH.
- * Argument errors (bad candidates, n_frames > max_frames, null pointers) return M1V_E_ARG. */
+ *                             The candidates' sizes come from m1v_frame_size_table_device: on the tile path one size-table pass,
+ *                             then the encode (about 3 plain encode kernels at K = 8); on the run path K probes +
+ *                             the encode, K + 1 encode kernels.  A probe that exhausts the overflow scratch reports
+ *                             M1V_STATUS_SCRATCH (run path only: the size table uses no scratch).
+ * m1v_frame_size_table_device the exact record size of every frame at each of n_qualities qualities (a HOST array, 1..8 entries,
+ *                             strictly increasing, each <= the encoder's quality): d_sizes[k * n_frames + f] (uint64, on the
+ *                             device) is what m1v_frame_sizes_device returns for frame f at the uniform quality qualities[k].
+ *                             d_status[k] (uint32[n_qualities], may be NULL) receives the status bits of quality k
+ *                             (M1V_STATUS_UNENCODABLE: some block cannot be coded at qualities[k], whose sizes are then
+ *                             undefined).  Nothing else is written.  Tile path: ONE pass of a fused kernel (pixel stage once,
+ *                             quantise and count per quality; no scratch, so never M1V_STATUS_SCRATCH); run path: one probe
+ *                             per quality.  n_frames == 0 writes nothing.
+ * Argument errors (bad candidates or qualities, n_frames > max_frames, null pointers) return M1V_E_ARG.
+ * Profiling (m1v_profile_*) counts one size-table pass on the tile path as ONE launch of the dominant kernel: a budget call
+ * with K candidates reports 2 launches there, K + 1 on the run path. */
 int m1v_encode_quality_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                               const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
                               uint64_t *d_total, uint32_t *d_status, void *stream);
@@ -145,6 +158,8 @@ int m1v_encode_budget_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frame
                              const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
                              uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                              uint32_t *d_status, void *stream);
+int m1v_frame_size_table_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
+                                uint64_t *d_sizes, uint32_t *d_status, void *stream);
 
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
@@ -231,7 +246,7 @@ int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint6
                      uint64_t first_frame_index, void *stream);
 
 /* Kernel timing by HIP events recorded on the launch stream around the dominant kernel
- * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
+ * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles for a size-table pass).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
  * and returns launches/total milliseconds since the last read. */
 int m1v_profile_enable(m1v_encoder *enc, int enable);
 int m1v_profile_read(m1v_encoder *enc, int *launches, double *total_ms);
@@ -254,7 +269,9 @@ void m1v_debug_fail_alloc(int nth);
 /* Test hook: the next m1v_encode_device that reaches `stage` returns M1V_E_HIP there, as a failed HIP call would: 1 = after
  * the internal counter set is chosen, before the encode kernel; 2 = after the encode kernel (and the run layout), before
  * the assembly; 3 = after the assembly, before the pipelined completion event.  One-shot; 0 = off.  Host side only: it
- * launches nothing and touches no device memory.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
+ * launches nothing and touches no device memory.  Inert unless the process runs with EC504_DEBUG_HOOKS=1.  A size-table pass
+ * of the tile path (m1v_frame_size_table_device, m1v_encode_budget_device) reaches the stages as: 1 = before its probe
+ * kernel, 2 = after the probe kernel, before the sizes kernel, 3 = after the sizes kernel. */
 void m1v_debug_fail_encode(int stage);
 /* Test hook: force how the RUN kernel loads its pixels (forcing a mode selects the run path): -1 = automatic (by width,
  * channel count and pointer alignment), 0 = byte loads (valid everywhere), 2 = 28-byte loads + funnel shift (3 channels,

@@ -5,11 +5,14 @@
     quality     m1v_encode_quality_device, every frame at the encoder's quality (one selection launch + one scalar load
                 per workgroup more than plain)
     probe       m1v_frame_sizes_device (the encode kernel + k_frame_sizes instead of k_assemble)
-    budget K    m1v_encode_budget_device with K candidates (K probes + the pick + one encode)
+    budget K    m1v_encode_budget_device with K candidates (tiles: one size-table pass + the pick + one encode; runs: K probes
+                + the pick + one encode)
+    table K     m1v_frame_size_table_device with K qualities (tiles: k_size_table_tiles + k_size_table_sizes; runs: K probes)
 
 Each leg: `--settle` untimed calls, then `--launches` timed back-to-back calls with one synchronisation (wall time per call),
 legs alternating for `--rounds` rounds; the median round is printed.  `kernel` is the median duration of the encode kernel
-(HIP events around it, a separate pass), so a budget call can be set against (K + 1) x the plain encode kernel.
+(HIP events around it, a separate pass; a size-table pass counts as one launch), so a budget call can be set against (K + 1) x
+the plain encode kernel, and a size table against K x.
     usage: quality_timing.py [--w 1920 --h 1080 --n 300] [--path tiles|runs]"""
 import argparse
 import ctypes as C
@@ -46,6 +49,10 @@ vp = C.c_void_p
 R, O, S, T, ST, Q = (vp(x) for x in (rgb.data_ptr(), out.data_ptr(), sizes.data_ptr(), meta.data_ptr(), meta.data_ptr() + 8,
                                      qual.data_ptr()))
 CANDS = {2: (6, 12), 4: (3, 6, 9, 12), 8: (2, 3, 4, 6, 8, 9, 10, 12)}
+table_sizes = torch.empty(8 * a.n, dtype=torch.int64, device="cuda")
+table_status = torch.zeros(8, dtype=torch.int32, device="cuda")
+TS, TST = vp(table_sizes.data_ptr()), vp(table_status.data_ptr())
+TABLES = {1: (a.q,), 2: CANDS[2], 4: CANDS[4], 8: CANDS[8]}
 budget = int(0.75 * a.w * a.h * 3 // 54)   # ~ the record of a noise frame at quality 8-9 (1080p: 114.5 KB at 12)
 
 
@@ -57,6 +64,9 @@ def legs():
         cand = (C.c_uint8 * k)(*[min(x, a.q) for x in c])
         yield f"budget K={k}", (lambda cand=cand, k=k: L.m1v_encode_budget_device(h, R, a.n, 0, cand, k, budget, None, None, O,
                                                                                   out.numel(), S, T, ST, None)), k + 1
+    for k, c in TABLES.items():
+        qs = (C.c_uint8 * k)(*[min(x, a.q) for x in c])
+        yield f"table K={k}", (lambda qs=qs, k=k: L.m1v_frame_size_table_device(h, R, a.n, qs, k, TS, TST, None)), k
 
 
 res = {}
@@ -71,6 +81,7 @@ for r in range(a.rounds):
         torch.cuda.synchronize()
         res.setdefault(name, []).append((time.perf_counter() - t0) / a.launches)
         assert int(meta[1].item()) & ~_ffi.STATUS_OVER_BUDGET == 0, (name, int(meta[1].item()))
+        assert int(table_status.abs().sum().item()) == 0, name
 kern = {}
 for name, go, per_call in legs():
     enc.profile(True)
@@ -87,6 +98,6 @@ for name, go, per_call in legs():
     step = statistics.median(res[name]) * 1e6
     k_us, launches = kern[name]
     print(f"{name:13s} step {step:8.1f} us  x{step / (statistics.median(res['plain']) * 1e6):5.2f} of plain  "
-          f"encode kernel {k_us:7.1f} us x {launches}  (K+1) x plain kernel = {per_call * plain_k:8.1f} us   rounds: "
+          f"encode kernel {k_us:7.1f} us x {launches} (x{k_us / plain_k:4.2f})  K(+1) x plain kernel = {per_call * plain_k:8.1f} us   rounds: "
           + " ".join(f"{x * 1e6:.1f}" for x in res[name]))
 enc.close()
