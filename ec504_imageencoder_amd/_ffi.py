@@ -22,7 +22,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_device_count", "m1v_warm_up", "m1v_last_error", "m1v_create", "m1v_destroy", "m1v_strips", "m1v_mb_rows",
     "m1v_frame_bound", "m1v_frame_bound_for", "m1v_frame_bytes_in", "m1v_file_prolog", "m1v_encode_device", "m1v_encode_host",
     "m1v_encode_planes_host", "m1v_encode_quality_device", "m1v_frame_sizes_device", "m1v_encode_budget_device",
-    "m1v_frame_size_table_device",
+    "m1v_frame_size_table_device", "m1v_encode_batch_budget_device", "m1v_encode_cbr_device",
     "m1v_set_pipelined", "m1v_flush", "m1v_alloc_host", "m1v_free_host", "m1v_alloc_device", "m1v_free_device",
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
@@ -79,6 +79,12 @@ def lib():
     L.m1v_encode_budget_device.restype = C.c_int
     L.m1v_frame_size_table_device.argtypes = [vp, vp, C.c_int, _u8p, C.c_int, vp, vp, vp]
     L.m1v_frame_size_table_device.restype = C.c_int
+    L.m1v_encode_batch_budget_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_uint64, vp,
+                                                 vp, C.c_size_t, vp, vp, vp, vp]
+    L.m1v_encode_batch_budget_device.restype = C.c_int
+    L.m1v_encode_cbr_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp,
+                                        vp, C.c_size_t, vp, vp, vp, vp]
+    L.m1v_encode_cbr_device.restype = C.c_int
     L.m1v_set_pipelined.argtypes = [vp, C.c_int]
     L.m1v_set_pipelined.restype = C.c_int
     L.m1v_flush.argtypes = [vp, vp]

@@ -1254,6 +1254,7 @@ struct QualityArgs {
     const unsigned long long *budget;        // [frame] per-frame budgets, or null: max_bytes for every frame
     unsigned long long max_bytes;
     const uint32_t *probe_status;            // [n_cand] status words of the probes
+    const uint32_t *pick_status;             // [1] k_rate_pick's status word (batch budget, bitrate), or null
     int n_frames;
     uint32_t *qsel;                          // out: [frame] offset of the frame's entry in rq_all
     uint8_t *chosen;                         // out (budget, may be null): [frame] the quality picked
@@ -1263,12 +1264,14 @@ struct QualityArgs {
 // One lane per frame: the frame's quality -> its offset in rq_all.  An entry outside 1..max_q sets M1V_STATUS_QUALITY and
 // encodes at max_q (every plan of the encoder holds there; the batch's output is undefined, as with the other status bits).
 // Budget form: the largest candidate whose probed record fits the frame's budget, else the smallest and
-// M1V_STATUS_OVER_BUDGET; a probe that ran out of overflow scratch (sizes undefined) passes M1V_STATUS_SCRATCH on.
+// M1V_STATUS_OVER_BUDGET; a probe that ran out of overflow scratch (sizes undefined) passes M1V_STATUS_SCRATCH on.  After
+// k_rate_pick (the caller's qualities are its picks) its status word's M1V_STATUS_OVER_BUDGET and M1V_STATUS_SCRATCH pass on.
 __global__ __launch_bounds__(256) void k_frame_quality(QualityArgs a) {
     const int f = (int)(blockIdx.x * 256 + threadIdx.x);
     uint32_t bits = 0;
     if (f == 0 && a.probe_sizes)
         for (int k = 0; k < a.n_cand; k++) bits |= a.probe_status[k] & (uint32_t)M1V_STATUS_SCRATCH;
+    if (f == 0 && a.pick_status) bits |= *a.pick_status & (uint32_t)(M1V_STATUS_OVER_BUDGET | M1V_STATUS_SCRATCH);
     if (f < a.n_frames) {
         int q;
         if (a.probe_sizes) {
@@ -1289,6 +1292,169 @@ __global__ __launch_bounds__(256) void k_frame_quality(QualityArgs a) {
         a.qsel[f] = (uint32_t)(q - 1) * 64u;
     }
     if (bits) atomicOr(a.status, bits);
+}
+
+// ---- batch byte budgets and constant bitrate (m1v_encode_batch_budget_device, m1v_encode_cbr_device) ---------------------
+// k_rate_pick: ONE workgroup between the size table and the encode, on the caller's stream.  It picks a candidate per frame
+// from the table (sizes[k * stride + frame], k < n_cand, candidates' qualities strictly increasing) by one of two rules
+// (include/mpeg1_hip.h), writes the candidate's quality to chosen[frame] (the encode's per-frame qualities) and writes its status
+// word: M1V_STATUS_OVER_BUDGET, and the table's M1V_STATUS_SCRATCH (k_frame_quality passes both on to the batch's status
+// word).  Written, not OR'ed: nothing needs clearing between calls.  Integer arithmetic, no scratch, no atomics.
+constexpr int kPickThreads = 1024;
+constexpr int kPickWaves = kPickThreads / kWave;
+constexpr int kCbrChunk = 512; // frames of the table staged in LDS per step of the bitrate walk
+
+struct PickArgs {
+    const unsigned long long *sizes; // [k * stride + frame] record bytes at candidate k
+    int stride, n_cand, n_frames;
+    unsigned long long cand;         // byte k: the quality of candidate k
+    const uint32_t *table_status;    // [n_cand] status words of the size table
+    unsigned long long budget;       // batch form: bytes for the sum of the batch's records
+    long long rate, capacity;        // bitrate form: refill per frame (>= 1), buffer capacity (rate .. 2^62 - 1)
+    const long long *level_in;       // bitrate form: bytes available to the first frame (may be level_out)
+    long long *level_out;            //   and to the frame after the batch
+    uint8_t *chosen;                 // out: [frame] the quality picked
+    uint32_t *status;                // out: [1]
+};
+
+__device__ __forceinline__ uint8_t cand_quality(unsigned long long cand, int k) { return (uint8_t)(cand >> (8 * k)); }
+__device__ __forceinline__ long long readlane_i64(long long v, int lane) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), lane);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// Batch form (kCbr = false).  T[k] = sum of row k; top = the largest k with T[k] <= budget (none: every frame at candidate 0 and
+// M1V_STATUS_OVER_BUDGET; top = n_cand - 1: every frame there).  Otherwise every frame goes to top or top + 1.  With
+// d[f] = s[top + 1][f] - s[top][f], the upgrades with d <= 0 are free and always taken; the others go cheapest first, (d, f)
+// ascending, while they fit: frame f is upgraded iff the positive d up to and including its own in that order sum to at most
+// room = budget - T[top] + (the bytes the free upgrades save).  Each frame's prefix sum is one pass over every frame's key
+// (d << 32 | frame), staged in LDS a block at a time: n^2 / kPickThreads compare-and-adds per lane.  A record is shorter than
+// 4 GiB (m1v_create bounds a frame's input below 4 GiB; a record holds at most 2.6 bytes per pixel), so d < 2^32 and the keys
+// order as (d, f) do.
+// Bitrate form (kCbr = true).  level = min(*level_in, capacity); per frame in order: the largest candidate whose record fits
+// level, else candidate 0 and M1V_STATUS_OVER_BUDGET; level = min(capacity, level - record + rate) (negative: a debt the later
+// refills repay; it stays above -2^63 while the stream owes less than 2^62 bytes).  *level_out = level.  The walk is wave 0's:
+// a chunk of the table is staged in LDS, [frame][candidate], and lane 8j + k holds candidate k of frame j of a step of eight,
+// so that the chain from one frame to the next is a compare, a ballot, a readlane and the level update.
+template <bool kCbr>
+__global__ __launch_bounds__(kPickThreads) void k_rate_pick(PickArgs a) {
+    const int t = (int)threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
+    const int n = a.n_frames, K = a.n_cand;
+    uint32_t bits = 0;
+    if (n > 0)
+        for (int k = 0; k < K; k++) bits |= a.table_status[k] & (uint32_t)M1V_STATUS_SCRATCH;
+    if constexpr (kCbr) {
+        __shared__ long long stage[kCbrChunk * kMaxCandidates];
+        __shared__ uint8_t picks[kCbrChunk];
+        long long level = *a.level_in; // (every read of level_in comes before the write of level_out)
+        level = level < a.capacity ? level : a.capacity;
+        bool over = false;
+        for (int f0 = 0; f0 < n; f0 += kCbrChunk) {
+            const int cnt = min(kCbrChunk, n - f0);
+            for (int i = t; i < kCbrChunk * kMaxCandidates; i += kPickThreads) {
+                const int k = i / kCbrChunk, j = i % kCbrChunk; // (coalesced reads along a row)
+                stage[j * kMaxCandidates + k] = k < K && j < cnt ? (long long)a.sizes[(size_t)k * a.stride + f0 + j] : 0x7fffffffffffffffll;
+            }
+            __syncthreads();
+            if (__builtin_amdgcn_readfirstlane(wave) == 0) {
+                for (int j0 = 0; j0 < cnt; j0 += 8) {
+                    const long long s = stage[j0 * kMaxCandidates + lane];
+                    int mine = 0;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        if (j0 + j < cnt) {
+                            const uint32_t fit = (uint32_t)(__ballot(s <= level) >> (8 * j)) & 0xffu;
+                            const int k = fit ? 31 - __clz((int)fit) : 0;
+                            over |= fit == 0;
+                            level -= readlane_i64(s, 8 * j + k);
+                            level += a.rate;
+                            level = level < a.capacity ? level : a.capacity;
+                            if ((lane >> 3) == j) mine = k;
+                        }
+                    }
+                    if ((lane & 7) == 0 && j0 + (lane >> 3) < cnt) picks[j0 + (lane >> 3)] = (uint8_t)mine;
+                }
+            }
+            __syncthreads();
+            for (int j = t; j < cnt; j += kPickThreads) a.chosen[f0 + j] = cand_quality(a.cand, picks[j]);
+        }
+        if (t == 0) { // (lane 0 of wave 0: it walked)
+            *a.level_out = level;
+            *a.status = bits | (over ? (uint32_t)M1V_STATUS_OVER_BUDGET : 0u);
+        }
+    } else {
+        __shared__ unsigned long long part[kPickWaves][2 * kMaxCandidates]; // per wave: T[k], then the savings of k -> k + 1
+        __shared__ unsigned long long tot[2 * kMaxCandidates];
+        __shared__ unsigned long long keys[kPickThreads];
+        unsigned long long sum[kMaxCandidates], save[kMaxCandidates];
+#pragma unroll
+        for (int k = 0; k < kMaxCandidates; k++) sum[k] = save[k] = 0;
+        for (int f = t; f < n; f += kPickThreads) {
+            unsigned long long prev = 0;
+#pragma unroll
+            for (int k = 0; k < kMaxCandidates; k++)
+                if (k < K) {
+                    const unsigned long long s = a.sizes[(size_t)k * a.stride + f];
+                    sum[k] += s;
+                    if (k > 0 && s < prev) save[k - 1] += prev - s;
+                    prev = s;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < kMaxCandidates; k++) {
+            const unsigned long long s = wave_sum_u64(sum[k]), v = wave_sum_u64(save[k]);
+            if (lane == 0) {
+                part[wave][k] = s;
+                part[wave][kMaxCandidates + k] = v;
+            }
+        }
+        __syncthreads();
+        if (t < 2 * kMaxCandidates) {
+            unsigned long long s = 0;
+            for (int w = 0; w < kPickWaves; w++) s += part[w][t];
+            tot[t] = s;
+        }
+        __syncthreads();
+        int top = -1;
+        for (int k = 0; k < K; k++)
+            if (tot[k] <= a.budget) top = k;
+        if (top < 0 || top == K - 1) {
+            const uint8_t q = cand_quality(a.cand, top < 0 ? 0 : top);
+            for (int f = t; f < n; f += kPickThreads) a.chosen[f] = q;
+        } else {
+            const unsigned long long room = a.budget - tot[top] + tot[kMaxCandidates + top];
+            const unsigned long long *lo = a.sizes + (size_t)top * a.stride, *hi = lo + a.stride;
+            for (int f0 = 0; f0 < n; f0 += kPickThreads) {
+                const int f = f0 + t;
+                const long long d = f < n ? (long long)(hi[f] - lo[f]) : 0;
+                const unsigned long long own = ((unsigned long long)(d > 0xffffffffll ? 0xffffffffll : (d > 0 ? d : 0)) << 32) | (uint32_t)f;
+                unsigned long long acc = 0; // the positive d whose keys are <= own
+                for (int c0 = 0; c0 < n; c0 += kPickThreads) {
+                    const int cnt = min(kPickThreads, n - c0), steps = (cnt + 7) & ~7;
+                    __syncthreads(); // (the previous block's keys are read)
+                    if (t < cnt) {
+                        const long long dj = (long long)(hi[c0 + t] - lo[c0 + t]);
+                        keys[t] = ((unsigned long long)(dj > 0xffffffffll ? 0xffffffffll : (dj > 0 ? dj : 0)) << 32) | (uint32_t)(c0 + t);
+                    } else if (t < steps) {
+                        keys[t] = 0; // adds nothing
+                    }
+                    __syncthreads();
+                    if (f < n && d > 0 && acc <= room) {
+                        for (int j = 0; j < steps; j += 8) {
+#pragma unroll
+                            for (int u = 0; u < 8; u++) {
+                                const unsigned long long kj = keys[j + u];
+                                acc += kj <= own ? (kj >> 32) : 0ull;
+                            }
+                        }
+                    }
+                }
+                if (f < n) a.chosen[f] = cand_quality(a.cand, d <= 0 || acc <= room ? top + 1 : top);
+            }
+        }
+        if (t == 0) *a.status = bits | (top < 0 ? (uint32_t)M1V_STATUS_OVER_BUDGET : 0u);
+    }
 }
 
 // The probe's place of k_assemble (one workgroup per frame): each record's size (its strips' bytes + 48 bytes of headers and
@@ -1533,6 +1699,7 @@ struct m1v_encoder {
     unsigned long long *d_probe_sizes = nullptr;
     uint32_t *d_probe_status = nullptr;
     uint8_t *d_chosen = nullptr;
+    uint32_t *d_pick_status = nullptr; // k_rate_pick's status word (batch-budget and bitrate calls)
     int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
     // The size table's counters (3-channel encoders): k_size_table_tiles adds, k_size_table_sizes reads and clears what it added.
     struct TableCounters {

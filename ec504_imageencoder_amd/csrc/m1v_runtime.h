@@ -384,6 +384,7 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
+    if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
     if (channels == 3) { // the size table's counters (tile path), clear
         const size_t kf = (size_t)kMaxCandidates * max_frames;
         if (err == hipSuccess) err = hipMalloc(&e->table.strip_ctr, kf * g.n_strips * 8);
@@ -423,6 +424,7 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipFree(e->d_probe_sizes);
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
+    (void)hipFree(e->d_pick_status);
     (void)hipFree(e->table.strip_ctr);
     (void)hipFree(e->table.frame_bytes);
     (void)hipFree(e->table.words);
@@ -654,6 +656,72 @@ int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames,
     qa.probe_status = e->d_probe_status;
     qa.chosen = d_chosen ? d_chosen : e->d_chosen;
     return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+}
+
+// A batch-budget or bitrate call after its arguments are checked: the size table, the pick (k_rate_pick, one workgroup) and the
+// encode at the picked qualities, all on `stream` with no host wait.  pa holds the rule's parameters; the rest is set here.
+static int rate_encode(m1v_encoder *e, PickArgs &pa, bool cbr, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                       const uint8_t *candidates, int n_candidates, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap,
+                       uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status, void *stream) {
+    // 1. the record size of every frame at every candidate ([kMaxCandidates][max_frames])
+    if (const int rc = size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames,
+                                  e->d_probe_status, stream))
+        return rc;
+    // 2. the pick
+    HIP_TRY(hipSetDevice(e->device));
+    pa.sizes = e->d_probe_sizes;
+    pa.stride = e->max_frames;
+    pa.n_cand = n_candidates;
+    pa.n_frames = n_frames;
+    pa.cand = 0;
+    for (int k = 0; k < n_candidates; k++) pa.cand |= (unsigned long long)candidates[k] << (8 * k);
+    pa.table_status = e->d_probe_status;
+    pa.chosen = d_chosen ? d_chosen : e->d_chosen;
+    pa.status = e->d_pick_status;
+    if (cbr)
+        hipLaunchKernelGGL(k_rate_pick<true>, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, pa);
+    else
+        hipLaunchKernelGGL(k_rate_pick<false>, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, pa);
+    HIP_TRY(hipGetLastError());
+    // 3. the encode at the picked qualities (k_frame_quality checks them and passes the pick's status bits on)
+    QualityArgs qa = {};
+    qa.quality = pa.chosen;
+    qa.pick_status = e->d_pick_status;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+}
+
+int m1v_encode_batch_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                                   const uint8_t *candidates, int n_candidates, uint64_t batch_bytes, uint8_t *d_chosen,
+                                   uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                                   uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    PickArgs pa = {};
+    pa.budget = batch_bytes;
+    return rate_encode(e, pa, false, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
+                       d_frame_sizes, d_total, d_status, stream);
+}
+
+int m1v_encode_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                          const uint8_t *candidates, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                          const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
+                          uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                          uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if ((!d_rgb && n_frames > 0) || !d_out || !d_level_in || !d_level_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
+        return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
+    PickArgs pa = {};
+    pa.rate = (long long)bytes_per_frame;
+    pa.capacity = (long long)buffer_bytes;
+    pa.level_in = (const long long *)d_level_in;
+    pa.level_out = (long long *)d_level_out;
+    return rate_encode(e, pa, true, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
+                       d_frame_sizes, d_total, d_status, stream);
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

@@ -144,6 +144,47 @@ class Mpeg1Encoder:
             raise EncoderError(rc, "m1v_frame_size_table_device")
         return sizes[:len(qs) * n].view(len(qs), n)
 
+    @staticmethod
+    def _candidates(candidates, where):
+        """1..8 candidate qualities as the HOST array the library reads (it checks order and range)."""
+        cands = [int(c) for c in candidates]
+        if not 1 <= len(cands) <= _ffi.MAX_CANDIDATES or any(c < 1 or c > 255 for c in cands):
+            raise EncoderError(_ffi.E_ARG, f"{where}: 1 to 8 candidate qualities")
+        return (C.c_uint8 * len(cands))(*cands)
+
+    def _encode_retrying(self, rgb, name, where, launch):
+        """Synchronous: launch(out, sizes, meta) queues one encode of rgb into those buffers (a C entry point, `where`).  On
+        STATUS_SCRATCH the worst-case scratch is reserved and on STATUS_NOSPACE `out` grows to the worst case, and the encode is
+        queued again, three times at most.  Returns (bytes, sizes, status bits)."""
+        import torch
+        n = rgb.shape[0]
+        out = None
+        for attempt in range(3):
+            if out is None:
+                out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
+            sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
+            meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
+            rc = launch(out, sizes, meta)
+            if rc != _ffi.OK:
+                raise EncoderError(rc, where)
+            self.flush()
+            torch.cuda.synchronize(rgb.device)
+            total, status = (int(x) for x in meta.cpu())
+            status &= 0xFFFFFFFF
+            if status & _ffi.STATUS_UNENCODABLE:
+                raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
+            if status & _ffi.STATUS_QUALITY:
+                raise EncoderError(_ffi.E_ARG, f"{name}: a quality outside 1 .. quality_factor")
+            if not status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
+                break
+            if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
+                self.reserve_scratch(True)
+            if status & _ffi.STATUS_NOSPACE:
+                out = torch.empty(self.frame_bound * max(n, 1), dtype=torch.uint8, device=rgb.device)
+        else:
+            raise EncoderError(_ffi.E_NOSPACE if status & _ffi.STATUS_NOSPACE else _ffi.E_SCRATCH, name)
+        return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:n].cpu()], status
+
     def encode_to_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
         """Synchronous: every frame at the largest of `candidates` (1..8 qualities, strictly increasing, each <= quality_factor)
         whose record fits its budget, else at the smallest.  max_frame_bytes: one budget for every frame, or one per frame
@@ -151,10 +192,7 @@ class Mpeg1Encoder:
         import torch
         n = rgb.shape[0]
         self._check_input(rgb)
-        cands = [int(c) for c in candidates]
-        if not 1 <= len(cands) <= _ffi.MAX_CANDIDATES or any(c < 1 or c > 255 for c in cands):
-            raise EncoderError(_ffi.E_ARG, "encode_to_budget: 1 to 8 candidate qualities")
-        cand_buf = (C.c_uint8 * len(cands))(*cands)
+        cand_buf = self._candidates(candidates, "encode_to_budget")
         if isinstance(max_frame_bytes, torch.Tensor):
             assert max_frame_bytes.is_cuda and max_frame_bytes.dtype == torch.int64 and max_frame_bytes.numel() == n
             budget, d_budget = 0, max_frame_bytes.contiguous()
@@ -165,38 +203,67 @@ class Mpeg1Encoder:
             assert len(b) == n, "max_frame_bytes: one entry per frame"
             budget, d_budget = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
         chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        out = None
-        for attempt in range(3):
-            if out is None:
-                out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
-            sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
-            meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
-            rc = _ffi.lib().m1v_encode_budget_device(self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cands), budget,
-                                                     _ptr(d_budget), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes),
-                                                     C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream())
-            if rc != _ffi.OK:
-                raise EncoderError(rc, "m1v_encode_budget_device")
-            self.flush()
-            torch.cuda.synchronize(rgb.device)
-            total, status = (int(x) for x in meta.cpu())
-            status &= 0xFFFFFFFF
-            if status & _ffi.STATUS_UNENCODABLE:
-                raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
-            if status & _ffi.STATUS_QUALITY:
-                raise EncoderError(_ffi.E_ARG, "encode_to_budget: a quality outside 1 .. quality_factor")
-            if not status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
-                break
-            if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
-                self.reserve_scratch(True)
-            if status & _ffi.STATUS_NOSPACE:
-                out = torch.empty(self.frame_bound * max(n, 1), dtype=torch.uint8, device=rgb.device)
-        else:
-            raise EncoderError(_ffi.E_NOSPACE if status & _ffi.STATUS_NOSPACE else _ffi.E_SCRATCH, "encode_to_budget")
-        sizes_l = [int(s) for s in sizes[:n].cpu()]
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, "encode_to_budget", "m1v_encode_budget_device",
+            lambda out, sizes, meta: _ffi.lib().m1v_encode_budget_device(
+                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), budget, _ptr(d_budget), _ptr(chosen),
+                _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream()))
         chosen_l = [int(c) for c in chosen[:n].cpu()]
         budgets = [budget] * n if d_budget is None else [int(x) for x in d_budget[:n].cpu()]
         over = [f for f in range(n) if sizes_l[f] > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
-        return out[:total].cpu().numpy().tobytes(), sizes_l, chosen_l, over
+        return data, sizes_l, chosen_l, over
+
+    def encode_to_batch_budget(self, rgb, batch_bytes, candidates, first_frame_index=0):
+        """Synchronous: the whole batch within batch_bytes (the sum of its records).  Every frame at one of two neighbouring
+        `candidates` (1..8 qualities, strictly increasing, each <= quality_factor): the highest level whose every-frame total
+        fits, and the leftover bytes spent on the cheapest upgrades to the next (include/mpeg1_hip.h,
+        m1v_encode_batch_budget_device).  over_budget: even every frame at the smallest candidate does not fit (all are there).
+        Returns (bytes, sizes, chosen, over_budget)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        cand_buf = self._candidates(candidates, "encode_to_batch_budget")
+        if not 0 <= int(batch_bytes) < 2 ** 64:
+            raise EncoderError(_ffi.E_ARG, "encode_to_batch_budget: batch_bytes must fit uint64")
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        data, sizes_l, status = self._encode_retrying(
+            rgb, "encode_to_batch_budget", "m1v_encode_batch_budget_device",
+            lambda out, sizes, meta: _ffi.lib().m1v_encode_batch_budget_device(
+                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), int(batch_bytes), _ptr(chosen),
+                _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream()))
+        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], bool(status & _ffi.STATUS_OVER_BUDGET)
+
+    def encode_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
+        """Synchronous constant bitrate (a leaky bucket, include/mpeg1_hip.h m1v_encode_cbr_device): bytes_per_frame per frame
+        into a buffer of buffer_bytes.  level: CUDA int64 tensor [1], the bytes available to the next frame; each frame goes at
+        the largest of `candidates` whose record fits it, else at the smallest.  The level is advanced over the batch in place,
+        only when the call succeeds, so that consecutive calls form one stream.  Returns (bytes, sizes, chosen,
+        over_budget_frames)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        assert level.is_cuda and level.dtype == torch.int64 and level.numel() == 1, "level: CUDA int64 tensor of one element"
+        cand_buf = self._candidates(candidates, "encode_at_bitrate")
+        rate, cap = int(bytes_per_frame), int(buffer_bytes)
+        if not 1 <= rate <= cap < 2 ** 62:
+            raise EncoderError(_ffi.E_ARG, "encode_at_bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62")
+        level_in = level.contiguous()
+        start = int(level_in.item())
+        level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, "encode_at_bitrate", "m1v_encode_cbr_device",
+            lambda out, sizes, meta: _ffi.lib().m1v_encode_cbr_device(
+                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap, _ptr(level_in),
+                _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()),
+                C.c_void_p(meta.data_ptr() + 8), _stream()))
+        level.copy_(level_out.view_as(level))
+        over, L = [], min(start, cap)                # the level before each frame, replayed from the sizes
+        for f, s in enumerate(sizes_l):
+            if s > L:
+                over.append(f)                       # (STATUS_OVER_BUDGET is set iff there are any)
+            L = min(cap, L - s + rate)
+        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], over
 
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.

@@ -19,6 +19,9 @@
  *                              write_to_bitstream (image_processing.c:753, called at encoder.h:461-465) stores
  *   m1v_encode_quality_device / m1v_frame_sizes_device / m1v_encode_budget_device
  *                              no reference counterpart (one quality per run there): per-frame quality, size probe, budget
+ *   m1v_frame_size_table_device / m1v_encode_batch_budget_device / m1v_encode_cbr_device
+ *                              no reference counterpart: sizes at up to 8 qualities, a byte budget for a whole batch, a
+ *                              constant bitrate through a leaky bucket
  *   m1v_set_pipelined / m1v_flush   no reference counterpart: overlap of one batch's gather with the next encode
  *   m1v_warm_up, m1v_alloc_host/_free_host   no reference counterpart: runtime start-up off the critical path, pinned buffers
  *   m1v_coefficients_device    fast_DCT + quantization + zigzag_scanning only (BASELINE config 2)
@@ -68,7 +71,9 @@ enum {
 /* bits of the device status word (m1v_encode_device's d_status) */
 enum { M1V_STATUS_UNENCODABLE = 1u, M1V_STATUS_NOSPACE = 2u, M1V_STATUS_SCRATCH = 4u };
 /* M1V_STATUS_QUALITY: a per-frame quality outside 1 .. the encoder's quality factor (output of the batch undefined);
- * M1V_STATUS_OVER_BUDGET: m1v_encode_budget_device found no candidate that fits some frame's budget (output valid) */
+ * M1V_STATUS_OVER_BUDGET (output valid): m1v_encode_budget_device found no candidate that fits some frame's budget,
+ * m1v_encode_batch_budget_device found that even every frame at the smallest candidate exceeds the batch's budget, or
+ * m1v_encode_cbr_device found no candidate that fits the buffer level of some frame */
 enum { M1V_STATUS_QUALITY = 8u, M1V_STATUS_OVER_BUDGET = 16u };
 
 typedef struct m1v_encoder m1v_encoder;
@@ -145,9 +150,36 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
  *                             undefined).  Nothing else is written.  Tile path: ONE pass of a fused kernel (pixel stage once,
  *                             quantise and count per quality; no scratch, so never M1V_STATUS_SCRATCH); run path: one probe
  *                             per quality.  n_frames == 0 writes nothing.
- * Argument errors (bad candidates or qualities, n_frames > max_frames, null pointers) return M1V_E_ARG.
- * Profiling (m1v_profile_*) counts one size-table pass on the tile path as ONE launch of the dominant kernel: a budget call
- * with K candidates reports 2 launches there, K + 1 on the run path. */
+ * m1v_encode_batch_budget_device   fit the whole batch into batch_bytes (the sum of its records, d_total) with no host wait.
+ *                             Candidates as for m1v_encode_budget_device; s[k][f] = the record size of frame f at candidate k
+ *                             and T[k] = sum over f of s[k][f].  With top = the LARGEST k with T[k] <= batch_bytes: none ->
+ *                             every frame at candidates[0] and M1V_STATUS_OVER_BUDGET; top = K - 1 -> every frame there;
+ *                             otherwise every frame at candidate top or top + 1: with d[f] = s[top + 1][f] - s[top][f]
+ *                             (signed), every frame with d[f] <= 0 goes up, then the frames with d[f] > 0 in the order of
+ *                             (d[f], f) ascending, the longest prefix of that order whose d sum to at most the bytes left.
+ *                             Without M1V_STATUS_OVER_BUDGET the total is at most batch_bytes.
+ * m1v_encode_cbr_device       a constant bitrate: bytes_per_frame (r >= 1) per frame interval into a buffer of buffer_bytes
+ *                             (C, r <= C < 2^62).  The level L (int64, bytes available to the next frame) starts at
+ *                             min(*d_level_in, C); per frame in order the LARGEST candidate whose record is at most L is
+ *                             picked, or candidates[0] and M1V_STATUS_OVER_BUDGET when none is, and L = min(C, L - record + r)
+ *                             (it may go negative: the debt is repaid by later refills; a stream may owe less than 2^62
+ *                             bytes).  The final L goes to *d_level_out (int64 on the device; may be d_level_in).  A call
+ *                             that passes the previous call's d_level_out as d_level_in continues its stream: the result is
+ *                             that of one call over the concatenated frames, and the host never reads the level.  Separate
+ *                             pointers let a failed or M1V_STATUS_SCRATCH call be repeated from the same level.  n_frames
+ *                             == 0 writes *d_total = 0, *d_status = 0 and *d_level_out = min(*d_level_in, C).
+ *                             Both: d_chosen (uint8[n_frames] on the device, may be NULL) receives the picked qualities.  A
+ *                             rule assumes nothing about how size grows with quality.  The headers are those of every other
+ *                             call (the rule limits bytes; it signals nothing in the stream), and every record is that of the
+ *                             frame at its picked quality.  One size table (m1v_frame_size_table_device), one pick kernel
+ *                             (a single workgroup, k_rate_pick) and one encode, all on `stream`: the cost of
+ *                             m1v_encode_budget_device with the same candidates plus that launch (17 us for the batch form,
+ *                             28 us for the bitrate form at 300 frames, K = 8).  M1V_STATUS_SCRATCH of a probe (run path)
+ *                             passes on as there.
+ * Argument errors (bad candidates or qualities, n_frames > max_frames, null pointers; for the bitrate: a null level pointer,
+ * bytes_per_frame == 0, buffer_bytes < bytes_per_frame or buffer_bytes >= 2^62) return M1V_E_ARG before anything is launched.
+ * Profiling (m1v_profile_*) counts one size-table pass on the tile path as ONE launch of the dominant kernel: a budget,
+ * batch-budget or bitrate call with K candidates reports 2 launches there, K + 1 on the run path. */
 int m1v_encode_quality_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                               const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
                               uint64_t *d_total, uint32_t *d_status, void *stream);
@@ -160,6 +192,15 @@ int m1v_encode_budget_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frame
                              uint32_t *d_status, void *stream);
 int m1v_frame_size_table_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
                                 uint64_t *d_sizes, uint32_t *d_status, void *stream);
+int m1v_encode_batch_budget_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                                   const uint8_t *candidates, int n_candidates, uint64_t batch_bytes, uint8_t *d_chosen,
+                                   uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                                   uint32_t *d_status, void *stream);
+int m1v_encode_cbr_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                          const uint8_t *candidates, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                          const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
+                          uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
+                          uint32_t *d_status, void *stream);
 
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
@@ -270,8 +311,9 @@ void m1v_debug_fail_alloc(int nth);
  * the internal counter set is chosen, before the encode kernel; 2 = after the encode kernel (and the run layout), before
  * the assembly; 3 = after the assembly, before the pipelined completion event.  One-shot; 0 = off.  Host side only: it
  * launches nothing and touches no device memory.  Inert unless the process runs with EC504_DEBUG_HOOKS=1.  A size-table pass
- * of the tile path (m1v_frame_size_table_device, m1v_encode_budget_device) reaches the stages as: 1 = before its probe
- * kernel, 2 = after the probe kernel, before the sizes kernel, 3 = after the sizes kernel. */
+ * of the tile path (m1v_frame_size_table_device, m1v_encode_budget_device, m1v_encode_batch_budget_device, m1v_encode_cbr_device)
+ * reaches the stages as: 1 = before its probe kernel, 2 = after the probe kernel, before the sizes kernel, 3 = after the sizes
+ * kernel. */
 void m1v_debug_fail_encode(int stage);
 /* Test hook: force how the RUN kernel loads its pixels (forcing a mode selects the run path): -1 = automatic (by width,
  * channel count and pointer alignment), 0 = byte loads (valid everywhere), 2 = 28-byte loads + funnel shift (3 channels,

@@ -7,6 +7,10 @@
     probe       m1v_frame_sizes_device (the encode kernel + k_frame_sizes instead of k_assemble)
     budget K    m1v_encode_budget_device with K candidates (tiles: one size-table pass + the pick + one encode; runs: K probes
                 + the pick + one encode)
+    batch K     m1v_encode_batch_budget_device with K candidates and a budget of n frames at that size (the size table of
+                budget K + k_rate_pick, one workgroup + one encode)
+    cbr K       m1v_encode_cbr_device with K candidates, that size per frame into a buffer of two frames (separate level
+                pointers: every call starts from the same level)
     table K     m1v_frame_size_table_device with K qualities (tiles: k_size_table_tiles + k_size_table_sizes; runs: K probes)
 
 Each leg: `--settle` untimed calls, then `--launches` timed back-to-back calls with one synchronisation (wall time per call),
@@ -54,6 +58,9 @@ table_status = torch.zeros(8, dtype=torch.int32, device="cuda")
 TS, TST = vp(table_sizes.data_ptr()), vp(table_status.data_ptr())
 TABLES = {1: (a.q,), 2: CANDS[2], 4: CANDS[4], 8: CANDS[8]}
 budget = int(0.75 * a.w * a.h * 3 // 54)   # ~ the record of a noise frame at quality 8-9 (1080p: 114.5 KB at 12)
+level_in = torch.full((1,), 2 * budget, dtype=torch.int64, device="cuda")
+level_out = torch.zeros(1, dtype=torch.int64, device="cuda")
+LI, LO = vp(level_in.data_ptr()), vp(level_out.data_ptr())
 
 
 def legs():
@@ -64,6 +71,10 @@ def legs():
         cand = (C.c_uint8 * k)(*[min(x, a.q) for x in c])
         yield f"budget K={k}", (lambda cand=cand, k=k: L.m1v_encode_budget_device(h, R, a.n, 0, cand, k, budget, None, None, O,
                                                                                   out.numel(), S, T, ST, None)), k + 1
+        yield f"batch K={k}", (lambda cand=cand, k=k: L.m1v_encode_batch_budget_device(h, R, a.n, 0, cand, k, budget * a.n, None, O,
+                                                                                       out.numel(), S, T, ST, None)), k + 1
+        yield f"cbr K={k}", (lambda cand=cand, k=k: L.m1v_encode_cbr_device(h, R, a.n, 0, cand, k, budget, 2 * budget, LI, LO, None,
+                                                                            O, out.numel(), S, T, ST, None)), k + 1
     for k, c in TABLES.items():
         qs = (C.c_uint8 * k)(*[min(x, a.q) for x in c])
         yield f"table K={k}", (lambda qs=qs, k=k: L.m1v_frame_size_table_device(h, R, a.n, qs, k, TS, TST, None)), k
