@@ -27,7 +27,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
     "m1v_debug_set_input_mode", "m1v_reserve_scratch", "m1v_scratch_bytes", "m1v_debug_set_path", "m1v_path_in_use", "m1v_debug_fail_alloc",
-    "m1v_debug_fail_encode",
+    "m1v_debug_fail_encode", "m1v_size_table_fused",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -129,6 +129,8 @@ def lib():
     L.m1v_debug_set_path.restype = C.c_int
     L.m1v_path_in_use.argtypes = [vp]
     L.m1v_path_in_use.restype = C.c_int
+    L.m1v_size_table_fused.argtypes = [vp]
+    L.m1v_size_table_fused.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

@@ -27,6 +27,8 @@
 //   k_dense_frame_layout   run kernel only: run metadata -> segment table, strip bit counts, frame bytes
 //   k_assemble        (m1v_assemble.h) ONE launch behind every encode kernel: frame and strip offsets, the strips' segments
 //                     at their final bit positions, frame headers, 16-bit length back-patch, trailer, sizes, status
+//   k_size_table_tiles, k_size_table_rgba   (m1v_tiles.h, m1v_size_table_body.h) record sizes at up to 8 qualities in one pass of the
+//                     tile workgroup, for 3- and 4-channel pictures; k_size_table_sizes writes them out
 //   k_coefficients    FDCT+quant+zigzag only (BASELINE config 2)
 //   k_convert, k_subsample, k_synth   plane conversion / 4:2:0 / synthetic input
 //
@@ -1667,8 +1669,11 @@ struct Plan {
     size_t scratch_bytes, meta_bytes, seg_bytes; // per batch state (meta: run metadata, dense only)
     int segs;               // segments per strip: tile rows (tiles), or the most runs a strip can touch (run kernels)
     int asm_group, asm_lanes_log2; // k_assemble: strips per workgroup, lanes per segment
-    uint32_t table_region;  // tiles: k_size_table_tiles' LDS bytes of a wave's ring / staging region
-    size_t table_lds_bytes; //        and its dynamic LDS
+    // The fused size table (k_size_table_tiles; k_size_table_rgba for 4-channel encoders, whatever their producer is): its
+    // own tile grid (tile_cols x tile_rows above), set when table_units != 0
+    int table_units;        // its workgroups per frame, 0 = no fused table: one probe per quality
+    uint32_t table_region;  // its LDS bytes of a wave's ring / staging region
+    size_t table_lds_bytes; // and its dynamic LDS
 };
 
 struct m1v_encoder {
@@ -1701,7 +1706,7 @@ struct m1v_encoder {
     uint8_t *d_chosen = nullptr;
     uint32_t *d_pick_status = nullptr; // k_rate_pick's status word (batch-budget and bitrate calls)
     int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
-    // The size table's counters (3-channel encoders): k_size_table_tiles adds, k_size_table_sizes reads and clears what it added.
+    // The size table's counters: k_size_table_tiles / k_size_table_rgba add, k_size_table_sizes reads and clears what it added.
     struct TableCounters {
         unsigned long long *strip_ctr = nullptr;   // [kMaxCandidates][max_frames][strip]
         unsigned long long *frame_bytes = nullptr; // [kMaxCandidates][max_frames]
@@ -1808,10 +1813,7 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
         p.image_words = (p.image_words + 3) & ~3; // cleared 16 bytes per lane
         p.lds_bytes = (size_t)kTileFixedWords * 4 + 2 * (size_t)p.luma_region + p.chroma_region + (size_t)p.image_words * 4;
         p.segs = p.tile_rows;
-        // the size table: the ring, or the staged levels at the widest quality the encoder allows, per wave; no image
-        p.table_region = p.luma_region;
-        p.table_lds_bytes = (size_t)kTableFixedWords * 4 + 3 * (size_t)p.table_region;
-        if (p.table_lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the size table does not fit%s");
+        p.table_units = p.units;
     } else if (e.dense) {
         const int T = e.forced_T > 0 ? e.forced_T : (bps >= 256 ? 256 : (bps / kWave) * kWave);
         if (T < kWave || T > 384 || T % kWave || T > bps) return fail(M1V_E_ARG, "bad dense run length%s");
@@ -1839,6 +1841,20 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
         p.segs = 1; // a strip is one piece
     }
     if (p.lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the LDS image is too large%s");
+    // The fused size table of a 4-channel encoder (k_size_table_rgba): the tile workgroup over the picture, whichever run kernel
+    // encodes it.  The test hooks that force a path, an input mode or a run length keep one probe per quality: the A/B
+    // reference inside one process.
+    if (g.C == 4 && e.forced_path < 0 && e.forced_mode < 0 && e.forced_T == 0) {
+        p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
+        p.tile_rows = (g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
+        p.table_units = p.tile_cols * p.tile_rows;
+    }
+    if (p.table_units) {
+        // per wave: the ring, or the staged levels at the widest quality the encoder allows; no image
+        p.table_region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * stride * 4)) + 15u) & ~15u;
+        p.table_lds_bytes = (size_t)kTableFixedWords * 4 + 3 * (size_t)p.table_region;
+        if (p.table_lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the size table does not fit%s");
+    }
     if (p.producer != Producer::strips) {
         // Scratch: one compact slot per unit + an overflow arena of worst-case slots for the units whose image outgrows LDS
         // (handed out by an atomic counter).  By default the arena holds 1/256 of the units (quality 12 noise needs none);
@@ -1882,9 +1898,10 @@ static const void *const kProducerKernels[3][4][2] = {
     {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
      {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
 
-// The size-table kernel of the tile path, [narrow staging] (m1v_create raises their dynamic LDS limit)
-static const void *const kTableKernels[2] = {(const void *)&k_size_table_tiles<false, M1V_TILE_RING>,
-                                             (const void *)&k_size_table_tiles<true, M1V_TILE_RING>};
+// The fused size-table kernels, [4-byte pixels][narrow staging] (m1v_create raises their dynamic LDS limit)
+static const void *const kTableKernels[2][2] = {
+    {(const void *)&k_size_table_tiles<false, M1V_TILE_RING>, (const void *)&k_size_table_tiles<true, M1V_TILE_RING>},
+    {(const void *)&k_size_table_rgba<false, M1V_TILE_RING>, (const void *)&k_size_table_rgba<true, M1V_TILE_RING>}};
 
 // defined in m1v_runtime.h
 static int profile_event(m1v_encoder *e, hipStream_t st);
@@ -2135,15 +2152,15 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
 }
 
 
-// The size table on the tile path: k_size_table_tiles, then k_size_table_sizes, both on the caller's stream (no Batch, no
-// scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
+// The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), then k_size_table_sizes,
+// both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
 // sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
-static int size_table_tiles(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
+static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
                             unsigned long long *sizes, size_t stride, uint32_t *status, hipStream_t st) {
     HIP_TRY(hipSetDevice(e->device));
     m1v_encoder::TableCounters &tc = e->table;
     const Plan &p = e->plan;
-    if (!tc.strip_ctr || p.producer != Producer::tiles) return fail(M1V_E_HIP, "the encoder has no size-table counters%s");
+    if (!tc.strip_ctr || !p.table_units) return fail(M1V_E_HIP, "the encoder has no size-table counters%s");
     if (tc.poisoned) { // the last call failed after its probe kernel may have added: clear every counter first
         HIP_TRY(table_clear(e, st));
         tc.poisoned = false;
@@ -2168,15 +2185,15 @@ static int size_table_tiles(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     a.n_frames = n_frames;
     a.tile_cols = p.tile_cols;
     a.tile_rows = p.tile_rows;
-    a.tiles_per_frame = p.units;
-    const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.units;
-    a.div_group = div_magic(8u * (uint32_t)p.units, units);
-    a.div_frame = div_magic((uint32_t)p.units, units);
-    a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.units);
+    a.tiles_per_frame = p.table_units;
+    const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.table_units;
+    a.div_group = div_magic(8u * (uint32_t)p.table_units, units);
+    a.div_frame = div_magic((uint32_t)p.table_units, units);
+    a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.table_units);
     a.tile_row_order = e->d_tile_order;
     a.region = p.table_region;
     void *args[] = {&a};
-    const void *kernel = kTableKernels[qualities[n_q - 1] <= e->narrow_q ? 1 : 0];
+    const void *kernel = kTableKernels[g.C == 4 ? 1 : 0][qualities[n_q - 1] <= e->narrow_q ? 1 : 0];
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
     (void)hipLaunchKernel(kernel, dim3((unsigned)units), dim3((unsigned)kTileThreads), args, p.table_lds_bytes, st);
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;

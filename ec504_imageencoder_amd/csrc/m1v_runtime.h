@@ -199,7 +199,7 @@ static int configure_path(m1v_encoder *e) {
         bool new_scratch, new_meta, new_seg, new_fixed;
     } fresh[2] = {};
     uint32_t *fresh_order = nullptr;
-    const bool new_order = p.producer == Producer::tiles && e->tile_order_rows != p.tile_rows;
+    const bool new_order = p.tile_rows != 0 && e->tile_order_rows != p.tile_rows; // the tile kernel's and the fused size table's
     bool ok = true;
     for (int i = 0; i < sets && ok; i++) {
         const m1v_encoder::Batch &bt = e->batch[i];
@@ -385,7 +385,7 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
     if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
-    if (channels == 3) { // the size table's counters (tile path), clear
+    { // the fused size table's counters, clear
         const size_t kf = (size_t)kMaxCandidates * max_frames;
         if (err == hipSuccess) err = hipMalloc(&e->table.strip_ctr, kf * g.n_strips * 8);
         if (err == hipSuccess) err = hipMalloc(&e->table.frame_bytes, kf * 8);
@@ -402,8 +402,9 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
         for (const auto &by_staging : by_mode)
             for (const void *kf : by_staging)
                 if (err == hipSuccess && kf) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    for (const void *kf : kTableKernels)
-        if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const auto &by_staging : kTableKernels)
+        for (const void *kf : by_staging)
+            if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err != hipSuccess) {
         fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
         m1v_destroy(e);
@@ -524,6 +525,8 @@ int m1v_debug_set_path(m1v_encoder *e, int path) {
 
 int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }
 
+int m1v_size_table_fused(const m1v_encoder *e) { return e ? (e->plan.table_units ? 1 : 0) : -1; }
+
 void m1v_debug_fail_alloc(int nth) {
     // fault injection for the tests: inert unless the process was started with EC504_DEBUG_HOOKS=1
     const char *on = getenv("EC504_DEBUG_HOOKS");
@@ -605,13 +608,14 @@ static int check_qualities(const m1v_encoder *e, const uint8_t *q, int n) {
     return M1V_OK;
 }
 
-// sizes[k * stride + frame] and status[k] of every quality: one k_size_table_tiles pass on the tile path; on the run path one
-// probe call (m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that
-// every row is complete in stream order.
+// sizes[k * stride + frame] and status[k] of every quality: one fused pass where the plan has one (3-channel tile encoders,
+// 4-channel encoders: m1v_size_table_fused); otherwise (a path, input mode or run length forced by a test hook) one probe call
+// (m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that every row is
+// complete in stream order.
 static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
                       unsigned long long *sizes, size_t stride, uint32_t *status, void *stream) {
-    if (e->plan.producer == Producer::tiles)
-        return size_table_tiles(e, d_rgb, n_frames, qualities, n_q, sizes, stride, status, (hipStream_t)stream);
+    if (e->plan.table_units)
+        return size_table_fused(e, d_rgb, n_frames, qualities, n_q, sizes, stride, status, (hipStream_t)stream);
     for (int k = 0; k < n_q; k++) {
         QualityArgs qa = {};
         qa.uniform = qualities[k];

@@ -1,0 +1,123 @@
+// ec504_imageencoder_amd/csrc/m1v_size_table_body.h — the body of k_size_table_tiles and k_size_table_rgba (m1v_tiles.h),
+// included inside each kernel.  In scope: STAGE8, R (template parameters), BPP (bytes per pixel), TableArgs a.
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const Geometry &g = a.g;
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool chroma = wave == 2; // wave-uniform
+    constexpr int kStride = STAGE8 ? kStageStride8 : kStageStride16;
+    const uint32_t *vlc = lds + wave * kVlcWords;
+    uint32_t *cnt = lds + kTableCnt;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds;
+    const uint32_t region_off = (uint32_t)kTableFixedWords * 4u + (uint32_t)wave * a.region; // bytes from lds
+
+    // the tile and its place in the tile-row order: as k_encode_tiles
+    int frame, tile;
+    frame_unit_of(blockIdx.x, a.n_frames, a.div_group, a.div_frame, frame, tile);
+    const int tk = (int)udiv((uint32_t)tile, a.div_cols), tc = tile - tk * a.tile_cols;
+    const int tr = (int)a.tile_row_order[tk];
+    const int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
+    const uint8_t *fbase = a.rgb + (unsigned long long)frame * g.frame_bytes;
+    auto owner = [&](int ln, int &j, int &m, int &blk) {
+        if (!chroma) {
+            m = 2 * wave + (ln >> 5);
+            blk = ((ln >> 4) & 1) * 2 + (ln & 1);
+            j = (ln >> 1) & 7;
+        } else {
+            m = (ln >> 3) & 3;
+            blk = 4 + (ln >> 5);
+            j = ln & 7;
+        }
+    };
+    const int strips_here = min(kTileStrips, g.n_strips - s0); // >= 1
+    int comp;
+    {
+        int j_, m_, blk_;
+        owner(lane, j_, m_, blk_);
+        comp = blk_ < 4 ? 0 : blk_ - 3;
+    }
+
+    // ---- pixel stage, once: the wave's VLC table is requested in front of the rows ----
+    RowStore<8> rows;
+    tile_pixel_rows<R, 8, false, BPP>(
+        g, fbase, lds0 + region_off, wave, lane, s0, m0, strips_here, comp,
+        [&]() {
+#pragma unroll
+            for (int q = 0; q < kVlcWords / kWave; q++)
+                dma4((uint32_t)lane * 4u, lds0 + (uint32_t)(wave * kVlcWords + q * kWave) * 4u, a.tab->vlc + q * kWave);
+        },
+        [] {}, rows);
+    // ---- column pass, once: coef[u * 8 + i] = coefficient (row u, column i) ----
+    float coef[64];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        float c[8];
+        m1vf::fdct_col_f<float>(rows.get(0, i), rows.get(1, i), rows.get(2, i), rows.get(3, i), rows.get(4, i), rows.get(5, i),
+                                rows.get(6, i), rows.get(7, i), c, i == 0 ? RowStore<8>::kBias0 : 0.0f);
+#pragma unroll
+        for (int u = 0; u < 8; u++) coef[u * 8 + i] = c[u];
+    }
+    int j, m, blk;
+    {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        owner(ln, j, m, blk);
+    }
+    const bool valid = j < strips_here && m0 + m < g.n_mbrows;
+    const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
+    // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
+    const uint32_t *blkp = lds + region_off / 4u + lane * kStride;
+    auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
+
+    // ---- per quality: quantise, stage, mask, count (pass 1) ----
+    uint32_t bad_q = 0; // bit k: an unencodable level at quality k
+    for (int k = 0; k < a.n_q; k++) {
+        const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(a.rq_all + a.qoff[k]));
+        uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint32_t *)blkp;
+        // the staging stores (asm, chained through lds_addr) stay behind the previous quality's reads of the staged levels
+        asm volatile("" : "+v"(lds_addr) : : "memory");
+        int dc = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int q = quant(coef[u * 8 + i], rq_t[i * 8 + u]);
+                const int p = scan_pos(u * 8 + i);
+                if (p == 0) dc = q;
+                if (STAGE8)
+                    asm("ds_write_b8 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte8(p)));
+                else
+                    asm("ds_write_b16 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte16(p)));
+            }
+        }
+        const unsigned long long nz = (stage_nonzero_mask<STAGE8>(blkp, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
+        uint32_t hdr = 0, bad = 0;
+        int hlen = 0;
+        BlockBits bb = {0, 0};
+        dc_header(dc, blk < 4, blk, vlc, hdr, hlen);
+        block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
+        cnt[k * kTileThreads + e] = valid ? (uint32_t)bb.tot : 0u;
+        bad_q |= (valid && bad) ? 1u << k : 0u;
+    }
+    lds_barrier();
+
+    // ---- wave 0, lane k * 8 + j: segment j at quality k (24 consecutive counts), then the strip's arrival ----
+    if (wave == 0) {
+        const int k = lane >> 3, jj = lane & 7;
+        if (k < a.n_q && jj < strips_here) {
+            const uint4 *c4 = reinterpret_cast<const uint4 *>(cnt + k * kTileThreads + jj * kTileSegBlocks);
+            uint32_t bits = tr == 0 ? 38u : 0u; // the strip starts in this tile: slice header in front (mpeg1_blk.c:12-16)
+#pragma unroll
+            for (int t = 0; t < kTileSegBlocks / 4; t++) {
+                const uint4 v = c4[t];
+                bits += v.x + v.y + v.z + v.w;
+            }
+            const unsigned long long kf = (unsigned long long)k * (unsigned)a.n_frames + (unsigned)frame;
+            const unsigned long long before = atomicAdd(a.strip_ctr + kf * (unsigned)g.n_strips + (unsigned)(s0 + jj),
+                                                        (1ull << kCtrCountShift) | (unsigned long long)bits);
+            if ((uint32_t)(before >> kCtrCountShift) == (uint32_t)a.tile_rows - 1u)
+                atomicAdd(&a.frame_bytes[kf], ((before & kCtrBitsMask) + bits + 7ull) >> 3);
+        }
+    }
+    for (uint32_t b = bad_q; b; b &= b - 1u) atomicOr(&a.status[__builtin_ctz(b)], (uint32_t)M1V_STATUS_UNENCODABLE); // (rare)

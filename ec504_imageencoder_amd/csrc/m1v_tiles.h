@@ -96,6 +96,19 @@ __device__ __forceinline__ Row24 ring_read24(uint32_t addr) {
     return v;
 }
 
+// 32 bytes (eight 4-byte pixels) at a 16-byte aligned LDS address, as ring_read24
+__device__ __forceinline__ Row32 ring_read32(uint32_t addr) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 r0, r1;
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(r0), "=&v"(r1)
+                 : "v"(addr));
+    Row32 v;
+    v.d[0] = r0.x; v.d[1] = r0.y; v.d[2] = r0.z; v.d[3] = r0.w;
+    v.d[4] = r1.x; v.d[5] = r1.y; v.d[6] = r1.z; v.d[7] = r1.w;
+    return v;
+}
+
 // column pass + quantise + stage in LDS (as block_to_stage's second half); returns the DC level
 template <bool STAGE8, int KEEP>
 __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, const M1V_CONST_AS float *rq_t, uint32_t &lds_addr) {
@@ -170,7 +183,13 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
 // region; wave 0, 1 = luma, wave 2 = chroma (see the head of this file); `first` / `meanwhile`: see below.  DOWN: the row
 // pass takes its rounded-down form (the wave has switched MODE: pixel_stage_rounds_down); false = the integer form of the run
 // kernels, right in the default mode (k_size_table_tiles).
-template <int R, int KEEP, bool DOWN = true, typename First, typename Meanwhile>
+// BPP = 4: 4-byte pixels (the alpha byte is skipped), the front half of k_size_table_rgba.  The same workgroup, ring and
+// vmcnt count; a picture row of a tile is 8 x 16 x 4 = 512 bytes, so
+//     luma    row-step = 4 pieces x 512 = the 2048 bytes of the slot: units 0..63 (pieces 0, 1) | units 64..127 (pieces 2, 3);
+//             lane L's 32 bytes sit at L * 32
+//     chroma  row-step = 4 macroblock rows x 256 bytes = ONE instruction; the second repeats it into the slot's other half
+// and every strip is a whole number of 16-byte units (64 luma, 32 chroma): no unit straddles the tile's last strip.
+template <int R, int KEEP, bool DOWN = true, int BPP = 3, typename First, typename Meanwhile>
 __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t *fbase, uint32_t ring, int wave, int lane, int s0,
                                                 int m0, int strips_here, int comp, First first, Meanwhile meanwhile,
                                                 RowStore<KEEP> &rows) {
@@ -191,7 +210,30 @@ __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t
         asm volatile("" : "+s"(v));
         return v;
     };
-    if (!chroma) {
+    if constexpr (BPP == 4) {
+        const uint32_t piece = (uint32_t)lane >> (chroma ? 4 : 5); // which of the instruction's pieces the lane's unit lies in
+        const uint32_t row_px = chroma ? (uint32_t)g.half_w : (uint32_t)g.W;
+        pitch = row_px * 4u;
+        const uint32_t vw = (uint32_t)strips_here * (chroma ? 32u : 64u); // bytes of a piece that lie inside the picture region
+        const uint32_t within = min(((uint32_t)lane & (chroma ? 15u : 31u)) * 16u, vw - 16u);
+        auto row_off = [&](uint32_t pc) { // uniform
+            if (!chroma) {
+                const uint32_t mb = (uint32_t)min(m0 + 2 * wave + (int)(pc >> 1), g.n_mbrows - 1);
+                return ((mb * 16u + (pc & 1u) * 8u) * row_px + (uint32_t)s0 * 16u) * 4u;
+            }
+            const uint32_t mb = (uint32_t)min(m0 + (int)pc, g.n_mbrows - 1);
+            return ((mb * 8u) * row_px + (uint32_t)s0 * 8u) * 4u;
+        };
+        const uint32_t r0 = uniform(row_off(0)), r1 = uniform(row_off(1)), r2 = uniform(row_off(2)), r3 = uniform(row_off(3));
+        if (!chroma) {
+            voff_a = (piece ? r1 : r0) + within;
+            voff_b = (piece ? r3 : r2) + within;
+            lane_row = ring + ((uint32_t)lane << 5);
+        } else {
+            voff_a = voff_b = (piece == 0 ? r0 : (piece == 1 ? r1 : (piece == 2 ? r2 : r3))) + within;
+            lane_row = ring + (((uint32_t)lane & 31u) << 5); // [macroblock row:2][strip:3] x 32 bytes; Cb and Cr read the same
+        }
+    } else if (!chroma) {
         pitch = (uint32_t)g.W * 3u;
         const uint32_t vw = (uint32_t)strips_here * 48u;
         // 16-byte unit L of the 1536-byte row-step: piece = L / 24 = picture row of the step, `within` inside its 384 bytes
@@ -253,10 +295,16 @@ __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t
         if (behind == 0) wait_vm<0>(); else if (behind == 1) wait_vm<2>(); else if (behind == 2) wait_vm<4>();
         else if (behind == 3) wait_vm<6>(); else if (behind == 4) wait_vm<8>(); else if (behind == 5) wait_vm<10>();
         else if (behind == 6) wait_vm<12>(); else wait_vm<14>();
-        const Row24 v = ring_read24(lane_row + (uint32_t)(i % R) * kSlot);
-        if (i + R < 8) issue_row(i + R);
         float px[8];
-        convert_row<3, M1V_TILE_LEAN>(v, kf, px);
+        if constexpr (BPP == 4) {
+            const Row32 v = ring_read32(lane_row + (uint32_t)(i % R) * kSlot);
+            if (i + R < 8) issue_row(i + R);
+            convert_row<4, true>(v, kf, px);
+        } else {
+            const Row24 v = ring_read24(lane_row + (uint32_t)(i % R) * kSlot);
+            if (i + R < 8) issue_row(i + R);
+            convert_row<3, M1V_TILE_LEAN>(v, kf, px);
+        }
         float ro[8];
         m1vf::fdct_row_f<float, DOWN>(px, ro); // DOWN: the wave rounds down, pixel_stage_rounds_down()
         rows.put(i, ro);
@@ -567,129 +615,20 @@ struct TableArgs {
 // LDS words in front of the per-wave regions: one VLC table per wave, the bit counts [quality][block in emission order]
 constexpr int kTableCnt = 3 * kVlcWords, kTableFixedWords = kTableCnt + kMaxCandidates * kTileThreads;
 
+// The body of both kernels is csrc/m1v_size_table_body.h, included into each with BPP = the bytes per pixel of its input (a
+// shared inline function would do, but the compiler then numbers the registers of the 3-channel kernel differently: its
+// code stays the parent's instruction for instruction this way).
 template <bool STAGE8, int R>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_tiles(TableArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const Geometry &g = a.g;
-    const int tid = threadIdx.x;
-    const int lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool chroma = wave == 2; // wave-uniform
-    constexpr int kStride = STAGE8 ? kStageStride8 : kStageStride16;
-    const uint32_t *vlc = lds + wave * kVlcWords;
-    uint32_t *cnt = lds + kTableCnt;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds;
-    const uint32_t region_off = (uint32_t)kTableFixedWords * 4u + (uint32_t)wave * a.region; // bytes from lds
-
-    // the tile and its place in the tile-row order: as k_encode_tiles
-    int frame, tile;
-    frame_unit_of(blockIdx.x, a.n_frames, a.div_group, a.div_frame, frame, tile);
-    const int tk = (int)udiv((uint32_t)tile, a.div_cols), tc = tile - tk * a.tile_cols;
-    const int tr = (int)a.tile_row_order[tk];
-    const int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
-    const uint8_t *fbase = a.rgb + (unsigned long long)frame * g.frame_bytes;
-    auto owner = [&](int ln, int &j, int &m, int &blk) {
-        if (!chroma) {
-            m = 2 * wave + (ln >> 5);
-            blk = ((ln >> 4) & 1) * 2 + (ln & 1);
-            j = (ln >> 1) & 7;
-        } else {
-            m = (ln >> 3) & 3;
-            blk = 4 + (ln >> 5);
-            j = ln & 7;
-        }
-    };
-    const int strips_here = min(kTileStrips, g.n_strips - s0); // >= 1
-    int comp;
-    {
-        int j_, m_, blk_;
-        owner(lane, j_, m_, blk_);
-        comp = blk_ < 4 ? 0 : blk_ - 3;
-    }
-
-    // ---- pixel stage, once: the wave's VLC table is requested in front of the rows ----
-    RowStore<8> rows;
-    tile_pixel_rows<R, 8, false>(
-        g, fbase, lds0 + region_off, wave, lane, s0, m0, strips_here, comp,
-        [&]() {
-#pragma unroll
-            for (int q = 0; q < kVlcWords / kWave; q++)
-                dma4((uint32_t)lane * 4u, lds0 + (uint32_t)(wave * kVlcWords + q * kWave) * 4u, a.tab->vlc + q * kWave);
-        },
-        [] {}, rows);
-    // ---- column pass, once: coef[u * 8 + i] = coefficient (row u, column i) ----
-    float coef[64];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        float c[8];
-        m1vf::fdct_col_f<float>(rows.get(0, i), rows.get(1, i), rows.get(2, i), rows.get(3, i), rows.get(4, i), rows.get(5, i),
-                                rows.get(6, i), rows.get(7, i), c, i == 0 ? RowStore<8>::kBias0 : 0.0f);
-#pragma unroll
-        for (int u = 0; u < 8; u++) coef[u * 8 + i] = c[u];
-    }
-    int j, m, blk;
-    {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        owner(ln, j, m, blk);
-    }
-    const bool valid = j < strips_here && m0 + m < g.n_mbrows;
-    const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
-    // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
-    const uint32_t *blkp = lds + region_off / 4u + lane * kStride;
-    auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
-
-    // ---- per quality: quantise, stage, mask, count (pass 1) ----
-    uint32_t bad_q = 0; // bit k: an unencodable level at quality k
-    for (int k = 0; k < a.n_q; k++) {
-        const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(a.rq_all + a.qoff[k]));
-        uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint32_t *)blkp;
-        // the staging stores (asm, chained through lds_addr) stay behind the previous quality's reads of the staged levels
-        asm volatile("" : "+v"(lds_addr) : : "memory");
-        int dc = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int q = quant(coef[u * 8 + i], rq_t[i * 8 + u]);
-                const int p = scan_pos(u * 8 + i);
-                if (p == 0) dc = q;
-                if (STAGE8)
-                    asm("ds_write_b8 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte8(p)));
-                else
-                    asm("ds_write_b16 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte16(p)));
-            }
-        }
-        const unsigned long long nz = (stage_nonzero_mask<STAGE8>(blkp, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
-        uint32_t hdr = 0, bad = 0;
-        int hlen = 0;
-        BlockBits bb = {0, 0};
-        dc_header(dc, blk < 4, blk, vlc, hdr, hlen);
-        block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
-        cnt[k * kTileThreads + e] = valid ? (uint32_t)bb.tot : 0u;
-        bad_q |= (valid && bad) ? 1u << k : 0u;
-    }
-    lds_barrier();
-
-    // ---- wave 0, lane k * 8 + j: segment j at quality k (24 consecutive counts), then the strip's arrival ----
-    if (wave == 0) {
-        const int k = lane >> 3, jj = lane & 7;
-        if (k < a.n_q && jj < strips_here) {
-            const uint4 *c4 = reinterpret_cast<const uint4 *>(cnt + k * kTileThreads + jj * kTileSegBlocks);
-            uint32_t bits = tr == 0 ? 38u : 0u; // the strip starts in this tile: slice header in front (mpeg1_blk.c:12-16)
-#pragma unroll
-            for (int t = 0; t < kTileSegBlocks / 4; t++) {
-                const uint4 v = c4[t];
-                bits += v.x + v.y + v.z + v.w;
-            }
-            const unsigned long long kf = (unsigned long long)k * (unsigned)a.n_frames + (unsigned)frame;
-            const unsigned long long before = atomicAdd(a.strip_ctr + kf * (unsigned)g.n_strips + (unsigned)(s0 + jj),
-                                                        (1ull << kCtrCountShift) | (unsigned long long)bits);
-            if ((uint32_t)(before >> kCtrCountShift) == (uint32_t)a.tile_rows - 1u)
-                atomicAdd(&a.frame_bytes[kf], ((before & kCtrBitsMask) + bits + 7ull) >> 3);
-        }
-    }
-    for (uint32_t b = bad_q; b; b &= b - 1u) atomicOr(&a.status[__builtin_ctz(b)], (uint32_t)M1V_STATUS_UNENCODABLE); // (rare)
+    constexpr int BPP = 3;
+#include "m1v_size_table_body.h"
+}
+// The same for 4-channel pictures, whatever kernel encodes them: the table places no bits, so it does not have to share the
+// shape of the encoder's producer (k_encode_dense, or k_encode_strips for short strips).
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void k_size_table_rgba(TableArgs a) {
+    constexpr int BPP = 4;
+#include "m1v_size_table_body.h"
 }
 
 // The size table's place of k_frame_sizes (one workgroup per frame and quality): the record size (48 bytes of headers and trailer

@@ -126,9 +126,10 @@ class Mpeg1Encoder:
 
     def frame_size_table(self, rgb, qualities, status=None):
         """The exact record size of every frame at each of `qualities` (1..8, strictly increasing, each <= quality_factor):
-        int64 CUDA tensor [K, n], row k = frame_sizes(rgb, quality=[qualities[k]] * n).  One fused pass on the tile path.
-        Asynchronous on torch's current stream (complete in stream order, pipelined mode included).  status: optional CUDA
-        int32 tensor [K] that receives each quality's status bits (STATUS_UNENCODABLE: that row is undefined)."""
+        int64 CUDA tensor [K, n], row k = frame_sizes(rgb, quality=[qualities[k]] * n).  One fused pass where size_table_fused
+        is 1 (3 channels on the tile path, 4 channels always).  Asynchronous on torch's current stream (complete in stream order,
+        pipelined mode included).  status: optional CUDA int32 tensor [K] that receives each quality's status bits
+        (STATUS_UNENCODABLE: that row is undefined)."""
         import torch
         n = rgb.shape[0]
         self._check_input(rgb)
@@ -429,6 +430,12 @@ class Mpeg1Encoder:
     @property
     def path(self):
         return "tiles" if _ffi.lib().m1v_path_in_use(self._h) == 1 else "runs"
+
+    @property
+    def size_table_fused(self):
+        """1: a size table (and the table of a budget, batch-budget or bitrate call) is one fused pass; 0: one probe per
+        quality (an encoder forced by a debug hook)."""
+        return _ffi.lib().m1v_size_table_fused(self._h)
 
     def debug_set_lds_words(self, words):
         rc = _ffi.lib().m1v_debug_set_lds_words(self._h, int(words))

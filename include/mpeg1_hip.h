@@ -138,18 +138,23 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
  *                             M1V_STATUS_OVER_BUDGET when none fits, then encodes once at the picked qualities.  The budget of
  *                             frame f is d_max_frame_bytes[f] (uint64[n_frames] on the device) or, when that is NULL,
  *                             max_frame_bytes.  d_chosen (uint8[n_frames] on the device, may be NULL) receives the picks.
- *                             The candidates' sizes come from m1v_frame_size_table_device: on the tile path one size-table pass,
- *                             then the encode (about 3 plain encode kernels at K = 8); on the run path K probes +
- *                             the encode, K + 1 encode kernels.  A probe that exhausts the overflow scratch reports
- *                             M1V_STATUS_SCRATCH (run path only: the size table uses no scratch).
+ *                             The candidates' sizes come from m1v_frame_size_table_device: where the table is fused
+ *                             (m1v_size_table_fused: 3-channel tile encoders and 4-channel encoders) one size-table pass, then
+ *                             the encode (about 3 plain encode kernels at K = 8); otherwise (only an encoder whose
+ *                             path, input mode or run length a m1v_debug_set_* hook has forced) K probes + the encode, K + 1
+ *                             encode kernels.  A probe that exhausts the overflow scratch reports M1V_STATUS_SCRATCH (probes
+ *                             only: the fused table uses no scratch).
  * m1v_frame_size_table_device the exact record size of every frame at each of n_qualities qualities (a HOST array, 1..8 entries,
  *                             strictly increasing, each <= the encoder's quality): d_sizes[k * n_frames + f] (uint64, on the
  *                             device) is what m1v_frame_sizes_device returns for frame f at the uniform quality qualities[k].
  *                             d_status[k] (uint32[n_qualities], may be NULL) receives the status bits of quality k
  *                             (M1V_STATUS_UNENCODABLE: some block cannot be coded at qualities[k], whose sizes are then
- *                             undefined).  Nothing else is written.  Tile path: ONE pass of a fused kernel (pixel stage once,
- *                             quantise and count per quality; no scratch, so never M1V_STATUS_SCRATCH); run path: one probe
- *                             per quality.  n_frames == 0 writes nothing.
+ *                             undefined).  Nothing else is written.  ONE pass of a fused kernel (pixel stage once, quantise
+ *                             and count per quality; no scratch, so never M1V_STATUS_SCRATCH) for 3-channel encoders on the tile
+ *                             path and for every 4-channel encoder, whose encodes stay on the run kernels; one probe per
+ *                             quality only for an encoder forced by a m1v_debug_set_* hook (3 channels forced to runs; 4
+ *                             channels with a forced path, input mode or run length).  m1v_size_table_fused tells which.
+ *                             n_frames == 0 writes nothing.
  * m1v_encode_batch_budget_device   fit the whole batch into batch_bytes (the sum of its records, d_total) with no host wait.
  *                             Candidates as for m1v_encode_budget_device; s[k][f] = the record size of frame f at candidate k
  *                             and T[k] = sum over f of s[k][f].  With top = the LARGEST k with T[k] <= batch_bytes: none ->
@@ -174,12 +179,16 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
  *                             frame at its picked quality.  One size table (m1v_frame_size_table_device), one pick kernel
  *                             (a single workgroup, k_rate_pick) and one encode, all on `stream`: the cost of
  *                             m1v_encode_budget_device with the same candidates plus that launch (17 us for the batch form,
- *                             28 us for the bitrate form at 300 frames, K = 8).  M1V_STATUS_SCRATCH of a probe (run path)
- *                             passes on as there.
+ *                             28 us for the bitrate form at 300 frames, K = 8).  M1V_STATUS_SCRATCH of a probe (hook-forced
+ *                             encoders only) passes on as there.
  * Argument errors (bad candidates or qualities, n_frames > max_frames, null pointers; for the bitrate: a null level pointer,
  * bytes_per_frame == 0, buffer_bytes < bytes_per_frame or buffer_bytes >= 2^62) return M1V_E_ARG before anything is launched.
- * Profiling (m1v_profile_*) counts one size-table pass on the tile path as ONE launch of the dominant kernel: a budget,
- * batch-budget or bitrate call with K candidates reports 2 launches there, K + 1 on the run path. */
+ * Profiling (m1v_profile_*) counts one fused size-table pass as ONE launch of the dominant kernel: a budget, batch-budget or
+ * bitrate call with K candidates reports 2 launches where m1v_size_table_fused is 1, K + 1 on a hook-forced encoder.
+ *
+ * m1v_size_table_fused        what a size table costs on this encoder, before a caller sizes K: 1 = one fused pass (about two
+ *                             plain encode kernels at K = 8), 0 = one probe (one encode kernel) per quality, -1 = null. */
+int m1v_size_table_fused(const m1v_encoder *enc);
 int m1v_encode_quality_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                               const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
                               uint64_t *d_total, uint32_t *d_status, void *stream);
@@ -287,7 +296,7 @@ int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint6
                      uint64_t first_frame_index, void *stream);
 
 /* Kernel timing by HIP events recorded on the launch stream around the dominant kernel
- * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles for a size-table pass).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
+ * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles / k_size_table_rgba for a size-table pass).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
  * and returns launches/total milliseconds since the last read. */
 int m1v_profile_enable(m1v_encoder *enc, int enable);
 int m1v_profile_read(m1v_encoder *enc, int *launches, double *total_ms);

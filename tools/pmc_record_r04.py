@@ -14,7 +14,8 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["ec504_imageencoder_amd/csrc/m1v_kernels.hip", "ec504_imageencoder_amd/csrc/m1v_tiles.h", "ec504_imageencoder_amd/csrc/m1v_assemble.h",
+SOURCES = ["ec504_imageencoder_amd/csrc/m1v_kernels.hip", "ec504_imageencoder_amd/csrc/m1v_tiles.h",
+           "ec504_imageencoder_amd/csrc/m1v_size_table_body.h", "ec504_imageencoder_amd/csrc/m1v_assemble.h",
            "ec504_imageencoder_amd/csrc/fdct_f32.h"]
 
 

@@ -11,13 +11,15 @@
                 budget K + k_rate_pick, one workgroup + one encode)
     cbr K       m1v_encode_cbr_device with K candidates, that size per frame into a buffer of two frames (separate level
                 pointers: every call starts from the same level)
-    table K     m1v_frame_size_table_device with K qualities (tiles: k_size_table_tiles + k_size_table_sizes; runs: K probes)
+    table K     m1v_frame_size_table_device with K qualities (one fused pass, k_size_table_tiles or, with --channels 4,
+                k_size_table_rgba, + k_size_table_sizes; an encoder forced by --path runs: K probes)
 
 Each leg: `--settle` untimed calls, then `--launches` timed back-to-back calls with one synchronisation (wall time per call),
 legs alternating for `--rounds` rounds; the median round is printed.  `kernel` is the median duration of the encode kernel
 (HIP events around it, a separate pass; a size-table pass counts as one launch), so a budget call can be set against (K + 1) x
 the plain encode kernel, and a size table against K x.
-    usage: quality_timing.py [--w 1920 --h 1080 --n 300] [--path tiles|runs]"""
+    usage: quality_timing.py [--w 1920 --h 1080 --n 300] [--channels 3|4] [--path tiles|runs] [--only plain,table,budget]
+A/B of the table and budget calls against another build of the library in one process: tools/rgba_table_timing.py."""
 import argparse
 import ctypes as C
 import os
@@ -33,6 +35,8 @@ ap.add_argument("--h", type=int, default=1080)
 ap.add_argument("--n", type=int, default=300)
 ap.add_argument("--q", type=int, default=12)
 ap.add_argument("--path", default="")
+ap.add_argument("--channels", type=int, default=3)
+ap.add_argument("--only", default="", help="comma-separated leg name prefixes (plain is always timed)")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--settle", type=int, default=100)
 ap.add_argument("--launches", type=int, default=200)
@@ -40,7 +44,7 @@ a = ap.parse_args()
 import torch
 from ec504_imageencoder_amd import Mpeg1Encoder, _ffi
 
-enc = Mpeg1Encoder(a.w, a.h, a.q, "full", max_frames=a.n)
+enc = Mpeg1Encoder(a.w, a.h, a.q, "full", channels=a.channels, max_frames=a.n)
 if a.path:
     enc.debug_set_path(a.path)
 L, h = _ffi.lib(), enc._h
@@ -64,6 +68,13 @@ LI, LO = vp(level_in.data_ptr()), vp(level_out.data_ptr())
 
 
 def legs():
+    only = tuple(x for x in a.only.split(",") if x)
+    for leg in all_legs():
+        if not only or leg[0] == "plain" or leg[0].startswith(only):
+            yield leg
+
+
+def all_legs():
     yield "plain", lambda: L.m1v_encode_device(h, R, a.n, 0, O, out.numel(), S, T, ST, None), 1
     yield "quality", lambda: L.m1v_encode_quality_device(h, R, a.n, 0, Q, O, out.numel(), S, T, ST, None), 1
     yield "probe", lambda: L.m1v_frame_sizes_device(h, R, a.n, None, S, ST, None), 1
@@ -104,7 +115,7 @@ for name, go, per_call in legs():
     enc.profile(False)
     kern[name] = statistics.median(t) * 1e3, len(t) // 50
 plain_k = kern["plain"][0]
-print(f"{a.n} x {a.w}x{a.h} q{a.q} path={enc.path}  budget={budget} B/frame")
+print(f"{a.n} x {a.w}x{a.h}x{a.channels} q{a.q} path={enc.path} size_table_fused={enc.size_table_fused}  budget={budget} B/frame")
 for name, go, per_call in legs():
     step = statistics.median(res[name]) * 1e6
     k_us, launches = kern[name]
