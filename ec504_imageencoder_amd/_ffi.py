@@ -14,6 +14,7 @@ MODE_STRICT, MODE_FULL = 0, 1
 OK, E_ARG, E_UNENCODABLE, E_NOSPACE, E_HIP, E_NODEVICE, E_SCRATCH = 0, -1, -2, -3, -4, -5, -6
 STATUS_UNENCODABLE, STATUS_NOSPACE, STATUS_SCRATCH, STATUS_QUALITY, STATUS_OVER_BUDGET = 1, 2, 4, 8, 16
 MAX_CANDIDATES = 8
+ORDER_RGB, ORDER_BGR = 0, 1
 
 _u8p = C.POINTER(C.c_uint8)
 
@@ -27,7 +28,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
     "m1v_debug_set_input_mode", "m1v_reserve_scratch", "m1v_scratch_bytes", "m1v_debug_set_path", "m1v_path_in_use", "m1v_debug_fail_alloc",
-    "m1v_debug_fail_encode", "m1v_size_table_fused",
+    "m1v_debug_fail_encode", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -131,6 +132,10 @@ def lib():
     L.m1v_path_in_use.restype = C.c_int
     L.m1v_size_table_fused.argtypes = [vp]
     L.m1v_size_table_fused.restype = C.c_int
+    L.m1v_set_input_layout.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.m1v_set_input_layout.restype = C.c_int
+    L.m1v_input_layout.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.m1v_input_layout.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

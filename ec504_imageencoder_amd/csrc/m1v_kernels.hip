@@ -3,6 +3,7 @@
 //
 // Data layout in HBM
 //   input    n_frames x (H x W x C) interleaved u8, as the reference's Image::data (jpeg_handler.h:6-11)
+//            (or, with a surface layout, windows of pitched surfaces: m1v_set_input_layout)
 //   scratch  one compact slot per unit of the encode kernel (a tile of 8 strips x 4 macroblock rows, or a run of 256 blocks)
 //            + an overflow arena of worst-case slots; a strip = 16-pixel-wide COLUMN of macroblocks (encoder.h:238
 //            iterates x outermost) and is byte aligned (encoder.h:442), so strips are independent units of bit packing;
@@ -12,6 +13,9 @@
 // Kernels
 //   k_encode_tiles    (m1v_tiles.h) the encode kernel of every 3-channel picture: a workgroup per tile of 8 strips x 4
 //                     macroblock rows, pixels in as whole 128-byte lines by LDS-DMA, one lane per 8x8 block
+//   k_encode_surface, k_size_table_surface   (m1v_tiles.h, m1v_encode_tile_body.h, m1v_size_table_body.h) the same tile
+//                     encode and size table on windows of pitched surfaces, 3- or 4-byte pixels in R,G,B or B,G,R order
+//                     (m1v_set_input_layout: row r of frame f at base + f * frame stride + r * row pitch)
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -287,10 +291,12 @@ struct __attribute__((aligned(4))) Row24 {
 // 8 pixels of one block row (24 or 32 bytes already in registers) -> 8 raw pixels.  One "is any pixel of this row
 // uncertain?" branch per row instead of one per pixel: the branch is taken by about half of the waves, and then only
 // the flagged pixels redo the fp64 expression.
-template <int BPP, bool LEAN, typename RowT>
+// ORDER: M1V_ORDER_BGR = colour ch is byte 2 - ch of the pixel.  The permutation is applied where the bytes are extracted: the
+// arithmetic below sees (r, g, b) in the orders tools/colour_fast_proof.c proves.
+template <int BPP, bool LEAN, int ORDER = 0, typename RowT>
 __device__ __forceinline__ void convert_row(const RowT &v, const CompCoefF &k, float out[8]) {
     auto chan = [&](int j, int ch) -> uint32_t {
-        int byte = BPP * j + ch;
+        int byte = BPP * j + (ORDER ? 2 - ch : ch);
         return (v.d[byte >> 2] >> ((byte & 3) * 8)) & 0xffu;
     };
     float lowest = 1.0f;
@@ -314,7 +320,7 @@ __device__ __forceinline__ void convert_row(const RowT &v, const CompCoefF &k, f
             for (int i = 0; i < (int)(sizeof(RowT) / 4); i++) asm("" : "+v"(w.d[i]));
         }
         auto chan2 = [&](int j, int ch) -> uint32_t {
-            int byte = BPP * j + ch;
+            int byte = BPP * j + (ORDER ? 2 - ch : ch);
             return (w.d[byte >> 2] >> ((byte & 3) * 8)) & 0xffu;
         };
         const CompCoef &d = k.d;
@@ -1648,7 +1654,7 @@ int fail(int code, const char *fmt, const char *detail = "") {
 #endif
 
 // Which encode kernel serves a batch.  Tiles (k_encode_tiles, m1v_tiles.h): 3-channel pictures, any width and alignment — the
-// default.  Runs: k_encode_dense (4-channel pictures, and whatever the test hooks force: m1v_debug_set_path, a forced input mode, a
+// default; with a surface layout (m1v_set_input_layout) k_encode_surface in their place, for 3 and 4 channels.  Runs: k_encode_dense (4-channel pictures, and whatever the test hooks force: m1v_debug_set_path, a forced input mode, a
 // forced run length), or k_encode_strips where a strip has fewer than 64 blocks.
 enum class Producer { tiles, dense, strips };
 
@@ -1690,6 +1696,13 @@ struct m1v_encoder {
     int forced_path = -1;       // m1v_debug_set_path: -1 = by geometry, 0 = runs, 1 = tiles
     int forced_T = 0;           // run length forced by m1v_debug_set_dense_threads (0 = default)
     bool pipelined = false;     // layout + gather of batch k on `side` while batch k+1 encodes on the caller's stream
+    // m1v_set_input_layout: the pictures are windows of a pitched surface (the surface kernels); the values in force, no zeros
+    struct Layout {
+        bool surface = false;
+        uint32_t row_pitch = 0;               // bytes from a picture row to the next
+        unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
+        int order = M1V_ORDER_RGB;
+    } layout;
     Plan plan = {};             // the plan configure_path set up
     unsigned calls = 0;
     hipStream_t side = nullptr;
@@ -1797,7 +1810,8 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     // (widths that are not a multiple of 8, buffers off a 4-byte boundary), 1 % faster at 4K (the order of the tile rows keeps
     // the chroma re-reads in L2, tile_row_order_for), and 0.5-1 % faster per step on aligned 1080p in a sustained run
     // (profiles/r03_ab_history.txt).  The run kernel serves 4-channel input and the m1v_debug_set_* hooks.
-    if (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0)) {
+    // A surface layout takes the same plan for 3 and 4 channels (k_encode_surface; no hook can be set beside it).
+    if (e.layout.surface || (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0))) {
         p.producer = Producer::tiles;
         p.block = kTileThreads;
         p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
@@ -1903,6 +1917,17 @@ static const void *const kTableKernels[2][2] = {
     {(const void *)&k_size_table_tiles<false, M1V_TILE_RING>, (const void *)&k_size_table_tiles<true, M1V_TILE_RING>},
     {(const void *)&k_size_table_rgba<false, M1V_TILE_RING>, (const void *)&k_size_table_rgba<true, M1V_TILE_RING>}};
 
+// The surface kernels (m1v_set_input_layout), [4-byte pixels][byte order][narrow staging]: the tile plan's producer and its
+// fused size table
+#define M1V_SURFACE_KERNELS(K)                                                                                          \
+    {{{(const void *)&K<false, M1V_TILE_RING, 3, 0>, (const void *)&K<true, M1V_TILE_RING, 3, 0>},                      \
+      {(const void *)&K<false, M1V_TILE_RING, 3, 1>, (const void *)&K<true, M1V_TILE_RING, 3, 1>}},                     \
+     {{(const void *)&K<false, M1V_TILE_RING, 4, 0>, (const void *)&K<true, M1V_TILE_RING, 4, 0>},                      \
+      {(const void *)&K<false, M1V_TILE_RING, 4, 1>, (const void *)&K<true, M1V_TILE_RING, 4, 1>}}}
+static const void *const kSurfaceKernels[2][2][2] = M1V_SURFACE_KERNELS(k_encode_surface);
+static const void *const kSurfaceTableKernels[2][2][2] = M1V_SURFACE_KERNELS(k_size_table_surface);
+#undef M1V_SURFACE_KERNELS
+
 // defined in m1v_runtime.h
 static int profile_event(m1v_encoder *e, hipStream_t st);
 static int fail_encode_at(int stage);
@@ -1916,6 +1941,7 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
 
 static const void *producer_kernel(const m1v_encoder *e, const uint8_t *d_rgb) {
+    if (e->layout.surface) return kSurfaceKernels[e->g.C == 4 ? 1 : 0][e->layout.order][e->narrow ? 1 : 0];
     const bool aligned4 = ((uintptr_t)d_rgb & 3) == 0, fast = fast_path(e, d_rgb);
     int mode = 0;
     if (e->plan.producer == Producer::strips) {
@@ -2047,7 +2073,12 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
+        if (e->layout.surface) {
+            SurfaceArgs sa = {a, e->layout.frame_stride, e->layout.row_pitch};
+            if (const int rc = launch_producer(e, bt, kernel, n_frames, sa, st, gs)) return rc;
+        } else if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) {
+            return rc;
+        }
     } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
@@ -2152,7 +2183,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
 }
 
 
-// The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), then k_size_table_sizes,
+// The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), or k_size_table_surface on
+// a surface layout, then k_size_table_sizes,
 // both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
 // sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
 static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
@@ -2192,8 +2224,10 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.table_units);
     a.tile_row_order = e->d_tile_order;
     a.region = p.table_region;
-    void *args[] = {&a};
-    const void *kernel = kTableKernels[g.C == 4 ? 1 : 0][qualities[n_q - 1] <= e->narrow_q ? 1 : 0];
+    SurfaceTableArgs on_surface = {a, e->layout.frame_stride, e->layout.row_pitch};
+    const int narrow = qualities[n_q - 1] <= e->narrow_q ? 1 : 0;
+    void *args[] = {e->layout.surface ? (void *)&on_surface : (void *)&a};
+    const void *kernel = e->layout.surface ? kSurfaceTableKernels[g.C == 4 ? 1 : 0][e->layout.order][narrow] : kTableKernels[g.C == 4 ? 1 : 0][narrow];
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
     (void)hipLaunchKernel(kernel, dim3((unsigned)units), dim3((unsigned)kTileThreads), args, p.table_lds_bytes, st);
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;

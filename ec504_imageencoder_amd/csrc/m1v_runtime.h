@@ -278,6 +278,12 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
     return rc;
 }
 
+// What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
+// the run kernels
+static int packed_only(const m1v_encoder *e) {
+    return e->layout.surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
+}
+
 extern "C" {
 
 const char *m1v_last_error(void) { return g_err; }
@@ -405,6 +411,11 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     for (const auto &by_staging : kTableKernels)
         for (const void *kf : by_staging)
             if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const auto *family : {&kSurfaceKernels, &kSurfaceTableKernels})
+        for (const auto &by_order : *family)
+            for (const auto &by_staging : by_order)
+                for (const void *kf : by_staging)
+                    if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err != hipSuccess) {
         fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
         m1v_destroy(e);
@@ -506,12 +517,16 @@ int m1v_flush(m1v_encoder *e, void *stream) {
 int m1v_debug_set_input_mode(m1v_encoder *e, int mode) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (mode != -1 && mode != 0 && mode != 2) return fail(M1V_E_ARG, "input mode must be -1 (auto), 0 (byte loads) or 2 (funnel)%s");
+    if (mode != -1)
+        if (const int rc = packed_only(e)) return rc;
     return reconfigure(e, &m1v_encoder::forced_mode, mode); // an input mode is a property of the run kernels: forcing one selects them
 }
 
 int m1v_debug_set_dense_threads(m1v_encoder *e, int threads) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (!e->dense) return M1V_OK;
+    if (threads > 0)
+        if (const int rc = packed_only(e)) return rc;
     // a run length is a property of the run kernels: forcing one selects them
     return reconfigure(e, &m1v_encoder::forced_T, threads > 0 ? threads : 0);
 }
@@ -520,7 +535,41 @@ int m1v_debug_set_path(m1v_encoder *e, int path) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (path < -1 || path > 1) return fail(M1V_E_ARG, "path must be -1 (by geometry), 0 (runs) or 1 (tiles)%s");
     if (path == 1 && e->g.C != 3) return fail(M1V_E_ARG, "the tile kernel takes 3-channel pictures%s");
+    if (path == 0)
+        if (const int rc = packed_only(e)) return rc;
     return reconfigure(e, &m1v_encoder::forced_path, path);
+}
+
+int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_stride_bytes, int order) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "order must be M1V_ORDER_RGB or M1V_ORDER_BGR%s");
+    const Geometry &g = e->g;
+    m1v_encoder::Layout want;
+    want.surface = row_pitch_bytes != 0 || frame_stride_bytes != 0 || order != M1V_ORDER_RGB;
+    if (want.surface) {
+        const unsigned long long row = (unsigned long long)g.W * g.C;
+        if (g.W & 1) return fail(M1V_E_ARG, "a surface layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
+        if (row_pitch_bytes != 0 && row_pitch_bytes < row) return fail(M1V_E_ARG, "row pitch below width * channels%s");
+        const unsigned long long pitch = row_pitch_bytes ? row_pitch_bytes : row;
+        if (pitch >= (1ull << 32) || (unsigned long long)(g.H - 1) * pitch + row >= (1ull << 32))
+            return fail(M1V_E_ARG, "a window of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        const unsigned long long extent = (unsigned long long)(g.H - 1) * pitch + row;
+        if (frame_stride_bytes != 0 && frame_stride_bytes < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's window spans%s");
+        if (e->forced_path == 0 || e->forced_mode >= 0 || e->forced_T > 0)
+            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
+        want.row_pitch = (uint32_t)pitch;
+        want.frame_stride = frame_stride_bytes ? frame_stride_bytes : (unsigned long long)g.H * pitch;
+        want.order = order;
+    }
+    return reconfigure(e, &m1v_encoder::layout, want);
+}
+
+int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (row_pitch_bytes) *row_pitch_bytes = e->layout.row_pitch;
+    if (frame_stride_bytes) *frame_stride_bytes = (size_t)e->layout.frame_stride;
+    if (order) *order = e->layout.order;
+    return M1V_OK;
 }
 
 int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }
@@ -901,6 +950,7 @@ void m1v_free_host(void *p) {
 long m1v_encode_planes_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first_frame_index,
                             uint8_t *out, size_t out_cap, uint64_t *frame_sizes, uint8_t *planes) {
     if (!e || !rgb || !out) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = packed_only(e)) return rc;
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     if (n_frames == 0) return 0;
     HIP_TRY(hipSetDevice(e->device));
@@ -991,6 +1041,7 @@ long m1v_encode_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, int first
 int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int16_t *d_coeffs,
                             void *stream) {
     if (!e || !d_rgb || !d_coeffs || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (const int rc = packed_only(e)) return rc;
     if (n_frames == 0) return M1V_OK;
     HIP_TRY(hipSetDevice(e->device));
     CoefArgs a;
@@ -1028,6 +1079,7 @@ int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
 int m1v_convert_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, uint8_t *d_planes,
                        void *stream) {
     if (!e || !d_rgb || !d_planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (const int rc = packed_only(e)) return rc;
     if (n_frames == 0) return M1V_OK;
     HIP_TRY(hipSetDevice(e->device));
     unsigned long long npx = (unsigned long long)e->g.W * e->g.H;
@@ -1053,6 +1105,7 @@ int m1v_convert_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, uint8
 
 int m1v_convert_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, uint8_t *planes) {
     if (!e || !rgb || !planes || n_frames < 0) return fail(M1V_E_ARG, "bad argument%s");
+    if (const int rc = packed_only(e)) return rc;
     if (n_frames == 0) return M1V_OK;
     HIP_TRY(hipSetDevice(e->device));
     size_t in_bytes = (size_t)e->g.frame_bytes * n_frames;

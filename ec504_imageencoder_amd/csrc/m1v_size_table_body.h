@@ -1,5 +1,6 @@
-// ec504_imageencoder_amd/csrc/m1v_size_table_body.h — the body of k_size_table_tiles and k_size_table_rgba (m1v_tiles.h),
-// included inside each kernel.  In scope: STAGE8, R (template parameters), BPP (bytes per pixel), TableArgs a.
+// ec504_imageencoder_amd/csrc/m1v_size_table_body.h — the body of k_size_table_tiles, k_size_table_rgba and k_size_table_surface
+// (m1v_tiles.h), included inside each kernel.  In scope: STAGE8, R (template parameters), TableArgs a, and the input layout:
+// BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows).
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const Geometry &g = a.g;
     const int tid = threadIdx.x;
@@ -18,7 +19,7 @@
     const int tk = (int)udiv((uint32_t)tile, a.div_cols), tc = tile - tk * a.tile_cols;
     const int tr = (int)a.tile_row_order[tk];
     const int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
-    const uint8_t *fbase = a.rgb + (unsigned long long)frame * g.frame_bytes;
+    const uint8_t *fbase = a.rgb + (unsigned long long)frame * (SURFACE ? frame_stride : g.frame_bytes);
     auto owner = [&](int ln, int &j, int &m, int &blk) {
         if (!chroma) {
             m = 2 * wave + (ln >> 5);
@@ -40,14 +41,14 @@
 
     // ---- pixel stage, once: the wave's VLC table is requested in front of the rows ----
     RowStore<8> rows;
-    tile_pixel_rows<R, 8, false, BPP>(
+    tile_pixel_rows<R, 8, false, BPP, SURFACE, ORDER>(
         g, fbase, lds0 + region_off, wave, lane, s0, m0, strips_here, comp,
         [&]() {
 #pragma unroll
             for (int q = 0; q < kVlcWords / kWave; q++)
                 dma4((uint32_t)lane * 4u, lds0 + (uint32_t)(wave * kVlcWords + q * kWave) * 4u, a.tab->vlc + q * kWave);
         },
-        [] {}, rows);
+        [] {}, rows, row_pitch);
     // ---- column pass, once: coef[u * 8 + i] = coefficient (row u, column i) ----
     float coef[64];
 #pragma unroll

@@ -27,6 +27,26 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def surface_strides(shape, strides):
+    """(row_pitch, frame_stride) in bytes of a uint8 [n, H, W, C] array with the given strides (in elements = bytes), as
+    Mpeg1Encoder.set_input_layout takes them: a packed tensor, rows with padding, a window surface[:, y0:y0+H, x0:x0+W, :] of a
+    larger surface, frames with a gap.  Raises ValueError for what no row pitch describes: pixels whose bytes are not adjacent
+    or whose stride is not C, a pitch below W * C, a frame stride below the bytes a frame's window spans.  Pure: no torch."""
+    if len(shape) != 4 or len(strides) != 4:
+        raise ValueError("frames must be [n, H, W, C]")
+    n, H, W, C = (int(x) for x in shape)
+    frame_stride, row_pitch, pixel, byte = (int(x) for x in strides)
+    if byte != 1 or pixel != C:
+        raise ValueError(f"the bytes of a pixel must be adjacent and pixels {C} bytes apart (strides {pixel}, {byte})")
+    if row_pitch < W * C:
+        raise ValueError(f"row pitch {row_pitch} below W * C = {W * C}")
+    if n > 1 and frame_stride < (H - 1) * row_pitch + W * C:
+        raise ValueError(f"frame stride {frame_stride} below the {(H - 1) * row_pitch + W * C} bytes a frame's window spans")
+    if n <= 1:  # (a single frame's stride is arbitrary)
+        frame_stride = H * row_pitch
+    return row_pitch, frame_stride
+
+
 class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
@@ -49,6 +69,7 @@ class Mpeg1Encoder:
         self.frame_bound = L.m1v_frame_bound(self._h)
         self.frame_bytes_in = L.m1v_frame_bytes_in(self._h)
         self.blocks_per_frame = self.strips * self.mb_rows * 6
+        self._layout = (0, 0, "rgb")    # what _check_input holds tensors against (set_input_layout)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -63,7 +84,8 @@ class Mpeg1Encoder:
 
     # ---- the hot path -------------------------------------------------------------------------
     def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
-        """rgb: uint8 CUDA tensor [n, H, W, C] (contiguous).  Asynchronous on torch's current stream.
+        """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
+        as surface[:, y0:y0+H, x0:x0+W, :].  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
         CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
@@ -94,8 +116,36 @@ class Mpeg1Encoder:
 
     def _check_input(self, rgb):
         import torch
-        assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
-        assert rgb.numel() == rgb.shape[0] * self.frame_bytes_in
+        row_pitch, frame_stride, _ = self._layout
+        if row_pitch == 0:      # the default layout: packed frames
+            assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+            assert rgb.numel() == rgb.shape[0] * self.frame_bytes_in
+            return
+        assert rgb.is_cuda and rgb.dtype == torch.uint8
+        assert tuple(rgb.shape[1:]) == (self.height, self.width, self.channels), "frames must be [n, H, W, C]"
+        pitch, stride = surface_strides(tuple(rgb.shape), tuple(rgb.stride()))
+        assert pitch == row_pitch and (rgb.shape[0] <= 1 or stride == frame_stride), \
+            f"strides {tuple(rgb.stride())} are not the input layout in force (row pitch {row_pitch}, frame stride {frame_stride})"
+
+    def set_input_layout(self, row_pitch=0, frame_stride=0, order="rgb"):
+        """Frames as windows of pitched device surfaces, in "rgb" or "bgr" byte order (a 4th byte is skipped), encoded where they
+        lie (include/mpeg1_hip.h, m1v_set_input_layout).  row_pitch / frame_stride in bytes, 0 = W * C / H * row_pitch (see
+        surface_strides).  Every call then takes tensors with those strides.  The defaults restore the packed layout and its
+        kernels.  A reconfiguration: call it between batches."""
+        code = {"rgb": _ffi.ORDER_RGB, "bgr": _ffi.ORDER_BGR}.get(order, order)
+        rc = _ffi.lib().m1v_set_input_layout(self._h, int(row_pitch), int(frame_stride), int(code))
+        if rc != _ffi.OK:
+            raise EncoderError(rc, "m1v_set_input_layout")
+        self._layout = self.input_layout
+
+    @property
+    def input_layout(self):
+        """(row_pitch, frame_stride, order) in force: (0, 0, "rgb") = packed frames, else the bytes the kernels step by."""
+        pitch, stride, order = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        rc = _ffi.lib().m1v_input_layout(self._h, C.byref(pitch), C.byref(stride), C.byref(order))
+        if rc != _ffi.OK:
+            raise EncoderError(rc, "m1v_input_layout")
+        return pitch.value, stride.value, "bgr" if order.value == _ffi.ORDER_BGR else "rgb"
 
     @staticmethod
     def _quality_tensor(quality, n, device):

@@ -107,7 +107,7 @@ size_t m1v_frame_bytes_in(const m1v_encoder *enc); /* width*height*channels */
 /* PACK(12)+SYS(15), written once per file.  Returns 27. */
 size_t m1v_file_prolog(uint8_t out[27]);
 
-/* n_frames frames, contiguous in d_rgb (interleaved, width*height*channels bytes each), to
+/* n_frames frames, contiguous in d_rgb (interleaved, width*height*channels bytes each; or laid out as m1v_set_input_layout says), to
  * contiguous frame records in d_out.  first_frame_index is the global index of frame 0 of the batch
  * (it drives the `hour` fields, encoder.h:42,475-484).  d_rgb is only read, but a kernel may read up to the next
  * 4-byte boundary past a row's last byte (three bytes at most, inside the aligned word that holds that byte; pictures
@@ -211,6 +211,45 @@ int m1v_encode_cbr_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, 
                           uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                           uint32_t *d_status, void *stream);
 
+/* Input layout: frames that already live on the device as windows of pitched surfaces, in R,G,B(,A) or B,G,R(,A) byte order,
+ * encoded where they lie (no compaction or swizzle copy in front of the encoder).
+ *
+ *   m1v_set_input_layout(enc, row_pitch_bytes, frame_stride_bytes, order)
+ *
+ * d_rgb of every *_device call then points at the first byte of the window's first pixel in frame 0; row y of frame f starts at
+ * d_rgb + f * frame_stride + y * row_pitch.  Any byte alignment of the pointer, the pitch and the stride is accepted.  order is
+ * the order of the three colour bytes of a pixel; a 4th byte is skipped.
+ *   (0, 0, M1V_ORDER_RGB)   the DEFAULT layout: packed frames, served by exactly the kernels of an encoder whose layout was never
+ *                           set.  Setting it again after a surface layout restores that plan (m1v_path_in_use is then 0 again
+ *                           for 4 channels).
+ *   anything else           a SURFACE layout, served by the surface kernels (k_encode_surface, k_size_table_surface: the tile
+ *                           workgroup behind a pitched front half), also when the pitch equals width * channels: the same
+ *                           packed buffer through both kernel families gives the same bytes (the A/B reference inside one
+ *                           process, like the m1v_debug_set_* hooks), and a 4-channel caller opts into the tile-shaped encode
+ *                           this way.  row_pitch 0 = width * channels; frame_stride 0 = height * row_pitch.
+ * With a surface layout m1v_path_in_use and m1v_size_table_fused are 1 for 3 and 4 channels, and every *_device encode, probe,
+ * size-table, budget, batch-budget and bitrate call, pipelined mode, m1v_reserve_scratch, m1v_debug_set_lds_words and
+ * m1v_delivery_* work as on the tile path.  It is a reconfiguration like m1v_reserve_scratch: call it between batches; new
+ * buffers are allocated first and swapped in on success, so a failed call (M1V_E_HIP) leaves the encoder as it was.
+ * M1V_E_ARG, before anything is launched or reallocated: 0 < row_pitch < width * channels; 0 < frame_stride <
+ * (height - 1) * row_pitch + width * channels; (height - 1) * row_pitch + width * channels >= 2^32 (offsets inside a frame are
+ * 32-bit); an unknown order; a surface layout with an odd width (the reference addresses its chroma plane with stride width / 2:
+ * with an odd width a chroma block row straddles two picture rows and is no run of bytes inside one pitched row; odd widths keep
+ * working on the default layout); a surface layout on an encoder that a hook has forced to the run kernels (m1v_debug_set_path 0,
+ * m1v_debug_set_input_mode, m1v_debug_set_dense_threads) — conversely those hooks return M1V_E_ARG on an encoder with a surface
+ * layout.
+ * Packed only: m1v_coefficients_device, m1v_convert_device, m1v_encode_host, m1v_encode_planes_host and m1v_convert_host return
+ * M1V_E_ARG while a surface layout is set.
+ * Read contract: of frame f a kernel reads only bytes of [d_rgb + f * frame_stride, d_rgb + f * frame_stride +
+ * (height - 1) * row_pitch + width * channels), rounded up to the next 4-byte boundary as for packed input.  Padding bytes inside
+ * that range (between a row's last pixel and the next row, a 4th byte of a pixel) may be read; they never influence the output.
+ *
+ *   m1v_input_layout(enc, &row_pitch, &frame_stride, &order)   the layout in force: (0, 0, M1V_ORDER_RGB) for the default, else
+ *                           the pitch and the stride in bytes as the kernels use them (no zeros).  Any pointer may be NULL. */
+enum { M1V_ORDER_RGB = 0, M1V_ORDER_BGR = 1 };   /* byte order of the three colour bytes of a pixel; a 4th byte is skipped */
+int m1v_set_input_layout(m1v_encoder *enc, size_t row_pitch_bytes, size_t frame_stride_bytes, int order);
+int m1v_input_layout(const m1v_encoder *enc, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order);
+
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
  * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.
@@ -278,7 +317,8 @@ void *m1v_alloc_host(size_t bytes);
 void m1v_free_host(void *p);
 
 /* The 64 zigzag-ordered quantised levels of every visited block, int16, in emission order
- * [frame][strip][macroblock][Y0 Y1 Y2 Y3 Cb Cr][64]. */
+ * [frame][strip][macroblock][Y0 Y1 Y2 Y3 Cb Cr][64].  Packed input only (as m1v_convert_* and the *_host entry points):
+ * M1V_E_ARG while a surface layout is set. */
 int m1v_coefficients_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int16_t *d_coeffs,
                             void *stream);
 
@@ -296,7 +336,8 @@ int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint6
                      uint64_t first_frame_index, void *stream);
 
 /* Kernel timing by HIP events recorded on the launch stream around the dominant kernel
- * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles / k_size_table_rgba for a size-table pass).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
+ * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles / k_size_table_rgba for a size-table pass;
+ * k_encode_surface / k_size_table_surface on a surface layout).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
  * and returns launches/total milliseconds since the last read. */
 int m1v_profile_enable(m1v_encoder *enc, int enable);
 int m1v_profile_read(m1v_encoder *enc, int *launches, double *total_ms);
@@ -309,10 +350,11 @@ int m1v_debug_set_lds_words(m1v_encoder *enc, int words);
 /* Two encode kernels serve the path.  TILES (default for 3-channel pictures of any width and alignment): a workgroup
  * owns 8 adjacent strips x 4 macroblock rows and brings the pixels in as whole 128-byte lines by LDS-DMA.  RUNS (4-channel
  * pictures): a workgroup owns 256 consecutive blocks of the stream, every lane loads its own 24-byte block rows.  Both
- * produce the same bytes.  Test hook: -1 = by geometry, 0 = runs, 1 = tiles (3 channels only). */
+ * produce the same bytes.  Test hook: -1 = by geometry, 0 = runs, 1 = tiles (3 channels only).  (A surface layout,
+ * m1v_set_input_layout, runs the tile workgroup for 3 and 4 channels and reports 1.) */
 int m1v_debug_set_path(m1v_encoder *enc, int path);
 int m1v_path_in_use(const m1v_encoder *enc); /* 1 = tiles, 0 = runs */
-/* Test hook: the nth device allocation made from now on by a reconfiguration (m1v_reserve_scratch, m1v_set_pipelined,
+/* Test hook: the nth device allocation made from now on by a reconfiguration (m1v_reserve_scratch, m1v_set_pipelined, m1v_set_input_layout,
  * the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
  * M1V_E_HIP and leaves the encoder exactly as it was.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
 void m1v_debug_fail_alloc(int nth);
