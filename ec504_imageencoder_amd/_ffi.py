@@ -15,6 +15,16 @@ OK, E_ARG, E_UNENCODABLE, E_NOSPACE, E_HIP, E_NODEVICE, E_SCRATCH = 0, -1, -2, -
 STATUS_UNENCODABLE, STATUS_NOSPACE, STATUS_SCRATCH, STATUS_QUALITY, STATUS_OVER_BUDGET = 1, 2, 4, 8, 16
 MAX_CANDIDATES = 8
 ORDER_RGB, ORDER_BGR = 0, 1
+PLANES_REFERENCE, PLANES_I420, PLANES_YV12, PLANES_NV12, PLANES_NV21 = 0, 1, 2, 3, 4
+PLANE_PRESETS = {"reference": PLANES_REFERENCE, "i420": PLANES_I420, "yv12": PLANES_YV12, "nv12": PLANES_NV12, "nv21": PLANES_NV21}
+
+
+class PlaneLayout(C.Structure):
+    """m1v_plane_layout (include/mpeg1_hip.h): where the Y, Cb and Cr samples of a frame lie, in bytes."""
+    _fields_ = [(name, C.c_size_t) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 _u8p = C.POINTER(C.c_uint8)
 
@@ -29,6 +39,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
     "m1v_debug_set_input_mode", "m1v_reserve_scratch", "m1v_scratch_bytes", "m1v_debug_set_path", "m1v_path_in_use", "m1v_debug_fail_alloc",
     "m1v_debug_fail_encode", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
+    "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -136,6 +147,12 @@ def lib():
     L.m1v_set_input_layout.restype = C.c_int
     L.m1v_input_layout.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.m1v_input_layout.restype = C.c_int
+    L.m1v_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(PlaneLayout)]
+    L.m1v_plane_layout_preset.restype = C.c_int
+    L.m1v_set_plane_layout.argtypes = [vp, C.POINTER(PlaneLayout)]
+    L.m1v_set_plane_layout.restype = C.c_int
+    L.m1v_plane_layout_in_force.argtypes = [vp, C.POINTER(PlaneLayout)]
+    L.m1v_plane_layout_in_force.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

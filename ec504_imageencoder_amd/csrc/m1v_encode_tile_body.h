@@ -1,7 +1,8 @@
 // ec504_imageencoder_amd/csrc/m1v_encode_tile_body.h — the body of k_encode_tiles and k_encode_surface (m1v_tiles.h), included
 // inside each kernel (a shared inline function would do, but the compiler may then number the registers of k_encode_tiles
 // differently: its code stays the parent's instruction for instruction this way).  In scope: STAGE8, R (template parameters),
-// TileArgs a, and the input layout: BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows).
+// TileArgs a, and the input layout: BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows).  The front
+// half is named by the macro M1V_FRONT_HALF: tile_pixel_rows, or PlaneFront::run for the plane kernels (m1v_planes.h).
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const Geometry &g = a.g;
     const int tid = threadIdx.x;
@@ -56,7 +57,7 @@
     const uint32_t ring = lds0 + region_off; // LDS byte address of this wave's region
     constexpr int kKeep = STAGE8 ? M1V_TILE_KEEP : M1V_TILE_KEEP_WIDE;
     RowStore<kKeep> rows;
-    tile_pixel_rows<R, kKeep, !SURFACE, BPP, SURFACE, ORDER>(
+    M1V_FRONT_HALF<R, kKeep, !SURFACE, BPP, SURFACE, ORDER>(
         g, fbase, ring, wave, lane, s0, m0, strips_here, comp,
         [&]() {
 #pragma unroll

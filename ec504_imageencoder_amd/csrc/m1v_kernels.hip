@@ -16,6 +16,9 @@
 //   k_encode_surface, k_size_table_surface   (m1v_tiles.h, m1v_encode_tile_body.h, m1v_size_table_body.h) the same tile
 //                     encode and size table on windows of pitched surfaces, 3- or 4-byte pixels in R,G,B or B,G,R order
 //                     (m1v_set_input_layout: row r of frame f at base + f * frame stride + r * row pitch)
+//   k_encode_planes, k_size_table_planes     (m1v_planes.h, the same two bodies) the tile encode and size table on planar and
+//                     semi-planar YCbCr frames (m1v_set_plane_layout: reference planes, I420 / YV12, NV12 / NV21, pitched
+//                     windows of them): no colour stage, bytes straight into the fp32 FDCT
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -1249,6 +1252,7 @@ __global__ __launch_bounds__(256) void k_dense_frame_layout(DenseGeom d, int seg
 constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 
 #include "m1v_tiles.h"
+#include "m1v_planes.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1702,6 +1706,12 @@ struct m1v_encoder {
         uint32_t row_pitch = 0;               // bytes from a picture row to the next
         unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
         int order = M1V_ORDER_RGB;
+        // m1v_set_plane_layout: the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h); surface and planes exclude
+        // each other
+        bool planes = false;
+        uint32_t y_off = 0, cb_off = 0, cr_off = 0, y_pitch = 0, c_pitch = 0, c_step = 0;
+        unsigned long long extent = 0;        // bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
+        bool tiles_only() const { return surface || planes; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
     unsigned calls = 0;
@@ -1810,8 +1820,9 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     // (widths that are not a multiple of 8, buffers off a 4-byte boundary), 1 % faster at 4K (the order of the tile rows keeps
     // the chroma re-reads in L2, tile_row_order_for), and 0.5-1 % faster per step on aligned 1080p in a sustained run
     // (profiles/r03_ab_history.txt).  The run kernel serves 4-channel input and the m1v_debug_set_* hooks.
-    // A surface layout takes the same plan for 3 and 4 channels (k_encode_surface; no hook can be set beside it).
-    if (e.layout.surface || (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0))) {
+    // A surface layout takes the same plan for 3 and 4 channels (k_encode_surface; no hook can be set beside it), and so does a
+    // plane layout (k_encode_planes, 3 channels).
+    if (e.layout.tiles_only() || (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0))) {
         p.producer = Producer::tiles;
         p.block = kTileThreads;
         p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
@@ -1928,6 +1939,14 @@ static const void *const kSurfaceKernels[2][2][2] = M1V_SURFACE_KERNELS(k_encode
 static const void *const kSurfaceTableKernels[2][2][2] = M1V_SURFACE_KERNELS(k_size_table_surface);
 #undef M1V_SURFACE_KERNELS
 
+// The plane kernels (m1v_set_plane_layout), [c_step - 1][narrow staging]
+static const void *const kPlaneKernels[2][2] = {
+    {(const void *)&k_encode_planes<false, M1V_TILE_RING, 1>, (const void *)&k_encode_planes<true, M1V_TILE_RING, 1>},
+    {(const void *)&k_encode_planes<false, M1V_TILE_RING, 2>, (const void *)&k_encode_planes<true, M1V_TILE_RING, 2>}};
+static const void *const kPlaneTableKernels[2][2] = {
+    {(const void *)&k_size_table_planes<false, M1V_TILE_RING, 1>, (const void *)&k_size_table_planes<true, M1V_TILE_RING, 1>},
+    {(const void *)&k_size_table_planes<false, M1V_TILE_RING, 2>, (const void *)&k_size_table_planes<true, M1V_TILE_RING, 2>}};
+
 // defined in m1v_runtime.h
 static int profile_event(m1v_encoder *e, hipStream_t st);
 static int fail_encode_at(int stage);
@@ -1940,7 +1959,14 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 
 static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
 
+// the plane layout in force as the plane kernels take it
+static PlaneFrontArgs plane_front_args(const m1v_encoder *e) {
+    const m1v_encoder::Layout &l = e->layout;
+    return {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)};
+}
+
 static const void *producer_kernel(const m1v_encoder *e, const uint8_t *d_rgb) {
+    if (e->layout.planes) return kPlaneKernels[e->layout.c_step - 1][e->narrow ? 1 : 0];
     if (e->layout.surface) return kSurfaceKernels[e->g.C == 4 ? 1 : 0][e->layout.order][e->narrow ? 1 : 0];
     const bool aligned4 = ((uintptr_t)d_rgb & 3) == 0, fast = fast_path(e, d_rgb);
     int mode = 0;
@@ -2073,7 +2099,10 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        if (e->layout.surface) {
+        if (e->layout.planes) {
+            PlaneArgs pa = {a, plane_front_args(e), e->layout.frame_stride};
+            if (const int rc = launch_producer(e, bt, kernel, n_frames, pa, st, gs)) return rc;
+        } else if (e->layout.surface) {
             SurfaceArgs sa = {a, e->layout.frame_stride, e->layout.row_pitch};
             if (const int rc = launch_producer(e, bt, kernel, n_frames, sa, st, gs)) return rc;
         } else if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) {
@@ -2184,7 +2213,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
 
 
 // The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), or k_size_table_surface on
-// a surface layout, then k_size_table_sizes,
+// a surface layout, or k_size_table_planes on a plane layout, then k_size_table_sizes,
 // both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
 // sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
 static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
@@ -2226,8 +2255,11 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     a.region = p.table_region;
     SurfaceTableArgs on_surface = {a, e->layout.frame_stride, e->layout.row_pitch};
     const int narrow = qualities[n_q - 1] <= e->narrow_q ? 1 : 0;
-    void *args[] = {e->layout.surface ? (void *)&on_surface : (void *)&a};
-    const void *kernel = e->layout.surface ? kSurfaceTableKernels[g.C == 4 ? 1 : 0][e->layout.order][narrow] : kTableKernels[g.C == 4 ? 1 : 0][narrow];
+    PlaneTableArgs on_planes = {a, plane_front_args(e), e->layout.frame_stride};
+    void *args[] = {e->layout.planes ? (void *)&on_planes : (e->layout.surface ? (void *)&on_surface : (void *)&a)};
+    const void *kernel = e->layout.planes    ? kPlaneTableKernels[e->layout.c_step - 1][narrow]
+                         : e->layout.surface ? kSurfaceTableKernels[g.C == 4 ? 1 : 0][e->layout.order][narrow]
+                                             : kTableKernels[g.C == 4 ? 1 : 0][narrow];
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
     (void)hipLaunchKernel(kernel, dim3((unsigned)units), dim3((unsigned)kTileThreads), args, p.table_lds_bytes, st);
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;

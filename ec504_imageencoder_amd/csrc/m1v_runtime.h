@@ -281,6 +281,7 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
 // What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
 // the run kernels
 static int packed_only(const m1v_encoder *e) {
+    if (e->layout.planes) return fail(M1V_E_ARG, "packed input only: a plane layout is set (m1v_set_plane_layout)%s");
     return e->layout.surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
 }
 
@@ -416,6 +417,10 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
             for (const auto &by_staging : by_order)
                 for (const void *kf : by_staging)
                     if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const auto *family : {&kPlaneKernels, &kPlaneTableKernels})
+        for (const auto &by_staging : *family)
+            for (const void *kf : by_staging)
+                if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err != hipSuccess) {
         fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
         m1v_destroy(e);
@@ -566,10 +571,87 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.planes) return fail(M1V_E_ARG, "a plane layout is in force: ask m1v_plane_layout_in_force%s");
     if (row_pitch_bytes) *row_pitch_bytes = e->layout.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)e->layout.frame_stride;
     if (order) *order = e->layout.order;
     return M1V_OK;
+}
+
+int m1v_plane_layout_preset(int width, int height, int preset, m1v_plane_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (preset < M1V_PLANES_REFERENCE || preset > M1V_PLANES_NV21) return fail(M1V_E_ARG, "unknown plane layout preset%s");
+    const size_t W = (size_t)width, H = (size_t)height, luma = W * H;
+    m1v_plane_layout l = {};
+    l.y_pitch = W;
+    if (preset == M1V_PLANES_REFERENCE) { // what m1v_convert_device writes: three full-resolution planes, chroma addressed with W / 2
+        l.cb_offset = luma;
+        l.cr_offset = 2 * luma;
+        l.c_pitch = W / 2;
+        l.c_step = 1;
+        l.frame_stride = 3 * luma;
+    } else {
+        if ((width | height) & 1) return fail(M1V_E_ARG, "a 4:2:0 preset needs an even width and height%s");
+        const size_t quarter = (W / 2) * (H / 2);
+        const bool planar = preset == M1V_PLANES_I420 || preset == M1V_PLANES_YV12;
+        const bool cr_first = preset == M1V_PLANES_YV12 || preset == M1V_PLANES_NV21;
+        const size_t second = planar ? quarter : 1;
+        l.cb_offset = luma + (cr_first ? second : 0);
+        l.cr_offset = luma + (cr_first ? 0 : second);
+        l.c_step = planar ? 1 : 2;
+        l.c_pitch = planar ? W / 2 : W;
+        l.frame_stride = luma * 3 / 2;
+    }
+    *out = l;
+    return M1V_OK;
+}
+
+int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a plane layout needs an encoder created with 3 channels%s");
+        if (layout->c_step > 2) return fail(M1V_E_ARG, "c_step must be 1 or 2 (0 = 1)%s");
+        if (layout->frame_stride == 0) return fail(M1V_E_ARG, "a plane layout needs a frame stride%s");
+        const unsigned long long W = (unsigned long long)g.W, half = W / 2, step = layout->c_step ? layout->c_step : 1;
+        if (layout->y_pitch != 0 && layout->y_pitch < W) return fail(M1V_E_ARG, "luma pitch below the width%s");
+        if (layout->c_pitch != 0 && layout->c_pitch < half * step) return fail(M1V_E_ARG, "chroma pitch below (width / 2) * c_step%s");
+        const unsigned long long y_pitch = layout->y_pitch ? layout->y_pitch : W, c_pitch = layout->c_pitch ? layout->c_pitch : half * step;
+        // the frame's extent: the read contract of mpeg1_hip.h (rows and row bytes of the region the encoder codes)
+        const unsigned long long xe = (unsigned long long)g.n_strips * 16, ye = (unsigned long long)g.n_mbrows * 16;
+        const unsigned long long limit = 1ull << 32;
+        if (y_pitch >= limit || c_pitch >= limit || layout->y_offset >= limit || layout->cb_offset >= limit || layout->cr_offset >= limit)
+            return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        const unsigned long long c_rows = (ye / 2 - 1) * c_pitch + (xe / 2 - 1) * step + 1; // one past a plane's last addressed byte
+        const unsigned long long extent = std::max(layout->y_offset + (ye - 1) * y_pitch + xe,
+                                                   std::max<unsigned long long>(layout->cb_offset, layout->cr_offset) + c_rows);
+        if (extent >= limit) return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
+        if (e->forced_path == 0 || e->forced_mode >= 0 || e->forced_T > 0)
+            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
+        want.planes = true;
+        want.y_off = (uint32_t)layout->y_offset;
+        want.cb_off = (uint32_t)layout->cb_offset;
+        want.cr_off = (uint32_t)layout->cr_offset;
+        want.y_pitch = (uint32_t)y_pitch;
+        want.c_pitch = (uint32_t)c_pitch;
+        want.c_step = (uint32_t)step;
+        want.extent = extent;
+        want.frame_stride = layout->frame_stride;
+    }
+    return reconfigure(e, &m1v_encoder::layout, want);
+}
+
+int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (!e->layout.planes) return 0;
+    if (out) {
+        const m1v_encoder::Layout &l = e->layout;
+        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.c_step, (size_t)l.frame_stride};
+    }
+    return 1;
 }
 
 int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }

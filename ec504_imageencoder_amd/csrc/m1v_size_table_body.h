@@ -1,6 +1,7 @@
 // ec504_imageencoder_amd/csrc/m1v_size_table_body.h — the body of k_size_table_tiles, k_size_table_rgba and k_size_table_surface
 // (m1v_tiles.h), included inside each kernel.  In scope: STAGE8, R (template parameters), TableArgs a, and the input layout:
-// BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows).
+// BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows); M1V_FRONT_HALF names the front half (as in
+// m1v_encode_tile_body.h).
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const Geometry &g = a.g;
     const int tid = threadIdx.x;
@@ -41,7 +42,7 @@
 
     // ---- pixel stage, once: the wave's VLC table is requested in front of the rows ----
     RowStore<8> rows;
-    tile_pixel_rows<R, 8, false, BPP, SURFACE, ORDER>(
+    M1V_FRONT_HALF<R, 8, false, BPP, SURFACE, ORDER>(
         g, fbase, lds0 + region_off, wave, lane, s0, m0, strips_here, comp,
         [&]() {
 #pragma unroll

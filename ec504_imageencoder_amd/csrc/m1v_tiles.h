@@ -180,6 +180,8 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
     constexpr int ORDER = 0;                                                                       \
     constexpr uint32_t row_pitch = 0;                                                              \
     constexpr unsigned long long frame_stride = 0
+// the front half the kernel bodies call (m1v_planes.h puts its own in this place for the plane kernels)
+#define M1V_FRONT_HALF tile_pixel_rows
 #ifndef M1V_TILE_WAVES_PER_EU
 #define M1V_TILE_WAVES_PER_EU 5
 #endif

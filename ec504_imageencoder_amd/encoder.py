@@ -47,6 +47,40 @@ def surface_strides(shape, strides):
     return row_pitch, frame_stride
 
 
+PLANE_LAYOUT_FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")
+
+
+def plane_layout_preset(width, height, name):
+    """The tightly packed plane layout `name` ("reference", "i420", "yv12", "nv12", "nv21") of a width x height frame as a dict
+    of PLANE_LAYOUT_FIELDS in bytes, as Mpeg1Encoder.set_plane_layout takes it (include/mpeg1_hip.h, m1v_plane_layout_preset,
+    whose values these are).  "reference" = the three full-resolution planes Mpeg1Encoder.convert writes.  Pure: no torch, no
+    library."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if name not in _ffi.PLANE_PRESETS:
+        raise ValueError(f"unknown plane layout preset {name!r}")
+    luma = W * H
+    if name == "reference":
+        return dict(y_offset=0, cb_offset=luma, cr_offset=2 * luma, y_pitch=W, c_pitch=W // 2, c_step=1, frame_stride=3 * luma)
+    if W % 2 or H % 2:
+        raise ValueError("a 4:2:0 preset needs an even width and height")
+    planar, cr_first = name in ("i420", "yv12"), name in ("yv12", "nv21")
+    second = (W // 2) * (H // 2) if planar else 1
+    return dict(y_offset=0, cb_offset=luma + (second if cr_first else 0), cr_offset=luma + (0 if cr_first else second),
+                y_pitch=W, c_pitch=W // 2 if planar else W, c_step=1 if planar else 2, frame_stride=luma * 3 // 2)
+
+
+def plane_layout_extent(layout, strips, mb_rows):
+    """Bytes of a frame the plane kernels may read (the read contract of include/mpeg1_hip.h): the largest
+    offset + (rows - 1) * pitch + row bytes over the three planes of the strips * 16 x mb_rows * 16 region (row bytes: up to a
+    row's last addressed byte).  layout: a dict of
+    PLANE_LAYOUT_FIELDS with no zeros (Mpeg1Encoder.plane_layout)."""
+    xe, ye = strips * 16, mb_rows * 16
+    chroma = (ye // 2 - 1) * layout["c_pitch"] + (xe // 2 - 1) * layout["c_step"] + 1
+    return max(layout["y_offset"] + (ye - 1) * layout["y_pitch"] + xe, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
+
+
 class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
@@ -70,6 +104,7 @@ class Mpeg1Encoder:
         self.frame_bytes_in = L.m1v_frame_bytes_in(self._h)
         self.blocks_per_frame = self.strips * self.mb_rows * 6
         self._layout = (0, 0, "rgb")    # what _check_input holds tensors against (set_input_layout)
+        self._planes = None             # the plane layout in force (set_plane_layout), a dict of PLANE_LAYOUT_FIELDS
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -85,7 +120,8 @@ class Mpeg1Encoder:
     # ---- the hot path -------------------------------------------------------------------------
     def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
-        as surface[:, y0:y0+H, x0:x0+W, :].  Asynchronous on torch's current stream.
+        as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes.  Asynchronous on torch's current
+        stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
         CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
@@ -116,6 +152,14 @@ class Mpeg1Encoder:
 
     def _check_input(self, rgb):
         import torch
+        if self._planes is not None:    # [n, L] bytes, frame f at row f: L covers the frame's extent, rows frame_stride apart
+            assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 2, "plane frames must be a CUDA uint8 tensor [n, L]"
+            extent = plane_layout_extent(self._planes, self.strips, self.mb_rows)
+            assert rgb.shape[0] == 0 or (rgb.stride(1) == 1 and rgb.shape[1] >= extent), \
+                f"a frame's row must be contiguous and hold the {extent} bytes its planes span"
+            assert rgb.shape[0] <= 1 or rgb.stride(0) == self._planes["frame_stride"], \
+                f"frames must lie {self._planes['frame_stride']} bytes apart (stride {rgb.stride(0)})"
+            return
         row_pitch, frame_stride, _ = self._layout
         if row_pitch == 0:      # the default layout: packed frames
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
@@ -136,7 +180,39 @@ class Mpeg1Encoder:
         rc = _ffi.lib().m1v_set_input_layout(self._h, int(row_pitch), int(frame_stride), int(code))
         if rc != _ffi.OK:
             raise EncoderError(rc, "m1v_set_input_layout")
+        self._planes = None             # one input layout is in force at a time
         self._layout = self.input_layout
+
+    def set_plane_layout(self, layout):
+        """Frames as Y, Cb, Cr planes on the device, encoded without a colour conversion (include/mpeg1_hip.h,
+        m1v_set_plane_layout; 3-channel encoders).  layout: a preset name ("reference", "i420", "yv12", "nv12", "nv21"), a dict
+        of PLANE_LAYOUT_FIELDS in bytes (plane_layout_preset gives one to start from; missing pitches and c_step default as in the
+        header), or None = back to the default layout and its kernels.  Every call then takes uint8 CUDA tensors [n, L] whose
+        rows are the frames: L >= the bytes a frame's planes span, rows frame_stride apart — convert(rgb).view(n, -1) and
+        torch.as_strided views go in as they are.  A reconfiguration: call it between batches."""
+        if layout is None:
+            rc = _ffi.lib().m1v_set_plane_layout(self._h, None)
+        else:
+            if isinstance(layout, str):
+                layout = plane_layout_preset(self.width, self.height, layout)
+            unknown = set(layout) - set(PLANE_LAYOUT_FIELDS)
+            if unknown:
+                raise ValueError(f"unknown plane layout fields {sorted(unknown)}")
+            c = _ffi.PlaneLayout(**{k: int(v) for k, v in layout.items()})
+            rc = _ffi.lib().m1v_set_plane_layout(self._h, C.byref(c))
+        if rc != _ffi.OK:
+            raise EncoderError(rc, "m1v_set_plane_layout")
+        self._planes = self.plane_layout
+        self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+
+    @property
+    def plane_layout(self):
+        """The plane layout in force as a dict of PLANE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros), or None."""
+        c = _ffi.PlaneLayout()
+        rc = _ffi.lib().m1v_plane_layout_in_force(self._h, C.byref(c))
+        if rc < 0:
+            raise EncoderError(rc, "m1v_plane_layout_in_force")
+        return c.as_dict() if rc == 1 else None
 
     @property
     def input_layout(self):

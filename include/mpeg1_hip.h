@@ -250,6 +250,59 @@ enum { M1V_ORDER_RGB = 0, M1V_ORDER_BGR = 1 };   /* byte order of the three colo
 int m1v_set_input_layout(m1v_encoder *enc, size_t row_pitch_bytes, size_t frame_stride_bytes, int order);
 int m1v_input_layout(const m1v_encoder *enc, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order);
 
+/* Plane layout: frames that are already YCbCr in planes on the device — the output of m1v_convert_device, of a hardware video or
+ * JPEG decoder (NV12), of a camera pipeline (I420) — encoded as they are: no colour conversion, and so no lossy
+ * YCbCr -> RGB -> YCbCr round trip in front of the encoder.  For encoders created with channels = 3.
+ *
+ * Definition.  Frame f starts at F = d_rgb + f * frame_stride; the region coded is xe x ye = (m1v_strips * 16) x (m1v_mb_rows * 16).
+ * The macroblock at (x, y) takes
+ *     luma block k (Y0..Y3), row i            the 8 bytes at  F + y_offset + (y + 8 * (k / 2) + i) * y_pitch + x + 8 * (k % 2)
+ *     chroma plane p (Cb, Cr), row i, sample j    the byte at  F + p_offset + (y / 2 + i) * c_pitch + (x / 2 + j) * c_step
+ * and the record is what the reference's frame body makes of those bytes behind its colour conversion (encoder.h:238-444): the
+ * same headers, first_frame_index, status bits, per-frame quality and sizes as the RGB calls.  The chroma formula is the
+ * reference's own (it cuts chroma blocks from its full-resolution Cb / Cr planes addressed with stride width / 2,
+ * encoder.h:347-348): with the planes m1v_convert_device writes and c_pitch = width / 2 the record IS the RGB record of the same
+ * picture; with true 4:2:0 planes (width / 2 x height / 2 samples) the same formula is ordinary 4:2:0 sampling.
+ * Any byte alignment of the pointer, the offsets, the pitches and the stride is accepted, and so are odd widths.  Planes may
+ * overlap (NV12's do); they are only read.
+ *
+ *   m1v_plane_layout_preset(width, height, preset, &layout)   pure host arithmetic (no encoder, no device): tightly packed
+ *     M1V_PLANES_REFERENCE   Y at 0, Cb at W*H, Cr at 2*W*H, pitches W and W/2, c_step 1, stride 3*W*H (m1v_convert_device's output)
+ *     M1V_PLANES_I420 / _YV12   W*H luma, then two (W/2)*(H/2) planes in Cb,Cr / Cr,Cb order, c_pitch W/2, stride W*H*3/2
+ *     M1V_PLANES_NV12 / _NV21   W*H luma, then one plane of interleaved Cb,Cr / Cr,Cb pairs: c_step 2, c_pitch W, the second
+ *                               component's offset = the first's + 1, stride W*H*3/2
+ *     The 4:2:0 presets need an even width and height (M1V_E_ARG otherwise); REFERENCE takes any.  M1V_E_ARG: unknown preset.
+ *   m1v_set_plane_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like m1v_set_input_layout (call it
+ *     between batches; buffers are allocated first and swapped in on success).  The encoder takes the tile plan (m1v_path_in_use
+ *     and m1v_size_table_fused are 1) behind the plane kernels (k_encode_planes, k_size_table_planes).  ONE input layout is in
+ *     force at a time: a plane layout replaces a surface layout and the other way round; m1v_set_plane_layout(enc, NULL) and
+ *     m1v_set_input_layout(enc, 0, 0, M1V_ORDER_RGB) both restore the default plan.  While a plane layout is in force
+ *     m1v_input_layout returns M1V_E_ARG.  Every *_device encode, probe, size-table, budget, batch-budget and bitrate call,
+ *     pipelined mode, m1v_reserve_scratch, m1v_debug_set_lds_words, m1v_delivery_* and the m1v_profile_* counters work on it.
+ *     M1V_E_ARG, before anything is launched or reallocated: a null encoder; channels != 3; c_step > 2; frame_stride 0;
+ *     0 < y_pitch < width; 0 < c_pitch < (width / 2) * c_step; a frame extent E (below) of 2^32 or more; frame_stride < E; an
+ *     encoder that a hook has forced to the run kernels (those hooks return M1V_E_ARG on an encoder with a plane layout).
+ *     Packed only: m1v_coefficients_device, m1v_convert_device, m1v_encode_host, m1v_encode_planes_host and m1v_convert_host
+ *     return M1V_E_ARG while a plane layout is set.
+ *   m1v_plane_layout_in_force(enc, &layout)   1 = a plane layout is in force (layout filled with the values the kernels use, no
+ *     zeros; may be NULL), 0 = none, < 0 = error.
+ * Read contract: of frame f a kernel reads only bytes of [F, F + E) rounded up to the next 4-byte boundary, where E, the frame's
+ * extent, is the largest  offset + (rows - 1) * pitch + row bytes  over the three planes (rows = ye for luma, ye / 2 for chroma;
+ * row bytes = xe and (xe / 2 - 1) * c_step + 1: up to the last byte the definition addresses, so that a tightly packed NV12 frame
+ * has E = width * height * 3 / 2, its frame stride).  Bytes inside that range that the definition does not address (row padding, gaps
+ * between planes, the surroundings of a window, chroma rows from ye / 2 on) may be read; they never influence the output. */
+typedef struct m1v_plane_layout {
+    size_t y_offset, cb_offset, cr_offset; /* bytes from the frame's base to sample (0,0) of each plane            */
+    size_t y_pitch;                        /* bytes between luma rows; 0 = width                                   */
+    size_t c_pitch;                        /* bytes between chroma rows of the addressing above; 0 = (width/2)*c_step */
+    size_t c_step;                         /* bytes between neighbouring samples of ONE chroma plane: 1 or 2; 0 = 1 */
+    size_t frame_stride;                   /* bytes between frames; never 0                                        */
+} m1v_plane_layout;
+enum { M1V_PLANES_REFERENCE = 0, M1V_PLANES_I420 = 1, M1V_PLANES_YV12 = 2, M1V_PLANES_NV12 = 3, M1V_PLANES_NV21 = 4 };
+int m1v_plane_layout_preset(int width, int height, int preset, m1v_plane_layout *out);
+int m1v_set_plane_layout(m1v_encoder *enc, const m1v_plane_layout *layout);
+int m1v_plane_layout_in_force(const m1v_encoder *enc, m1v_plane_layout *out);
+
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
  * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.
