@@ -1700,18 +1700,25 @@ struct m1v_encoder {
     int forced_path = -1;       // m1v_debug_set_path: -1 = by geometry, 0 = runs, 1 = tiles
     int forced_T = 0;           // run length forced by m1v_debug_set_dense_threads (0 = default)
     bool pipelined = false;     // layout + gather of batch k on `side` while batch k+1 encodes on the caller's stream
-    // m1v_set_input_layout: the pictures are windows of a pitched surface (the surface kernels); the values in force, no zeros
+    // What the debug hooks force, as each place that reads them asks.  The four differ on purpose:
+    // m1v_coefficients_device: its run-shaped kernel has no run length, so a forced one does not select it
+    bool runs_by_path_or_mode() const { return forced_path == 0 || forced_mode >= 0; }
+    // plan_for's producer: a forced run length selects the run kernels too, unless the path hook says tiles
+    bool forced_to_runs() const { return runs_by_path_or_mode() || (forced_path < 0 && forced_T > 0); }
+    // the layout setters: a forced run length refuses a tile-only layout even beside a forced tile path (lifting that would apply it)
+    bool run_hook_set() const { return runs_by_path_or_mode() || forced_T > 0; }
+    // plan_for's 4-channel fused table: every hook keeps one probe per quality, the A/B reference inside one process
+    bool any_hook_set() const { return forced_path >= 0 || forced_mode >= 0 || forced_T != 0; }
+    // The input layout in force, no zeros.  surface (m1v_set_input_layout): the pictures are windows of a pitched surface (the
+    // surface kernels); planes (m1v_set_plane_layout): the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h)
     struct Layout {
-        bool surface = false;
+        enum class Kind { packed, surface, planes } kind = Kind::packed;
         uint32_t row_pitch = 0;               // bytes from a picture row to the next
         unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
         int order = M1V_ORDER_RGB;
-        // m1v_set_plane_layout: the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h); surface and planes exclude
-        // each other
-        bool planes = false;
         uint32_t y_off = 0, cb_off = 0, cr_off = 0, y_pitch = 0, c_pitch = 0, c_step = 0;
         unsigned long long extent = 0;        // bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
-        bool tiles_only() const { return surface || planes; }
+        bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
     unsigned calls = 0;
@@ -1772,6 +1779,8 @@ struct m1v_encoder {
     size_t ev_used = 0;
 };
 
+using LayoutKind = m1v_encoder::Layout::Kind;
+
 // The order in which a frame's tile rows are processed.  Tile row R (macroblock rows 4R..4R+3) reads its luma from picture
 // rows [64R, 64R+64) and — the chroma quirk, encoder.h:347-348 — its chroma from rows [16R, 16R+16), i.e. from one quarter of
 // the luma region of tile row R/4.  Every byte of the top quarter of the picture is therefore read twice, once as luma and once
@@ -1808,6 +1817,27 @@ static void tile_row_order_for(int tile_rows, std::vector<uint32_t> &order) {
     order = Arrange{tile_rows, size}.run(0);
 }
 
+// The region of a width x height picture that `mode` codes: every whole macroblock, or the reference's 96x144 corner
+struct CodedRegion {
+    int xe, ye;
+    CodedRegion(int width, int height, int mode) : xe(mode == M1V_MODE_FULL ? (width & ~15) : 96), ye(mode == M1V_MODE_FULL ? (height & ~15) : 144) {}
+    bool fits(int width, int height) const { return xe <= width && ye <= height; }
+    // worst case of a strip: its slice header, then per macroblock row two bits and six blocks
+    unsigned long long strip_bits() const { return 38ull + (unsigned long long)(ye / 16) * (2 + 6 * kMaxBlockBits); }
+};
+
+// The tile grid over a picture (the tile kernels, the fused size table, k_coefficient_tiles)
+struct TileGrid {
+    int cols, rows;
+    explicit TileGrid(const Geometry &g) : cols((g.n_strips + kTileStrips - 1) / kTileStrips), rows((g.n_mbrows + kTileMbRows - 1) / kTileMbRows) {}
+    int units() const { return cols * rows; }
+};
+
+// LDS bytes of a wave's region in those kernels: its ring of pixel slots, or the `stage_words` it stages per lane if that is more
+static uint32_t wave_region(size_t stage_words) {
+    return (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * stage_words * 4)) + 15u) & ~15u;
+}
+
 // The plan of an encoder: a pure function of its geometry, its quality and its settings; M1V_E_ARG for settings that cannot
 // launch.  e.forced_T: run length of the run kernels (0 = default: 256 blocks = 4 waves, one per SIMD, so that 5 workgroups of
 // 96-VGPR waves share a CU; or the largest multiple of 64 that the strip holds when it has fewer than 256 blocks).
@@ -1822,14 +1852,14 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     // (profiles/r03_ab_history.txt).  The run kernel serves 4-channel input and the m1v_debug_set_* hooks.
     // A surface layout takes the same plan for 3 and 4 channels (k_encode_surface; no hook can be set beside it), and so does a
     // plane layout (k_encode_planes, 3 channels).
-    if (e.layout.tiles_only() || (g.C == 3 && e.forced_path != 0 && e.forced_mode < 0 && !(e.forced_path < 0 && e.forced_T > 0))) {
+    const TileGrid grid(g);
+    if (e.layout.tiles_only() || (g.C == 3 && !e.forced_to_runs())) {
         p.producer = Producer::tiles;
         p.block = kTileThreads;
-        p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
-        p.tile_rows = (g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
-        p.units = p.tile_cols * p.tile_rows;
-        const uint32_t stage = (uint32_t)(kWave * stride * 4);
-        p.luma_region = p.chroma_region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, stage) + 15u) & ~15u;
+        p.tile_cols = grid.cols;
+        p.tile_rows = grid.rows;
+        p.units = grid.units();
+        p.luma_region = p.chroma_region = wave_region(stride);
         // worst case of a tile: 8 word-aligned segments of 24 blocks of <= 886 + 2 bits, 8 slice headers, slack
         p.run_cap = (uint32_t)(((((size_t)kTileThreads * (kMaxBlockBits + 2) + kTileStrips * (38 + 32) + 64 + 7) / 8) + 32 + 15) & ~(size_t)15);
         // LDS image of the tile's bits (192 blocks: ~115 words at quality 12 on noise), scaled with the quantiser like the
@@ -1869,14 +1899,14 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     // The fused size table of a 4-channel encoder (k_size_table_rgba): the tile workgroup over the picture, whichever run kernel
     // encodes it.  The test hooks that force a path, an input mode or a run length keep one probe per quality: the A/B
     // reference inside one process.
-    if (g.C == 4 && e.forced_path < 0 && e.forced_mode < 0 && e.forced_T == 0) {
-        p.tile_cols = (g.n_strips + kTileStrips - 1) / kTileStrips;
-        p.tile_rows = (g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
-        p.table_units = p.tile_cols * p.tile_rows;
+    if (g.C == 4 && !e.any_hook_set()) {
+        p.tile_cols = grid.cols;
+        p.tile_rows = grid.rows;
+        p.table_units = grid.units();
     }
     if (p.table_units) {
         // per wave: the ring, or the staged levels at the widest quality the encoder allows; no image
-        p.table_region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * stride * 4)) + 15u) & ~15u;
+        p.table_region = wave_region(stride);
         p.table_lds_bytes = (size_t)kTableFixedWords * 4 + 3 * (size_t)p.table_region;
         if (p.table_lds_bytes > 160 * 1024) return fail(M1V_E_ARG, "LDS budget exceeded: the size table does not fit%s");
     }
@@ -1910,42 +1940,35 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     return M1V_OK;
 }
 
-// Every instantiation of the producer kernels, [producer][input mode][narrow staging]: the launch picks from it (producer_kernel)
-// and m1v_create raises the dynamic LDS limit of each.  Input modes of the pixel loads (load_block_rows): 1 = aligned rows, 2 = any
-// row offset in an aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The tile kernel takes any input in
-// one mode; the strip kernel has modes 0 and 1 and stages every level wide.
-static const void *const kProducerKernels[3][4][2] = {
-    {{(const void *)&k_encode_tiles<false, M1V_TILE_RING>, (const void *)&k_encode_tiles<true, M1V_TILE_RING>}},
+// Every kernel that takes dynamic LDS: the launches pick from it (tile_variant, run_kernel) and m1v_create raises the limit of
+// each.  [narrow staging] last; a null entry is a variant that does not exist.
+//   tile[encode | size table][tile_variant()]: the tile-shaped kernels of every input layout
+//   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
+//   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
+//   every level wide.
+enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kTileVariants = kPlanes + 2 };
+#define M1V_PAIR(K, ...) {(const void *)&K<false, __VA_ARGS__>, (const void *)&K<true, __VA_ARGS__>}
+#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES)                                                              \
+    {PACKED3, PACKED4, M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 1),                  \
+     M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 1), M1V_PAIR(PLANES, M1V_TILE_RING, 1), \
+     M1V_PAIR(PLANES, M1V_TILE_RING, 2)}
+static const struct Kernels {
+    const void *tile[2][kTileVariants][2];
+    const void *dense[4][2];
+    const void *strips[2][2];
+} kKernels = {
+    // (packed 4-channel pictures encode on the run kernels)
+    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes),
+     M1V_TILE_FAMILY(M1V_PAIR(k_size_table_tiles, M1V_TILE_RING), M1V_PAIR(k_size_table_rgba, M1V_TILE_RING), k_size_table_surface,
+                     k_size_table_planes)},
     {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
      {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
      {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
      {(const void *)&k_encode_dense<3, false>, (const void *)&k_encode_dense<3, true>}},
     {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
      {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
-
-// The fused size-table kernels, [4-byte pixels][narrow staging] (m1v_create raises their dynamic LDS limit)
-static const void *const kTableKernels[2][2] = {
-    {(const void *)&k_size_table_tiles<false, M1V_TILE_RING>, (const void *)&k_size_table_tiles<true, M1V_TILE_RING>},
-    {(const void *)&k_size_table_rgba<false, M1V_TILE_RING>, (const void *)&k_size_table_rgba<true, M1V_TILE_RING>}};
-
-// The surface kernels (m1v_set_input_layout), [4-byte pixels][byte order][narrow staging]: the tile plan's producer and its
-// fused size table
-#define M1V_SURFACE_KERNELS(K)                                                                                          \
-    {{{(const void *)&K<false, M1V_TILE_RING, 3, 0>, (const void *)&K<true, M1V_TILE_RING, 3, 0>},                      \
-      {(const void *)&K<false, M1V_TILE_RING, 3, 1>, (const void *)&K<true, M1V_TILE_RING, 3, 1>}},                     \
-     {{(const void *)&K<false, M1V_TILE_RING, 4, 0>, (const void *)&K<true, M1V_TILE_RING, 4, 0>},                      \
-      {(const void *)&K<false, M1V_TILE_RING, 4, 1>, (const void *)&K<true, M1V_TILE_RING, 4, 1>}}}
-static const void *const kSurfaceKernels[2][2][2] = M1V_SURFACE_KERNELS(k_encode_surface);
-static const void *const kSurfaceTableKernels[2][2][2] = M1V_SURFACE_KERNELS(k_size_table_surface);
-#undef M1V_SURFACE_KERNELS
-
-// The plane kernels (m1v_set_plane_layout), [c_step - 1][narrow staging]
-static const void *const kPlaneKernels[2][2] = {
-    {(const void *)&k_encode_planes<false, M1V_TILE_RING, 1>, (const void *)&k_encode_planes<true, M1V_TILE_RING, 1>},
-    {(const void *)&k_encode_planes<false, M1V_TILE_RING, 2>, (const void *)&k_encode_planes<true, M1V_TILE_RING, 2>}};
-static const void *const kPlaneTableKernels[2][2] = {
-    {(const void *)&k_size_table_planes<false, M1V_TILE_RING, 1>, (const void *)&k_size_table_planes<true, M1V_TILE_RING, 1>},
-    {(const void *)&k_size_table_planes<false, M1V_TILE_RING, 2>, (const void *)&k_size_table_planes<true, M1V_TILE_RING, 2>}};
+#undef M1V_TILE_FAMILY
+#undef M1V_PAIR
 
 // defined in m1v_runtime.h
 static int profile_event(m1v_encoder *e, hipStream_t st);
@@ -1959,43 +1982,72 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 
 static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
 
-// the plane layout in force as the plane kernels take it
-static PlaneFrontArgs plane_front_args(const m1v_encoder *e) {
+// The tile-shaped kernels' variant for the layout in force (Kernels::tile): the one place that maps channels, byte order and
+// chroma step to an instantiation
+static int tile_variant(const m1v_encoder *e) {
     const m1v_encoder::Layout &l = e->layout;
-    return {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)};
+    if (l.kind == LayoutKind::planes) return kPlanes + (int)l.c_step - 1;
+    if (l.kind == LayoutKind::surface) return kSurface + (e->g.C == 4 ? 2 : 0) + l.order;
+    return e->g.C == 4 ? kPacked4 : kPacked3;
 }
 
-static const void *producer_kernel(const m1v_encoder *e, const uint8_t *d_rgb) {
-    if (e->layout.planes) return kPlaneKernels[e->layout.c_step - 1][e->narrow ? 1 : 0];
-    if (e->layout.surface) return kSurfaceKernels[e->g.C == 4 ? 1 : 0][e->layout.order][e->narrow ? 1 : 0];
+// the run kernel (plan: dense or strips) for this input pointer
+static const void *run_kernel(const m1v_encoder *e, const uint8_t *d_rgb) {
     const bool aligned4 = ((uintptr_t)d_rgb & 3) == 0, fast = fast_path(e, d_rgb);
-    int mode = 0;
-    if (e->plan.producer == Producer::strips) {
-        mode = fast ? 1 : 0;
-    } else if (e->plan.producer == Producer::dense) {
-        mode = fast ? 1 : (aligned4 && e->g.C == 3 ? 2 : (aligned4 && e->g.C == 4 ? 3 : 0));
-        if (e->forced_mode == 0 || (e->forced_mode == 2 && mode == 1)) mode = e->forced_mode; // only modes that are valid here
-    }
-    return kProducerKernels[(int)e->plan.producer][mode][e->narrow ? 1 : 0];
+    if (e->plan.producer == Producer::strips) return kKernels.strips[fast ? 1 : 0][e->narrow ? 1 : 0];
+    int mode = fast ? 1 : (aligned4 && e->g.C == 3 ? 2 : (aligned4 && e->g.C == 4 ? 3 : 0));
+    if (e->forced_mode == 0 || (e->forced_mode == 2 && mode == 1)) mode = e->forced_mode; // only modes that are valid here
+    return kKernels.dense[mode][e->narrow ? 1 : 0];
 }
 
-// The plan's producer kernel over n_frames, with profile events around it; in pipelined mode the layout + gather stream gs
-// then waits for it.
-template <typename Args>
-static int launch_producer(m1v_encoder *e, m1v_encoder::Batch &bt, const void *kernel, int n_frames, Args &a, hipStream_t st,
-                           hipStream_t gs) {
-    const Plan &p = e->plan;
-    void *args[] = {&a};
+// One launch of a kernel that takes its arguments as one struct, with profile events around it
+static int launch_profiled(m1v_encoder *e, const void *kernel, size_t grid, int block, void *arg, size_t lds, hipStream_t st) {
+    void *args[] = {arg};
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-    (void)hipLaunchKernel(kernel, dim3((unsigned)((size_t)n_frames * p.units)), dim3((unsigned)p.block), args, p.lds_bytes, st);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3((unsigned)block), args, lds, st);
     if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
     HIP_TRY(hipGetLastError());
-    if (e->pipelined) {
-        HIP_TRY(hipEventRecord(bt.enc_done, st));
-        HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
-    }
     return M1V_OK;
 }
+
+// What TileArgs and TableArgs share: the input, the tables and the tile grid of the plan over n_frames
+template <typename Args>
+static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_frames, Args &a) {
+    const Plan &p = e->plan;
+    a.g = e->g;
+    a.rgb = d_rgb;
+    a.tab = e->d_tab;
+    a.rq_all = e->d_rq_all;
+    a.n_frames = n_frames;
+    a.tile_cols = p.tile_cols;
+    a.tile_rows = p.tile_rows;
+    a.tiles_per_frame = p.tile_cols * p.tile_rows; // (Plan::units of the tile producer, Plan::table_units)
+    const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)a.tiles_per_frame;
+    a.div_group = div_magic(8u * (uint32_t)a.tiles_per_frame, units);
+    a.div_frame = div_magic((uint32_t)a.tiles_per_frame, units);
+    a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)a.tiles_per_frame);
+    a.tile_row_order = e->d_tile_order;
+}
+
+// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs; 1 = size table: their table
+// counterparts) over the grid fill_tile_grid set, with a wrapped for the layout in force
+template <typename Surface, typename Planes, typename Args>
+static int launch_tiles(m1v_encoder *e, int family, bool narrow, Args &a, size_t lds, hipStream_t st) {
+    const m1v_encoder::Layout &l = e->layout;
+    Surface on_surface = {a, l.frame_stride, l.row_pitch};
+    // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
+    Planes on_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride};
+    void *arg = l.kind == LayoutKind::planes ? (void *)&on_planes
+                : l.kind == LayoutKind::surface ? (void *)&on_surface : (void *)&a;
+    return launch_profiled(e, kKernels.tile[family][tile_variant(e)][narrow ? 1 : 0], (size_t)a.n_frames * a.tiles_per_frame, kTileThreads,
+                           arg, lds, st);
+}
+
+// From its construction on, an error return leaves counters half used: the flag tells the next call to clear them first
+struct PoisonOnReturn {
+    bool *flag;
+    ~PoisonOnReturn() { if (flag) *flag = true; }
+};
 
 // The counter hand-over of a batch's last kernel (k_assemble or k_frame_sizes): it clears the first next_frames frames of the set
 // the next batch on this Batch adds to.  What a longer batch than this one left there beyond n_frames is cleared here, on gs.
@@ -2052,11 +2104,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     // the counters this batch adds to, and the set the next batch of this Batch will use (k_assemble clears it)
     m1v_encoder::Counters &cur = bt.ctr[bt.turn & 1u], &nxt = bt.ctr[(bt.turn + 1u) & 1u];
     bt.turn++;
-    // From here on an error return leaves the counters half used: the next call on this Batch clears them first.
-    struct PoisonOnReturn {
-        bool *flag;
-        ~PoisonOnReturn() { if (flag) *flag = true; }
-    } poison{&bt.poisoned};
+    PoisonOnReturn poison{&bt.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
     const uint32_t *qsel = e->d_qsel_own;
     if (qa) {
@@ -2068,13 +2116,12 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         HIP_TRY(hipGetLastError());
         qsel = e->d_qsel;
     }
-    const void *kernel = producer_kernel(e, d_rgb);
+    // the plan's producer kernel over n_frames
+    const size_t grid = (size_t)n_frames * p.units;
+    int rc;
     if (p.producer == Producer::tiles) {
         TileArgs a;
-        a.g = g;
-        a.rgb = d_rgb;
-        a.tab = e->d_tab;
-        a.rq_all = e->d_rq_all;
+        fill_tile_grid(e, d_rgb, n_frames, a);
         a.qsel = qsel;
         a.scratch = bt.scratch;
         a.seg = bt.seg;
@@ -2085,29 +2132,12 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.arena_slots = p.arena_slots;
         a.arena_off = p.arena_off;
         a.status = cur.words;
-        a.n_frames = n_frames;
-        a.tile_cols = p.tile_cols;
-        a.tile_rows = p.tile_rows;
-        a.tiles_per_frame = p.units;
-        const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.units;
-        a.div_group = div_magic(8u * (uint32_t)p.units, units);
-        a.div_frame = div_magic((uint32_t)p.units, units);
-        a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.units);
-        a.tile_row_order = e->d_tile_order;
         a.lds_words = p.image_words;
         a.run_cap = p.run_cap;
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        if (e->layout.planes) {
-            PlaneArgs pa = {a, plane_front_args(e), e->layout.frame_stride};
-            if (const int rc = launch_producer(e, bt, kernel, n_frames, pa, st, gs)) return rc;
-        } else if (e->layout.surface) {
-            SurfaceArgs sa = {a, e->layout.frame_stride, e->layout.row_pitch};
-            if (const int rc = launch_producer(e, bt, kernel, n_frames, sa, st, gs)) return rc;
-        } else if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) {
-            return rc;
-        }
+        rc = launch_tiles<SurfaceArgs, PlaneArgs>(e, 0, e->narrow, a, p.lds_bytes, st);
     } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
@@ -2129,16 +2159,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.arena_next = cur.words + 2;
         a.stamps = e->d_stamps;
         a.zero_iters = p.zero_iters;
-        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
-        DenseGeom d;
-        d.n_frames = n_frames;
-        d.n_strips = g.n_strips;
-        d.bps = g.n_mbrows * 6;
-        d.T = p.block;
-        d.runs_per_frame = p.units;
-        hipLaunchKernelGGL(k_dense_frame_layout, dim3(n_frames), dim3(256), 0, gs, d, p.segs, bt.run_meta, bt.seg, cur.strip_ctr,
-                           cur.frame_bytes);
-        HIP_TRY(hipGetLastError());
+        rc = launch_profiled(e, run_kernel(e, d_rgb), grid, p.block, &a, p.lds_bytes, st);
     } else {
         EncodeArgs a;
         a.g = g;
@@ -2155,7 +2176,23 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.threads = p.block;
         a.lds_words = p.image_words;
         a.stamps = e->d_stamps;
-        if (const int rc = launch_producer(e, bt, kernel, n_frames, a, st, gs)) return rc;
+        rc = launch_profiled(e, run_kernel(e, d_rgb), grid, p.block, &a, p.lds_bytes, st);
+    }
+    if (rc != M1V_OK) return rc;
+    if (e->pipelined) { // the layout + gather stream waits for the producer
+        HIP_TRY(hipEventRecord(bt.enc_done, st));
+        HIP_TRY(hipStreamWaitEvent(gs, bt.enc_done, 0));
+    }
+    if (p.producer == Producer::dense) {
+        DenseGeom d;
+        d.n_frames = n_frames;
+        d.n_strips = g.n_strips;
+        d.bps = g.n_mbrows * 6;
+        d.T = p.block;
+        d.runs_per_frame = p.units;
+        hipLaunchKernelGGL(k_dense_frame_layout, dim3(n_frames), dim3(256), 0, gs, d, p.segs, bt.run_meta, bt.seg, cur.strip_ctr,
+                           cur.frame_bytes);
+        HIP_TRY(hipGetLastError());
     }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
     if (probe) {
@@ -2211,7 +2248,6 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     return M1V_OK;
 }
 
-
 // The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), or k_size_table_surface on
 // a surface layout, or k_size_table_planes on a plane layout, then k_size_table_sizes,
 // both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
@@ -2227,47 +2263,21 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
         tc.poisoned = false;
     }
     if (n_frames == 0) return M1V_OK;
-    struct PoisonOnReturn {
-        bool *flag;
-        ~PoisonOnReturn() { if (flag) *flag = true; }
-    } poison{&tc.poisoned};
+    PoisonOnReturn poison{&tc.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
-    const Geometry &g = e->g;
     TableArgs a;
-    a.g = g;
-    a.rgb = d_rgb;
-    a.tab = e->d_tab;
-    a.rq_all = e->d_rq_all;
+    fill_tile_grid(e, d_rgb, n_frames, a);
     for (int k = 0; k < kMaxCandidates; k++) a.qoff[k] = k < n_q ? (uint32_t)(qualities[k] - 1) * 64u : 0u;
     a.n_q = n_q;
     a.strip_ctr = tc.strip_ctr;
     a.frame_bytes = tc.frame_bytes;
     a.status = tc.words;
-    a.n_frames = n_frames;
-    a.tile_cols = p.tile_cols;
-    a.tile_rows = p.tile_rows;
-    a.tiles_per_frame = p.table_units;
-    const unsigned long long units = (unsigned long long)n_frames * (unsigned long long)p.table_units;
-    a.div_group = div_magic(8u * (uint32_t)p.table_units, units);
-    a.div_frame = div_magic((uint32_t)p.table_units, units);
-    a.div_cols = div_magic((uint32_t)p.tile_cols, (unsigned long long)p.table_units);
-    a.tile_row_order = e->d_tile_order;
     a.region = p.table_region;
-    SurfaceTableArgs on_surface = {a, e->layout.frame_stride, e->layout.row_pitch};
-    const int narrow = qualities[n_q - 1] <= e->narrow_q ? 1 : 0;
-    PlaneTableArgs on_planes = {a, plane_front_args(e), e->layout.frame_stride};
-    void *args[] = {e->layout.planes ? (void *)&on_planes : (e->layout.surface ? (void *)&on_surface : (void *)&a)};
-    const void *kernel = e->layout.planes    ? kPlaneTableKernels[e->layout.c_step - 1][narrow]
-                         : e->layout.surface ? kSurfaceTableKernels[g.C == 4 ? 1 : 0][e->layout.order][narrow]
-                                             : kTableKernels[g.C == 4 ? 1 : 0][narrow];
-    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-    (void)hipLaunchKernel(kernel, dim3((unsigned)units), dim3((unsigned)kTileThreads), args, p.table_lds_bytes, st);
-    if (e->prof && profile_event(e, st) != M1V_OK) return M1V_E_HIP;
-    HIP_TRY(hipGetLastError());
+    if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs>(e, 1, qualities[n_q - 1] <= e->narrow_q, a, p.table_lds_bytes, st)) return rc;
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
     TableSizesArgs sa;
     sa.n_frames = n_frames;
-    sa.n_strips = g.n_strips;
+    sa.n_strips = e->g.n_strips;
     sa.strip_ctr = tc.strip_ctr;
     sa.frame_bytes = tc.frame_bytes;
     sa.status = tc.words;

@@ -1,6 +1,9 @@
 // ec504_imageencoder_amd/csrc/m1v_runtime.h — the C-ABI of include/mpeg1_hip.h around the plan and the launches of
-// m1v_kernels.hip: object lifetime, buffer allocation, counters, streams and events, the quality and budget entry points,
-// delivery, the host path, profiling and the debug hooks.  Not standalone: included once, at the end of m1v_kernels.hip.
+// m1v_kernels.hip: object lifetime, buffer allocation, counters (an alloc / clear / free trio per kind), streams and events, the
+// quality, size-table and rate entry points (one argument check, check_candidate_call, and one probe step, probe_candidates, for
+// those that take candidates), delivery, the host path, profiling and the debug hooks.  Geometry (CodedRegion, TileGrid,
+// wave_region), the kernel registry (kKernels) and the hook predicates of m1v_encoder come from m1v_kernels.hip.  Not
+// standalone: included once, at the end of m1v_kernels.hip.
 
 namespace {
 
@@ -138,7 +141,7 @@ static void counters_free(m1v_encoder::Counters &c) {
     (void)hipFree(c.words);
 }
 
-// The size table's counters, cleared in full on a stream
+// The size table's counters: the same three (allocated by m1v_create, so not through plan_malloc)
 static hipError_t table_clear(const m1v_encoder *e, hipStream_t st) {
     const m1v_encoder::TableCounters &t = e->table;
     const size_t kf = (size_t)kMaxCandidates * e->max_frames;
@@ -146,6 +149,27 @@ static hipError_t table_clear(const m1v_encoder *e, hipStream_t st) {
     if (err == hipSuccess) err = hipMemsetAsync(t.frame_bytes, 0, kf * 8, st);
     if (err == hipSuccess) err = hipMemsetAsync(t.words, 0, kMaxCandidates * sizeof(uint32_t), st);
     return err;
+}
+static hipError_t table_alloc(m1v_encoder *e) {
+    m1v_encoder::TableCounters &t = e->table;
+    const size_t kf = (size_t)kMaxCandidates * e->max_frames;
+    hipError_t err = hipMalloc(&t.strip_ctr, kf * e->g.n_strips * 8);
+    if (err == hipSuccess) err = hipMalloc(&t.frame_bytes, kf * 8);
+    if (err == hipSuccess) err = hipMalloc(&t.words, kMaxCandidates * sizeof(uint32_t));
+    if (err == hipSuccess) err = table_clear(e, nullptr);
+    return err == hipSuccess ? hipStreamSynchronize(nullptr) : err;
+}
+static void table_free(m1v_encoder::TableCounters &t) {
+    (void)hipFree(t.strip_ctr);
+    (void)hipFree(t.frame_bytes);
+    (void)hipFree(t.words);
+}
+
+// A constant table of m1v_create: allocated and uploaded
+template <typename T>
+static hipError_t upload(T **dst, const T *src, size_t count) {
+    const hipError_t err = hipMalloc(dst, count * sizeof(T));
+    return err == hipSuccess ? hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice) : err;
 }
 
 static void batch_free(m1v_encoder::Batch &bt) {
@@ -281,8 +305,8 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
 // What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
 // the run kernels
 static int packed_only(const m1v_encoder *e) {
-    if (e->layout.planes) return fail(M1V_E_ARG, "packed input only: a plane layout is set (m1v_set_plane_layout)%s");
-    return e->layout.surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
+    if (e->layout.kind == LayoutKind::planes) return fail(M1V_E_ARG, "packed input only: a plane layout is set (m1v_set_plane_layout)%s");
+    return e->layout.kind == LayoutKind::surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
 }
 
 extern "C" {
@@ -323,11 +347,9 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (width <= 0 || height <= 0 || channels < 3 || channels > 4 || max_frames <= 0)
         return fail(M1V_E_ARG, "bad geometry%s");
     if (mode != M1V_MODE_STRICT && mode != M1V_MODE_FULL) return fail(M1V_E_ARG, "bad mode%s");
-    int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96;
-    int ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
-    if (xe > width || ye > height)
-        return fail(M1V_E_ARG, "picture smaller than the 96x144 region the reference encodes%s");
-    if (xe == 0 || ye == 0) return fail(M1V_E_ARG, "picture smaller than one macroblock%s");
+    const CodedRegion coded(width, height, mode);
+    if (!coded.fits(width, height)) return fail(M1V_E_ARG, "picture smaller than the 96x144 region the reference encodes%s");
+    if (coded.xe == 0 || coded.ye == 0) return fail(M1V_E_ARG, "picture smaller than one macroblock%s");
     if ((unsigned long long)width * height * channels >= (1ull << 32))
         return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
     int n = m1v_device_count();
@@ -342,11 +364,10 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     e->max_frames = max_frames;
     Geometry &g = e->g;
     g.W = width; g.H = height; g.C = channels;
-    g.n_strips = xe / 16; g.n_mbrows = ye / 16;
+    g.n_strips = coded.xe / 16; g.n_mbrows = coded.ye / 16;
     g.half_w = width / 2;
     g.frame_bytes = (unsigned long long)width * height * channels;
-    unsigned long long strip_bits = 38ull + (unsigned long long)g.n_mbrows * (2 + 6 * kMaxBlockBits);
-    g.strip_cap = (uint32_t)((((strip_bits + 7) / 8) + 16 + 15) & ~15ull);
+    g.strip_cap = (uint32_t)((((coded.strip_bits() + 7) / 8) + 16 + 15) & ~15ull);
     e->dense = g.n_mbrows * 6 >= kWave;
     e->fast_ok = channels == 3 && (width % 8) == 0;
 
@@ -379,48 +400,24 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     for (int h = 0; h < 256; h++) build_frame_header(t->hdr[h], width, height, h);
     const std::vector<uint32_t> sel((size_t)max_frames, (uint32_t)(own - 1) * 64u);
 
-    hipError_t err = hipMalloc(&e->d_tab, sizeof(Tables));
-    if (err == hipSuccess) err = hipMemcpy(e->d_tab, t, sizeof(Tables), hipMemcpyHostToDevice);
+    hipError_t err = upload(&e->d_tab, t, 1);
     delete t;
-    if (err == hipSuccess) err = hipMalloc(&e->d_rq_all, rq_all.size() * sizeof(float));
-    if (err == hipSuccess) err = hipMemcpy(e->d_rq_all, rq_all.data(), rq_all.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMalloc(&e->d_qsel_own, sel.size() * sizeof(uint32_t));
-    if (err == hipSuccess) err = hipMemcpy(e->d_qsel_own, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMalloc(&e->d_qsel, sel.size() * sizeof(uint32_t));
-    if (err == hipSuccess) err = hipMemcpy(e->d_qsel, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = upload(&e->d_rq_all, rq_all.data(), rq_all.size());
+    if (err == hipSuccess) err = upload(&e->d_qsel_own, sel.data(), sel.size());
+    if (err == hipSuccess) err = upload(&e->d_qsel, sel.data(), sel.size());
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
     if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
-    { // the fused size table's counters, clear
-        const size_t kf = (size_t)kMaxCandidates * max_frames;
-        if (err == hipSuccess) err = hipMalloc(&e->table.strip_ctr, kf * g.n_strips * 8);
-        if (err == hipSuccess) err = hipMalloc(&e->table.frame_bytes, kf * 8);
-        if (err == hipSuccess) err = hipMalloc(&e->table.words, kMaxCandidates * sizeof(uint32_t));
-        if (err == hipSuccess) err = table_clear(e, nullptr);
-        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-    }
+    if (err == hipSuccess) err = table_alloc(e);
 #if defined(M1V_STAMPS) || defined(M1V_TILE_STAMPS) || defined(M1V_ASM_STAMPS)
     if (err == hipSuccess) err = hipMalloc(&e->d_stamps, (32 + 8 * 65536) * 8); // [32] phase sums, then a timeline of 8 stamps per workgroup
     if (err == hipSuccess) err = hipMemset(e->d_stamps, 0, (32 + 8 * 65536) * 8);
 #endif
     if (err == hipSuccess) err = configure_path(e) == M1V_OK ? hipSuccess : hipErrorOutOfMemory;
-    for (const auto &by_mode : kProducerKernels)
-        for (const auto &by_staging : by_mode)
-            for (const void *kf : by_staging)
-                if (err == hipSuccess && kf) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    for (const auto &by_staging : kTableKernels)
-        for (const void *kf : by_staging)
-            if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    for (const auto *family : {&kSurfaceKernels, &kSurfaceTableKernels})
-        for (const auto &by_order : *family)
-            for (const auto &by_staging : by_order)
-                for (const void *kf : by_staging)
-                    if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    for (const auto *family : {&kPlaneKernels, &kPlaneTableKernels})
-        for (const auto &by_staging : *family)
-            for (const void *kf : by_staging)
-                if (err == hipSuccess) err = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *const *registered = &kKernels.tile[0][0][0]; // (Kernels holds nothing but kernels)
+    for (size_t k = 0; k < sizeof kKernels / sizeof *registered; k++)
+        if (err == hipSuccess && registered[k]) err = hipFuncSetAttribute(registered[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err != hipSuccess) {
         fail(M1V_E_HIP, "allocation failed: %s", hipGetErrorString(err));
         m1v_destroy(e);
@@ -442,9 +439,7 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
     (void)hipFree(e->d_pick_status);
-    (void)hipFree(e->table.strip_ctr);
-    (void)hipFree(e->table.frame_bytes);
-    (void)hipFree(e->table.words);
+    table_free(e->table);
     for (m1v_encoder::Batch &bt : e->batch) batch_free(bt);
     if (e->side) (void)hipStreamDestroy(e->side);
     (void)hipFree(e->hp.d_in);
@@ -465,10 +460,9 @@ int m1v_mb_rows(const m1v_encoder *e) { return e ? e->g.n_mbrows : 0; }
 size_t m1v_frame_bytes_in(const m1v_encoder *e) { return e ? (size_t)e->g.frame_bytes : 0; }
 
 size_t m1v_frame_bound_for(int width, int height, int mode) {
-    const int xe = mode == M1V_MODE_FULL ? (width & ~15) : 96, ye = mode == M1V_MODE_FULL ? (height & ~15) : 144;
-    if (width <= 0 || height <= 0 || xe <= 0 || ye <= 0 || xe > width || ye > height) return 0;
-    const size_t strip_bits = 38 + (size_t)(ye / 16) * (2 + 6 * kMaxBlockBits);
-    return 44 + (size_t)(xe / 16) * ((strip_bits + 7) / 8) + 4;
+    const CodedRegion coded(width, height, mode);
+    if (width <= 0 || height <= 0 || coded.xe <= 0 || coded.ye <= 0 || !coded.fits(width, height)) return 0;
+    return 44 + (size_t)(coded.xe / 16) * (size_t)((coded.strip_bits() + 7) / 8) + 4;
 }
 
 size_t m1v_frame_bound(const m1v_encoder *e) { return e ? m1v_frame_bound_for(e->g.W, e->g.H, e->mode) : 0; }
@@ -550,8 +544,8 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
     if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "order must be M1V_ORDER_RGB or M1V_ORDER_BGR%s");
     const Geometry &g = e->g;
     m1v_encoder::Layout want;
-    want.surface = row_pitch_bytes != 0 || frame_stride_bytes != 0 || order != M1V_ORDER_RGB;
-    if (want.surface) {
+    if (row_pitch_bytes != 0 || frame_stride_bytes != 0 || order != M1V_ORDER_RGB) {
+        want.kind = LayoutKind::surface;
         const unsigned long long row = (unsigned long long)g.W * g.C;
         if (g.W & 1) return fail(M1V_E_ARG, "a surface layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
         if (row_pitch_bytes != 0 && row_pitch_bytes < row) return fail(M1V_E_ARG, "row pitch below width * channels%s");
@@ -560,7 +554,7 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
             return fail(M1V_E_ARG, "a window of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
         const unsigned long long extent = (unsigned long long)(g.H - 1) * pitch + row;
         if (frame_stride_bytes != 0 && frame_stride_bytes < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's window spans%s");
-        if (e->forced_path == 0 || e->forced_mode >= 0 || e->forced_T > 0)
+        if (e->run_hook_set())
             return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
         want.row_pitch = (uint32_t)pitch;
         want.frame_stride = frame_stride_bytes ? frame_stride_bytes : (unsigned long long)g.H * pitch;
@@ -571,7 +565,7 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.planes) return fail(M1V_E_ARG, "a plane layout is in force: ask m1v_plane_layout_in_force%s");
+    if (e->layout.kind == LayoutKind::planes) return fail(M1V_E_ARG, "a plane layout is in force: ask m1v_plane_layout_in_force%s");
     if (row_pitch_bytes) *row_pitch_bytes = e->layout.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)e->layout.frame_stride;
     if (order) *order = e->layout.order;
@@ -629,9 +623,9 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
                                                    std::max<unsigned long long>(layout->cb_offset, layout->cr_offset) + c_rows);
         if (extent >= limit) return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
         if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
-        if (e->forced_path == 0 || e->forced_mode >= 0 || e->forced_T > 0)
+        if (e->run_hook_set())
             return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
-        want.planes = true;
+        want.kind = LayoutKind::planes;
         want.y_off = (uint32_t)layout->y_offset;
         want.cb_off = (uint32_t)layout->cb_offset;
         want.cr_off = (uint32_t)layout->cr_offset;
@@ -646,7 +640,7 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (!e->layout.planes) return 0;
+    if (e->layout.kind != LayoutKind::planes) return 0;
     if (out) {
         const m1v_encoder::Layout &l = e->layout;
         *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.c_step, (size_t)l.frame_stride};
@@ -739,6 +733,15 @@ static int check_qualities(const m1v_encoder *e, const uint8_t *q, int n) {
     return M1V_OK;
 }
 
+// The checks the candidate-taking calls share, in the order every one of them has: the encoder and what the call checks before
+// its candidates (`first`), the candidates, n_frames, what it checks after them (`then`)
+static int check_candidate_call(const m1v_encoder *e, bool first, const uint8_t *q, int n_q, int n_frames, bool then) {
+    if (!e || !first) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_qualities(e, q, n_q)) return rc;
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    return then ? M1V_OK : fail(M1V_E_ARG, "null pointer%s");
+}
+
 // sizes[k * stride + frame] and status[k] of every quality: one fused pass where the plan has one (3-channel tile encoders,
 // 4-channel encoders: m1v_size_table_fused); otherwise (a path, input mode or run length forced by a test hook) one probe call
 // (m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that every row is
@@ -758,11 +761,16 @@ static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const 
     return e->pipelined ? m1v_flush(e, stream) : M1V_OK;
 }
 
+// The first step of the budget, batch-budget and bitrate calls: the record size of every frame at every candidate into the
+// encoder's own table (d_probe_sizes [kMaxCandidates][max_frames], d_probe_status)
+static int probe_candidates(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *candidates, int n_candidates, void *stream) {
+    return size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames, e->d_probe_status, stream);
+}
+
 int m1v_frame_size_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
                                 uint64_t *d_sizes, uint32_t *d_status, void *stream) {
-    if (!e || !d_sizes || (!d_rgb && n_frames > 0)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
-    if (const int rc = check_qualities(e, qualities, n_qualities)) return rc;
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    // (an empty batch reads no input)
+    if (const int rc = check_candidate_call(e, d_sizes && (d_rgb || n_frames <= 0), qualities, n_qualities, n_frames, true)) return rc;
     if (n_frames == 0) return M1V_OK;
     return size_table(e, d_rgb, n_frames, qualities, n_qualities, (unsigned long long *)d_sizes, (size_t)n_frames, d_status, stream);
 }
@@ -772,14 +780,8 @@ int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames,
                              const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
                              uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                              uint32_t *d_status, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null pointer%s");
-    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
-    // 1. the record size of every frame at every candidate ([kMaxCandidates][max_frames])
-    if (const int rc = size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames,
-                                  e->d_probe_status, stream))
-        return rc;
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
+    if (const int rc = probe_candidates(e, d_rgb, n_frames, candidates, n_candidates, stream)) return rc; // 1. the table
     // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
     QualityArgs qa = {};
     qa.probe_sizes = e->d_probe_sizes;
@@ -798,10 +800,7 @@ int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames,
 static int rate_encode(m1v_encoder *e, PickArgs &pa, bool cbr, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                        const uint8_t *candidates, int n_candidates, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap,
                        uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status, void *stream) {
-    // 1. the record size of every frame at every candidate ([kMaxCandidates][max_frames])
-    if (const int rc = size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames,
-                                  e->d_probe_status, stream))
-        return rc;
+    if (const int rc = probe_candidates(e, d_rgb, n_frames, candidates, n_candidates, stream)) return rc; // 1. the table
     // 2. the pick
     HIP_TRY(hipSetDevice(e->device));
     pa.sizes = e->d_probe_sizes;
@@ -829,10 +828,7 @@ int m1v_encode_batch_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_f
                                    const uint8_t *candidates, int n_candidates, uint64_t batch_bytes, uint8_t *d_chosen,
                                    uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                                    uint32_t *d_status, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null pointer%s");
-    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
     PickArgs pa = {};
     pa.budget = batch_bytes;
     return rate_encode(e, pa, false, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
@@ -844,10 +840,8 @@ int m1v_encode_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, in
                           const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
                           uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                           uint32_t *d_status, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null pointer%s");
-    if (const int rc = check_qualities(e, candidates, n_candidates)) return rc;
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    if ((!d_rgb && n_frames > 0) || !d_out || !d_level_in || !d_level_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out && d_level_in && d_level_out))
+        return rc;
     if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
         return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
     PickArgs pa = {};
@@ -1132,17 +1126,18 @@ int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     a.tab = e->d_tab;
     a.out = d_coeffs;
     a.n_frames = n_frames;
-    if (e->g.C == 3 && e->forced_mode < 0 && e->forced_path != 0) { // tiles (any width, any alignment); the run-shaped kernel serves 4 channels
+    if (e->g.C == 3 && !e->runs_by_path_or_mode()) { // tiles (any width, any alignment); the run-shaped kernel serves 4 channels
         CoefTileArgs t;
         t.g = e->g;
         t.rgb = d_rgb;
         t.tab = e->d_tab;
         t.out = d_coeffs;
         t.n_frames = n_frames;
-        t.tile_cols = (e->g.n_strips + kTileStrips - 1) / kTileStrips;
-        t.tile_rows = (e->g.n_mbrows + kTileMbRows - 1) / kTileMbRows;
-        t.tiles_per_frame = t.tile_cols * t.tile_rows;
-        t.region = (std::max<uint32_t>((uint32_t)M1V_TILE_RING * kTileSlot, (uint32_t)(kWave * kCoefStride * 4)) + 15u) & ~15u;
+        const TileGrid grid(e->g);
+        t.tile_cols = grid.cols;
+        t.tile_rows = grid.rows;
+        t.tiles_per_frame = grid.units();
+        t.region = wave_region(kCoefStride);
         hipLaunchKernelGGL((k_coefficient_tiles<M1V_TILE_RING>), dim3((unsigned)((size_t)n_frames * t.tiles_per_frame)),
                            dim3(kTileThreads), 3 * (size_t)t.region, (hipStream_t)stream, t);
         HIP_TRY(hipGetLastError());

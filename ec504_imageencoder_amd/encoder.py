@@ -27,6 +27,18 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(name, *args):
+    """The C entry point `name`, whose success value is OK; EncoderError otherwise."""
+    rc = getattr(_ffi.lib(), name)(*args)
+    if rc != _ffi.OK:
+        raise EncoderError(rc, name)
+
+
+def _meta_ptrs(meta):
+    """Where the entry points write a batch's total bytes and its status word: the two elements of meta."""
+    return C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8)
+
+
 def surface_strides(shape, strides):
     """(row_pitch, frame_stride) in bytes of a uint8 [n, H, W, C] array with the given strides (in elements = bytes), as
     Mpeg1Encoder.set_input_layout takes them: a packed tensor, rows with padding, a window surface[:, y0:y0+H, x0:x0+W, :] of a
@@ -135,19 +147,12 @@ class Mpeg1Encoder:
             sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
         if meta is None:
             meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
+        results = (_ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream())
         if quality is None:
-            rc = _ffi.lib().m1v_encode_device(self._h, _ptr(rgb), n, int(first_frame_index), _ptr(out), out.numel(),
-                                              _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8),
-                                              _stream())
-            where = "m1v_encode_device"
+            _call("m1v_encode_device", self._h, _ptr(rgb), n, int(first_frame_index), *results)
         else:
             q = self._quality_tensor(quality, n, rgb.device)
-            rc = _ffi.lib().m1v_encode_quality_device(self._h, _ptr(rgb), n, int(first_frame_index), _ptr(q), _ptr(out),
-                                                      out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()),
-                                                      C.c_void_p(meta.data_ptr() + 8), _stream())
-            where = "m1v_encode_quality_device"
-        if rc != _ffi.OK:
-            raise EncoderError(rc, where)
+            _call("m1v_encode_quality_device", self._h, _ptr(rgb), n, int(first_frame_index), _ptr(q), *results)
         return out, sizes, meta
 
     def _check_input(self, rgb):
@@ -177,9 +182,7 @@ class Mpeg1Encoder:
         surface_strides).  Every call then takes tensors with those strides.  The defaults restore the packed layout and its
         kernels.  A reconfiguration: call it between batches."""
         code = {"rgb": _ffi.ORDER_RGB, "bgr": _ffi.ORDER_BGR}.get(order, order)
-        rc = _ffi.lib().m1v_set_input_layout(self._h, int(row_pitch), int(frame_stride), int(code))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_set_input_layout")
+        _call("m1v_set_input_layout", self._h, int(row_pitch), int(frame_stride), int(code))
         self._planes = None             # one input layout is in force at a time
         self._layout = self.input_layout
 
@@ -190,18 +193,15 @@ class Mpeg1Encoder:
         header), or None = back to the default layout and its kernels.  Every call then takes uint8 CUDA tensors [n, L] whose
         rows are the frames: L >= the bytes a frame's planes span, rows frame_stride apart — convert(rgb).view(n, -1) and
         torch.as_strided views go in as they are.  A reconfiguration: call it between batches."""
-        if layout is None:
-            rc = _ffi.lib().m1v_set_plane_layout(self._h, None)
-        else:
+        c = None
+        if layout is not None:
             if isinstance(layout, str):
                 layout = plane_layout_preset(self.width, self.height, layout)
             unknown = set(layout) - set(PLANE_LAYOUT_FIELDS)
             if unknown:
                 raise ValueError(f"unknown plane layout fields {sorted(unknown)}")
-            c = _ffi.PlaneLayout(**{k: int(v) for k, v in layout.items()})
-            rc = _ffi.lib().m1v_set_plane_layout(self._h, C.byref(c))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_set_plane_layout")
+            c = C.byref(_ffi.PlaneLayout(**{k: int(v) for k, v in layout.items()}))
+        _call("m1v_set_plane_layout", self._h, c)
         self._planes = self.plane_layout
         self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
 
@@ -218,9 +218,7 @@ class Mpeg1Encoder:
     def input_layout(self):
         """(row_pitch, frame_stride, order) in force: (0, 0, "rgb") = packed frames, else the bytes the kernels step by."""
         pitch, stride, order = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
-        rc = _ffi.lib().m1v_input_layout(self._h, C.byref(pitch), C.byref(stride), C.byref(order))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_input_layout")
+        _call("m1v_input_layout", self._h, C.byref(pitch), C.byref(stride), C.byref(order))
         return pitch.value, stride.value, "bgr" if order.value == _ffi.ORDER_BGR else "rgb"
 
     @staticmethod
@@ -245,9 +243,7 @@ class Mpeg1Encoder:
         self._check_input(rgb)
         sizes = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
         q = self._quality_tensor(quality, n, rgb.device) if quality is not None else None
-        rc = _ffi.lib().m1v_frame_sizes_device(self._h, _ptr(rgb), n, _ptr(q), _ptr(sizes), _ptr(status), _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_frame_sizes_device")
+        _call("m1v_frame_sizes_device", self._h, _ptr(rgb), n, _ptr(q), _ptr(sizes), _ptr(status), _stream())
         return sizes[:n]
 
     def frame_size_table(self, rgb, qualities, status=None):
@@ -266,9 +262,7 @@ class Mpeg1Encoder:
             assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= len(qs), "status: CUDA int32, one per quality"
         q_buf = (C.c_uint8 * len(qs))(*qs)
         sizes = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
-        rc = _ffi.lib().m1v_frame_size_table_device(self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(status), _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_frame_size_table_device")
+        _call("m1v_frame_size_table_device", self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(status), _stream())
         return sizes[:len(qs) * n].view(len(qs), n)
 
     @staticmethod
@@ -279,8 +273,8 @@ class Mpeg1Encoder:
             raise EncoderError(_ffi.E_ARG, f"{where}: 1 to 8 candidate qualities")
         return (C.c_uint8 * len(cands))(*cands)
 
-    def _encode_retrying(self, rgb, name, where, launch):
-        """Synchronous: launch(out, sizes, meta) queues one encode of rgb into those buffers (a C entry point, `where`).  On
+    def _encode_retrying(self, rgb, name, launch):
+        """Synchronous: launch(out, sizes, meta) queues one encode of rgb into those buffers for the method `name`.  On
         STATUS_SCRATCH the worst-case scratch is reserved and on STATUS_NOSPACE `out` grows to the worst case, and the encode is
         queued again, three times at most.  Returns (bytes, sizes, status bits)."""
         import torch
@@ -291,9 +285,7 @@ class Mpeg1Encoder:
                 out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
             sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
             meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
-            rc = launch(out, sizes, meta)
-            if rc != _ffi.OK:
-                raise EncoderError(rc, where)
+            launch(out, sizes, meta)
             self.flush()
             torch.cuda.synchronize(rgb.device)
             total, status = (int(x) for x in meta.cpu())
@@ -331,10 +323,10 @@ class Mpeg1Encoder:
             budget, d_budget = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
         chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
         data, sizes_l, _ = self._encode_retrying(
-            rgb, "encode_to_budget", "m1v_encode_budget_device",
-            lambda out, sizes, meta: _ffi.lib().m1v_encode_budget_device(
-                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), budget, _ptr(d_budget), _ptr(chosen),
-                _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream()))
+            rgb, "encode_to_budget",
+            lambda out, sizes, meta: _call(
+                "m1v_encode_budget_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), budget,
+                _ptr(d_budget), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
         chosen_l = [int(c) for c in chosen[:n].cpu()]
         budgets = [budget] * n if d_budget is None else [int(x) for x in d_budget[:n].cpu()]
         over = [f for f in range(n) if sizes_l[f] > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
@@ -354,10 +346,10 @@ class Mpeg1Encoder:
             raise EncoderError(_ffi.E_ARG, "encode_to_batch_budget: batch_bytes must fit uint64")
         chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
         data, sizes_l, status = self._encode_retrying(
-            rgb, "encode_to_batch_budget", "m1v_encode_batch_budget_device",
-            lambda out, sizes, meta: _ffi.lib().m1v_encode_batch_budget_device(
-                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), int(batch_bytes), _ptr(chosen),
-                _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8), _stream()))
+            rgb, "encode_to_batch_budget",
+            lambda out, sizes, meta: _call(
+                "m1v_encode_batch_budget_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf),
+                int(batch_bytes), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
         return data, sizes_l, [int(c) for c in chosen[:n].cpu()], bool(status & _ffi.STATUS_OVER_BUDGET)
 
     def encode_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
@@ -379,11 +371,10 @@ class Mpeg1Encoder:
         level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
         chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
         data, sizes_l, _ = self._encode_retrying(
-            rgb, "encode_at_bitrate", "m1v_encode_cbr_device",
-            lambda out, sizes, meta: _ffi.lib().m1v_encode_cbr_device(
-                self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap, _ptr(level_in),
-                _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), C.c_void_p(meta.data_ptr()),
-                C.c_void_p(meta.data_ptr() + 8), _stream()))
+            rgb, "encode_at_bitrate",
+            lambda out, sizes, meta: _call(
+                "m1v_encode_cbr_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap,
+                _ptr(level_in), _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
         level.copy_(level_out.view_as(level))
         over, L = [], min(start, cap)                # the level before each frame, replayed from the sizes
         for f, s in enumerate(sizes_l):
@@ -395,17 +386,13 @@ class Mpeg1Encoder:
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.
         Outputs of a batch are complete only behind flush(); callers double-buffer `out`."""
-        rc = _ffi.lib().m1v_set_pipelined(self._h, 1 if enable else 0)
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_set_pipelined")
+        _call("m1v_set_pipelined", self._h, 1 if enable else 0)
 
     def flush(self, stream=None):
         """Make `stream` (torch stream, default: the current one) wait for all pending gathers."""
         import torch
         st = stream if stream is not None else torch.cuda.current_stream()
-        rc = _ffi.lib().m1v_flush(self._h, C.c_void_p(st.cuda_stream))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_flush")
+        _call("m1v_flush", self._h, C.c_void_p(st.cuda_stream))
 
     def default_out_capacity(self, n):
         # typical output is far below the worst-case bound; callers that need the guarantee pass
@@ -414,45 +401,11 @@ class Mpeg1Encoder:
 
     def encode_to_bytes(self, rgb, first_frame_index=0, quality=None):
         """Synchronous convenience: returns (bytes, [sizes]).  quality: as in encode()."""
-        import torch
         if quality is not None:     # one upload, reused by a retry
             quality = self._quality_tensor(quality, rgb.shape[0], rgb.device)
-        out, sizes, meta = self.encode(rgb, first_frame_index, quality=quality)
-        self.flush()
-        torch.cuda.synchronize(rgb.device)
-        total, status = (int(x) for x in meta.cpu())
-        status &= 0xFFFFFFFF
-        if status & _ffi.STATUS_UNENCODABLE:
-            raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
-        if status & _ffi.STATUS_QUALITY:
-            raise EncoderError(_ffi.E_ARG, "encode: a quality outside 1 .. quality_factor")
-        if status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
-            if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
-                self.reserve_scratch(True)
-            if status & _ffi.STATUS_NOSPACE:
-                out = torch.empty(self.frame_bound * rgb.shape[0], dtype=torch.uint8, device=rgb.device)
-            return self._retry_bytes(rgb, first_frame_index, out, quality)
-        return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:rgb.shape[0]].cpu()]
-
-    def _retry_bytes(self, rgb, first_frame_index, out, quality=None):
-        import torch
-        out, sizes, meta = self.encode(rgb, first_frame_index, out=out, quality=quality)
-        self.flush()
-        torch.cuda.synchronize(rgb.device)
-        total, status = (int(x) for x in meta.cpu())
-        status &= 0xFFFFFFFF
-        if status & _ffi.STATUS_NOSPACE:            # scratch was the first obstacle, the output buffer is the second
-            out = torch.empty(self.frame_bound * rgb.shape[0], dtype=torch.uint8, device=rgb.device)
-            out, sizes, meta = self.encode(rgb, first_frame_index, out=out, quality=quality)
-            self.flush()
-            torch.cuda.synchronize(rgb.device)
-            total, status = (int(x) for x in meta.cpu())
-            status &= 0xFFFFFFFF
-        if status & _ffi.STATUS_UNENCODABLE:
-            raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
-        if status:
-            raise EncoderError(_ffi.E_NOSPACE if status & _ffi.STATUS_NOSPACE else _ffi.E_SCRATCH, "encode")
-        return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:rgb.shape[0]].cpu()]
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, "encode", lambda out, sizes, meta: self.encode(rgb, first_frame_index, out, sizes, meta, quality))
+        return data, sizes_l
 
     def encode_host(self, rgb_np, first_frame_index=0, with_planes=False):
         """numpy uint8 [n,H,W,C] through the host-buffer entry point (PCIe inclusive).  with_planes: also return the
@@ -477,9 +430,7 @@ class Mpeg1Encoder:
         import torch
         n = rgb.shape[0]
         out = torch.empty((n, self.blocks_per_frame, 64), dtype=torch.int16, device=rgb.device)
-        rc = _ffi.lib().m1v_coefficients_device(self._h, _ptr(rgb), n, _ptr(out), _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_coefficients_device")
+        _call("m1v_coefficients_device", self._h, _ptr(rgb), n, _ptr(out), _stream())
         return out
 
     def convert(self, rgb):
@@ -487,9 +438,7 @@ class Mpeg1Encoder:
         import torch
         n = rgb.shape[0]
         out = torch.empty((n, 3, self.height * self.width), dtype=torch.uint8, device=rgb.device)
-        rc = _ffi.lib().m1v_convert_device(self._h, _ptr(rgb), n, _ptr(out), _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_convert_device")
+        _call("m1v_convert_device", self._h, _ptr(rgb), n, _ptr(out), _stream())
         return out
 
     def subsample(self, cb, cr):
@@ -497,9 +446,7 @@ class Mpeg1Encoder:
         n = (self.width // 2) * (self.height // 2)
         a = torch.empty(n, dtype=torch.uint8, device=cb.device)
         b = torch.empty(n, dtype=torch.uint8, device=cb.device)
-        rc = _ffi.lib().m1v_subsample_device(self._h, _ptr(cb), _ptr(cr), _ptr(a), _ptr(b), _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_subsample_device")
+        _call("m1v_subsample_device", self._h, _ptr(cb), _ptr(cr), _ptr(a), _ptr(b), _stream())
         return a, b
 
     def synth(self, n_frames, seed=504, first_frame_index=0, device=None, out=None):
@@ -508,9 +455,7 @@ class Mpeg1Encoder:
         dev = device or torch.device("cuda", self.device)
         rgb = out if out is not None else torch.empty((n_frames, self.height, self.width, self.channels), dtype=torch.uint8, device=dev)
         assert rgb.numel() == n_frames * self.frame_bytes_in and rgb.is_contiguous()
-        rc = _ffi.lib().m1v_synth_device(_ptr(rgb), self.frame_bytes_in, n_frames, seed, first_frame_index, _stream())
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_synth_device")
+        _call("m1v_synth_device", _ptr(rgb), self.frame_bytes_in, n_frames, seed, first_frame_index, _stream())
         return rgb
 
     # ---- measurement ----------------------------------------------------------------------------
@@ -519,39 +464,29 @@ class Mpeg1Encoder:
 
     def profile_read(self):
         n, ms = C.c_int(0), C.c_double(0.0)
-        rc = _ffi.lib().m1v_profile_read(self._h, C.byref(n), C.byref(ms))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_profile_read")
+        _call("m1v_profile_read", self._h, C.byref(n), C.byref(ms))
         return n.value, ms.value
 
     def profile_read_times(self, cap=4096):
         """Durations (ms) of the dominant kernel's launches since profile(True), in launch order."""
         buf, n = (C.c_float * cap)(), C.c_int(0)
-        rc = _ffi.lib().m1v_profile_read_times(self._h, buf, cap, C.byref(n))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_profile_read_times")
+        _call("m1v_profile_read_times", self._h, buf, cap, C.byref(n))
         return [float(buf[i]) for i in range(min(n.value, cap))]
 
     def reserve_scratch(self, worst_case=True):
         """Size the overflow arena for every run (True) or return to the default 1/256 (False); see mpeg1_hip.h."""
-        rc = _ffi.lib().m1v_reserve_scratch(self._h, 1 if worst_case else 0)
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_reserve_scratch")
+        _call("m1v_reserve_scratch", self._h, 1 if worst_case else 0)
 
     def scratch_bytes(self):
         return int(_ffi.lib().m1v_scratch_bytes(self._h))
 
     def debug_set_input_mode(self, mode):
         """Test hook: -1 automatic, 0 byte loads, 2 funnel-shifted 28-byte loads (see mpeg1_hip.h)."""
-        rc = _ffi.lib().m1v_debug_set_input_mode(self._h, int(mode))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_debug_set_input_mode")
+        _call("m1v_debug_set_input_mode", self._h, int(mode))
 
     def debug_set_path(self, path):
         """Test hook: which encode kernel serves the batches: -1 by geometry, 0 runs, 1 tiles (see mpeg1_hip.h)."""
-        rc = _ffi.lib().m1v_debug_set_path(self._h, {"auto": -1, "runs": 0, "tiles": 1}.get(path, path))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_debug_set_path")
+        _call("m1v_debug_set_path", self._h, {"auto": -1, "runs": 0, "tiles": 1}.get(path, path))
 
     @property
     def path(self):
@@ -564,14 +499,10 @@ class Mpeg1Encoder:
         return _ffi.lib().m1v_size_table_fused(self._h)
 
     def debug_set_lds_words(self, words):
-        rc = _ffi.lib().m1v_debug_set_lds_words(self._h, int(words))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_debug_set_lds_words")
+        _call("m1v_debug_set_lds_words", self._h, int(words))
 
     def debug_set_dense_threads(self, threads):
-        rc = _ffi.lib().m1v_debug_set_dense_threads(self._h, int(threads))
-        if rc != _ffi.OK:
-            raise EncoderError(rc, "m1v_debug_set_dense_threads")
+        _call("m1v_debug_set_dense_threads", self._h, int(threads))
 
 
 def file_prolog():

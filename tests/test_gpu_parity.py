@@ -710,6 +710,64 @@ def test_unencodable_level_is_reported(torch_cuda, orc):
     enc.close()
 
 
+def _per_frame_oracle(orc, host, W, H, first, qs):
+    recs = [orc.encode_frame(host[f], W, H, first + f, q, orc.MODE_FULL) for f, q in enumerate(qs)]
+    return b"".join(recs), [len(r) for r in recs]
+
+
+def test_encode_to_bytes_grows_an_output_buffer_that_is_too_small(torch_cuda, orc):
+    """A first output buffer of 100 bytes for two records of a few hundred: STATUS_NOSPACE, and encode_to_bytes encodes again
+    into a worst-case buffer.  What it returns is the oracle's stream, at the encoder's quality and at one quality per frame."""
+    W, H, n = 96, 48, 2
+    enc = _enc(W, H, 12, "full", max_frames=n)
+    enc.default_out_capacity = lambda n_frames: 100
+    rgb = enc.synth(n, seed=61)
+    host = rgb.cpu().numpy()
+    want, wsizes = orc.encode_frames(host, n, W, H, 4, 12, orc.MODE_FULL)
+    assert len(want) > 100
+    assert enc.encode_to_bytes(rgb, 4) == (want, [int(x) for x in wsizes])
+    assert enc.encode_to_bytes(rgb, 4, quality=[5, 12]) == _per_frame_oracle(orc, host, W, H, 4, [5, 12])
+    enc.close()
+
+
+def test_encode_to_bytes_recovers_from_scratch_and_output_together(torch_cuda, orc):
+    """A forced 8-word LDS image sends all 45 tile units of the batch to an overflow arena of 32 slots (STATUS_SCRATCH) and the
+    first output buffer holds 100 bytes (STATUS_NOSPACE): within its three attempts encode_to_bytes reserves the worst-case
+    scratch, takes a worst-case output buffer and returns the oracle's stream; the next call on the encoder is exact too."""
+    W, H, n = 352, 288, 3
+    enc = _enc(W, H, 12, "full", max_frames=n)
+    enc.debug_set_lds_words(8)
+    enc.default_out_capacity = lambda n_frames: 100
+    rgb = enc.synth(n, seed=62)
+    want, wsizes = orc.encode_frames(rgb.cpu().numpy(), n, W, H, 9, 12, orc.MODE_FULL)
+    before = enc.scratch_bytes()
+    assert enc.encode_to_bytes(rgb, 9) == (want, [int(x) for x in wsizes])
+    assert enc.scratch_bytes() > before
+    assert enc.encode_to_bytes(rgb, 9) == (want, [int(x) for x in wsizes])
+    enc.close()
+
+
+def test_encode_to_bytes_refuses_an_unencodable_frame_and_goes_on(torch_cuda, orc):
+    """Bands of four rows of 255 / 0 at quality 92 hold a level the VLC cannot code (the oracle refuses the frame; it codes
+    an all-noise frame even at quality 100, so that is no refusal case): encode_to_bytes raises E_UNENCODABLE without a retry,
+    and the encoder then encodes a plain frame exactly."""
+    torch = torch_cuda
+    from ec504_imageencoder_amd import EncoderError, _ffi
+    W, H, qf = 96, 48, 92
+    bands = np.where((np.arange(H)[:, None] % 8) < 4, 255, 0).astype(np.uint8).repeat(W, axis=1)
+    pic = np.stack([bands, bands, bands], -1)[None]
+    with pytest.raises(ValueError):
+        orc.encode_frame(pic[0], W, H, 0, qf, orc.MODE_FULL)
+    enc = _enc(W, H, qf, "full", max_frames=1)
+    with pytest.raises(EncoderError) as ei:
+        enc.encode_to_bytes(torch.from_numpy(pic).cuda(), 0)
+    assert ei.value.code == _ffi.E_UNENCODABLE
+    rgb = enc.synth(1, seed=63)
+    want, wsizes = orc.encode_frames(rgb.cpu().numpy(), 1, W, H, 2, qf, orc.MODE_FULL)
+    assert enc.encode_to_bytes(rgb, 2) == (want, [int(x) for x in wsizes])
+    enc.close()
+
+
 def test_argument_errors(torch_cuda):
     from ec504_imageencoder_amd import EncoderError, Mpeg1Encoder
     with pytest.raises(EncoderError):

@@ -6,7 +6,13 @@ summaries of tools/pmc_r04.sh (one directory per kernel and workload):
 
 The record carries the SHA-256 of the kernel sources it was measured on; bench.py reports whether that still matches the
 tree (`pmc_fresh`) and tests/test_bench_record.py fails on a stale record, so a kernel change cannot leave old counters in
-the bench line unnoticed."""
+the bench line unnoticed.
+
+A change that leaves every kernel's code as it was (tools/device_code_diff.py says so) keeps the counters and takes the hash again:
+
+    python tools/pmc_record_r04.py --rehash [record.json]
+
+recomputes `source_sha256` over the record's own `sources` and leaves everything else in the file as it is."""
 import hashlib
 import json
 import os
@@ -14,18 +20,27 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["ec504_imageencoder_amd/csrc/m1v_kernels.hip", "ec504_imageencoder_amd/csrc/m1v_tiles.h",
-           "ec504_imageencoder_amd/csrc/m1v_size_table_body.h", "ec504_imageencoder_amd/csrc/m1v_assemble.h",
-           "ec504_imageencoder_amd/csrc/fdct_f32.h"]
+RECORD = os.path.join(ROOT, "profiles", "r04_pmc.json")
+SOURCES = ["ec504_imageencoder_amd/csrc/" + f for f in ("m1v_kernels.hip", "m1v_tiles.h", "m1v_planes.h", "m1v_encode_tile_body.h",
+                                                        "m1v_size_table_body.h", "m1v_assemble.h", "fdct_f32.h")]
 
 
-def source_sha256():
+def source_sha256(sources=SOURCES):
     """bench.py's own hash (over the sources without comments and whitespace differences), so that both sides agree."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return mod._pmc_sources_sha256(SOURCES)
+    return mod._pmc_sources_sha256(sources)
+
+
+def rehash(path=RECORD):
+    """Replaces the record's hash by the tree's over the record's own sources, in the text: nothing else in the file moves."""
+    text = open(path).read()
+    doc = json.loads(text)
+    old, new = doc["source_sha256"], source_sha256(doc["sources"])
+    open(path, "w").write(text.replace(f'"{old}"', f'"{new}"'))
+    print(f"{path}: source_sha256 {old} -> {new}" if old != new else f"{path}: source_sha256 {old} is current")
 
 
 def parse(path):
@@ -42,6 +57,8 @@ def parse(path):
 
 
 def main():
+    if sys.argv[1:2] == ["--rehash"]:
+        return rehash(*sys.argv[2:3])
     recs = []
     for d in sys.argv[1:]:
         m = re.search(r"pmc4_(\w+?)_(runs|tiles)_(\d+)x(\d+)(?:_n(\d+))?", os.path.basename(d.rstrip("/")))
@@ -66,7 +83,7 @@ def main():
                                "fetch_size_kib": asm.get("FETCH_SIZE"), "write_size_kib": asm.get("WRITE_SIZE"),
                                "insts_valu": int(asm["SQ_INSTS_VALU"]), "insts_salu": int(asm["SQ_INSTS_SALU"]), "waves": int(asm["SQ_WAVES"])}
         recs.append(rec)
-    out = os.path.join(ROOT, "profiles", "r04_pmc.json")
+    out = RECORD
     json.dump({"source_sha256": source_sha256(), "sources": SOURCES, "workloads": recs}, open(out, "w"), indent=1)
     print(open(out).read())
 
