@@ -1,0 +1,266 @@
+"""GPU tests of the entropy stage on hard content through every kernel family (-m gpu): the fused size tables (k_size_table_tiles,
+_rgba, _surface, _planes; narrow and wide staging), per-frame quality, the frame_sizes probe, the rate calls, and the surface
+and plane encode kernels, on the content of tests/hard_content.py — every run length, levels on both sides of every table row's
+end, 20- and 28-bit escapes, blocks of more than 64 and 128 bits (tests/test_hard_content_cpu.py pins that census).  The
+content of the other GPU test modules is noise, which codes little more than DC sizes.
+
+Every comparison is for equality with the CPU oracle (tests/plane_oracle.py for planes); every status word is 0.  Sizes are
+352x288 and, for a partial last tile column, 176x208.  The oracle's records are cached per module."""
+import numpy as np
+import pytest
+
+import hard_content as hc
+import plane_oracle
+from test_gpu_planes import _buffer, _layout, _oracle_on_buffer, _plane_encoder, _view, _write_planes
+from test_gpu_size_table import _frames, _table
+from test_gpu_surface import _encode, _frame_rule, _surface, _surface_encoder
+from test_rate_abi import batch_rule, cbr_rule
+
+pytestmark = pytest.mark.gpu
+
+Q = hc.ENCODER_Q
+FIRST = 17
+HARD3 = (0, 1, 2)             # sweep, heavy 10/130/0.4, heavy 16/120: encodable at every quality up to Q
+HARD4 = (0, 1, 2, 3)          # ... and the extreme-pattern frame, coded at 76 and 77 only
+RATE6 = (0, 4, 1, 5, 2, 6)    # hard and flat frames in turn
+SIZES = [(352, 288), (176, 208)]
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+# ---- content and the oracle's records, once per module ----------------------------------------------------------------------
+_content_cache = {}
+_record_cache = {}
+
+
+def _content(orc, kind, W, H):
+    """Seven frames: hard_frames / hard_planes 0..3, then three gentle ones (noise of amplitude 4, 40, 20 around mid-grey).
+    kind "rgb": [7, H, W, 3]; "rgba": the same pixels with noise in alpha; "planes": (Y, Cb, Cr)."""
+    key = (kind, W, H)
+    if key not in _content_cache:
+        rng = np.random.default_rng(W + H)
+        if kind == "planes":
+            Y, Cb, Cr = hc.hard_planes(orc, W, H)
+            gentle = [np.concatenate([_frames(rng, 1, w, h, 1, amp)[..., 0] for amp in (4, 40, 20)])
+                      for (w, h) in ((W, H), (W // 2, H // 2), (W // 2, H // 2))]
+            _content_cache[key] = tuple(np.concatenate([a, g]) for a, g in zip((Y, Cb, Cr), gentle))
+        else:
+            px = np.concatenate([hc.hard_frames(orc, W, H)] + [_frames(rng, 1, W, H, 3, amp) for amp in (4, 40, 20)])
+            if kind == "rgba":
+                px = np.concatenate([px, rng.integers(0, 256, px.shape[:3] + (1,), dtype=np.uint8)], -1)
+            _content_cache[key] = np.ascontiguousarray(px)
+    return _content_cache[key]
+
+
+def _record(orc, kind, W, H, c, q, index):
+    """The oracle's record of content frame c at quality q as frame `index` (raises where the frame is unencodable)."""
+    key = (kind, W, H, c, q, index)
+    if key not in _record_cache:
+        if kind == "planes":
+            Y, Cb, Cr = _content(orc, kind, W, H)
+            frame = np.concatenate([Y[c].reshape(-1), Cb[c].reshape(-1), Cr[c].reshape(-1)])
+            lay = dict(y_offset=0, cb_offset=W * H, cr_offset=W * H + W * H // 4, y_pitch=W, c_pitch=W // 2, c_step=1,
+                       frame_stride=frame.size)
+            _record_cache[key] = plane_oracle.encode_layout(frame, lay, W, H, index, q, orc.MODE_FULL)
+        else:
+            px = _content(orc, kind, W, H)
+            _record_cache[key] = orc.encode_frame(px[c], W, H, index, q, orc.MODE_FULL, channels=px.shape[-1])
+    return _record_cache[key]
+
+
+class _Case:
+    """One encoder of quality Q on one input family with a batch of content frames on the device.
+    family: "rgb" | "rgba" (packed, default layout) | "surface-<channels>-<order>-<layout>" | "planes-<layout>"."""
+
+    def __init__(self, torch, orc, family, W, H, ids, forced_runs=False):
+        from ec504_imageencoder_amd import Mpeg1Encoder
+        self.torch, self.orc, self.W, self.H, self.ids, self.n = torch, orc, W, H, tuple(ids), len(ids)
+        sel = list(ids)
+        n = self.n
+        if family.startswith("planes-"):
+            self.kind = "planes"
+            Y, Cb, Cr = _content(orc, "planes", W, H)
+            self.lay, self.base = _layout(family.split("-")[1], W, H)
+            self.buf = _buffer(torch, n, self.lay, self.base, fill_seed=len(family))
+            _write_planes(torch, self.buf, self.lay, self.base, Y[sel], Cb[sel], Cr[sel])
+            self.enc = _plane_encoder(W, H, Q, "full", n, self.lay)
+            self.dev = _view(torch, self.buf, n, self.lay, self.base, self.enc)
+        elif family.startswith("surface-"):
+            _, channels, order, layout = family.split("-")
+            self.kind = "rgb" if channels == "3" else "rgba"
+            px = _content(orc, self.kind, W, H)[sel]
+            self.dev, pitch, stride = _surface(torch, px, layout, order, fill_seed=len(family))
+            self.enc = _surface_encoder(W, H, Q, "full", int(channels), n, pitch, stride, order)
+        else:
+            self.kind = family
+            px = _content(orc, family, W, H)[sel]
+            self.dev = torch.from_numpy(px).cuda()
+            self.enc = Mpeg1Encoder(W, H, Q, "full", channels=px.shape[-1], max_frames=n)
+            if forced_runs:                       # the K-probe fallback: one run-kernel probe per quality
+                self.enc.debug_set_path("runs")
+                assert self.enc.path == "runs" and self.enc.size_table_fused == 0
+            else:                                 # README: 3 channels on the tile path and 4 channels always take the fused pass
+                assert self.enc.path == ("tiles" if family == "rgb" else "runs") and self.enc.size_table_fused == 1
+
+    def record(self, f, q):
+        return _record(self.orc, self.kind, self.W, self.H, self.ids[f], q, FIRST + f)
+
+    def sizes(self, q):
+        return [len(self.record(f, q)) for f in range(self.n)]
+
+    def records(self, qs):
+        recs = [self.record(f, q) for f, q in enumerate(qs)]
+        return b"".join(recs), [len(r) for r in recs]
+
+    def table(self, quals):
+        got, status = _table(self.torch, self.enc, self.dev, quals)
+        assert status == [0] * len(quals), (quals, status)
+        return got
+
+    def probe(self, qs):
+        st = self.torch.full((1,), 0x40, dtype=self.torch.int32, device="cuda")
+        sizes = self.enc.frame_sizes(self.dev, quality=qs, status=st)
+        self.enc.flush()
+        self.torch.cuda.synchronize()
+        assert int(st.cpu()[0]) == 0
+        return [int(s) for s in sizes.cpu()]
+
+    def close(self):
+        self.enc.close()
+
+
+TABLE_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "surface-3-rgb-odd", "planes-nv12", "planes-odd"]
+KERNEL_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12"]     # one per size-table kernel
+
+
+# ---- 1. size tables against the oracle --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("family", TABLE_FAMILIES)
+def test_size_tables_match_the_oracle(torch_cuda, orc, family, W, H):
+    """(20, 50, 76) takes the narrow kernel (qualities[-1] <= narrow_q = 76 for this matrix), K = 8 up to 92 the wide one; the
+    narrow call also carries the extreme-pattern frame (levels up to 115 in one byte)."""
+    case = _Case(torch_cuda, orc, family, W, H, HARD4)
+    assert case.table(hc.TABLE_NARROW) == [case.sizes(q) for q in hc.TABLE_NARROW]
+    if case.kind == "planes" and "odd" in family:       # the samples lie in the device buffer where the layout says
+        want = _oracle_on_buffer(orc, case.buf, case.n, case.lay, case.base, W, H, FIRST, [76] * case.n, orc.MODE_FULL)
+        assert want == [case.record(f, 76) for f in range(case.n)]
+    case.close()
+    case = _Case(torch_cuda, orc, family, W, H, HARD3)
+    assert case.table(hc.TABLE_WIDE) == [case.sizes(q) for q in hc.TABLE_WIDE]
+    case.close()
+
+
+# ---- 2. a row does not depend on its neighbours -----------------------------------------------------------------------------
+@pytest.mark.parametrize("family", KERNEL_FAMILIES)
+def test_a_row_does_not_depend_on_its_neighbours(torch_cuda, orc, family):
+    """The rows of 50 and 76 from the narrow kernel equal the same rows of a call that also asks for 77 (the wide kernel:
+    the extreme-pattern frame has levels of 128 and more there); both are the oracle's."""
+    W, H = 352, 288
+    case = _Case(torch_cuda, orc, family, W, H, HARD4)
+    narrow = case.table((20, 50, 76))
+    wide = case.table((20, 50, 76, 77))
+    assert narrow == wide[:3]
+    assert wide == [case.sizes(q) for q in (20, 50, 76, 77)]
+    assert case.table((50,)) == [wide[1]] and case.table((76, 77)) == wide[2:]
+    case.close()
+
+
+# ---- 3. the fused table equals the probes -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("family", KERNEL_FAMILIES)
+def test_fused_table_equals_the_probes(torch_cuda, orc, family):
+    """frame_size_table row k == frame_sizes(quality=[q_k] * n) on the same encoder, and — where the hook exists: packed 3 and
+    4 channels — the table of an encoder forced to the run kernels (size_table_fused == 0: one probe per quality)."""
+    W, H = 352, 288
+    case = _Case(torch_cuda, orc, family, W, H, HARD3)
+    table = case.table(hc.TABLE_WIDE)
+    for k, q in enumerate(hc.TABLE_WIDE):
+        assert case.probe([q] * case.n) == table[k], q
+    assert table == [case.sizes(q) for q in hc.TABLE_WIDE]
+    case.close()
+    if family in ("rgb", "rgba"):
+        forced = _Case(torch_cuda, orc, family, W, H, HARD3, forced_runs=True)
+        assert forced.table(hc.TABLE_WIDE) == table
+        forced.close()
+
+
+# ---- 4. encode, encode with per-frame quality, frame_sizes ------------------------------------------------------------------
+ENCODE_FAMILIES = (["rgb", "rgba"] + [f"surface-{c}-{o}-{l}" for c in (3, 4) for o in ("rgb", "bgr") for l in ("odd", "window")]
+                   + [f"planes-{l}" for l in ("i420", "nv12", "pitched", "odd")])
+QS_A = (92, 50, 76, 77)
+QS_B = (77, 92, 50, 76)
+
+
+def _encodes(torch, case3, case4):
+    assert _encode(torch, case3.enc, case3.dev, FIRST) == case3.records([Q] * case3.n)
+    for qs in (QS_A, QS_B):
+        assert _encode(torch, case4.enc, case4.dev, FIRST, quality=list(qs)) == case4.records(qs), qs
+        assert case4.probe(list(qs)) == case4.records(qs)[1], qs
+
+
+@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("family", ENCODE_FAMILIES)
+def test_encode_per_frame_quality_and_probe(torch_cuda, orc, family, W, H):
+    """Three hard frames at the encoder's quality 92, and four (with the extreme-pattern frame at 76 / 77) at qualities that
+    mix 50, 76, 77 and 92 in one batch; then the same with an 8-word LDS image and the worst-case arena reserved, which sends
+    every unit — blocks over 64 bits included — through the global-memory fallback."""
+    torch = torch_cuda
+    case3, case4 = _Case(torch, orc, family, W, H, HARD3), _Case(torch, orc, family, W, H, HARD4)
+    _encodes(torch, case3, case4)
+    for case in (case3, case4):
+        case.enc.debug_set_lds_words(8)
+        case.enc.reserve_scratch(True)
+    _encodes(torch, case3, case4)
+    for case in (case3, case4):
+        case.enc.debug_set_lds_words(0)
+        case.enc.reserve_scratch(False)
+    _encodes(torch, case3, case4)
+    case3.close()
+    case4.close()
+
+
+# ---- 5. the rate calls ------------------------------------------------------------------------------------------------------
+CANDS = (20, 50, 76, 85, 92)
+
+
+@pytest.mark.parametrize("family", ["rgb", "surface-4-bgr-gap", "planes-nv12"])
+def test_rate_calls(torch_cuda, orc, family):
+    """encode_to_budget, encode_to_batch_budget and a three-call chain of encode_at_bitrate on six frames, hard and flat in
+    turn: picks, sizes and bytes are the rules of tests/test_rate_abi.py on the oracle's sizes, with budgets taken from those
+    sizes so that the choice differs between frames."""
+    torch = torch_cuda
+    W, H = 352, 288
+    case = _Case(torch, orc, family, W, H, RATE6)
+    enc, dev, n = case.enc, case.dev, case.n
+    s = [case.sizes(c) for c in CANDS]
+
+    def want(pick):
+        return case.records([CANDS[k] for k in pick])
+
+    cap = sorted(s[2])[n // 2]                                     # the median size at candidate 76
+    pick, over = _frame_rule(s, cap)
+    assert len(set(pick)) > 1, pick
+    got, sizes, ch, ov = enc.encode_to_budget(dev, cap, CANDS, first_frame_index=FIRST)
+    assert (ch, ov, (got, sizes)) == ([CANDS[k] for k in pick], over, want(pick))
+
+    B = (sum(s[2]) + sum(s[3])) // 2
+    pick, over = batch_rule(s, B)
+    assert len(set(pick)) > 1 and not over, pick
+    got, sizes, ch, ov = enc.encode_to_batch_budget(dev, B, CANDS, first_frame_index=FIRST)
+    assert (ch, ov, (got, sizes)) == ([CANDS[k] for k in pick], over, want(pick))
+
+    r = sorted(s[2])[n // 2]
+    start = 2 * r
+    pick, over, lvl = cbr_rule(s, r, 2 * r, start)
+    assert len(set(pick)) > 1, pick
+    level = torch.full((1,), start, dtype=torch.int64, device="cuda")
+    parts = [enc.encode_at_bitrate(dev[a:a + 2], r, 2 * r, CANDS, level, first_frame_index=FIRST + a) for a in (0, 2, 4)]
+    assert int(level.cpu()[0]) == lvl
+    assert [c for p in parts for c in p[2]] == [CANDS[k] for k in pick]
+    assert [f + 2 * i for i, p in enumerate(parts) for f in p[3]] == over
+    assert (b"".join(p[0] for p in parts), [x for p in parts for x in p[1]]) == want(pick)
+    case.close()

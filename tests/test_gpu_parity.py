@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import golden_io as G
+# the hard-content generators live in tests/hard_content.py; tests/test_host_driver_cpu.py imports _heavy_picture from here
+from hard_content import _ZIGZAG, _emitted_levels, _heavy_picture, extreme_pattern_picture  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -506,44 +508,6 @@ def test_rgba_input(torch_cuda, orc):
     enc.close()
 
 
-_ZIGZAG = np.array([0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24,
-                    31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56,
-                    59, 61, 35, 36, 48, 49, 57, 58, 62, 63])
-
-
-def _heavy_picture(rng, W, H, npos, amp, big_fraction=0.0):
-    """Grey picture whose every 8x8 block is an inverse DCT of `npos` ISOLATED coefficients (odd zigzag
-    positions, so each has run >= 1 and VLC_encode never stops early) of magnitude up to `amp`:
-    long code sequences, table codes and 20-bit escapes.  A `big_fraction` of the blocks instead carries
-    ONE coefficient of magnitude 400..500 at zigzag position 1 or 3 (level >= 128 at qf 92: 28-bit escape)."""
-    from scipy.fft import idctn
-    inv = np.argsort(_ZIGZAG)
-    pic = np.zeros((H, W, 3), np.uint8)
-    for by in range(0, H, 8):
-        for bx in range(0, W, 8):
-            c = np.zeros(64)
-            c[0] = 8 * 128
-            if rng.random() < big_fraction:
-                c[inv[rng.choice([1, 3])]] = rng.choice([-1, 1]) * rng.uniform(400, 500)
-            else:
-                pos = rng.choice(np.arange(1, 64, 2), size=npos, replace=False)
-                c[inv[pos]] = rng.choice([-1, 1], npos) * rng.uniform(amp * 0.5, amp, npos)
-            g = np.clip(np.round(idctn(c.reshape(8, 8), norm="ortho")), 0, 255).astype(np.uint8)
-            pic[by:by + 8, bx:bx + 8, :] = g[..., None]
-    return pic
-
-
-def _emitted_levels(z):
-    """AC levels VLC_encode actually codes: up to the first non-zero whose predecessor is non-zero."""
-    out = []
-    for p in range(1, 64):
-        if z[p] != 0:
-            if z[p - 1] != 0:
-                break
-            out.append(int(z[p]))
-    return out
-
-
 @pytest.mark.parametrize("qf,npos,amp,big", [(12, 6, 700, 0.0), (50, 8, 300, 0.0), (90, 16, 120, 0.0), (92, 10, 130, 0.4)])
 def test_long_blocks_and_global_fallback(torch_cuda, orc, qf, npos, amp, big):
     """Blocks longer than 64 bits (register accumulator overflows -> second walk), 20- and 28-bit
@@ -585,18 +549,10 @@ def test_extreme_levels_at_the_narrow_staging_boundary(torch_cuda, orc, qf):
     coefficients and the smallest divisors exercise the largest levels either side of the switch."""
     torch = torch_cuda
     W, H = 256, 144
-    i, j = np.divmod(np.arange(64), 8)
-    pats = []
-    for (u, v) in ((0, 4), (4, 0), (4, 4), (0, 1), (1, 0), (7, 7)):
-        b = np.cos((2 * i + 1) * u * np.pi / 16) * np.cos((2 * j + 1) * v * np.pi / 16)
-        pats += [((b > 0) * 255).astype(np.uint8).reshape(8, 8), ((b < 0) * 255).astype(np.uint8).reshape(8, 8)]
     rng = np.random.default_rng(qf)
     pics = []
     for _ in range(3):
-        pic = np.zeros((H, W, 3), np.uint8)
-        for by in range(0, H, 8):
-            for bx in range(0, W, 8):
-                pic[by:by + 8, bx:bx + 8, :] = pats[rng.integers(len(pats))][..., None]
+        pic = extreme_pattern_picture(rng, W, H)
         try:
             orc.encode_frame(pic, W, H, 0, qf, orc.MODE_FULL)
             pics.append(pic)
