@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("EC504_LIBENCODER") or os.path.join(PKG_DIR, "libencod
 MODE_STRICT, MODE_FULL = 0, 1
 OK, E_ARG, E_UNENCODABLE, E_NOSPACE, E_HIP, E_NODEVICE, E_SCRATCH = 0, -1, -2, -3, -4, -5, -6
 STATUS_UNENCODABLE, STATUS_NOSPACE, STATUS_SCRATCH, STATUS_QUALITY, STATUS_OVER_BUDGET = 1, 2, 4, 8, 16
+STATUS_OVER_DISTORTION = 32
+RD_BEST_IN_BUDGET, RD_SMALLEST_AT_DISTORTION = 0, 1
 MAX_CANDIDATES = 8
 ORDER_RGB, ORDER_BGR = 0, 1
 PLANES_REFERENCE, PLANES_I420, PLANES_YV12, PLANES_NV12, PLANES_NV21 = 0, 1, 2, 3, 4
@@ -34,6 +36,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_frame_bound", "m1v_frame_bound_for", "m1v_frame_bytes_in", "m1v_file_prolog", "m1v_encode_device", "m1v_encode_host",
     "m1v_encode_planes_host", "m1v_encode_quality_device", "m1v_frame_sizes_device", "m1v_encode_budget_device",
     "m1v_frame_size_table_device", "m1v_encode_batch_budget_device", "m1v_encode_cbr_device",
+    "m1v_frame_rd_table_device", "m1v_encode_rd_device",
     "m1v_set_pipelined", "m1v_flush", "m1v_alloc_host", "m1v_free_host", "m1v_alloc_device", "m1v_free_device",
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
@@ -97,6 +100,11 @@ def lib():
     L.m1v_encode_cbr_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp,
                                         vp, C.c_size_t, vp, vp, vp, vp]
     L.m1v_encode_cbr_device.restype = C.c_int
+    L.m1v_frame_rd_table_device.argtypes = [vp, vp, C.c_int, _u8p, C.c_int, vp, vp, vp, vp]
+    L.m1v_frame_rd_table_device.restype = C.c_int
+    L.m1v_encode_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_uint64, vp, vp,
+                                       vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.m1v_encode_rd_device.restype = C.c_int
     L.m1v_set_pipelined.argtypes = [vp, C.c_int]
     L.m1v_set_pipelined.restype = C.c_int
     L.m1v_flush.argtypes = [vp, vp]

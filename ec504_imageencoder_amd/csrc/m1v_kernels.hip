@@ -36,6 +36,9 @@
 //                     at their final bit positions, frame headers, 16-bit length back-patch, trailer, sizes, status
 //   k_size_table_tiles, k_size_table_rgba   (m1v_tiles.h, m1v_size_table_body.h) record sizes at up to 8 qualities in one pass of the
 //                     tile workgroup, for 3- and 4-channel pictures; k_size_table_sizes writes them out
+//   k_rd_table_tiles, _rgba, _surface, _planes   (the same body with its distortion stage) the size table plus the exact
+//                     distortion of every frame at every quality; k_rd_table_sizes writes both out.  k_rd_pick picks a candidate
+//                     per frame by both (m1v_encode_rd_device)
 //   k_coefficients    FDCT+quant+zigzag only (BASELINE config 2)
 //   k_convert, k_subsample, k_synth   plane conversion / 4:2:0 / synthetic input
 //
@@ -1306,6 +1309,61 @@ __global__ __launch_bounds__(256) void k_frame_quality(QualityArgs a) {
     if (bits) atomicOr(a.status, bits);
 }
 
+// ---- rate-distortion picks (m1v_encode_rd_device) ------------------------------------------------------------------------------
+// k_rd_pick stands where k_frame_quality stands in a budget call: one lane per frame, between the rd table and the encode.  From
+// sizes / dist[k * stride + frame] it picks a candidate per frame by one of two rules (include/mpeg1_hip.h), writes the frame's
+// offset in rq_all, its quality (chosen, may be null) and the picked candidate's distortion (frame_dist, may be null), and ORs
+// M1V_STATUS_OVER_BUDGET / M1V_STATUS_OVER_DISTORTION into the batch's status word.  A candidate whose table status carries
+// M1V_STATUS_UNENCODABLE (its rows are undefined) is out of the running for every frame; with every candidate out the frames go
+// to candidate 0, whose encode reports the bit itself.
+struct RdPickArgs {
+    const unsigned long long *sizes, *dist;  // [k * stride + frame]
+    int stride, n_cand, n_frames;
+    uint8_t cand[kMaxCandidates];
+    int rule;                                // M1V_RD_BEST_IN_BUDGET, M1V_RD_SMALLEST_AT_DISTORTION
+    const unsigned long long *limits;        // [frame] per-frame limits, or null: `limit` for every frame
+    unsigned long long limit;
+    const uint32_t *table_status;            // [n_cand] status words of the rd table
+    uint32_t *qsel;                          // out: [frame] offset of the frame's entry in rq_all
+    uint8_t *chosen;                         // out (may be null): [frame] the quality picked
+    unsigned long long *frame_dist;          // out (may be null): [frame] the distortion at the pick
+    uint32_t *status;                        // the batch's status word
+};
+
+__global__ __launch_bounds__(256) void k_rd_pick(RdPickArgs a) {
+    const int f = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (f >= a.n_frames) return;
+    const bool by_bytes = a.rule == M1V_RD_BEST_IN_BUDGET;
+    const unsigned long long lim = a.limits ? a.limits[f] : a.limit;
+    // bound = what the limit bounds (bytes | distortion), other = what is minimised under it (distortion | bytes)
+    int pick = -1, least = -1;
+    unsigned long long pick_bound = 0, pick_other = 0, least_bound = 0, least_other = 0;
+    for (int k = 0; k < a.n_cand; k++) {
+        if (a.table_status[k] & (uint32_t)M1V_STATUS_UNENCODABLE) continue;
+        const unsigned long long s = a.sizes[(size_t)k * a.stride + f], d = a.dist[(size_t)k * a.stride + f];
+        const unsigned long long bound = by_bytes ? s : d, other = by_bytes ? d : s;
+        // within the limit: the least `other`, ties by the smaller `bound`, then the smaller k
+        if (bound <= lim && (pick < 0 || other < pick_other || (other == pick_other && bound < pick_bound))) {
+            pick = k;
+            pick_bound = bound;
+            pick_other = other;
+        }
+        // nothing within it: the least `bound`; ties by the smaller record (the distortion rule only), then the smaller k
+        if (least < 0 || bound < least_bound || (!by_bytes && bound == least_bound && other < least_other)) {
+            least = k;
+            least_bound = bound;
+            least_other = other;
+        }
+    }
+    uint32_t bits = 0;
+    if (pick < 0 && least >= 0) bits = by_bytes ? (uint32_t)M1V_STATUS_OVER_BUDGET : (uint32_t)M1V_STATUS_OVER_DISTORTION;
+    const int k = pick >= 0 ? pick : (least >= 0 ? least : 0);
+    a.qsel[f] = (uint32_t)(a.cand[k] - 1) * 64u;
+    if (a.chosen) a.chosen[f] = a.cand[k];
+    if (a.frame_dist) a.frame_dist[f] = a.dist[(size_t)k * a.stride + f];
+    if (bits) atomicOr(a.status, bits);
+}
+
 // ---- batch byte budgets and constant bitrate (m1v_encode_batch_budget_device, m1v_encode_cbr_device) ---------------------
 // k_rate_pick: ONE workgroup between the size table and the encode, on the caller's stream.  It picks a candidate per frame
 // from the table (sizes[k * stride + frame], k < n_cand, candidates' qualities strictly increasing) by one of two rules
@@ -1730,16 +1788,20 @@ struct m1v_encoder {
     // own quality, [max_frames]); the selection k_frame_quality writes; the budget call's probes ([kMaxCandidates][max_frames]
     // sizes, kMaxCandidates status words) and its choice when the caller does not want it
     float *d_rq_all = nullptr;
+    float *d_dq_all = nullptr;  // the divisors themselves, indexed as d_rq_all (the rd table's distortion stage)
     uint32_t *d_qsel_own = nullptr, *d_qsel = nullptr;
     unsigned long long *d_probe_sizes = nullptr;
+    unsigned long long *d_probe_dist = nullptr; // m1v_encode_rd_device: the distortions beside d_probe_sizes, same shape
     uint32_t *d_probe_status = nullptr;
     uint8_t *d_chosen = nullptr;
     uint32_t *d_pick_status = nullptr; // k_rate_pick's status word (batch-budget and bitrate calls)
     int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
-    // The size table's counters: k_size_table_tiles / k_size_table_rgba add, k_size_table_sizes reads and clears what it added.
+    // The size table's counters: the k_size_table_* / k_rd_table_* kernels add, k_size_table_sizes / k_rd_table_sizes reads and
+    // clears what they added.
     struct TableCounters {
         unsigned long long *strip_ctr = nullptr;   // [kMaxCandidates][max_frames][strip]
         unsigned long long *frame_bytes = nullptr; // [kMaxCandidates][max_frames]
+        unsigned long long *frame_dist = nullptr;  // [kMaxCandidates][max_frames] the rd table's distortion sums
         uint32_t *words = nullptr;                 // [kMaxCandidates] status words
         bool poisoned = false;                     // a call returned an error after its probe may have added: clear in full
     } table;
@@ -1942,7 +2004,7 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 
 // Every kernel that takes dynamic LDS: the launches pick from it (tile_variant, run_kernel) and m1v_create raises the limit of
 // each.  [narrow staging] last; a null entry is a variant that does not exist.
-//   tile[encode | size table][tile_variant()]: the tile-shaped kernels of every input layout
+//   tile[encode | size table | rd table][tile_variant()]: the tile-shaped kernels of every input layout
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
@@ -1953,14 +2015,16 @@ enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kTileVariants = kPl
      M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 1), M1V_PAIR(PLANES, M1V_TILE_RING, 1), \
      M1V_PAIR(PLANES, M1V_TILE_RING, 2)}
 static const struct Kernels {
-    const void *tile[2][kTileVariants][2];
+    const void *tile[3][kTileVariants][2];
     const void *dense[4][2];
     const void *strips[2][2];
 } kKernels = {
     // (packed 4-channel pictures encode on the run kernels)
     {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes),
      M1V_TILE_FAMILY(M1V_PAIR(k_size_table_tiles, M1V_TILE_RING), M1V_PAIR(k_size_table_rgba, M1V_TILE_RING), k_size_table_surface,
-                     k_size_table_planes)},
+                     k_size_table_planes),
+     M1V_TILE_FAMILY(M1V_PAIR(k_rd_table_tiles, M1V_TILE_RING), M1V_PAIR(k_rd_table_rgba, M1V_TILE_RING), k_rd_table_surface,
+                     k_rd_table_planes)},
     {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
      {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
      {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
@@ -2029,17 +2093,17 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
     a.tile_row_order = e->d_tile_order;
 }
 
-// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs; 1 = size table: their table
-// counterparts) over the grid fill_tile_grid set, with a wrapped for the layout in force
+// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs; 1 = size table, 2 = rd table: their
+// table counterparts) over the grid a's TileArgs / TableArgs carries (fill_tile_grid), with a wrapped for the layout in force
 template <typename Surface, typename Planes, typename Args>
-static int launch_tiles(m1v_encoder *e, int family, bool narrow, Args &a, size_t lds, hipStream_t st) {
+static int launch_tiles(m1v_encoder *e, int family, bool narrow, Args &a, size_t grid, size_t lds, hipStream_t st) {
     const m1v_encoder::Layout &l = e->layout;
     Surface on_surface = {a, l.frame_stride, l.row_pitch};
     // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
     Planes on_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride};
     void *arg = l.kind == LayoutKind::planes ? (void *)&on_planes
                 : l.kind == LayoutKind::surface ? (void *)&on_surface : (void *)&a;
-    return launch_profiled(e, kKernels.tile[family][tile_variant(e)][narrow ? 1 : 0], (size_t)a.n_frames * a.tiles_per_frame, kTileThreads,
+    return launch_profiled(e, kKernels.tile[family][tile_variant(e)][narrow ? 1 : 0], grid, kTileThreads,
                            arg, lds, st);
 }
 
@@ -2070,9 +2134,10 @@ static int hand_over(Args &a, m1v_encoder::Counters &cur, m1v_encoder::Counters 
 // One batch through the encode kernel of the encoder's plan.  qa == null: every frame at the encoder's own quality (the plain
 // path); otherwise k_frame_quality first writes the per-frame selection (into the batch's status word) from qa.  probe: the
 // counter hand-over ends in k_frame_sizes instead of k_assemble (record sizes and status only; d_out is not touched).
+// rd != null (and qa == null): k_rd_pick writes the selection from the rd table instead.
 static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, QualityArgs *qa, bool probe,
                         uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status,
-                        void *stream) {
+                        void *stream, RdPickArgs *rd = nullptr) {
     if (!e || (!d_rgb && n_frames > 0) || (!d_out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     hipStream_t st = (hipStream_t)stream;
@@ -2115,6 +2180,13 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         hipLaunchKernelGGL(k_frame_quality, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, *qa);
         HIP_TRY(hipGetLastError());
         qsel = e->d_qsel;
+    } else if (rd) {
+        rd->n_frames = n_frames;
+        rd->qsel = e->d_qsel;
+        rd->status = cur.words;
+        hipLaunchKernelGGL(k_rd_pick, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, *rd);
+        HIP_TRY(hipGetLastError());
+        qsel = e->d_qsel;
     }
     // the plan's producer kernel over n_frames
     const size_t grid = (size_t)n_frames * p.units;
@@ -2137,7 +2209,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        rc = launch_tiles<SurfaceArgs, PlaneArgs>(e, 0, e->narrow, a, p.lds_bytes, st);
+        rc = launch_tiles<SurfaceArgs, PlaneArgs>(e, 0, e->narrow, a, grid, p.lds_bytes, st);
     } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
@@ -2252,8 +2324,9 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
 // a surface layout, or k_size_table_planes on a plane layout, then k_size_table_sizes,
 // both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
 // sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
+// dist != null: the rd table (the k_rd_table_* kernels and k_rd_table_sizes in their places), dist[k * stride + frame] beside the sizes.
 static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
-                            unsigned long long *sizes, size_t stride, uint32_t *status, hipStream_t st) {
+                            unsigned long long *sizes, unsigned long long *dist, size_t stride, uint32_t *status, hipStream_t st) {
     HIP_TRY(hipSetDevice(e->device));
     m1v_encoder::TableCounters &tc = e->table;
     const Plan &p = e->plan;
@@ -2273,7 +2346,14 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     a.frame_bytes = tc.frame_bytes;
     a.status = tc.words;
     a.region = p.table_region;
-    if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs>(e, 1, qualities[n_q - 1] <= e->narrow_q, a, p.table_lds_bytes, st)) return rc;
+    const bool narrow = qualities[n_q - 1] <= e->narrow_q;
+    const size_t grid = (size_t)n_frames * p.table_units;
+    if (dist) {
+        RdTableArgs ra = {a, e->d_dq_all, tc.frame_dist};
+        if (const int rc = launch_tiles<SurfaceRdArgs, PlaneRdArgs>(e, 2, narrow, ra, grid, p.table_lds_bytes + kRdPartWords * 4, st)) return rc;
+    } else if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs>(e, 1, narrow, a, grid, p.table_lds_bytes, st)) {
+        return rc;
+    }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;
     TableSizesArgs sa;
     sa.n_frames = n_frames;
@@ -2284,7 +2364,12 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     sa.out_sizes = sizes;
     sa.stride = stride;
     sa.out_status = status;
-    hipLaunchKernelGGL(k_size_table_sizes, dim3((unsigned)n_frames, (unsigned)n_q), dim3(256), 0, st, sa);
+    if (dist) {
+        const RdSizesArgs rs = {sa, tc.frame_dist, dist};
+        hipLaunchKernelGGL(k_rd_table_sizes, dim3((unsigned)n_frames, (unsigned)n_q), dim3(256), 0, st, rs);
+    } else {
+        hipLaunchKernelGGL(k_size_table_sizes, dim3((unsigned)n_frames, (unsigned)n_q), dim3(256), 0, st, sa);
+    }
     HIP_TRY(hipGetLastError());
     if (fail_encode_at(3) != M1V_OK) return M1V_E_HIP;
     poison.flag = nullptr;

@@ -205,6 +205,19 @@ template <bool STAGE8, int R, int CSTEP>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_planes(PlaneTableArgs pa) {
     M1V_PLANE_INPUT;
     const TableArgs &a = pa.t;
+    M1V_SIZES_ONLY;
+#include "m1v_size_table_body.h"
+}
+
+struct PlaneRdArgs {
+    RdTableArgs t;
+    PlaneFrontArgs pl;
+    unsigned long long frame_stride;
+};
+template <bool STAGE8, int R, int CSTEP>
+__global__ __launch_bounds__(kTileThreads) void k_rd_table_planes(PlaneRdArgs pa) {
+    M1V_PLANE_INPUT;
+    M1V_RD_INPUT(pa.t);
 #include "m1v_size_table_body.h"
 }
 

@@ -141,12 +141,13 @@ static void counters_free(m1v_encoder::Counters &c) {
     (void)hipFree(c.words);
 }
 
-// The size table's counters: the same three (allocated by m1v_create, so not through plan_malloc)
+// The size table's counters: the same three and the rd table's distortion sums (allocated by m1v_create, so not through plan_malloc)
 static hipError_t table_clear(const m1v_encoder *e, hipStream_t st) {
     const m1v_encoder::TableCounters &t = e->table;
     const size_t kf = (size_t)kMaxCandidates * e->max_frames;
     hipError_t err = hipMemsetAsync(t.strip_ctr, 0, kf * e->g.n_strips * 8, st);
     if (err == hipSuccess) err = hipMemsetAsync(t.frame_bytes, 0, kf * 8, st);
+    if (err == hipSuccess) err = hipMemsetAsync(t.frame_dist, 0, kf * 8, st);
     if (err == hipSuccess) err = hipMemsetAsync(t.words, 0, kMaxCandidates * sizeof(uint32_t), st);
     return err;
 }
@@ -155,6 +156,7 @@ static hipError_t table_alloc(m1v_encoder *e) {
     const size_t kf = (size_t)kMaxCandidates * e->max_frames;
     hipError_t err = hipMalloc(&t.strip_ctr, kf * e->g.n_strips * 8);
     if (err == hipSuccess) err = hipMalloc(&t.frame_bytes, kf * 8);
+    if (err == hipSuccess) err = hipMalloc(&t.frame_dist, kf * 8);
     if (err == hipSuccess) err = hipMalloc(&t.words, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = table_clear(e, nullptr);
     return err == hipSuccess ? hipStreamSynchronize(nullptr) : err;
@@ -162,6 +164,7 @@ static hipError_t table_alloc(m1v_encoder *e) {
 static void table_free(m1v_encoder::TableCounters &t) {
     (void)hipFree(t.strip_ctr);
     (void)hipFree(t.frame_bytes);
+    (void)hipFree(t.frame_dist);
     (void)hipFree(t.words);
 }
 
@@ -374,14 +377,16 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     // Per-frame quality: the transposed reciprocal table of every quality ([100][64], frame_rq_t); Tables::rq_t is the row of the
     // encoder's own quality, Tables::rq that row in natural order
     const int own = encoder_quality(e);
-    std::vector<float> rq_all(100 * 64);
+    std::vector<float> rq_all(100 * 64), dq_all(100 * 64); // (dq_all: the divisors themselves, for the rd table)
     int min_ac = 0;
     for (int qf = 1; qf <= 100; qf++) {
         int q[64];
         scaled_matrix(qf, q);
         for (int u = 0; u < 8; u++)
-            for (int i = 0; i < 8; i++)
+            for (int i = 0; i < 8; i++) {
                 rq_all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)((1.0 / q[u * 8 + i]) * (1.0 + 1.0 / 1048576.0));
+                dq_all[(size_t)(qf - 1) * 64 + i * 8 + u] = (float)q[u * 8 + i];
+            }
         const int ac = *std::min_element(q + 1, q + 64);
         if (qf == own) min_ac = ac;
         if (ac >= 8) e->narrow_q = qf; // (the divisors shrink as the quality grows)
@@ -403,9 +408,11 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     hipError_t err = upload(&e->d_tab, t, 1);
     delete t;
     if (err == hipSuccess) err = upload(&e->d_rq_all, rq_all.data(), rq_all.size());
+    if (err == hipSuccess) err = upload(&e->d_dq_all, dq_all.data(), dq_all.size());
     if (err == hipSuccess) err = upload(&e->d_qsel_own, sel.data(), sel.size());
     if (err == hipSuccess) err = upload(&e->d_qsel, sel.data(), sel.size());
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc(&e->d_probe_dist, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
     if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
@@ -433,9 +440,11 @@ void m1v_destroy(m1v_encoder *e) {
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     (void)hipFree(e->d_tab);
     (void)hipFree(e->d_rq_all);
+    (void)hipFree(e->d_dq_all);
     (void)hipFree(e->d_qsel_own);
     (void)hipFree(e->d_qsel);
     (void)hipFree(e->d_probe_sizes);
+    (void)hipFree(e->d_probe_dist);
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
     (void)hipFree(e->d_pick_status);
@@ -749,7 +758,7 @@ static int check_candidate_call(const m1v_encoder *e, bool first, const uint8_t 
 static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
                       unsigned long long *sizes, size_t stride, uint32_t *status, void *stream) {
     if (e->plan.table_units)
-        return size_table_fused(e, d_rgb, n_frames, qualities, n_q, sizes, stride, status, (hipStream_t)stream);
+        return size_table_fused(e, d_rgb, n_frames, qualities, n_q, sizes, nullptr, stride, status, (hipStream_t)stream);
     for (int k = 0; k < n_q; k++) {
         QualityArgs qa = {};
         qa.uniform = qualities[k];
@@ -773,6 +782,42 @@ int m1v_frame_size_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_fram
     if (const int rc = check_candidate_call(e, d_sizes && (d_rgb || n_frames <= 0), qualities, n_qualities, n_frames, true)) return rc;
     if (n_frames == 0) return M1V_OK;
     return size_table(e, d_rgb, n_frames, qualities, n_qualities, (unsigned long long *)d_sizes, (size_t)n_frames, d_status, stream);
+}
+
+int m1v_frame_rd_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
+                              uint64_t *d_sizes, uint64_t *d_distortion, uint32_t *d_status, void *stream) {
+    if (const int rc = check_candidate_call(e, d_sizes && d_distortion && (d_rgb || n_frames <= 0), qualities, n_qualities, n_frames, true))
+        return rc;
+    if (!e->plan.table_units) return fail(M1V_E_ARG, "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s");
+    if (n_frames == 0) return M1V_OK;
+    return size_table_fused(e, d_rgb, n_frames, qualities, n_qualities, (unsigned long long *)d_sizes, (unsigned long long *)d_distortion,
+                            (size_t)n_frames, d_status, (hipStream_t)stream);
+}
+
+// One rd table into the encoder's own (d_probe_sizes, d_probe_dist, d_probe_status), then the encode with k_rd_pick in front of it
+int m1v_encode_rd_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                         const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, const uint64_t *d_limits,
+                         uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                         uint64_t *d_frame_distortion, uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
+    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
+    if (!e->plan.table_units) return fail(M1V_E_ARG, "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s");
+    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
+                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
+        return rc;
+    RdPickArgs ra = {};
+    ra.sizes = e->d_probe_sizes;
+    ra.dist = e->d_probe_dist;
+    ra.stride = e->max_frames;
+    ra.n_cand = n_candidates;
+    for (int k = 0; k < n_candidates; k++) ra.cand[k] = candidates[k];
+    ra.rule = rule;
+    ra.limits = (const unsigned long long *)d_limits;
+    ra.limit = limit;
+    ra.table_status = e->d_probe_status;
+    ra.chosen = d_chosen;
+    ra.frame_dist = (unsigned long long *)d_frame_distortion;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream, &ra);
 }
 
 int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,

@@ -2,6 +2,9 @@
 // (m1v_tiles.h), included inside each kernel.  In scope: STAGE8, R (template parameters), TableArgs a, and the input layout:
 // BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows); M1V_FRONT_HALF names the front half (as in
 // m1v_encode_tile_body.h).
+// RD (a constant in scope) = true makes it the body of the k_rd_table_* kernels: the same sizes plus the distortion of every
+// frame and quality into rd_dist[k][frame], with rd_dq = the divisors of every quality in the index order of rq_all (M1V_SIZES_ONLY
+// sets the three for the size-table kernels, whose code the RD statements leave as it was).
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const Geometry &g = a.g;
     const int tid = threadIdx.x;
@@ -11,6 +14,7 @@
     constexpr int kStride = STAGE8 ? kStageStride8 : kStageStride16;
     const uint32_t *vlc = lds + wave * kVlcWords;
     uint32_t *cnt = lds + kTableCnt;
+    [[maybe_unused]] uint32_t *rd_part = lds + kTableFixedWords + 3u * (a.region / 4u); // RD: [quality][wave] sums, behind the waves' regions
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds;
     const uint32_t region_off = (uint32_t)kTableFixedWords * 4u + (uint32_t)wave * a.region; // bytes from lds
 
@@ -60,6 +64,16 @@
 #pragma unroll
         for (int u = 0; u < 8; u++) coef[u * 8 + i] = c[u];
     }
+    // RD.  With t = l * d (what a decoder would put in the place of coefficient c), a position the record carries costs
+    // (c - t)^2 and any other position c^2, so  D(block) = sum of c^2 over all 64  -  sum of t * (2c - t) over the carried ones.
+    // Every fp32 value here is an exact integer: |c| <= 2040, l * d lies between 0 and c (truncating division), so
+    // 0 <= t * (2c - t) = c^2 - (c - t)^2 <= c^2 < 2^23, and every partial sum is at most the sum of c^2 of the block, which is
+    // below 2^24 (about the sum of the 64 squared pixels, <= 4.2 M).
+    [[maybe_unused]] float sumsq = 0.0f;
+    if constexpr (RD) {
+#pragma unroll
+        for (int t = 0; t < 64; t++) sumsq = __builtin_fmaf(coef[t], coef[t], sumsq);
+    }
     int j, m, blk;
     {
         int ln = lane;
@@ -101,6 +115,29 @@
         block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
         cnt[k * kTileThreads + e] = valid ? (uint32_t)bb.tot : 0u;
         bad_q |= (valid && bad) ? 1u << k : 0u;
+        if constexpr (RD) {
+            // a second pass over the coefficients in their registers (static indices): the level again, as quant() yields it
+            // (the same product, truncated), and the bit of the position in the set the record carries (DC + emit_set)
+            const M1V_CONST_AS float *dq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(rd_dq + a.qoff[k]));
+            const unsigned long long keep = emit_set(nz) | 1ull;
+            const uint32_t keep_lo = (uint32_t)keep, keep_hi = (uint32_t)(keep >> 32);
+            float gain = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int p = scan_pos(u * 8 + i);
+                    const float c = coef[u * 8 + i];
+                    const float t = __builtin_truncf(c * rq_t[i * 8 + u]) * dq_t[i * 8 + u];
+                    const float w = __builtin_fmaf(2.0f, c, -t);
+                    const int carried = (int)((p < 32 ? keep_lo : keep_hi) << (31 - (p & 31))) >> 31; // 0 or -1
+                    gain = __builtin_fmaf(__uint_as_float(__float_as_uint(t) & (uint32_t)carried), w, gain);
+                }
+            }
+            // lanes outside the picture ran on re-read bytes: they add nothing.  A wave's sum is below 64 * 2^24.
+            const uint32_t dw = wave_sum_u32(valid ? (uint32_t)(sumsq - gain) : 0u);
+            if (lane == 0) rd_part[k * 3 + wave] = dw;
+        }
     }
     lds_barrier();
 
@@ -120,6 +157,8 @@
                                                         (1ull << kCtrCountShift) | (unsigned long long)bits);
             if ((uint32_t)(before >> kCtrCountShift) == (uint32_t)a.tile_rows - 1u)
                 atomicAdd(&a.frame_bytes[kf], ((before & kCtrBitsMask) + bits + 7ull) >> 3);
+            if constexpr (RD)
+                if (jj == 0) atomicAdd(rd_dist + kf, (unsigned long long)rd_part[k * 3] + rd_part[k * 3 + 1] + rd_part[k * 3 + 2]);
         }
     }
     for (uint32_t b = bad_q; b; b &= b - 1u) atomicOr(&a.status[__builtin_ctz(b)], (uint32_t)M1V_STATUS_UNENCODABLE); // (rare)

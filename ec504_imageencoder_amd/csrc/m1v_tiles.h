@@ -460,6 +460,12 @@ struct TableArgs {
 // LDS words in front of the per-wave regions: one VLC table per wave, the bit counts [quality][block in emission order]
 constexpr int kTableCnt = 3 * kVlcWords, kTableFixedWords = kTableCnt + kMaxCandidates * kTileThreads;
 
+// what the body's distortion stage (the k_rd_table_* kernels below) reads, for the kernels that write sizes only
+#define M1V_SIZES_ONLY                                                                             \
+    constexpr bool RD = false;                                                                     \
+    constexpr const float *rd_dq = nullptr;                                                        \
+    constexpr unsigned long long *rd_dist = nullptr
+
 // The body of both kernels is csrc/m1v_size_table_body.h, included into each with BPP = the bytes per pixel of its input (a
 // shared inline function would do, but the compiler then numbers the registers of the 3-channel kernel differently: its
 // code stays the parent's instruction for instruction this way).
@@ -467,6 +473,7 @@ template <bool STAGE8, int R>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_tiles(TableArgs a) {
     constexpr int BPP = 3;
     M1V_PACKED_INPUT;
+    M1V_SIZES_ONLY;
 #include "m1v_size_table_body.h"
 }
 // The same for 4-channel pictures, whatever kernel encodes them: the table places no bits, so it does not have to share the
@@ -475,6 +482,7 @@ template <bool STAGE8, int R>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_rgba(TableArgs a) {
     constexpr int BPP = 4;
     M1V_PACKED_INPUT;
+    M1V_SIZES_ONLY;
 #include "m1v_size_table_body.h"
 }
 // The same on a window of a pitched surface (m1v_set_input_layout), the front half of k_encode_surface.
@@ -489,6 +497,7 @@ __global__ __launch_bounds__(kTileThreads) void k_size_table_surface(SurfaceTabl
     const TableArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
+    M1V_SIZES_ONLY;
 #include "m1v_size_table_body.h"
 }
 
@@ -509,6 +518,73 @@ __global__ __launch_bounds__(256) void k_size_table_sizes(TableSizesArgs a) {
     if (threadIdx.x == 0) {
         a.out_sizes[blockIdx.y * a.stride + blockIdx.x] = 48ull + a.frame_bytes[kf];
         a.frame_bytes[kf] = 0ull;
+        if (blockIdx.x == 0) {
+            if (a.out_status) a.out_status[blockIdx.y] = a.status[blockIdx.y];
+            a.status[blockIdx.y] = 0u;
+        }
+    }
+}
+
+// ---- the rate-distortion table (m1v_frame_rd_table_device): the size table plus the distortion of every frame at every quality ----
+// The size-table body with its distortion stage (RD): per quality a second statically unrolled pass over the 64 coefficients in
+// their registers, a sum per wave (DPP), a sum per tile in LDS (3 x kMaxCandidates words behind the waves' regions) and one
+// 64-bit atomic per tile and quality into frame_dist[k][frame].  The arguments wrap TableArgs, as SurfaceTableArgs does: the
+// kernarg layout of the size-table kernels stays as it is.
+struct RdTableArgs {
+    TableArgs t;
+    const float *dq_all;             // the divisors of every quality, in the index order of rq_all (exact small integers)
+    unsigned long long *frame_dist;  // [k][frame]: sum of the frame's block distortions
+};
+constexpr int kRdPartWords = 3 * kMaxCandidates; // LDS words of the per-wave sums
+#define M1V_RD_INPUT(ra)                                                                           \
+    constexpr bool RD = true;                                                                      \
+    const TableArgs &a = (ra).t;                                                                   \
+    const float *rd_dq = (ra).dq_all;                                                              \
+    unsigned long long *rd_dist = (ra).frame_dist
+
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void k_rd_table_tiles(RdTableArgs ra) {
+    constexpr int BPP = 3;
+    M1V_PACKED_INPUT;
+    M1V_RD_INPUT(ra);
+#include "m1v_size_table_body.h"
+}
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void k_rd_table_rgba(RdTableArgs ra) {
+    constexpr int BPP = 4;
+    M1V_PACKED_INPUT;
+    M1V_RD_INPUT(ra);
+#include "m1v_size_table_body.h"
+}
+struct SurfaceRdArgs {
+    RdTableArgs t;
+    unsigned long long frame_stride;
+    uint32_t row_pitch;
+};
+template <bool STAGE8, int R, int BPP, int ORDER>
+__global__ __launch_bounds__(kTileThreads) void k_rd_table_surface(SurfaceRdArgs sa) {
+    constexpr bool SURFACE = true;
+    const uint32_t row_pitch = sa.row_pitch;
+    const unsigned long long frame_stride = sa.frame_stride;
+    M1V_RD_INPUT(sa.t);
+#include "m1v_size_table_body.h"
+}
+
+// k_size_table_sizes for the rd table: sizes, distortions and status out, every counter the pass added to cleared
+struct RdSizesArgs {
+    TableSizesArgs s;
+    unsigned long long *frame_dist; // [k][frame]
+    unsigned long long *out_dist;   // out_dist[k * s.stride + frame]
+};
+__global__ __launch_bounds__(256) void k_rd_table_sizes(RdSizesArgs ra) {
+    const TableSizesArgs &a = ra.s;
+    const unsigned long long kf = (unsigned long long)blockIdx.y * (unsigned)a.n_frames + blockIdx.x;
+    for (int s = threadIdx.x; s < a.n_strips; s += 256) a.strip_ctr[kf * (unsigned)a.n_strips + s] = 0ull;
+    if (threadIdx.x == 0) {
+        a.out_sizes[blockIdx.y * a.stride + blockIdx.x] = 48ull + a.frame_bytes[kf];
+        ra.out_dist[blockIdx.y * a.stride + blockIdx.x] = ra.frame_dist[kf];
+        a.frame_bytes[kf] = 0ull;
+        ra.frame_dist[kf] = 0ull;
         if (blockIdx.x == 0) {
             if (a.out_status) a.out_status[blockIdx.y] = a.status[blockIdx.y];
             a.status[blockIdx.y] = 0u;

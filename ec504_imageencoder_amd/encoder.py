@@ -59,6 +59,24 @@ def surface_strides(shape, strides):
     return row_pitch, frame_stride
 
 
+def distortion_to_psnr(d, blocks):
+    """The distortion d of a frame of `blocks` blocks (Mpeg1Encoder.blocks_per_frame = strips * mb_rows * 6) as a PSNR in dB:
+    10 * log10(255^2 * 64 * blocks / d), the coefficient-domain squared error read as a pixel-domain one (the FDCT is scaled like
+    the orthonormal transform).  inf for d == 0.  Pure: no torch, no library."""
+    import math
+    if d < 0 or blocks <= 0:
+        raise ValueError("need d >= 0 and blocks > 0")
+    return math.inf if d == 0 else 10.0 * math.log10(255.0 ** 2 * 64 * blocks / d)
+
+
+def psnr_to_distortion(db, blocks):
+    """The largest integer distortion whose distortion_to_psnr is at least db (up to floating-point rounding of the power): the
+    ceiling a caller of Mpeg1Encoder.encode_to_distortion states in dB.  Pure."""
+    if blocks <= 0:
+        raise ValueError("need blocks > 0")
+    return int(255.0 ** 2 * 64 * blocks / 10.0 ** (db / 10.0))
+
+
 PLANE_LAYOUT_FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")
 
 
@@ -265,6 +283,26 @@ class Mpeg1Encoder:
         _call("m1v_frame_size_table_device", self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(status), _stream())
         return sizes[:len(qs) * n].view(len(qs), n)
 
+    def frame_rd_table(self, rgb, qualities, status=None):
+        """frame_size_table plus the distortion (include/mpeg1_hip.h, m1v_frame_rd_table_device): (sizes, distortion), two int64
+        CUDA tensors [K, n].  sizes is exactly frame_size_table(rgb, qualities); distortion[k, f] is the exact squared error, in the
+        reference's coefficient domain, between what the encoder transformed of frame f and what its record at qualities[k]
+        carries.  One fused pass; needs size_table_fused.  Asynchronous on torch's current stream.  status: as frame_size_table
+        (STATUS_UNENCODABLE at k: both rows k are undefined)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        qs = [int(q) for q in qualities]
+        if not 1 <= len(qs) <= _ffi.MAX_CANDIDATES or any(q < 1 or q > 255 for q in qs):
+            raise EncoderError(_ffi.E_ARG, "frame_rd_table: 1 to 8 qualities")
+        if status is not None:
+            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= len(qs), "status: CUDA int32, one per quality"
+        q_buf = (C.c_uint8 * len(qs))(*qs)
+        sizes = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
+        dist = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
+        _call("m1v_frame_rd_table_device", self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(dist), _ptr(status), _stream())
+        return sizes[:len(qs) * n].view(len(qs), n), dist[:len(qs) * n].view(len(qs), n)
+
     @staticmethod
     def _candidates(candidates, where):
         """1..8 candidate qualities as the HOST array the library reads (it checks order and range)."""
@@ -331,6 +369,59 @@ class Mpeg1Encoder:
         budgets = [budget] * n if d_budget is None else [int(x) for x in d_budget[:n].cpu()]
         over = [f for f in range(n) if sizes_l[f] > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
         return data, sizes_l, chosen_l, over
+
+    def _encode_rd(self, name, rule, rgb, limit, candidates, first_frame_index):
+        """The two rate-distortion encodes: (bytes, sizes, chosen, frames over their limit, distortion per frame)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        cand_buf = self._candidates(candidates, name)
+        if isinstance(limit, torch.Tensor):
+            assert limit.is_cuda and limit.dtype == torch.int64 and limit.numel() == n, "limit: CUDA int64, one per frame"
+            scalar, d_limits = 0, limit.contiguous()
+        elif isinstance(limit, numbers.Integral):
+            if not 0 <= int(limit) < 2 ** 64:
+                raise EncoderError(_ffi.E_ARG, f"{name}: the limit must fit uint64")
+            scalar, d_limits = int(limit), None
+        else:
+            b = [int(x) for x in limit]
+            assert len(b) == n, "limit: one entry per frame"
+            scalar, d_limits = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, name,
+            lambda out, sizes, meta: _call(
+                "m1v_encode_rd_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rule, scalar,
+                _ptr(d_limits), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist), *_meta_ptrs(meta), _stream()))
+        dist_l = [int(d) for d in dist[:n].cpu()]
+        limits = [scalar] * n if d_limits is None else [int(x) for x in d_limits[:n].cpu()]
+        bounded = sizes_l if rule == _ffi.RD_BEST_IN_BUDGET else dist_l
+        over = [f for f in range(n) if bounded[f] > limits[f]]  # (the rule's status bit is set iff there are any)
+        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], over, dist_l
+
+    def encode_best_in_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
+        """Synchronous: every frame at the candidate of LEAST DISTORTION among those whose record fits its budget (ties: the
+        smaller record, then the smaller quality), else at the candidate of smallest record.  encode_to_budget takes the largest
+        quality that fits, which in this encoder can be far from the best picture (include/mpeg1_hip.h, m1v_encode_rd_device).
+        max_frame_bytes: one budget for every frame, or one per frame (a sequence or a CUDA int64 tensor).  Candidates that cannot
+        be coded are skipped.  Returns (bytes, sizes, chosen, over_budget_frames, distortion)."""
+        return self._encode_rd("encode_best_in_budget", _ffi.RD_BEST_IN_BUDGET, rgb, max_frame_bytes, candidates, first_frame_index)
+
+    def encode_to_distortion(self, rgb, max_distortion, candidates, first_frame_index=0):
+        """Synchronous: every frame at the candidate of SMALLEST RECORD among those whose distortion (frame_rd_table's measure;
+        psnr_to_distortion states it in dB) is at most its ceiling (ties: the less distortion, then the smaller quality), else at
+        the candidate of least distortion.  max_distortion: one ceiling for every frame, or one per frame.  Returns
+        (bytes, sizes, chosen, over_distortion_frames, distortion)."""
+        return self._encode_rd("encode_to_distortion", _ffi.RD_SMALLEST_AT_DISTORTION, rgb, max_distortion, candidates, first_frame_index)
+
+    def distortion_to_psnr(self, d):
+        """A frame's distortion as a PSNR in dB (the module's distortion_to_psnr with this encoder's blocks_per_frame).  Pure."""
+        return distortion_to_psnr(d, self.blocks_per_frame)
+
+    def psnr_to_distortion(self, db):
+        """The distortion ceiling of a frame that a PSNR of db dB stands for (encode_to_distortion's max_distortion).  Pure."""
+        return psnr_to_distortion(db, self.blocks_per_frame)
 
     def encode_to_batch_budget(self, rgb, batch_bytes, candidates, first_frame_index=0):
         """Synchronous: the whole batch within batch_bytes (the sum of its records).  Every frame at one of two neighbouring

@@ -22,6 +22,9 @@
  *   m1v_frame_size_table_device / m1v_encode_batch_budget_device / m1v_encode_cbr_device
  *                              no reference counterpart: sizes at up to 8 qualities, a byte budget for a whole batch, a
  *                              constant bitrate through a leaky bucket
+ *   m1v_frame_rd_table_device / m1v_encode_rd_device
+ *                              no reference counterpart: the distortion beside the size at up to 8 qualities, and encodes that
+ *                              pick per frame by both
  *   m1v_set_pipelined / m1v_flush   no reference counterpart: overlap of one batch's gather with the next encode
  *   m1v_warm_up, m1v_alloc_host/_free_host   no reference counterpart: runtime start-up off the critical path, pinned buffers
  *   m1v_coefficients_device    fast_DCT + quantization + zigzag_scanning only (BASELINE config 2)
@@ -174,7 +177,8 @@ int m1v_encode_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int 
  *                             pointers let a failed or M1V_STATUS_SCRATCH call be repeated from the same level.  n_frames
  *                             == 0 writes *d_total = 0, *d_status = 0 and *d_level_out = min(*d_level_in, C).
  *                             Both: d_chosen (uint8[n_frames] on the device, may be NULL) receives the picked qualities.  A
- *                             rule assumes nothing about how size grows with quality.  The headers are those of every other
+ *                             rule assumes nothing about how size grows with quality (but "the largest that fits" assumes that
+ *                             the larger quality is the better picture: see m1v_encode_rd_device).  The headers are those of every other
  *                             call (the rule limits bytes; it signals nothing in the stream), and every record is that of the
  *                             frame at its picked quality.  One size table (m1v_frame_size_table_device), one pick kernel
  *                             (a single workgroup, k_rate_pick) and one encode, all on `stream`: the cost of
@@ -210,6 +214,58 @@ int m1v_encode_cbr_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, 
                           const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
                           uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                           uint32_t *d_status, void *stream);
+
+/* Distortion and rate-distortion picks.  The byte rules above take the LARGEST candidate that fits, which assumes that a larger
+ * quality factor gives a better picture.  In this encoder it need not: VLC_encode codes the AC levels of a block only up to the
+ * first non-zero level whose predecessor is non-zero too and drops the rest, and a finer quantiser makes that stop come earlier
+ * ("Distortion and rate-distortion picks": a smooth gradient loses 15 times more at quality 92 than at 38).  These two
+ * calls tell the caller, and pick by it.
+ *
+ * The measure, an exact integer.  For one block at one quality: c[p] the 64 unquantised coefficients in zigzag position (the
+ * reference's fast_DCT), d[p] the quality's divisors (scale_quantization_matrix), l[p] = c[p] / d[p] by C's truncating division
+ * (quantization), E = position 0 and the AC positions the record codes (the non-zero l[p], p >= 1, below the first p >= 1 with
+ * l[p] != 0 and l[p - 1] != 0):
+ *     D(block) = sum over p in E of (c[p] - l[p] * d[p])^2  +  sum over p not in E of c[p]^2
+ * and D(frame, quality) is the sum over every block the macroblock loops visit.  It is the squared error, in the reference's
+ * coefficient domain, between what the encoder transformed and what the record carries; that FDCT is scaled like the orthonormal
+ * one (DC = sum of the pixels / 8), so D tracks the squared error in the pixel domain.  An encoder-side measure: the library
+ * decodes nothing.
+ *
+ * m1v_frame_rd_table_device   m1v_frame_size_table_device plus the distortion: d_sizes[k * n_frames + f] is exactly what that call
+ *                             writes, d_distortion[k * n_frames + f] (uint64, on the device) = D(frame f, qualities[k]).
+ *                             d_status[k] as there (may be NULL); with M1V_STATUS_UNENCODABLE at k both rows of k are undefined,
+ *                             the other rows stay exact.  Qualities are checked as there; every input layout in force is
+ *                             served (packed 3 and 4 channels, surface, planes).  ONE pass of a fused kernel (the k_rd_table_*
+ *                             kernels: the size-table pass with a second sweep over the block's coefficients per quality; cost
+ *                             beside the size table: not measured yet, tools/rd_table_timing.py), on `stream`, no scratch, in
+ *                             pipelined mode too; m1v_profile_* counts it as one launch.  n_frames == 0 writes nothing.  An
+ *                             encoder whose size table is not fused (m1v_size_table_fused == 0: hook-forced only) returns
+ *                             M1V_E_ARG: there is no probe fallback for the distortion.  m1v_debug_fail_encode reaches its
+ *                             stages as those of the size table.
+ * m1v_encode_rd_device        one rd table over `candidates` (as m1v_encode_budget_device's), one pick kernel (k_rd_pick, a lane
+ *                             per frame) and one encode at the picked per-frame qualities, all on `stream` with no host wait.
+ *                             The limit of frame f is d_limits[f] (uint64[n_frames] on the device) or, when that is NULL, `limit`.
+ *                             A candidate whose table status carries M1V_STATUS_UNENCODABLE is out of the running for every
+ *                             frame; with every candidate out each frame goes to candidates[0] and the encode reports the bit.
+ *                             Among the others, with s = the record size and D = the distortion of the frame at a candidate:
+ *     M1V_RD_BEST_IN_BUDGET            of those with s <= limit the least D (ties: the smaller record, then the smaller k); if none
+ *                                      fits, the smallest record (ties: the smaller k) and M1V_STATUS_OVER_BUDGET.
+ *     M1V_RD_SMALLEST_AT_DISTORTION    of those with D <= limit the smallest record (ties: the less D, then the smaller k); if none
+ *                                      qualifies, the least D (ties: the smaller record, then the smaller k) and
+ *                                      M1V_STATUS_OVER_DISTORTION (output valid).
+ *                             d_chosen (uint8[n_frames]) and d_frame_distortion (uint64[n_frames], the picked candidate's D) may
+ *                             be NULL; the other outputs are m1v_encode_device's, and every record is that of the frame at its
+ *                             picked quality.  M1V_E_ARG before anything is launched: an unknown rule, bad candidates, n_frames >
+ *                             max_frames, a null d_rgb or d_out, an encoder whose size table is not fused.  A profiled call
+ *                             reports 2 launches. */
+enum { M1V_RD_BEST_IN_BUDGET = 0, M1V_RD_SMALLEST_AT_DISTORTION = 1 };
+enum { M1V_STATUS_OVER_DISTORTION = 32u };
+int m1v_frame_rd_table_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
+                              uint64_t *d_sizes, uint64_t *d_distortion, uint32_t *d_status, void *stream);
+int m1v_encode_rd_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                         const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, const uint64_t *d_limits,
+                         uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                         uint64_t *d_frame_distortion, uint64_t *d_total, uint32_t *d_status, void *stream);
 
 /* Input layout: frames that already live on the device as windows of pitched surfaces, in R,G,B(,A) or B,G,R(,A) byte order,
  * encoded where they lie (no compaction or swizzle copy in front of the encoder).
@@ -389,7 +445,8 @@ int m1v_synth_device(uint8_t *d_rgb, size_t bytes_per_frame, int n_frames, uint6
                      uint64_t first_frame_index, void *stream);
 
 /* Kernel timing by HIP events recorded on the launch stream around the dominant kernel
- * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles / k_size_table_rgba for a size-table pass;
+ * (k_encode_tiles; k_encode_dense / k_encode_strips on the run path; k_size_table_tiles / k_size_table_rgba for a size-table pass,
+ * the k_rd_table_* kernels for an rd-table pass;
  * k_encode_surface / k_size_table_surface on a surface layout).  enable!=0 starts collecting; m1v_profile_read synchronises the recorded events
  * and returns launches/total milliseconds since the last read. */
 int m1v_profile_enable(m1v_encoder *enc, int enable);
@@ -415,7 +472,7 @@ void m1v_debug_fail_alloc(int nth);
  * the internal counter set is chosen, before the encode kernel; 2 = after the encode kernel (and the run layout), before
  * the assembly; 3 = after the assembly, before the pipelined completion event.  One-shot; 0 = off.  Host side only: it
  * launches nothing and touches no device memory.  Inert unless the process runs with EC504_DEBUG_HOOKS=1.  A size-table pass
- * of the tile path (m1v_frame_size_table_device, m1v_encode_budget_device, m1v_encode_batch_budget_device, m1v_encode_cbr_device)
+ * of the tile path (m1v_frame_size_table_device, m1v_frame_rd_table_device, m1v_encode_rd_device, m1v_encode_budget_device, m1v_encode_batch_budget_device, m1v_encode_cbr_device)
  * reaches the stages as: 1 = before its probe kernel, 2 = after the probe kernel, before the sizes kernel, 3 = after the sizes
  * kernel. */
 void m1v_debug_fail_encode(int stage);
