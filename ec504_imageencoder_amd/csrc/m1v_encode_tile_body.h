@@ -70,8 +70,17 @@
         },
         rows, row_pitch);
     const M1V_CONST_AS float *rq_t = reinterpret_cast<const M1V_CONST_AS float *>(reinterpret_cast<uintptr_t>(frame_rq_t(a.rq_all, a.qsel, frame)));
-    // The lane's place in the tile, derived again behind the pixel stage (from an opaque copy of the lane id: five values
-    // less to carry through the stage, whose register budget decides the waves per SIMD)
+    // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
+    uint32_t *blkp = lds + region_off / 4u + lane * kStride;
+    uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)blkp;
+    TSTAMP(2);
+    unsigned long long nz_ac;
+    const int dc = columns_to_stage<STAGE8, kKeep>(rows, rq_t, lds_addr, nz_ac);
+    const unsigned long long nz = nz_ac | (dc != 0 ? 1ull : 0ull);
+    TSTAMP(3);
+    // The lane's place in the tile, derived again behind the pixel and column stages (from an opaque copy of the lane id, in a
+    // volatile statement, which stays behind the volatile wait of the staging: five values less to carry through the stages,
+    // whose register budget decides the waves per SIMD)
     int j, m, blk;
     {
         int ln = lane;
@@ -80,13 +89,6 @@
     }
     const bool valid = j < strips_here && m0 + m < g.n_mbrows;
     const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
-    // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
-    uint32_t *blkp = lds + region_off / 4u + lane * kStride;
-    uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)blkp;
-    TSTAMP(2);
-    const int dc = columns_to_stage<STAGE8, kKeep>(rows, rq_t, lds_addr);
-    const unsigned long long nz = (stage_nonzero_mask<STAGE8>(blkp, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
-    TSTAMP(3);
 
     // ---- entropy pass 1 (private: own staged levels, shared read-only VLC table) ----
     auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
@@ -108,7 +110,13 @@
     TSTAMP(5);
 
     // ---- every wave scans the 192 counts (emission order) itself: no second barrier ----
-    const uint32_t c0 = cnt[lane], c1 = cnt[64 + lane], c2 = cnt[128 + lane];
+    //      (the three reads and their wait in one statement, as the ring reads: one instruction less than three plain reads)
+    uint32_t c0;
+    unsigned long long c12;
+    asm volatile("ds_read_b32 %0, %2\n\tds_read2_b32 %1, %2 offset0:64 offset1:128\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(c0), "=&v"(c12)
+                 : "v"(lds0 + (uint32_t)(kTileCnt + lane) * 4u));
+    const uint32_t c1 = (uint32_t)c12, c2 = (uint32_t)(c12 >> 32);
     const uint32_t i0 = wave_scan_inclusive(c0), i1 = wave_scan_inclusive(c1), i2 = wave_scan_inclusive(c2);
     const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 63), t1 = (uint32_t)__builtin_amdgcn_readlane((int)i1, 63);
     G[lane] = i0 - c0;                 // all three waves store the same values: whichever lands last, a wave reads what

@@ -52,6 +52,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 #include <algorithm>
 #include <vector>
 
@@ -100,6 +101,8 @@ __host__ __device__ constexpr int scan_inv(int p) {
 // holds positions p and p+16.  The point of the layout: the "is this byte non-zero" flags of one word, computed for
 // all four bytes at once, land on zigzag positions that differ by 8, so ONE shift puts them in place in the 64-bit
 // non-zero mask (stage_nonzero_mask) — 1.25 instructions per coefficient instead of a compare, a select and an OR.
+// The run kernels fill the words with one LDS byte (halfword) store per level (block_to_stage) and read them back for the mask;
+// the tile kernels build the same words in registers and store them whole (StagePack, m1v_tiles.h).
 constexpr int kStageStride8 = 17, kStageStride16 = 33;
 __host__ __device__ constexpr int stage_byte8(int p) { return ((p & 7) + 8 * (p >> 5)) * 4 + ((p >> 3) & 3); }
 __host__ __device__ constexpr int stage_byte16(int p) { return ((p & 15) + 16 * (p >> 5)) * 4 + 2 * ((p >> 4) & 1); }

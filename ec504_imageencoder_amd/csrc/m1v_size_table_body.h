@@ -94,20 +94,13 @@
         // the staging stores (asm, chained through lds_addr) stay behind the previous quality's reads of the staged levels
         asm volatile("" : "+v"(lds_addr) : : "memory");
         int dc = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int q = quant(coef[u * 8 + i], rq_t[i * 8 + u]);
-                const int p = scan_pos(u * 8 + i);
-                if (p == 0) dc = q;
-                if (STAGE8)
-                    asm("ds_write_b8 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte8(p)));
-                else
-                    asm("ds_write_b16 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte16(p)));
-            }
-        }
-        const unsigned long long nz = (stage_nonzero_mask<STAGE8>(blkp, lds_addr) & ~1ull) | (dc != 0 ? 1ull : 0ull);
+        StagePack<STAGE8> pk; // the staging words in registers (m1v_tiles.h), levels in the order of the column pass
+        static_for<64>([&](auto N) {
+            constexpr int n = decltype(N)::value, i = n >> 3, u = n & 7;
+            dc |= pk.template level<n>(coef[u * 8 + i], rq_t[i * 8 + u], lds_addr);
+        });
+        pk.finish(lds_addr);
+        const unsigned long long nz = pk.mask_and_fence(lds_addr) | (dc != 0 ? 1ull : 0ull);
         uint32_t hdr = 0, bad = 0;
         int hlen = 0;
         BlockBits bb = {0, 0};

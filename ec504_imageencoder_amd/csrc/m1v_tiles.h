@@ -109,26 +109,167 @@ __device__ __forceinline__ Row32 ring_read32(uint32_t addr) {
     return v;
 }
 
-// column pass + quantise + stage in LDS (as block_to_stage's second half); returns the DC level
-template <bool STAGE8, int KEEP>
-__device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, const M1V_CONST_AS float *rq_t, uint32_t &lds_addr) {
-    int dc = 0;
+// ---- packed staging -----------------------------------------------------------------------------------------------------
+// The run kernels stage a block with one LDS byte (halfword) store per level and read the words back for the non-zero mask
+// (block_to_stage, stage_nonzero_mask).  The tile kernels build the same staging words in registers instead: every level
+// passes through one v_cvt_i32_f32 anyway, and as an SDWA instruction that conversion writes its result into byte k
+// (halfword k) of a register and leaves the other bytes as they are (dst_sel:BYTE_k dst_unused:UNUSED_PRESERVE; the first
+// write to a word takes UNUSED_PAD, which clears the rest: no register is initialised).  Packing so costs no vector
+// instruction, a finished word leaves as half of a ds_write2_b32, and the mask comes from the registers the lane holds.
+//
+// Levels are taken in the order of the column pass, n = 8 i + u (column i, row u of the coefficient matrix).  One asm
+// statement per level: the conversion of level n, then the quantiser multiply of level n + 1.  gfx950 wants one wait state
+// between a VALU write with a destination select and a VALU read of that register; inside asm nobody inserts it, so every
+// statement ends in an instruction without a destination select (the multiply; s_nop after the last level) and whatever the
+// compiler puts behind a statement is safe.  The statements are pure as far as the compiler knows (not volatile: the scalar
+// loads of the quantiser table stay scalar, m1v_kernels.hip block_to_stage); the word registers chain them.
+template <int... Is, typename F>
+__device__ __forceinline__ void static_for_each(std::integer_sequence<int, Is...>, F &&f) { (f(std::integral_constant<int, Is>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F &&f) { static_for_each(std::make_integer_sequence<int, N>{}, f); }
+
+template <bool STAGE8>
+struct StagePack {
+    static constexpr int kWords = STAGE8 ? 16 : 32, kParts = STAGE8 ? 4 : 2;
+    static constexpr int pos(int n) { return scan_pos((n & 7) * 8 + (n >> 3)); } // zigzag position of level n
+    static constexpr int word(int n) { return (STAGE8 ? stage_byte8(pos(n)) : stage_byte16(pos(n))) >> 2; }
+    static constexpr int part(int n) { return STAGE8 ? (stage_byte8(pos(n)) & 3) : ((stage_byte16(pos(n)) >> 1) & 1); }
+    // level 0 is the DC level (zigzag position 0): it stays in a register, its byte of word 0 stays zero
+    static constexpr bool first(int n) { // the first level written to its word
+        for (int k = 1; k < n; k++)
+            if (word(k) == word(n)) return false;
+        return true;
+    }
+    static constexpr int done(int w) { // the column whose levels complete word w
+        int last = 0;
+        for (int n = 1; n < 64; n++)
+            if (word(n) == w) last = n;
+        return last >> 3;
+    }
+    // Finished words leave in pairs, in the order they finish: member `which` of the k-th pair that is complete behind column
+    // `col`, or -1.  (The number of words is even, so no word is left over behind column 7.)
+    static constexpr int pair(int col, int k, int which) {
+        int held = -1;
+        for (int c = 0; c < 8; c++) {
+            int seen = 0;
+            for (int w = 0; w < kWords; w++) {
+                if (done(w) != c) continue;
+                if (held < 0) {
+                    held = w;
+                    continue;
+                }
+                if (c == col && seen == k) return which ? w : held;
+                seen++;
+                held = -1;
+            }
+        }
+        return -1;
+    }
+
+    uint32_t w[kWords];
+    float t; // the product of the level that is converted next
+
+    // level N into its word; `next` = coefficient x reciprocal of the level behind it
+    template <int N, bool LAST = false>
+    __device__ __forceinline__ void convert(float c_next, float rq_next) {
+        constexpr int W = word(N), P = part(N);
+        if constexpr (LAST) {
+            if constexpr (STAGE8)
+                asm("v_cvt_i32_f32_sdwa %0, %1 dst_sel:BYTE_%2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\ts_nop 0" : "+v"(w[W]) : "v"(t), "n"(P));
+            else
+                asm("v_cvt_i32_f32_sdwa %0, %1 dst_sel:WORD_%2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\ts_nop 0" : "+v"(w[W]) : "v"(t), "n"(P));
+        } else if constexpr (first(N)) { // (early clobber: the word may not take the register of c_next)
+            if constexpr (STAGE8)
+                asm("v_cvt_i32_f32_sdwa %0, %2 dst_sel:BYTE_%5 dst_unused:UNUSED_PAD src0_sel:DWORD\n\tv_mul_f32 %1, %4, %3"
+                    : "=&v"(w[W]), "=v"(t) : "v"(t), "v"(c_next), "s"(rq_next), "n"(P));
+            else
+                asm("v_cvt_i32_f32_sdwa %0, %2 dst_sel:WORD_%5 dst_unused:UNUSED_PAD src0_sel:DWORD\n\tv_mul_f32 %1, %4, %3"
+                    : "=&v"(w[W]), "=v"(t) : "v"(t), "v"(c_next), "s"(rq_next), "n"(P));
+        } else {
+            if constexpr (STAGE8)
+                asm("v_cvt_i32_f32_sdwa %0, %2 dst_sel:BYTE_%5 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\tv_mul_f32 %1, %4, %3"
+                    : "+v"(w[W]), "=v"(t) : "v"(t), "v"(c_next), "s"(rq_next), "n"(P));
+            else
+                asm("v_cvt_i32_f32_sdwa %0, %2 dst_sel:WORD_%5 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\tv_mul_f32 %1, %4, %3"
+                    : "+v"(w[W]), "=v"(t) : "v"(t), "v"(c_next), "s"(rq_next), "n"(P));
+        }
+    }
+    // Level N = 8 I + U arrives as coefficient c with its reciprocal rq: the level in front of it is converted (with N's multiply
+    // in the same statement), the words that column I - 1 completed leave once its last level is in.  Returns the DC level for
+    // N = 0, otherwise 0.
+    template <int N>
+    __device__ __forceinline__ int level(float c, float rq, uint32_t &lds_addr) {
+        if constexpr (N == 0) {
+            return quant(c, rq);
+        } else if constexpr (N == 1) {
+            t = c * rq;
+            return 0;
+        } else {
+            convert<N - 1>(c, rq);
+            if constexpr ((N & 7) == 0) store<(N >> 3) - 1>(lds_addr);
+            return 0;
+        }
+    }
+    __device__ __forceinline__ void finish(uint32_t &lds_addr) {
+        convert<63, true>(0.0f, 0.0f);
+        store<7>(lds_addr);
+    }
+    // the words complete behind column COL, two per LDS instruction, chained through the address register as the byte stores
+    // of the run kernels are
+    template <int COL, int K = 0>
+    __device__ __forceinline__ void store(uint32_t &lds_addr) {
+        constexpr int A = pair(COL, K, 0), B = pair(COL, K, 1);
+        if constexpr (A >= 0) {
+            asm("ds_write2_b32 %0, %1, %2 offset0:%3 offset1:%4" : "+v"(lds_addr) : "v"(w[A]), "v"(w[B]), "n"(A), "n"(B));
+            store<COL, K + 1>(lds_addr);
+        }
+    }
+    // stage_nonzero_mask on the registers (bit 0, the DC level's, is clear: the caller sets it), then the stores are waited
+    // for: the lane's LDS reads of its staged levels (fetch_level) come behind this statement, and so does every use of the
+    // mask, so the wait sits behind the mask arithmetic.
+    __device__ __forceinline__ unsigned long long mask_and_fence(uint32_t &lds_addr) const {
+        uint32_t half[2] = {0u, 0u};
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
+        for (int h = 0; h < 2; h++) {
+            if (STAGE8) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const uint32_t f = ((w[h * 8 + j] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w[h * 8 + j];
+                    half[h] |= (f >> (7 - j)) & (0x01010101u << j);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const uint32_t f = ((w[h * 16 + j] & 0x7fff7fffu) + 0x7fff7fffu) | w[h * 16 + j];
+                    half[h] |= (f >> (15 - j)) & (0x00010001u << j);
+                }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(half[0]), "+v"(half[1]), "+v"(lds_addr) : : "memory");
+        return ((unsigned long long)half[1] << 32) | half[0];
+    }
+};
+// (tests/test_stage_packing.py replays the whole plan; here only its first pair: the narrow form finishes no word before column 4)
+static_assert(StagePack<true>::pair(3, 0, 0) == -1 && StagePack<true>::pair(4, 0, 0) == 0 && StagePack<true>::pair(4, 0, 1) == 1, "narrow staging plan");
+
+// column pass + quantise + stage in LDS; returns the DC level, nz = the non-zero mask of the AC levels (bit 0 clear)
+template <bool STAGE8, int KEEP>
+__device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, const M1V_CONST_AS float *rq_t, uint32_t &lds_addr,
+                                                unsigned long long &nz) {
+    int dc = 0;
+    StagePack<STAGE8> pk;
+    static_for<8>([&](auto I) {
+        constexpr int i = decltype(I)::value;
         float c[8];
         m1vf::fdct_col_f<float>(rows.get(0, i), rows.get(1, i), rows.get(2, i), rows.get(3, i), rows.get(4, i), rows.get(5, i),
                                 rows.get(6, i), rows.get(7, i), c, i == 0 ? RowStore<KEEP>::kBias0 : 0.0f);
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int q = quant(c[u], rq_t[i * 8 + u]);
-            const int p = scan_pos(u * 8 + i);
-            if (p == 0) dc = q;
-            if (STAGE8)
-                asm("ds_write_b8 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte8(p)));
-            else
-                asm("ds_write_b16 %0, %1 offset:%2" : "+v"(lds_addr) : "v"(q), "n"(stage_byte16(p)));
-        }
-    }
+        static_for<8>([&](auto U) {
+            constexpr int u = decltype(U)::value;
+            dc |= pk.template level<i * 8 + u>(c[u], rq_t[i * 8 + u], lds_addr);
+        });
+    });
+    pk.finish(lds_addr);
+    nz = pk.mask_and_fence(lds_addr);
     return dc;
 }
 

@@ -12,7 +12,14 @@ A change that leaves every kernel's code as it was (tools/device_code_diff.py sa
 
     python tools/pmc_record_r04.py --rehash [record.json]
 
-recomputes `source_sha256` over the record's own `sources` and leaves everything else in the file as it is."""
+recomputes `source_sha256` over the record's own `sources` and leaves everything else in the file as it is.
+
+A change that leaves SOME kernels' code as it was (tools/device_code_diff.py names the ones that differ) measures the changed
+ones again and keeps the counters of the others:
+
+    python tools/pmc_record_r04.py --update OUT/pmc4_base_tiles_1920x1080 OUT/pmc4_base_tiles_3840x2160      (OUT: where tools/pmc_r04.sh wrote)
+
+replaces the workloads of the given directories (same kernel, width and height) in the record and takes the hash again."""
 import hashlib
 import json
 import os
@@ -56,34 +63,48 @@ def parse(path):
     return out
 
 
+def record_of(d):
+    m = re.search(r"pmc4_(\w+?)_(runs|tiles)_(\d+)x(\d+)(?:_n(\d+))?", os.path.basename(d.rstrip("/")))
+    if not m:
+        raise SystemExit(f"{d}: not a tools/pmc_r04.sh directory")
+    kernel = "k_encode_tiles" if m.group(2) == "tiles" else "k_encode_dense"
+    c = parse(os.path.join(d, "summary.txt")).get(kernel)
+    if not c:
+        raise SystemExit(f"{d}: no counters of {kernel}")
+    W, H = int(m.group(3)), int(m.group(4))
+    rec = {"kernel": kernel, "width": W, "height": H, "frames": 300, "fetch_size_kib": c["FETCH_SIZE"], "write_size_kib": c["WRITE_SIZE"],
+           "kernel_us_under_profiler": round(c["DURATION_NS"] / 1e3, 1), "l1_to_l2_read_requests": int(c["TCP_TCC_READ_REQ_sum"]),
+           "pixel_lines_128B": W * H * 3 * 300 // 128, "source_dir": os.path.basename(d.rstrip("/")),
+           "valu": {"insts_per_launch": int(c["SQ_INSTS_VALU"]), "simds": 1024,
+                    "clock_ghz": round(c["GRBM_GUI_ACTIVE"] / 8 / (c["DURATION_NS"] * 1e-9) / 1e9, 3),
+                    "source": "rocprofv3 --pmc SQ_INSTS_VALU (tools/pmc_r04.sh)"},
+           "waves": int(c["SQ_WAVES"]), "wave_quad_cycles": c["SQ_WAVE_CYCLES"], "wait_any_quad_cycles": c["SQ_WAIT_ANY"],
+           "ta_addr_stalled_by_tc_cycles": c["TA_ADDR_STALLED_BY_TC_CYCLES_sum"], "l2_hits": c["TCC_HIT_sum"], "l2_misses": c["TCC_MISS_sum"]}
+    asm = parse(os.path.join(d, "summary.txt")).get("k_assemble")
+    if asm:
+        rec["assemble"] = {"kernel": "k_assemble", "kernel_us_under_profiler": round(asm["DURATION_NS"] / 1e3, 1),
+                           "fetch_size_kib": asm.get("FETCH_SIZE"), "write_size_kib": asm.get("WRITE_SIZE"),
+                           "insts_valu": int(asm["SQ_INSTS_VALU"]), "insts_salu": int(asm["SQ_INSTS_SALU"]), "waves": int(asm["SQ_WAVES"])}
+    return rec
+
+
 def main():
     if sys.argv[1:2] == ["--rehash"]:
         return rehash(*sys.argv[2:3])
-    recs = []
-    for d in sys.argv[1:]:
-        m = re.search(r"pmc4_(\w+?)_(runs|tiles)_(\d+)x(\d+)(?:_n(\d+))?", os.path.basename(d.rstrip("/")))
-        if not m:
-            raise SystemExit(f"{d}: not a tools/pmc_r04.sh directory")
-        kernel = "k_encode_tiles" if m.group(2) == "tiles" else "k_encode_dense"
-        c = parse(os.path.join(d, "summary.txt")).get(kernel)
-        if not c:
-            raise SystemExit(f"{d}: no counters of {kernel}")
-        W, H = int(m.group(3)), int(m.group(4))
-        rec = {"kernel": kernel, "width": W, "height": H, "frames": 300, "fetch_size_kib": c["FETCH_SIZE"], "write_size_kib": c["WRITE_SIZE"],
-               "kernel_us_under_profiler": round(c["DURATION_NS"] / 1e3, 1), "l1_to_l2_read_requests": int(c["TCP_TCC_READ_REQ_sum"]),
-               "pixel_lines_128B": W * H * 3 * 300 // 128, "source_dir": os.path.basename(d.rstrip("/")),
-               "valu": {"insts_per_launch": int(c["SQ_INSTS_VALU"]), "simds": 1024,
-                        "clock_ghz": round(c["GRBM_GUI_ACTIVE"] / 8 / (c["DURATION_NS"] * 1e-9) / 1e9, 3),
-                        "source": "rocprofv3 --pmc SQ_INSTS_VALU (tools/pmc_r04.sh)"},
-               "waves": int(c["SQ_WAVES"]), "wave_quad_cycles": c["SQ_WAVE_CYCLES"], "wait_any_quad_cycles": c["SQ_WAIT_ANY"],
-               "ta_addr_stalled_by_tc_cycles": c["TA_ADDR_STALLED_BY_TC_CYCLES_sum"], "l2_hits": c["TCC_HIT_sum"], "l2_misses": c["TCC_MISS_sum"]}
-        asm = parse(os.path.join(d, "summary.txt")).get("k_assemble")
-        if asm:
-            rec["assemble"] = {"kernel": "k_assemble", "kernel_us_under_profiler": round(asm["DURATION_NS"] / 1e3, 1),
-                               "fetch_size_kib": asm.get("FETCH_SIZE"), "write_size_kib": asm.get("WRITE_SIZE"),
-                               "insts_valu": int(asm["SQ_INSTS_VALU"]), "insts_salu": int(asm["SQ_INSTS_SALU"]), "waves": int(asm["SQ_WAVES"])}
-        recs.append(rec)
     out = RECORD
+    if sys.argv[1:2] == ["--update"]:
+        doc = json.load(open(out))
+        for rec in (record_of(d) for d in sys.argv[2:]):
+            key = lambda r: (r["kernel"], r["width"], r["height"], r["frames"])
+            at = [i for i, r in enumerate(doc["workloads"]) if key(r) == key(rec)]
+            if not at:
+                raise SystemExit(f"{rec['source_dir']}: the record has no such workload")
+            doc["workloads"][at[0]] = rec
+        doc["source_sha256"] = source_sha256(doc["sources"])
+        json.dump(doc, open(out, "w"), indent=1)
+        print(open(out).read())
+        return
+    recs = [record_of(d) for d in sys.argv[1:]]
     json.dump({"source_sha256": source_sha256(), "sources": SOURCES, "workloads": recs}, open(out, "w"), indent=1)
     print(open(out).read())
 
