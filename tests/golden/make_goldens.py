@@ -5,7 +5,8 @@
 Everything written here is DATA: inputs (pixels as decoded by the reference's stb_image, blocks,
 coefficient arrays) and the outputs the reference produced for them.  No reference source text.
 
-    python tests/golden/make_goldens.py
+    python tests/golden/make_goldens.py              (everything)
+    python tests/golden/make_goldens.py code_space   (only vlc_code_space.json)
 """
 import hashlib
 import json
@@ -91,8 +92,22 @@ def save_e2e(name, res, extra=None):
     print(name, {k: (v.shape if hasattr(v, "shape") else v) for k, v in d.items() if k.startswith("mpeg")})
 
 
+def code_space_goldens():
+    """vlc_code_space.json: the reference's block bits over tests/code_space.exhaustive_groups, one SHA-256 per group."""
+    import code_space as cs
+    groups = cs.exhaustive_groups()
+    json.dump({"order": "per group: the bit strings of ref_ffi.block_bits(is_luma, z) in the order of "
+                        "tests/code_space.exhaustive_groups, joined by newlines",
+               "blocks": sum(len(b) for b in groups.values()),
+               "sha256": {name: cs.group_digest(ref.block_bits, blocks) for name, blocks in groups.items()}},
+              open(os.path.join(HERE, "vlc_code_space.json"), "w"), indent=1)
+
+
 def main():
     assert ref.ensure_built(), "reference sources not available"
+    if sys.argv[1:] == ["code_space"]:          # only tests/golden/vlc_code_space.json
+        code_space_goldens()
+        return
     rng = np.random.default_rng(504)
 
     # 1. block-level known answers: u8 block -> FDCT -> quantise+zigzag (qf 12/50/100) -> block bits
@@ -211,6 +226,9 @@ def main():
 
     # 9. one 1080p picture (BASELINE configs 1-2 geometry), STRICT and FULL
     save_e2e("e2e_1080p.npz", run_folder(smooth_frames(rng, 1, 1920, 1080, amp=2), [12], ["strict", "full"], jpeg_quality=50))
+
+    # 10. the whole code space of the block coder, as hashes
+    code_space_goldens()
 
     for f in sorted(os.listdir(HERE)):
         print(f"{os.path.getsize(os.path.join(HERE, f)):>10}  {f}")

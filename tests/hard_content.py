@@ -10,7 +10,7 @@ more than 128 bits.
   _heavy_picture, _emitted_levels, _ZIGZAG   the generator of tests/test_gpu_parity.py (moved here unchanged)
   extreme_pattern_picture                    the sign patterns of test_extreme_levels_at_the_narrow_staging_boundary
   sweep_picture, plane_sweep                 one isolated coefficient per block, position and level cycling (below)
-  census                                     the reference's walk of a set of zigzag blocks, counted
+  coded_pairs, census                        the reference's walk of one zigzag block; of a set of blocks, counted
 
 A DC level of 0 changes the first run (`prev = -1` in block_bits_pass1), so sweep pictures also carry blocks of a few lit
 pixels on black.  Such a block never codes an AC level, though: a block of pixel sum S has DC coefficient (S + 16) >> 3, which
@@ -296,6 +296,22 @@ def _ac_bits(orc, r, level):
     return _code_len[key]
 
 
+def coded_pairs(z):
+    """The reference's walk of one zigzag block: [(run - 1, level)] behind the DC, or from position 0 when the DC level is 0,
+    up to the first non-zero level without a zero before it."""
+    zeros = 0 if z[0] != 0 else 1
+    mine = []
+    for p in range(1, 64):
+        if z[p] == 0:
+            zeros += 1
+            continue
+        if zeros == 0:
+            break
+        mine.append((zeros - 1, int(z[p])))
+        zeros = 0
+    return mine
+
+
 def census(orc, coefficients, is_luma=None):
     """What the reference codes of zigzag blocks [n, 64].  is_luma: one flag for all blocks, or None for the macroblock order
     of orc.frame_coefficients (four luma blocks, then Cb and Cr).  The walk is the reference's: (level, zeros before it)
@@ -315,16 +331,7 @@ def census(orc, coefficients, is_luma=None):
         luma = (i % 6) < 4 if is_luma is None else bool(is_luma)
         rc, s = orc.encode_block_bits(luma, z)
         assert rc == 0, f"census: block {i} is unencodable"
-        zeros = 0 if z[0] != 0 else 1
-        mine = []
-        for p in range(1, 64):
-            if z[p] == 0:
-                zeros += 1
-                continue
-            if zeros == 0:
-                break
-            mine.append((zeros - 1, int(z[p])))
-            zeros = 0
+        mine = coded_pairs(z)
         total = _dc_bits(orc, luma, z[0]) + 2
         for r, level in mine:
             n = _ac_bits(orc, r, level)

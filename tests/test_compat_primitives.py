@@ -102,6 +102,32 @@ def test_block_chain_matches_the_oracle(lib, orc):
                 assert "".join(f"{x:08b}" for x in raw)[:n] == want
 
 
+def test_block_coder_over_the_whole_code_space(lib, orc):
+    """run_length_encode -> encode_block_header_i -> encode_block_end through the shim over tests/code_space.exhaustive_groups:
+    every run row with every level -255..255 behind a DC level of 1 and of 0, every DC level -2042..2042, luma and chroma.  The
+    shim's own copy of the 110-entry table, its escapes and its DC size tables give the oracle's bits, entry by entry."""
+    import code_space as cs
+    lib.bitvector_new.restype = C.POINTER(BitVector)
+    lib.bitvector_new.argtypes = [C.c_char_p, C.c_longlong]
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    pairs = np.zeros(136, np.int32)
+    for name, blocks in cs.exhaustive_groups().items():
+        for luma, zz in blocks:
+            rc, want = orc.encode_block_bits(luma, zz)
+            assert rc == 0
+            lib.run_length_encode(zz.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p))
+            bv = lib.bitvector_new(b"", 8)
+            lib.encode_block_header_i(luma, pairs.ctypes.data_as(C.c_void_p), bv)
+            lib.encode_block_end(bv)
+            n = bv.contents.cap
+            raw = C.string_at(bv.contents.value, (n + 7) // 8)
+            got = "".join(f"{x:08b}" for x in raw)[:n]
+            libc.free(C.cast(bv.contents.value, C.c_void_p))
+            libc.free(C.cast(bv, C.c_void_p))
+            assert got == want, (name, "luma" if luma else "chroma", "levels", zz[zz != 0].tolist(), got, want)
+
+
 @pytest.mark.reference
 def test_reference_main_object_links_and_matches(ref, lib, tmp_path):
     """main.o built from the reference's main.c AND the reference's header by `make -C oracle _ref` (the driver is inside main.o and needs

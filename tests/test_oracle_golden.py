@@ -41,6 +41,23 @@ def test_kat_vlc(orc):
             assert orc.encode_block_bits(luma, zz[i]) == (0, want[i]), (name, i)
 
 
+def test_vlc_code_space(orc):
+    """The reference's bits for every run row x level x sign (behind a DC level of 1 and of 0) and for every DC level, luma and
+    chroma, as one SHA-256 per group (tests/code_space.exhaustive_groups): pins the oracle's 110-entry table, its escapes and
+    its DC size tables entry by entry where the reference is absent."""
+    import code_space as cs
+    want = G.load_json("vlc_code_space.json")["sha256"]
+    groups = cs.exhaustive_groups()
+    assert sorted(want) == sorted(groups)
+
+    def bits(is_luma, z):
+        rc, s = orc.encode_block_bits(is_luma, z)
+        assert rc == 0, (is_luma, z)
+        return s
+    wrong = [name for name, blocks in groups.items() if cs.group_digest(bits, blocks) != want[name]]
+    assert not wrong, wrong
+
+
 def test_qmatrix(orc):
     qm = np.load(G.GOLDEN + "/qmatrix.npy")
     for k, qf in enumerate(range(-1, 103)):

@@ -139,6 +139,19 @@ def test_block_bits_vs_reference(ref, orc):
             assert mine == ref.block_bits(is_luma, z), (is_luma, z)
 
 
+def test_block_bits_over_the_whole_code_space(ref, orc):
+    """tests/code_space.exhaustive_groups: every run row with every level -255..255 behind a non-zero DC and behind a DC
+    level of 0, and every DC level -2042..2042, as luma and as chroma — about 130,000 blocks, each compared bit for bit.
+    tests/golden/vlc_code_space.json records the reference's side of this for machines without it."""
+    import code_space as cs
+    for name, blocks in cs.exhaustive_groups().items():
+        for is_luma, z in blocks:
+            rc, mine = orc.encode_block_bits(is_luma, z)
+            assert rc == 0, (name, is_luma, z[0], np.flatnonzero(z[1:]) + 1, z[z != 0])
+            theirs = ref.block_bits(is_luma, z)
+            assert mine == theirs, (name, "luma" if is_luma else "chroma", "levels", z[z != 0].tolist(), mine, theirs)
+
+
 def test_block_bits_known_answers(orc):
     # SURVEY §8(a) rows 10-11 (captured from the reference): bits before the EOB "10"
     def dc(v, luma=1):
