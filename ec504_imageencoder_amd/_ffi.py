@@ -37,6 +37,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_encode_planes_host", "m1v_encode_quality_device", "m1v_frame_sizes_device", "m1v_encode_budget_device",
     "m1v_frame_size_table_device", "m1v_encode_batch_budget_device", "m1v_encode_cbr_device",
     "m1v_frame_rd_table_device", "m1v_encode_rd_device",
+    "m1v_encode_rd_batch_device", "m1v_encode_rd_cbr_device", "m1v_rd_batch_pick_device", "m1v_rd_cbr_pick_device",
     "m1v_set_pipelined", "m1v_flush", "m1v_alloc_host", "m1v_free_host", "m1v_alloc_device", "m1v_free_device",
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
@@ -105,6 +106,16 @@ def lib():
     L.m1v_encode_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_uint64, vp, vp,
                                        vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.m1v_encode_rd_device.restype = C.c_int
+    L.m1v_encode_rd_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.c_uint64, vp,
+                                             vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.m1v_encode_rd_batch_device.restype = C.c_int
+    L.m1v_encode_rd_cbr_device.argtypes = [vp, vp, C.c_int, C.c_int, _u8p, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp,
+                                           vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.m1v_encode_rd_cbr_device.restype = C.c_int
+    L.m1v_rd_batch_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp]
+    L.m1v_rd_batch_pick_device.restype = C.c_int
+    L.m1v_rd_cbr_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp]
+    L.m1v_rd_cbr_pick_device.restype = C.c_int
     L.m1v_set_pipelined.argtypes = [vp, C.c_int]
     L.m1v_set_pipelined.restype = C.c_int
     L.m1v_flush.argtypes = [vp, vp]

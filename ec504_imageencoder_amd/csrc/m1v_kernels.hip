@@ -1530,6 +1530,8 @@ __global__ __launch_bounds__(kPickThreads) void k_rate_pick(PickArgs a) {
     }
 }
 
+#include "m1v_rd_rate.h"
+
 // The probe's place of k_assemble (one workgroup per frame): each record's size (its strips' bytes + 48 bytes of headers and
 // trailer, what k_assemble derives) and the status word, and the same counter hand-over — the set the next call adds into is
 // cleared for the frames this launch reaches (the host clears the rest).  Nothing is assembled, nothing written to d_out.
@@ -1798,6 +1800,7 @@ struct m1v_encoder {
     uint32_t *d_probe_status = nullptr;
     uint8_t *d_chosen = nullptr;
     uint32_t *d_pick_status = nullptr; // k_rate_pick's status word (batch-budget and bitrate calls)
+    RdStep *d_rd_steps = nullptr;      // k_rd_chains' step table [max_frames][kMaxCandidates] (m1v_encode_rd_batch_device, m1v_rd_batch_pick_device)
     int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
     // The size table's counters: the k_size_table_* / k_rd_table_* kernels add, k_size_table_sizes / k_rd_table_sizes reads and
     // clears what they added.
@@ -2138,9 +2141,10 @@ static int hand_over(Args &a, m1v_encoder::Counters &cur, m1v_encoder::Counters 
 // path); otherwise k_frame_quality first writes the per-frame selection (into the batch's status word) from qa.  probe: the
 // counter hand-over ends in k_frame_sizes instead of k_assemble (record sizes and status only; d_out is not touched).
 // rd != null (and qa == null): k_rd_pick writes the selection from the rd table instead.
+// rb != null (with qa): k_rd_batch_pick first writes the qualities qa reads; the batch's status word is known only here.
 static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, QualityArgs *qa, bool probe,
                         uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status,
-                        void *stream, RdPickArgs *rd = nullptr) {
+                        void *stream, RdPickArgs *rd = nullptr, RdBatchArgs *rb = nullptr) {
     if (!e || (!d_rgb && n_frames > 0) || (!d_out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     hipStream_t st = (hipStream_t)stream;
@@ -2175,6 +2179,12 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     PoisonOnReturn poison{&bt.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
     const uint32_t *qsel = e->d_qsel_own;
+    if (rb) {
+        rb->batch_status = cur.words;
+        hipLaunchKernelGGL(k_rd_batch_pick, dim3((unsigned)((n_frames * kMaxCandidates + kRdPickThreads - 1) / kRdPickThreads)),
+                           dim3(kRdPickThreads), 0, st, *rb);
+        HIP_TRY(hipGetLastError());
+    }
     if (qa) {
         qa->max_q = encoder_quality(e);
         qa->n_frames = n_frames;

@@ -413,6 +413,7 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (err == hipSuccess) err = upload(&e->d_qsel, sel.data(), sel.size());
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_dist, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc(&e->d_rd_steps, (size_t)kMaxCandidates * max_frames * sizeof(RdStep));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
     if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
@@ -445,6 +446,7 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipFree(e->d_qsel);
     (void)hipFree(e->d_probe_sizes);
     (void)hipFree(e->d_probe_dist);
+    (void)hipFree(e->d_rd_steps);
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
     (void)hipFree(e->d_pick_status);
@@ -896,6 +898,171 @@ int m1v_encode_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, in
     pa.level_out = (long long *)d_level_out;
     return rate_encode(e, pa, true, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
                        d_frame_sizes, d_total, d_status, stream);
+}
+
+// ---- batch budgets and constant bitrate that pick by distortion (m1v_rd_rate.h) -------------------------------------------------
+static unsigned long long pack_candidates(const uint8_t *candidates, int n_candidates) {
+    unsigned long long cand = 0;
+    for (int k = 0; k < n_candidates; k++) cand |= (unsigned long long)candidates[k] << (8 * k);
+    return cand;
+}
+
+static int launch_rd_chains(m1v_encoder *e, const unsigned long long *sizes, const unsigned long long *dist, int stride, int n_cand,
+                            int n_frames, const uint32_t *table_status, hipStream_t st) {
+    RdChainArgs ca = {sizes, dist, stride, n_cand, n_frames, table_status, e->d_rd_steps};
+    hipLaunchKernelGGL(k_rd_chains, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, ca);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+static int check_cbr_rate(uint64_t bytes_per_frame, uint64_t buffer_bytes) {
+    if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
+        return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
+    return M1V_OK;
+}
+
+static const char kNotFused[] = "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s";
+
+// One rd table into the encoder's own tables, the chains and (inside encode_batch, where the batch's status word is known) the
+// batch pick, then the encode at the picked qualities as rate_encode's
+int m1v_encode_rd_batch_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                               const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, uint8_t *d_chosen,
+                               uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_frame_distortion,
+                               uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
+    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
+    if (!e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
+    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
+                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
+        return rc;
+    if (n_frames > 0)
+        if (const int rc = launch_rd_chains(e, e->d_probe_sizes, e->d_probe_dist, e->max_frames, n_candidates, n_frames,
+                                            e->d_probe_status, (hipStream_t)stream))
+            return rc;
+    RdBatchArgs ba = {};
+    ba.steps = e->d_rd_steps;
+    ba.dist = e->d_probe_dist;
+    ba.stride = e->max_frames;
+    ba.n_frames = n_frames;
+    ba.n_cand = n_candidates;
+    ba.rule = rule;
+    ba.limit = limit;
+    ba.cand = pack_candidates(candidates, n_candidates);
+    ba.table_status = e->d_probe_status;
+    ba.chosen = d_chosen ? d_chosen : e->d_chosen;
+    ba.pick_dist = (unsigned long long *)d_frame_distortion;
+    ba.status = e->d_pick_status;
+    QualityArgs qa = {};
+    qa.quality = ba.chosen;
+    qa.pick_status = e->d_pick_status;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream,
+                        nullptr, &ba);
+}
+
+static void launch_rd_cbr(RdCbrArgs &ca, hipStream_t st) {
+    hipLaunchKernelGGL(k_rd_cbr_pick, dim3(1), dim3(kPickThreads), 0, st, ca);
+}
+
+int m1v_encode_rd_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                             const uint8_t *candidates, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                             const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
+                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_frame_distortion,
+                             uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out && d_level_in && d_level_out))
+        return rc;
+    if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
+    if (!e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
+    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
+                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
+        return rc;
+    RdCbrArgs ca = {};
+    ca.sizes = e->d_probe_sizes;
+    ca.dist = e->d_probe_dist;
+    ca.stride = e->max_frames;
+    ca.n_cand = n_candidates;
+    ca.n_frames = n_frames;
+    ca.cand = pack_candidates(candidates, n_candidates);
+    ca.table_status = e->d_probe_status;
+    ca.rate = (long long)bytes_per_frame;
+    ca.capacity = (long long)buffer_bytes;
+    ca.level_in = (const long long *)d_level_in;
+    ca.level_out = (long long *)d_level_out;
+    ca.chosen = d_chosen ? d_chosen : e->d_chosen;
+    ca.pick_dist = (unsigned long long *)d_frame_distortion;
+    ca.status = e->d_pick_status;
+    launch_rd_cbr(ca, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    QualityArgs qa = {};
+    qa.quality = ca.chosen;
+    qa.pick_status = e->d_pick_status;
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+}
+
+// The picks alone, on a table the caller holds ([k * n_frames + f])
+static int check_pick_call(const m1v_encoder *e, const void *d_sizes, const void *d_distortion, int n_frames, int n_candidates,
+                           const void *d_picks, const void *d_status) {
+    if (!e || !d_sizes || !d_distortion || !d_picks || !d_status) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidates%s");
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    return M1V_OK;
+}
+
+int m1v_rd_batch_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                             int n_frames, int n_candidates, int rule, uint64_t limit, uint8_t *d_picks,
+                             uint64_t *d_pick_distortion, uint32_t *d_status, void *stream) {
+    if (const int rc = check_pick_call(e, d_sizes, d_distortion, n_frames, n_candidates, d_picks, d_status)) return rc;
+    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (n_frames == 0) {
+        HIP_TRY(hipMemsetAsync(d_status, 0, 4, (hipStream_t)stream));
+        return M1V_OK;
+    }
+    if (const int rc = launch_rd_chains(e, (const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames,
+                                        n_candidates, n_frames, d_table_status, (hipStream_t)stream))
+        return rc;
+    RdBatchArgs ba = {};
+    ba.steps = e->d_rd_steps;
+    ba.dist = (const unsigned long long *)d_distortion;
+    ba.stride = n_frames;
+    ba.n_frames = n_frames;
+    ba.n_cand = n_candidates;
+    ba.rule = rule;
+    ba.limit = limit;
+    ba.table_status = d_table_status;
+    ba.picks = d_picks;
+    ba.pick_dist = (unsigned long long *)d_pick_distortion;
+    ba.status = d_status;
+    hipLaunchKernelGGL(k_rd_batch_pick, dim3((unsigned)((n_frames * kMaxCandidates + kRdPickThreads - 1) / kRdPickThreads)),
+                       dim3(kRdPickThreads), 0, (hipStream_t)stream, ba);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+int m1v_rd_cbr_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                           int n_frames, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                           const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                           uint32_t *d_status, void *stream) {
+    if (const int rc = check_pick_call(e, d_sizes, d_distortion, n_frames, n_candidates, d_picks, d_status)) return rc;
+    if (!d_level_in || !d_level_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    RdCbrArgs ca = {};
+    ca.sizes = (const unsigned long long *)d_sizes;
+    ca.dist = (const unsigned long long *)d_distortion;
+    ca.stride = n_frames;
+    ca.n_cand = n_candidates;
+    ca.n_frames = n_frames;
+    ca.table_status = d_table_status;
+    ca.rate = (long long)bytes_per_frame;
+    ca.capacity = (long long)buffer_bytes;
+    ca.level_in = (const long long *)d_level_in;
+    ca.level_out = (long long *)d_level_out;
+    ca.picks = d_picks;
+    ca.pick_dist = (unsigned long long *)d_pick_distortion;
+    ca.status = d_status;
+    launch_rd_cbr(ca, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

@@ -474,6 +474,129 @@ class Mpeg1Encoder:
             L = min(cap, L - s + rate)
         return data, sizes_l, [int(c) for c in chosen[:n].cpu()], over
 
+    def _encode_rd_batch(self, name, rule, rgb, limit, candidates, first_frame_index):
+        """The two batch forms that pick by distortion: (bytes, sizes, chosen, over the limit, distortion per frame)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        cand_buf = self._candidates(candidates, name)
+        if not 0 <= int(limit) < 2 ** 64:
+            raise EncoderError(_ffi.E_ARG, f"{name}: the limit must fit uint64")
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
+        data, sizes_l, status = self._encode_retrying(
+            rgb, name,
+            lambda out, sizes, meta: _call(
+                "m1v_encode_rd_batch_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rule,
+                int(limit), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist), *_meta_ptrs(meta), _stream()))
+        bit = _ffi.STATUS_OVER_BUDGET if rule == _ffi.RD_BEST_IN_BUDGET else _ffi.STATUS_OVER_DISTORTION
+        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], bool(status & bit), [int(d) for d in dist[:n].cpu()]
+
+    def encode_best_in_batch_budget(self, rgb, batch_bytes, candidates, first_frame_index=0):
+        """Synchronous: the whole batch within batch_bytes (the sum of its records) at the least total distortion the greedy
+        on each frame's convex hull finds (include/mpeg1_hip.h, m1v_encode_rd_batch_device): every frame starts at its smallest
+        record and the steps along the hulls are taken steepest first (distortion saved per byte) while they fit.  Not the
+        knapsack optimum.  encode_to_batch_budget takes the largest qualities that fit, which here can be far from the best
+        picture.  over_budget: even every frame at its smallest record does not fit (all are there).  Returns
+        (bytes, sizes, chosen, over_budget, distortion)."""
+        return self._encode_rd_batch("encode_best_in_batch_budget", _ffi.RD_BEST_IN_BUDGET, rgb, batch_bytes, candidates,
+                                     first_frame_index)
+
+    def encode_batch_to_distortion(self, rgb, total_distortion, candidates, first_frame_index=0):
+        """Synchronous: the fewest steps of encode_best_in_batch_budget's order after which the batch's distortions sum to at
+        most total_distortion.  over_distortion: even every frame at its least distortion does not reach it (all are there; the
+        output is valid).  Returns (bytes, sizes, chosen, over_distortion, distortion)."""
+        return self._encode_rd_batch("encode_batch_to_distortion", _ffi.RD_SMALLEST_AT_DISTORTION, rgb, total_distortion,
+                                     candidates, first_frame_index)
+
+    @staticmethod
+    def _bitrate_args(name, bytes_per_frame, buffer_bytes, level):
+        import torch
+        assert level.is_cuda and level.dtype == torch.int64 and level.numel() == 1, "level: CUDA int64 tensor of one element"
+        rate, cap = int(bytes_per_frame), int(buffer_bytes)
+        if not 1 <= rate <= cap < 2 ** 62:
+            raise EncoderError(_ffi.E_ARG, f"{name}: need 1 <= bytes_per_frame <= buffer_bytes < 2^62")
+        return rate, cap
+
+    @staticmethod
+    def _over_level(sizes_l, start, rate, cap):
+        """The frames whose record exceeds the level before them, replayed from the sizes."""
+        over, L = [], min(start, cap)
+        for f, s in enumerate(sizes_l):
+            if s > L:
+                over.append(f)
+            L = min(cap, L - s + rate)
+        return over
+
+    def encode_best_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
+        """Synchronous constant bitrate that picks by distortion (include/mpeg1_hip.h, m1v_encode_rd_cbr_device): the leaky bucket
+        of encode_at_bitrate, each frame at the candidate of LEAST DISTORTION whose record fits the level (ties: the smaller
+        record, then the smaller quality), else at its smallest record.  The level is advanced over the batch in place, only
+        when the call succeeds.  Returns (bytes, sizes, chosen, over_budget_frames, distortion)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        rate, cap = self._bitrate_args("encode_best_at_bitrate", bytes_per_frame, buffer_bytes, level)
+        cand_buf = self._candidates(candidates, "encode_best_at_bitrate")
+        level_in = level.contiguous()
+        start = int(level_in.item())
+        level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, "encode_best_at_bitrate",
+            lambda out, sizes, meta: _call(
+                "m1v_encode_rd_cbr_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap,
+                _ptr(level_in), _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist),
+                *_meta_ptrs(meta), _stream()))
+        level.copy_(level_out.view_as(level))
+        return (data, sizes_l, [int(c) for c in chosen[:n].cpu()], self._over_level(sizes_l, start, rate, cap),
+                [int(d) for d in dist[:n].cpu()])
+
+    @staticmethod
+    def _rd_tables(sizes, dist, status):
+        import torch
+        assert sizes.is_cuda and sizes.dtype == torch.int64 and sizes.dim() == 2, "sizes: CUDA int64 [K, n]"
+        assert dist.is_cuda and dist.dtype == torch.int64 and dist.shape == sizes.shape, "dist: CUDA int64 [K, n]"
+        K, n = sizes.shape
+        if status is not None:
+            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= K, "status: CUDA int32, one per candidate"
+        return sizes.contiguous(), dist.contiguous(), K, n
+
+    def rd_batch_pick(self, sizes, dist, rule, limit, status=None):
+        """The batch pick alone on an rd table the caller holds (frame_rd_table's two CUDA int64 tensors [K, n]; status: its
+        CUDA int32 status words, or None): re-pick at another limit without another table pass.  Synchronous.  Returns
+        (picks, over): the candidate INDEX of every frame and whether the rule's limit was missed."""
+        import torch
+        sizes, dist, K, n = self._rd_tables(sizes, dist, status)
+        if not 0 <= int(limit) < 2 ** 64:
+            raise EncoderError(_ffi.E_ARG, "rd_batch_pick: the limit must fit uint64")
+        picks = torch.zeros(max(n, 1), dtype=torch.uint8, device=sizes.device)
+        word = torch.zeros(1, dtype=torch.int32, device=sizes.device)
+        _call("m1v_rd_batch_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, int(rule), int(limit), _ptr(picks),
+              None, _ptr(word), _stream())
+        bits = int(word.item())
+        return [int(k) for k in picks[:n].cpu()], bool(bits & (_ffi.STATUS_OVER_BUDGET | _ffi.STATUS_OVER_DISTORTION))
+
+    def rd_bitrate_pick(self, sizes, dist, bytes_per_frame, buffer_bytes, level, status=None):
+        """The bitrate pick alone on an rd table the caller holds (as rd_batch_pick).  level: CUDA int64 tensor [1], advanced in
+        place.  Synchronous.  Returns (picks, over_frames): the candidate index of every frame and the frames that fitted
+        nothing."""
+        import torch
+        sizes, dist, K, n = self._rd_tables(sizes, dist, status)
+        rate, cap = self._bitrate_args("rd_bitrate_pick", bytes_per_frame, buffer_bytes, level)
+        level_in = level.contiguous()
+        start = int(level_in.item())
+        level_out = torch.empty(1, dtype=torch.int64, device=level.device)
+        picks = torch.zeros(max(n, 1), dtype=torch.uint8, device=sizes.device)
+        word = torch.zeros(1, dtype=torch.int32, device=sizes.device)
+        _call("m1v_rd_cbr_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, rate, cap, _ptr(level_in),
+              _ptr(level_out), _ptr(picks), None, _ptr(word), _stream())
+        picks_l = [int(k) for k in picks[:n].cpu()]
+        level.copy_(level_out.view_as(level))
+        rows = sizes.cpu()
+        return picks_l, self._over_level([int(rows[k, f]) for f, k in enumerate(picks_l)], start, rate, cap)
+
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.
         Outputs of a batch are complete only behind flush(); callers double-buffer `out`."""

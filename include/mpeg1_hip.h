@@ -267,6 +267,90 @@ int m1v_encode_rd_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, i
                          uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
                          uint64_t *d_frame_distortion, uint64_t *d_total, uint32_t *d_status, void *stream);
 
+/* Batch budgets and constant bitrate that pick by distortion: "this batch in B bytes" and "this stream at r bytes per frame" by
+ * the rd table instead of by "the largest quality that fits", with no host wait.  The table is the rd table's: s[k][f] record
+ * bytes and D[k][f] distortion of frame f at candidate k.
+ *
+ * A candidate whose table status carries M1V_STATUS_UNENCODABLE is out of the running for every frame.  With every candidate out,
+ * each frame goes to candidate 0 (candidate 0 alone is then in the running) and the encode reports the bit.
+ *
+ * The chain of a frame is the lower convex hull of its (s, D) points, walked from the smallest record towards less distortion:
+ *   - v0 = the candidate with the least s.  Ties go to the less D, then the smaller k.
+ *   - From vertex v, the next vertex is, among candidates with s > s[v] and D < D[v], the one with the greatest
+ *     (D[v] - D) / (s - s[v]).
+ *   - Ratios are compared exactly, by cross products in 128 bits.
+ *   - Ties go to the smaller s, then the smaller k.
+ *   - The chain ends when no such candidate exists.
+ * Step j >= 1 of frame f has ds > 0 bytes and dd > 0 distortion gained.  Along a chain dd / ds never increases.
+ *
+ * The order of all steps of a batch: dd / ds descending (exact cross products).  Ties go by frame ascending, then j ascending.
+ *
+ * Batch form, M1V_RD_BEST_IN_BUDGET, limit = bytes for the sum of the records.
+ *   - Every frame starts at its v0.
+ *   - If those records sum to more than the limit, every frame stays at v0 and the status is M1V_STATUS_OVER_BUDGET.
+ *   - Otherwise the steps are taken in that order: the longest prefix whose ds sum to at most the bytes left.  Every ds is
+ *     positive, so a step is taken iff its own inclusive prefix sum fits.
+ *   - A frame ends at the vertex its last taken step reaches.
+ *   - Without the status bit, the total is at most the limit.
+ * Batch form, M1V_RD_SMALLEST_AT_DISTORTION, limit = ceiling for the sum of the frames' D.
+ *   - Same start and same order.
+ *   - The shortest prefix after which the sum of D is at most the limit is taken.  That is none if the start already qualifies.
+ *   - If even every step does not reach the limit, every frame is at its chain's end and the status is
+ *     M1V_STATUS_OVER_DISTORTION.  The output is valid.
+ * Bitrate form.
+ *   - It is the leaky bucket of m1v_encode_cbr_device, unchanged: level, refill, capacity, d_level_in / d_level_out, chaining,
+ *     and debts.
+ *   - Per frame, the pick is M1V_RD_BEST_IN_BUDGET with the level as the limit.  That is the least D among records <= level,
+ *     with ties to the smaller record, then the smaller k.
+ *   - If nothing fits, the frame takes the smallest record, with ties to the smaller k, and the status is
+ *     M1V_STATUS_OVER_BUDGET.
+ *
+ * The batch forms are the Lagrangian greedy on each frame's hull, NOT the knapsack optimum: a prefix of the steps by slope is the
+ * best allocation for the bytes it uses, but the bytes left behind the last step that fits are not spent on a cheaper step
+ * further down.  On random 4 x 5 tables a CPU prototype stayed within 1 % of the exhaustive optimum's distortion on average; the
+ * worst case was 29 %.
+ *
+ * m1v_encode_rd_batch_device  m1v_encode_rd_device with the batch pick: the same checks in the same order, one rd table into the
+ *                             encoder's own tables, the pick (k_rd_chains, a lane per frame, then k_rd_batch_pick, a lane per
+ *                             step over a grid of workgroups) and one encode at the picked qualities, all on `stream`, in
+ *                             pipelined mode too.  Every input layout is served.  d_chosen and d_frame_distortion may be NULL.
+ *                             A profiled call reports 2 launches.  Cost at 300 x 1080p, K = 8: 1.19 x m1v_encode_rd_device
+ *                             (the pick takes 0.44 ms; profiles/r15_rd_rate_timing.txt), the bitrate form 1.01 x.
+ * m1v_encode_rd_cbr_device    m1v_encode_cbr_device with the bitrate pick above (k_rd_cbr_pick, one workgroup): its arguments
+ *                             and their checks, then "not fused" as m1v_encode_rd_device.
+ *                             Both: n_frames == 0 writes *d_total = 0 and *d_status = 0 (the bitrate form also *d_level_out =
+ *                             min(*d_level_in, C)) and nothing else.  m1v_debug_fail_encode reaches the table's and the
+ *                             encode's stages as in m1v_encode_rd_device.
+ * m1v_rd_batch_pick_device, m1v_rd_cbr_pick_device
+ *                             the pick alone, on a table the caller holds on the device in m1v_frame_rd_table_device's layout
+ *                             ([k * n_frames + f]; d_table_status uint32[n_candidates], may be NULL: every candidate in the
+ *                             running): re-pick at another limit without another table pass.  d_picks (uint8[n_frames]) receives
+ *                             the candidate INDEX of every frame, d_pick_distortion (uint64[n_frames], may be NULL) its D,
+ *                             d_status (uint32[1]) the status word, WRITTEN, not OR'ed; the bitrate form moves the level as the
+ *                             encode does.  Only the pick is launched (the batch form uses the encoder's step table: calls on
+ *                             one encoder are ordered by the stream).  Needs n_frames <= max_frames, 1 <= n_candidates <= 8 and
+ *                             non-null tables, picks and status (the bitrate form: level pointers and rates as
+ *                             m1v_encode_cbr_device); M1V_E_ARG before anything is launched otherwise.  Preconditions (the
+ *                             library's own tables meet them): every s < 2^32 and every D < 2^63.  A table outside that gives
+ *                             unspecified picks but no access outside the arrays.  n_frames == 0 writes *d_status = 0 (the
+ *                             bitrate form also the level) and nothing else. */
+int m1v_encode_rd_batch_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                               const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, uint8_t *d_chosen,
+                               uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_frame_distortion,
+                               uint64_t *d_total, uint32_t *d_status, void *stream);
+int m1v_encode_rd_cbr_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                             const uint8_t *candidates, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                             const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_chosen,
+                             uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_frame_distortion,
+                             uint64_t *d_total, uint32_t *d_status, void *stream);
+int m1v_rd_batch_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                             int n_frames, int n_candidates, int rule, uint64_t limit, uint8_t *d_picks,
+                             uint64_t *d_pick_distortion, uint32_t *d_status, void *stream);
+int m1v_rd_cbr_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                           int n_frames, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
+                           const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                           uint32_t *d_status, void *stream);
+
 /* Input layout: frames that already live on the device as windows of pitched surfaces, in R,G,B(,A) or B,G,R(,A) byte order,
  * encoded where they lie (no compaction or swizzle copy in front of the encoder).
  *
