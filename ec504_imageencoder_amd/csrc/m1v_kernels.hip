@@ -2137,15 +2137,29 @@ static int hand_over(Args &a, m1v_encoder::Counters &cur, m1v_encoder::Counters 
     return M1V_OK;
 }
 
-// One batch through the encode kernel of the encoder's plan.  qa == null: every frame at the encoder's own quality (the plain
-// path); otherwise k_frame_quality first writes the per-frame selection (into the batch's status word) from qa.  probe: the
-// counter hand-over ends in k_frame_sizes instead of k_assemble (record sizes and status only; d_out is not touched).
-// rd != null (and qa == null): k_rd_pick writes the selection from the rd table instead.
-// rb != null (with qa): k_rd_batch_pick first writes the qualities qa reads; the batch's status word is known only here.
-static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, QualityArgs *qa, bool probe,
-                        uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status,
-                        void *stream, RdPickArgs *rd = nullptr, RdBatchArgs *rb = nullptr) {
-    if (!e || (!d_rgb && n_frames > 0) || (!d_out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
+// What writes the per-frame selection (e->d_qsel) of a batch that is not encoded at the encoder's own quality: launch() queues,
+// on st, whatever does (k_frame_quality; k_rd_pick; k_rd_batch_pick, then k_frame_quality: m1v_runtime.h) with `args`, the
+// batch's status word and n_frames.  One step per batch: a batch cannot be given two.
+struct Selection {
+    int (*launch)(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st);
+    void *args;
+};
+
+// Where a batch's results go (the last five arguments of m1v_encode_device).  A probe writes frame_sizes and status only.
+struct EncodeOut {
+    uint8_t *out;
+    size_t cap;
+    uint64_t *frame_sizes, *total;
+    uint32_t *status;
+};
+
+// One batch through the encode kernel of the encoder's plan.  sel == null: every frame at the encoder's own quality (the plain
+// path); otherwise sel's step first writes the per-frame selection, behind the poison / hand-over logic and fail stage 1 and in
+// front of the producer kernel, on the caller's stream.  An empty batch returns before it.  probe: the counter hand-over ends in
+// k_frame_sizes instead of k_assemble (record sizes and status only; o.out is not touched).
+static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, const Selection *sel, bool probe,
+                        const EncodeOut &o, void *stream) {
+    if (!e || (!d_rgb && n_frames > 0) || (!o.out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));
@@ -2165,8 +2179,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         bt.poisoned = false;
     }
     if (n_frames == 0) {
-        if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
-        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, 4, st));
+        if (o.total) HIP_TRY(hipMemsetAsync(o.total, 0, 8, st));
+        if (o.status) HIP_TRY(hipMemsetAsync(o.status, 0, 4, st));
         return M1V_OK;
     }
     const Geometry &g = e->g;
@@ -2178,29 +2192,9 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     bt.turn++;
     PoisonOnReturn poison{&bt.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
-    const uint32_t *qsel = e->d_qsel_own;
-    if (rb) {
-        rb->batch_status = cur.words;
-        hipLaunchKernelGGL(k_rd_batch_pick, dim3((unsigned)((n_frames * kMaxCandidates + kRdPickThreads - 1) / kRdPickThreads)),
-                           dim3(kRdPickThreads), 0, st, *rb);
-        HIP_TRY(hipGetLastError());
-    }
-    if (qa) {
-        qa->max_q = encoder_quality(e);
-        qa->n_frames = n_frames;
-        qa->qsel = e->d_qsel;
-        qa->status = cur.words;
-        hipLaunchKernelGGL(k_frame_quality, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, *qa);
-        HIP_TRY(hipGetLastError());
-        qsel = e->d_qsel;
-    } else if (rd) {
-        rd->n_frames = n_frames;
-        rd->qsel = e->d_qsel;
-        rd->status = cur.words;
-        hipLaunchKernelGGL(k_rd_pick, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, *rd);
-        HIP_TRY(hipGetLastError());
-        qsel = e->d_qsel;
-    }
+    if (sel)
+        if (const int rc = sel->launch(e, sel->args, cur.words, n_frames, st)) return rc;
+    const uint32_t *qsel = sel ? e->d_qsel : e->d_qsel_own;
     // the plan's producer kernel over n_frames
     const size_t grid = (size_t)n_frames * p.units;
     int rc;
@@ -2288,8 +2282,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         sa.frame_bytes = cur.frame_bytes;
         sa.enc_words = cur.words;
         if (const int rc = hand_over(sa, cur, nxt, n_frames, g.n_strips, gs)) return rc;
-        sa.out_sizes = (unsigned long long *)d_frame_sizes;
-        sa.out_status = d_status ? d_status : cur.words + 1;
+        sa.out_sizes = (unsigned long long *)o.frame_sizes;
+        sa.out_status = o.status ? o.status : cur.words + 1;
         hipLaunchKernelGGL(k_frame_sizes, dim3((unsigned)n_frames), dim3(256), 0, gs, sa);
         HIP_TRY(hipGetLastError());
     } else {
@@ -2309,11 +2303,11 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         ga.enc_words = cur.words;
         if (const int rc = hand_over(ga, cur, nxt, n_frames, g.n_strips, gs)) return rc;
         ga.tab = e->d_tab;
-        ga.out = d_out;
-        ga.out_cap = out_cap;
-        ga.out_sizes = (unsigned long long *)d_frame_sizes;
-        ga.out_total = (unsigned long long *)d_total;
-        ga.out_status = d_status ? d_status : cur.words + 1;
+        ga.out = o.out;
+        ga.out_cap = o.cap;
+        ga.out_sizes = (unsigned long long *)o.frame_sizes;
+        ga.out_total = (unsigned long long *)o.total;
+        ga.out_status = o.status ? o.status : cur.words + 1;
         ga.first_index = first_frame_index;
         ga.stamps = e->d_stamps;
         const dim3 grid((unsigned)((g.n_strips + p.asm_group - 1) / p.asm_group), (unsigned)n_frames);

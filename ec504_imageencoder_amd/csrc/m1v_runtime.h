@@ -1,9 +1,11 @@
 // ec504_imageencoder_amd/csrc/m1v_runtime.h — the C-ABI of include/mpeg1_hip.h around the plan and the launches of
 // m1v_kernels.hip: object lifetime, buffer allocation, counters (an alloc / clear / free trio per kind), streams and events, the
-// quality, size-table and rate entry points (one argument check, check_candidate_call, and one probe step, probe_candidates, for
-// those that take candidates), delivery, the host path, profiling and the debug hooks.  Geometry (CodedRegion, TileGrid,
-// wave_region), the kernel registry (kKernels) and the hook predicates of m1v_encoder come from m1v_kernels.hip.  Not
-// standalone: included once, at the end of m1v_kernels.hip.
+// quality, size-table and rate entry points, delivery, the host path, profiling and the debug hooks.  The calls that take
+// candidates share one argument check (check_candidate_call, the pick-only calls included), one table step (own_table, into the
+// encoder's own buffers), one description of the table a pick reads (PickTable, the encoder's own or the caller's) and one launch
+// site per pick kernel; what writes a batch's per-frame selection reaches encode_batch as a Selection (the select_by_* steps).
+// Geometry (CodedRegion, TileGrid, wave_region), the kernel registry (kKernels) and the hook predicates of m1v_encoder come from
+// m1v_kernels.hip.  Not standalone: included once, at the end of m1v_kernels.hip.
 
 namespace {
 
@@ -710,52 +712,106 @@ int m1v_profile_read_times(m1v_encoder *e, float *ms, int cap, int *launches) {
     return profile_times(e, ms, cap, launches, nullptr);
 }
 
+// ---- what writes a batch's per-frame selection (the steps a Selection of encode_batch names) ------------------------------------
+static int select_by_quality(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+    QualityArgs &qa = *static_cast<QualityArgs *>(args);
+    qa.max_q = encoder_quality(e);
+    qa.n_frames = n_frames;
+    qa.qsel = e->d_qsel;
+    qa.status = batch_status;
+    hipLaunchKernelGGL(k_frame_quality, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, qa);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+static int select_by_rd(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+    RdPickArgs &ra = *static_cast<RdPickArgs *>(args);
+    ra.n_frames = n_frames;
+    ra.qsel = e->d_qsel;
+    ra.status = batch_status;
+    hipLaunchKernelGGL(k_rd_pick, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, ra);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+// batch_status: an encode's status word (the pick ORs M1V_STATUS_OVER_DISTORTION into it), or null
+static int launch_rd_batch_pick(RdBatchArgs &ba, uint32_t *batch_status, hipStream_t st) {
+    ba.batch_status = batch_status;
+    hipLaunchKernelGGL(k_rd_batch_pick, dim3((unsigned)((ba.n_frames * kMaxCandidates + kRdPickThreads - 1) / kRdPickThreads)),
+                       dim3(kRdPickThreads), 0, st, ba);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+// The batch pick (here, where the batch's status word is known), then k_frame_quality on the qualities and status word it wrote
+static int select_by_rd_batch(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+    RdBatchArgs &ba = *static_cast<RdBatchArgs *>(args);
+    if (const int rc = launch_rd_batch_pick(ba, batch_status, st)) return rc;
+    QualityArgs qa = {};
+    qa.quality = ba.chosen;
+    qa.pick_status = ba.status;
+    return select_by_quality(e, &qa, batch_status, n_frames, st);
+}
+
+// A batch at one quality per frame (null: the encoder's own), which a pick may have written with its status word (pick_status,
+// or null): k_frame_quality checks the qualities and passes the pick's status bits on
+static int encode_at(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, const uint8_t *d_quality,
+                     const uint32_t *pick_status, bool probe, const EncodeOut &o, void *stream) {
+    if (!d_quality) return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, probe, o, stream);
+    QualityArgs qa = {};
+    qa.quality = d_quality;
+    qa.pick_status = pick_status;
+    const Selection sel = {select_by_quality, &qa};
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &sel, probe, o, stream);
+}
+
 int m1v_encode_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                       uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                       uint32_t *d_status, void *stream) {
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status,
-                        stream);
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 int m1v_encode_quality_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                               const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
                               uint64_t *d_total, uint32_t *d_status, void *stream) {
-    QualityArgs qa = {};
-    qa.quality = d_quality;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, d_quality ? &qa : nullptr, false, d_out, out_cap, d_frame_sizes,
-                        d_total, d_status, stream);
+    return encode_at(e, d_rgb, n_frames, first_frame_index, d_quality, nullptr, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 int m1v_frame_sizes_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *d_quality,
                            uint64_t *d_frame_sizes, uint32_t *d_status, void *stream) {
-    QualityArgs qa = {};
-    qa.quality = d_quality;
-    return encode_batch(e, d_rgb, n_frames, 0, d_quality ? &qa : nullptr, true, nullptr, 0, d_frame_sizes, nullptr, d_status,
-                        stream);
+    return encode_at(e, d_rgb, n_frames, 0, d_quality, nullptr, true, {nullptr, 0, d_frame_sizes, nullptr, d_status}, stream);
 }
 
-// A list of 1..8 strictly increasing qualities, each within 1 .. the encoder's quality factor
-static int check_qualities(const m1v_encoder *e, const uint8_t *q, int n) {
-    if (!q) return fail(M1V_E_ARG, "null pointer%s");
-    if (n < 1 || n > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidate qualities%s");
-    for (int k = 0; k < n; k++)
+// ---- candidates: the checks, the table, the picks ------------------------------------------------------------------------------
+// The checks the candidate-taking calls share, in the order every one of them has: the encoder and what the call checks before
+// its candidates (`first`); the candidates, 1..8 strictly increasing qualities, each within 1 .. the encoder's quality factor;
+// n_frames; what it checks after them (`then`).  on_table: a pick-only call, whose candidates are the rows of a table the
+// caller holds: there are no qualities (q is not read), only their number.
+static int check_candidate_call(const m1v_encoder *e, bool first, const uint8_t *q, int n_q, int n_frames, bool then, bool on_table = false) {
+    if (!e || !first || (!q && !on_table)) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_q < 1 || n_q > kMaxCandidates) return fail(M1V_E_ARG, on_table ? "1 to 8 candidates%s" : "1 to 8 candidate qualities%s");
+    for (int k = 0; k < n_q && !on_table; k++)
         if (q[k] < 1 || q[k] > encoder_quality(e) || (k > 0 && q[k] <= q[k - 1]))
             return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
-    return M1V_OK;
-}
-
-// The checks the candidate-taking calls share, in the order every one of them has: the encoder and what the call checks before
-// its candidates (`first`), the candidates, n_frames, what it checks after them (`then`)
-static int check_candidate_call(const m1v_encoder *e, bool first, const uint8_t *q, int n_q, int n_frames, bool then) {
-    if (!e || !first) return fail(M1V_E_ARG, "null pointer%s");
-    if (const int rc = check_qualities(e, q, n_q)) return rc;
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     return then ? M1V_OK : fail(M1V_E_ARG, "null pointer%s");
 }
 
+static int check_rd_rule(int rule) {
+    return rule == M1V_RD_BEST_IN_BUDGET || rule == M1V_RD_SMALLEST_AT_DISTORTION ? M1V_OK : fail(M1V_E_ARG, "unknown rate-distortion rule%s");
+}
+
+static int check_cbr_rate(uint64_t bytes_per_frame, uint64_t buffer_bytes) {
+    if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
+        return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
+    return M1V_OK;
+}
+
+static const char kNotFused[] = "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s";
+
 // sizes[k * stride + frame] and status[k] of every quality: one fused pass where the plan has one (3-channel tile encoders,
 // 4-channel encoders: m1v_size_table_fused); otherwise (a path, input mode or run length forced by a test hook) one probe call
-// (m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that every row is
+// (as m1v_frame_sizes_device) per quality, each with its own counter hand-over, then (pipelined) a flush, so that every row is
 // complete in stream order.
 static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
                       unsigned long long *sizes, size_t stride, uint32_t *status, void *stream) {
@@ -764,18 +820,13 @@ static int size_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const 
     for (int k = 0; k < n_q; k++) {
         QualityArgs qa = {};
         qa.uniform = qualities[k];
-        const int rc = encode_batch(e, d_rgb, n_frames, 0, &qa, true, nullptr, 0, (uint64_t *)(sizes + (size_t)k * stride), nullptr,
-                                    status ? status + k : nullptr, stream);
+        const Selection sel = {select_by_quality, &qa};
+        const int rc = encode_batch(e, d_rgb, n_frames, 0, &sel, true,
+                                    {nullptr, 0, (uint64_t *)(sizes + (size_t)k * stride), nullptr, status ? status + k : nullptr}, stream);
         if (rc != M1V_OK) return rc;
     }
     // (pipelined: the probes' sizes are written on the internal stream)
     return e->pipelined ? m1v_flush(e, stream) : M1V_OK;
-}
-
-// The first step of the budget, batch-budget and bitrate calls: the record size of every frame at every candidate into the
-// encoder's own table (d_probe_sizes [kMaxCandidates][max_frames], d_probe_status)
-static int probe_candidates(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *candidates, int n_candidates, void *stream) {
-    return size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames, e->d_probe_status, stream);
 }
 
 int m1v_frame_size_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_qualities,
@@ -790,85 +841,128 @@ int m1v_frame_rd_table_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames
                               uint64_t *d_sizes, uint64_t *d_distortion, uint32_t *d_status, void *stream) {
     if (const int rc = check_candidate_call(e, d_sizes && d_distortion && (d_rgb || n_frames <= 0), qualities, n_qualities, n_frames, true))
         return rc;
-    if (!e->plan.table_units) return fail(M1V_E_ARG, "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s");
+    if (!e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
     if (n_frames == 0) return M1V_OK;
     return size_table_fused(e, d_rgb, n_frames, qualities, n_qualities, (unsigned long long *)d_sizes, (unsigned long long *)d_distortion,
                             (size_t)n_frames, d_status, (hipStream_t)stream);
 }
 
-// One rd table into the encoder's own (d_probe_sizes, d_probe_dist, d_probe_status), then the encode with k_rd_pick in front of it
-int m1v_encode_rd_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                         const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, const uint64_t *d_limits,
-                         uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
-                         uint64_t *d_frame_distortion, uint64_t *d_total, uint32_t *d_status, void *stream) {
-    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
-    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
-    if (!e->plan.table_units) return fail(M1V_E_ARG, "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s");
-    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
-                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
-        return rc;
-    RdPickArgs ra = {};
-    ra.sizes = e->d_probe_sizes;
-    ra.dist = e->d_probe_dist;
-    ra.stride = e->max_frames;
-    ra.n_cand = n_candidates;
-    for (int k = 0; k < n_candidates; k++) ra.cand[k] = candidates[k];
-    ra.rule = rule;
-    ra.limits = (const unsigned long long *)d_limits;
-    ra.limit = limit;
-    ra.table_status = e->d_probe_status;
-    ra.chosen = d_chosen;
-    ra.frame_dist = (unsigned long long *)d_frame_distortion;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, nullptr, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream, &ra);
+// The table a pick reads: the encoder's own (own_table) or one the caller holds (rows n_frames apart, no qualities)
+struct PickTable {
+    const unsigned long long *sizes, *dist; // [k * stride + frame]; dist null: a size table
+    int stride, n_cand;
+    unsigned long long cand;                // byte k: the quality of candidate k
+    const uint32_t *status;                 // [n_cand] the table's status words, or null
+};
+
+static unsigned long long pack_candidates(const uint8_t *candidates, int n_candidates) {
+    unsigned long long cand = 0;
+    for (int k = 0; k < n_candidates; k++) cand |= (unsigned long long)candidates[k] << (8 * k);
+    return cand;
 }
 
+static void unpack_candidates(unsigned long long cand, uint8_t out[kMaxCandidates]) { // (for the kernels that take them as an array)
+    for (int k = 0; k < kMaxCandidates; k++) out[k] = (uint8_t)(cand >> (8 * k));
+}
+
+// The first step of every encode that takes candidates: every frame at every candidate into the encoder's own table
+// (d_probe_sizes, d_probe_dist [kMaxCandidates][max_frames], d_probe_status), which t then describes.  with_dist: the rd table,
+// which only the fused pass makes.
+static int own_table(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *candidates, int n_candidates, bool with_dist,
+                     void *stream, PickTable &t) {
+    if (with_dist && !e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
+    const int rc = with_dist ? size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
+                                                (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream)
+                             : size_table(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, (size_t)e->max_frames,
+                                          e->d_probe_status, stream);
+    t = {e->d_probe_sizes, with_dist ? e->d_probe_dist : nullptr, e->max_frames, n_candidates, pack_candidates(candidates, n_candidates),
+         e->d_probe_status};
+    return rc;
+}
+
+// k_rd_chains over a table (an empty batch has none), and what k_rd_batch_pick behind it reads; its outputs are the caller's to set
+static int rd_batch_chains(m1v_encoder *e, const PickTable &t, int n_frames, int rule, uint64_t limit, hipStream_t st, RdBatchArgs &ba) {
+    if (n_frames > 0) {
+        RdChainArgs ca = {t.sizes, t.dist, t.stride, t.n_cand, n_frames, t.status, e->d_rd_steps};
+        hipLaunchKernelGGL(k_rd_chains, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, ca);
+        HIP_TRY(hipGetLastError());
+    }
+    ba = {};
+    ba.dist = t.dist; ba.stride = t.stride; ba.n_cand = t.n_cand; ba.cand = t.cand; ba.table_status = t.status; // the table
+    ba.steps = e->d_rd_steps;
+    ba.n_frames = n_frames;
+    ba.rule = rule;
+    ba.limit = limit;
+    return M1V_OK;
+}
+
+// k_rd_cbr_pick over a table (an empty batch too: it writes the level); ca comes with its outputs set (picks, chosen, pick_dist, status)
+static int launch_rd_cbr_pick(const PickTable &t, int n_frames, uint64_t bytes_per_frame, uint64_t buffer_bytes, const int64_t *d_level_in,
+                              int64_t *d_level_out, RdCbrArgs ca, hipStream_t st) {
+    ca.sizes = t.sizes; ca.dist = t.dist; ca.stride = t.stride; ca.n_cand = t.n_cand; ca.cand = t.cand; ca.table_status = t.status; // the table
+    ca.n_frames = n_frames;
+    ca.rate = (long long)bytes_per_frame;
+    ca.capacity = (long long)buffer_bytes;
+    ca.level_in = (const long long *)d_level_in;
+    ca.level_out = (long long *)d_level_out;
+    hipLaunchKernelGGL(k_rd_cbr_pick, dim3(1), dim3(kPickThreads), 0, st, ca);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+// ---- the encodes that take candidates: their own checks, the table (own_table), their rule's parameters, the pick and encode ---
 int m1v_encode_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                              const uint8_t *candidates, int n_candidates, uint64_t max_frame_bytes,
                              const uint64_t *d_max_frame_bytes, uint8_t *d_chosen,
                              uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_total,
                              uint32_t *d_status, void *stream) {
     if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
-    if (const int rc = probe_candidates(e, d_rgb, n_frames, candidates, n_candidates, stream)) return rc; // 1. the table
-    // 2. + 3. the pick (k_frame_quality) and the encode at the picked qualities
-    QualityArgs qa = {};
-    qa.probe_sizes = e->d_probe_sizes;
-    qa.stride = e->max_frames;
-    qa.n_cand = n_candidates;
-    for (int k = 0; k < n_candidates; k++) qa.cand[k] = candidates[k];
+    PickTable t;
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, false, stream, t)) return rc;
+    QualityArgs qa = {}; // k_frame_quality's budget form is the pick
+    qa.probe_sizes = t.sizes; qa.stride = t.stride; qa.n_cand = t.n_cand; qa.probe_status = t.status; // the table
+    unpack_candidates(t.cand, qa.cand);
     qa.budget = (const unsigned long long *)d_max_frame_bytes;
     qa.max_bytes = max_frame_bytes;
-    qa.probe_status = e->d_probe_status;
     qa.chosen = d_chosen ? d_chosen : e->d_chosen;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+    const Selection sel = {select_by_quality, &qa};
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &sel, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
+}
+
+int m1v_encode_rd_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
+                         const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, const uint64_t *d_limits,
+                         uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                         uint64_t *d_frame_distortion, uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
+    if (const int rc = check_rd_rule(rule)) return rc;
+    PickTable t;
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, true, stream, t)) return rc;
+    RdPickArgs ra = {};
+    ra.sizes = t.sizes; ra.dist = t.dist; ra.stride = t.stride; ra.n_cand = t.n_cand; ra.table_status = t.status; // the table
+    unpack_candidates(t.cand, ra.cand);
+    ra.rule = rule;
+    ra.limits = (const unsigned long long *)d_limits;
+    ra.limit = limit;
+    ra.chosen = d_chosen;
+    ra.frame_dist = (unsigned long long *)d_frame_distortion;
+    const Selection sel = {select_by_rd, &ra};
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &sel, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 // A batch-budget or bitrate call after its arguments are checked: the size table, the pick (k_rate_pick, one workgroup) and the
 // encode at the picked qualities, all on `stream` with no host wait.  pa holds the rule's parameters; the rest is set here.
 static int rate_encode(m1v_encoder *e, PickArgs &pa, bool cbr, const uint8_t *d_rgb, int n_frames, int first_frame_index,
-                       const uint8_t *candidates, int n_candidates, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap,
-                       uint64_t *d_frame_sizes, uint64_t *d_total, uint32_t *d_status, void *stream) {
-    if (const int rc = probe_candidates(e, d_rgb, n_frames, candidates, n_candidates, stream)) return rc; // 1. the table
-    // 2. the pick
-    HIP_TRY(hipSetDevice(e->device));
-    pa.sizes = e->d_probe_sizes;
-    pa.stride = e->max_frames;
-    pa.n_cand = n_candidates;
+                       const uint8_t *candidates, int n_candidates, uint8_t *d_chosen, const EncodeOut &o, void *stream) {
+    PickTable t;
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, false, stream, t)) return rc;
+    pa.sizes = t.sizes; pa.stride = t.stride; pa.n_cand = t.n_cand; pa.cand = t.cand; pa.table_status = t.status; // the table
     pa.n_frames = n_frames;
-    pa.cand = 0;
-    for (int k = 0; k < n_candidates; k++) pa.cand |= (unsigned long long)candidates[k] << (8 * k);
-    pa.table_status = e->d_probe_status;
     pa.chosen = d_chosen ? d_chosen : e->d_chosen;
     pa.status = e->d_pick_status;
-    if (cbr)
-        hipLaunchKernelGGL(k_rate_pick<true>, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, pa);
-    else
-        hipLaunchKernelGGL(k_rate_pick<false>, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, pa);
+    const auto pick = cbr ? k_rate_pick<true> : k_rate_pick<false>;
+    hipLaunchKernelGGL(pick, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, pa);
     HIP_TRY(hipGetLastError());
-    // 3. the encode at the picked qualities (k_frame_quality checks them and passes the pick's status bits on)
-    QualityArgs qa = {};
-    qa.quality = pa.chosen;
-    qa.pick_status = e->d_pick_status;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+    return encode_at(e, d_rgb, n_frames, first_frame_index, pa.chosen, pa.status, false, o, stream);
 }
 
 int m1v_encode_batch_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
@@ -878,8 +972,8 @@ int m1v_encode_batch_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_f
     if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
     PickArgs pa = {};
     pa.budget = batch_bytes;
-    return rate_encode(e, pa, false, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
-                       d_frame_sizes, d_total, d_status, stream);
+    return rate_encode(e, pa, false, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen,
+                       {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 int m1v_encode_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
@@ -889,78 +983,32 @@ int m1v_encode_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, in
                           uint32_t *d_status, void *stream) {
     if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out && d_level_in && d_level_out))
         return rc;
-    if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
-        return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
+    if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
     PickArgs pa = {};
     pa.rate = (long long)bytes_per_frame;
     pa.capacity = (long long)buffer_bytes;
     pa.level_in = (const long long *)d_level_in;
     pa.level_out = (long long *)d_level_out;
-    return rate_encode(e, pa, true, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen, d_out, out_cap,
-                       d_frame_sizes, d_total, d_status, stream);
+    return rate_encode(e, pa, true, d_rgb, n_frames, first_frame_index, candidates, n_candidates, d_chosen,
+                       {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 // ---- batch budgets and constant bitrate that pick by distortion (m1v_rd_rate.h) -------------------------------------------------
-static unsigned long long pack_candidates(const uint8_t *candidates, int n_candidates) {
-    unsigned long long cand = 0;
-    for (int k = 0; k < n_candidates; k++) cand |= (unsigned long long)candidates[k] << (8 * k);
-    return cand;
-}
-
-static int launch_rd_chains(m1v_encoder *e, const unsigned long long *sizes, const unsigned long long *dist, int stride, int n_cand,
-                            int n_frames, const uint32_t *table_status, hipStream_t st) {
-    RdChainArgs ca = {sizes, dist, stride, n_cand, n_frames, table_status, e->d_rd_steps};
-    hipLaunchKernelGGL(k_rd_chains, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, ca);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
-}
-
-static int check_cbr_rate(uint64_t bytes_per_frame, uint64_t buffer_bytes) {
-    if (bytes_per_frame == 0 || buffer_bytes < bytes_per_frame || buffer_bytes >= (1ull << 62))
-        return fail(M1V_E_ARG, "bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62%s");
-    return M1V_OK;
-}
-
-static const char kNotFused[] = "the rd table needs the fused size table (m1v_size_table_fused): a debug hook has forced this encoder%s";
-
-// One rd table into the encoder's own tables, the chains and (inside encode_batch, where the batch's status word is known) the
-// batch pick, then the encode at the picked qualities as rate_encode's
 int m1v_encode_rd_batch_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
                                const uint8_t *candidates, int n_candidates, int rule, uint64_t limit, uint8_t *d_chosen,
                                uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes, uint64_t *d_frame_distortion,
                                uint64_t *d_total, uint32_t *d_status, void *stream) {
     if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
-    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
-    if (!e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
-    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
-                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
-        return rc;
-    if (n_frames > 0)
-        if (const int rc = launch_rd_chains(e, e->d_probe_sizes, e->d_probe_dist, e->max_frames, n_candidates, n_frames,
-                                            e->d_probe_status, (hipStream_t)stream))
-            return rc;
-    RdBatchArgs ba = {};
-    ba.steps = e->d_rd_steps;
-    ba.dist = e->d_probe_dist;
-    ba.stride = e->max_frames;
-    ba.n_frames = n_frames;
-    ba.n_cand = n_candidates;
-    ba.rule = rule;
-    ba.limit = limit;
-    ba.cand = pack_candidates(candidates, n_candidates);
-    ba.table_status = e->d_probe_status;
+    if (const int rc = check_rd_rule(rule)) return rc;
+    PickTable t;
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, true, stream, t)) return rc;
+    RdBatchArgs ba;
+    if (const int rc = rd_batch_chains(e, t, n_frames, rule, limit, (hipStream_t)stream, ba)) return rc;
     ba.chosen = d_chosen ? d_chosen : e->d_chosen;
     ba.pick_dist = (unsigned long long *)d_frame_distortion;
     ba.status = e->d_pick_status;
-    QualityArgs qa = {};
-    qa.quality = ba.chosen;
-    qa.pick_status = e->d_pick_status;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream,
-                        nullptr, &ba);
-}
-
-static void launch_rd_cbr(RdCbrArgs &ca, hipStream_t st) {
-    hipLaunchKernelGGL(k_rd_cbr_pick, dim3(1), dim3(kPickThreads), 0, st, ca);
+    const Selection sel = {select_by_rd_batch, &ba};
+    return encode_batch(e, d_rgb, n_frames, first_frame_index, &sel, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 int m1v_encode_rd_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index,
@@ -971,98 +1019,51 @@ int m1v_encode_rd_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames,
     if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out && d_level_in && d_level_out))
         return rc;
     if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
-    if (!e->plan.table_units) return fail(M1V_E_ARG, kNotFused);
-    if (const int rc = size_table_fused(e, d_rgb, n_frames, candidates, n_candidates, e->d_probe_sizes, e->d_probe_dist,
-                                        (size_t)e->max_frames, e->d_probe_status, (hipStream_t)stream))
-        return rc;
-    RdCbrArgs ca = {};
-    ca.sizes = e->d_probe_sizes;
-    ca.dist = e->d_probe_dist;
-    ca.stride = e->max_frames;
-    ca.n_cand = n_candidates;
-    ca.n_frames = n_frames;
-    ca.cand = pack_candidates(candidates, n_candidates);
-    ca.table_status = e->d_probe_status;
-    ca.rate = (long long)bytes_per_frame;
-    ca.capacity = (long long)buffer_bytes;
-    ca.level_in = (const long long *)d_level_in;
-    ca.level_out = (long long *)d_level_out;
-    ca.chosen = d_chosen ? d_chosen : e->d_chosen;
-    ca.pick_dist = (unsigned long long *)d_frame_distortion;
-    ca.status = e->d_pick_status;
-    launch_rd_cbr(ca, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    QualityArgs qa = {};
-    qa.quality = ca.chosen;
-    qa.pick_status = e->d_pick_status;
-    return encode_batch(e, d_rgb, n_frames, first_frame_index, &qa, false, d_out, out_cap, d_frame_sizes, d_total, d_status, stream);
+    PickTable t;
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, true, stream, t)) return rc;
+    RdCbrArgs out = {};
+    out.chosen = d_chosen ? d_chosen : e->d_chosen;
+    out.pick_dist = (unsigned long long *)d_frame_distortion;
+    out.status = e->d_pick_status;
+    if (const int rc = launch_rd_cbr_pick(t, n_frames, bytes_per_frame, buffer_bytes, d_level_in, d_level_out, out, (hipStream_t)stream)) return rc;
+    return encode_at(e, d_rgb, n_frames, first_frame_index, out.chosen, out.status, false, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
 }
 
 // The picks alone, on a table the caller holds ([k * n_frames + f])
-static int check_pick_call(const m1v_encoder *e, const void *d_sizes, const void *d_distortion, int n_frames, int n_candidates,
-                           const void *d_picks, const void *d_status) {
-    if (!e || !d_sizes || !d_distortion || !d_picks || !d_status) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_candidates < 1 || n_candidates > kMaxCandidates) return fail(M1V_E_ARG, "1 to 8 candidates%s");
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
-    return M1V_OK;
-}
-
 int m1v_rd_batch_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
                              int n_frames, int n_candidates, int rule, uint64_t limit, uint8_t *d_picks,
                              uint64_t *d_pick_distortion, uint32_t *d_status, void *stream) {
-    if (const int rc = check_pick_call(e, d_sizes, d_distortion, n_frames, n_candidates, d_picks, d_status)) return rc;
-    if (rule != M1V_RD_BEST_IN_BUDGET && rule != M1V_RD_SMALLEST_AT_DISTORTION) return fail(M1V_E_ARG, "unknown rate-distortion rule%s");
+    if (const int rc = check_candidate_call(e, d_sizes && d_distortion && d_picks && d_status, nullptr, n_candidates, n_frames, true, true)) return rc;
+    if (const int rc = check_rd_rule(rule)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     if (n_frames == 0) {
         HIP_TRY(hipMemsetAsync(d_status, 0, 4, (hipStream_t)stream));
         return M1V_OK;
     }
-    if (const int rc = launch_rd_chains(e, (const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames,
-                                        n_candidates, n_frames, d_table_status, (hipStream_t)stream))
-        return rc;
-    RdBatchArgs ba = {};
-    ba.steps = e->d_rd_steps;
-    ba.dist = (const unsigned long long *)d_distortion;
-    ba.stride = n_frames;
-    ba.n_frames = n_frames;
-    ba.n_cand = n_candidates;
-    ba.rule = rule;
-    ba.limit = limit;
-    ba.table_status = d_table_status;
+    const PickTable t = {(const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames, n_candidates, 0, d_table_status};
+    RdBatchArgs ba;
+    if (const int rc = rd_batch_chains(e, t, n_frames, rule, limit, (hipStream_t)stream, ba)) return rc;
     ba.picks = d_picks;
     ba.pick_dist = (unsigned long long *)d_pick_distortion;
     ba.status = d_status;
-    hipLaunchKernelGGL(k_rd_batch_pick, dim3((unsigned)((n_frames * kMaxCandidates + kRdPickThreads - 1) / kRdPickThreads)),
-                       dim3(kRdPickThreads), 0, (hipStream_t)stream, ba);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
+    return launch_rd_batch_pick(ba, nullptr, (hipStream_t)stream);
 }
 
 int m1v_rd_cbr_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
                            int n_frames, int n_candidates, uint64_t bytes_per_frame, uint64_t buffer_bytes,
                            const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
                            uint32_t *d_status, void *stream) {
-    if (const int rc = check_pick_call(e, d_sizes, d_distortion, n_frames, n_candidates, d_picks, d_status)) return rc;
-    if (!d_level_in || !d_level_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (const int rc = check_candidate_call(e, d_sizes && d_distortion && d_picks && d_status, nullptr, n_candidates, n_frames,
+                                            d_level_in && d_level_out, true))
+        return rc;
     if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    RdCbrArgs ca = {};
-    ca.sizes = (const unsigned long long *)d_sizes;
-    ca.dist = (const unsigned long long *)d_distortion;
-    ca.stride = n_frames;
-    ca.n_cand = n_candidates;
-    ca.n_frames = n_frames;
-    ca.table_status = d_table_status;
-    ca.rate = (long long)bytes_per_frame;
-    ca.capacity = (long long)buffer_bytes;
-    ca.level_in = (const long long *)d_level_in;
-    ca.level_out = (long long *)d_level_out;
-    ca.picks = d_picks;
-    ca.pick_dist = (unsigned long long *)d_pick_distortion;
-    ca.status = d_status;
-    launch_rd_cbr(ca, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return M1V_OK;
+    const PickTable t = {(const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames, n_candidates, 0, d_table_status};
+    RdCbrArgs out = {};
+    out.picks = d_picks;
+    out.pick_dist = (unsigned long long *)d_pick_distortion;
+    out.status = d_status;
+    return launch_rd_cbr_pick(t, n_frames, bytes_per_frame, buffer_bytes, d_level_in, d_level_out, out, (hipStream_t)stream);
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

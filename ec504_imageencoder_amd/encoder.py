@@ -270,18 +270,23 @@ class Mpeg1Encoder:
         is 1 (3 channels on the tile path, 4 channels always).  Asynchronous on torch's current stream (complete in stream order,
         pipelined mode included).  status: optional CUDA int32 tensor [K] that receives each quality's status bits
         (STATUS_UNENCODABLE: that row is undefined)."""
+        return self._table("frame_size_table", rgb, qualities, status, False)[0]
+
+    def _table(self, name, rgb, qualities, status, with_dist):
+        """The table call behind the method `name`: its [K, n] rows, (sizes,) or with_dist (sizes, distortion)."""
         import torch
         n = rgb.shape[0]
         self._check_input(rgb)
         qs = [int(q) for q in qualities]
         if not 1 <= len(qs) <= _ffi.MAX_CANDIDATES or any(q < 1 or q > 255 for q in qs):
-            raise EncoderError(_ffi.E_ARG, "frame_size_table: 1 to 8 qualities")
+            raise EncoderError(_ffi.E_ARG, f"{name}: 1 to 8 qualities")
         if status is not None:
             assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= len(qs), "status: CUDA int32, one per quality"
         q_buf = (C.c_uint8 * len(qs))(*qs)
-        sizes = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
-        _call("m1v_frame_size_table_device", self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(status), _stream())
-        return sizes[:len(qs) * n].view(len(qs), n)
+        rows = [torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device) for _ in range(2 if with_dist else 1)]
+        _call("m1v_frame_rd_table_device" if with_dist else "m1v_frame_size_table_device", self._h, _ptr(rgb), n, q_buf, len(qs),
+              *(_ptr(r) for r in rows), _ptr(status), _stream())
+        return tuple(r[:len(qs) * n].view(len(qs), n) for r in rows)
 
     def frame_rd_table(self, rgb, qualities, status=None):
         """frame_size_table plus the distortion (include/mpeg1_hip.h, m1v_frame_rd_table_device): (sizes, distortion), two int64
@@ -289,19 +294,7 @@ class Mpeg1Encoder:
         reference's coefficient domain, between what the encoder transformed of frame f and what its record at qualities[k]
         carries.  One fused pass; needs size_table_fused.  Asynchronous on torch's current stream.  status: as frame_size_table
         (STATUS_UNENCODABLE at k: both rows k are undefined)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        qs = [int(q) for q in qualities]
-        if not 1 <= len(qs) <= _ffi.MAX_CANDIDATES or any(q < 1 or q > 255 for q in qs):
-            raise EncoderError(_ffi.E_ARG, "frame_rd_table: 1 to 8 qualities")
-        if status is not None:
-            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= len(qs), "status: CUDA int32, one per quality"
-        q_buf = (C.c_uint8 * len(qs))(*qs)
-        sizes = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
-        dist = torch.zeros(max(len(qs) * n, 1), dtype=torch.int64, device=rgb.device)
-        _call("m1v_frame_rd_table_device", self._h, _ptr(rgb), n, q_buf, len(qs), _ptr(sizes), _ptr(dist), _ptr(status), _stream())
-        return sizes[:len(qs) * n].view(len(qs), n), dist[:len(qs) * n].view(len(qs), n)
+        return self._table("frame_rd_table", rgb, qualities, status, True)
 
     @staticmethod
     def _candidates(candidates, where):
@@ -342,63 +335,65 @@ class Mpeg1Encoder:
             raise EncoderError(_ffi.E_NOSPACE if status & _ffi.STATUS_NOSPACE else _ffi.E_SCRATCH, name)
         return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:n].cpu()], status
 
-    def encode_to_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
-        """Synchronous: every frame at the largest of `candidates` (1..8 qualities, strictly increasing, each <= quality_factor)
-        whose record fits its budget, else at the smallest.  max_frame_bytes: one budget for every frame, or one per frame
-        (a sequence or a CUDA int64 tensor).  Returns (bytes, sizes, chosen, over_budget_frames)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        cand_buf = self._candidates(candidates, "encode_to_budget")
-        if isinstance(max_frame_bytes, torch.Tensor):
-            assert max_frame_bytes.is_cuda and max_frame_bytes.dtype == torch.int64 and max_frame_bytes.numel() == n
-            budget, d_budget = 0, max_frame_bytes.contiguous()
-        elif isinstance(max_frame_bytes, numbers.Integral):
-            budget, d_budget = max_frame_bytes, None
-        else:
-            b = [int(x) for x in max_frame_bytes]
-            assert len(b) == n, "max_frame_bytes: one entry per frame"
-            budget, d_budget = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
-        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        data, sizes_l, _ = self._encode_retrying(
-            rgb, "encode_to_budget",
-            lambda out, sizes, meta: _call(
-                "m1v_encode_budget_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), budget,
-                _ptr(d_budget), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
-        chosen_l = [int(c) for c in chosen[:n].cpu()]
-        budgets = [budget] * n if d_budget is None else [int(x) for x in d_budget[:n].cpu()]
-        over = [f for f in range(n) if sizes_l[f] > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
-        return data, sizes_l, chosen_l, over
-
-    def _encode_rd(self, name, rule, rgb, limit, candidates, first_frame_index):
-        """The two rate-distortion encodes: (bytes, sizes, chosen, frames over their limit, distortion per frame)."""
+    def _encode_candidates(self, name, fn, rgb, candidates, first_frame_index, middle, with_dist=False):
+        """The encodes that take candidates, for the method `name`: the C function `fn`, whose arguments between the candidates
+        and d_chosen (its rule's) are `middle`, through _encode_retrying.  Returns (bytes, sizes, chosen, distortion per frame
+        or None, status bits)."""
         import torch
         n = rgb.shape[0]
         self._check_input(rgb)
         cand_buf = self._candidates(candidates, name)
-        if isinstance(limit, torch.Tensor):
-            assert limit.is_cuda and limit.dtype == torch.int64 and limit.numel() == n, "limit: CUDA int64, one per frame"
-            scalar, d_limits = 0, limit.contiguous()
-        elif isinstance(limit, numbers.Integral):
-            if not 0 <= int(limit) < 2 ** 64:
-                raise EncoderError(_ffi.E_ARG, f"{name}: the limit must fit uint64")
-            scalar, d_limits = int(limit), None
-        else:
-            b = [int(x) for x in limit]
-            assert len(b) == n, "limit: one entry per frame"
-            scalar, d_limits = 0, torch.tensor(b if b else [0], dtype=torch.int64).to(rgb.device)
         chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
-        data, sizes_l, _ = self._encode_retrying(
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device) if with_dist else None
+        data, sizes_l, status = self._encode_retrying(
             rgb, name,
             lambda out, sizes, meta: _call(
-                "m1v_encode_rd_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rule, scalar,
-                _ptr(d_limits), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist), *_meta_ptrs(meta), _stream()))
-        dist_l = [int(d) for d in dist[:n].cpu()]
-        limits = [scalar] * n if d_limits is None else [int(x) for x in d_limits[:n].cpu()]
+                fn, self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), *middle, _ptr(chosen), _ptr(out),
+                out.numel(), _ptr(sizes), *((_ptr(dist),) if with_dist else ()), *_meta_ptrs(meta), _stream()))
+        return (data, sizes_l, [int(c) for c in chosen[:n].cpu()], [int(d) for d in dist[:n].cpu()] if with_dist else None, status)
+
+    @staticmethod
+    def _uint64(value, what):
+        if not 0 <= int(value) < 2 ** 64:
+            raise EncoderError(_ffi.E_ARG, f"{what} must fit uint64")
+        return int(value)
+
+    @staticmethod
+    def _per_frame_limit(name, limit, n, device):
+        """One limit for every frame, or one per frame (a sequence or a CUDA int64 tensor): (scalar, tensor or None)."""
+        import torch
+        if isinstance(limit, torch.Tensor):
+            assert limit.is_cuda and limit.dtype == torch.int64 and limit.numel() == n, "limit: CUDA int64, one per frame"
+            return 0, limit.contiguous()
+        if isinstance(limit, numbers.Integral):
+            return Mpeg1Encoder._uint64(limit, f"{name}: the limit"), None
+        b = [int(x) for x in limit]
+        assert len(b) == n, "limit: one entry per frame"
+        return 0, torch.tensor(b if b else [0], dtype=torch.int64).to(device)
+
+    def _encode_per_frame(self, name, fn, rule_args, rgb, limit, candidates, first_frame_index, with_dist):
+        """The encodes with a limit per frame: _encode_candidates' results and each frame's limit."""
+        n = rgb.shape[0]
+        scalar, d_limits = self._per_frame_limit(name, limit, n, rgb.device)
+        res = self._encode_candidates(name, fn, rgb, candidates, first_frame_index, (*rule_args, scalar, _ptr(d_limits)), with_dist)
+        return res, [scalar] * n if d_limits is None else [int(x) for x in d_limits[:n].cpu()]
+
+    def encode_to_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
+        """Synchronous: every frame at the largest of `candidates` (1..8 qualities, strictly increasing, each <= quality_factor)
+        whose record fits its budget, else at the smallest.  max_frame_bytes: one budget for every frame, or one per frame
+        (a sequence or a CUDA int64 tensor).  Returns (bytes, sizes, chosen, over_budget_frames)."""
+        (data, sizes_l, chosen_l, _, _), budgets = self._encode_per_frame(
+            "encode_to_budget", "m1v_encode_budget_device", (), rgb, max_frame_bytes, candidates, first_frame_index, False)
+        over = [f for f, s in enumerate(sizes_l) if s > budgets[f]]   # (STATUS_OVER_BUDGET is set iff there are any)
+        return data, sizes_l, chosen_l, over
+
+    def _encode_rd(self, name, rule, rgb, limit, candidates, first_frame_index):
+        """The two rate-distortion encodes: (bytes, sizes, chosen, frames over their limit, distortion per frame)."""
+        (data, sizes_l, chosen_l, dist_l, _), limits = self._encode_per_frame(
+            name, "m1v_encode_rd_device", (rule,), rgb, limit, candidates, first_frame_index, True)
         bounded = sizes_l if rule == _ffi.RD_BEST_IN_BUDGET else dist_l
-        over = [f for f in range(n) if bounded[f] > limits[f]]  # (the rule's status bit is set iff there are any)
-        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], over, dist_l
+        over = [f for f, x in enumerate(bounded) if x > limits[f]]  # (the rule's status bit is set iff there are any)
+        return data, sizes_l, chosen_l, over, dist_l
 
     def encode_best_in_budget(self, rgb, max_frame_bytes, candidates, first_frame_index=0):
         """Synchronous: every frame at the candidate of LEAST DISTORTION among those whose record fits its budget (ties: the
@@ -429,68 +424,18 @@ class Mpeg1Encoder:
         fits, and the leftover bytes spent on the cheapest upgrades to the next (include/mpeg1_hip.h,
         m1v_encode_batch_budget_device).  over_budget: even every frame at the smallest candidate does not fit (all are there).
         Returns (bytes, sizes, chosen, over_budget)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        cand_buf = self._candidates(candidates, "encode_to_batch_budget")
-        if not 0 <= int(batch_bytes) < 2 ** 64:
-            raise EncoderError(_ffi.E_ARG, "encode_to_batch_budget: batch_bytes must fit uint64")
-        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        data, sizes_l, status = self._encode_retrying(
-            rgb, "encode_to_batch_budget",
-            lambda out, sizes, meta: _call(
-                "m1v_encode_batch_budget_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf),
-                int(batch_bytes), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
-        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], bool(status & _ffi.STATUS_OVER_BUDGET)
-
-    def encode_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
-        """Synchronous constant bitrate (a leaky bucket, include/mpeg1_hip.h m1v_encode_cbr_device): bytes_per_frame per frame
-        into a buffer of buffer_bytes.  level: CUDA int64 tensor [1], the bytes available to the next frame; each frame goes at
-        the largest of `candidates` whose record fits it, else at the smallest.  The level is advanced over the batch in place,
-        only when the call succeeds, so that consecutive calls form one stream.  Returns (bytes, sizes, chosen,
-        over_budget_frames)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        assert level.is_cuda and level.dtype == torch.int64 and level.numel() == 1, "level: CUDA int64 tensor of one element"
-        cand_buf = self._candidates(candidates, "encode_at_bitrate")
-        rate, cap = int(bytes_per_frame), int(buffer_bytes)
-        if not 1 <= rate <= cap < 2 ** 62:
-            raise EncoderError(_ffi.E_ARG, "encode_at_bitrate: need 1 <= bytes_per_frame <= buffer_bytes < 2^62")
-        level_in = level.contiguous()
-        start = int(level_in.item())
-        level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
-        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        data, sizes_l, _ = self._encode_retrying(
-            rgb, "encode_at_bitrate",
-            lambda out, sizes, meta: _call(
-                "m1v_encode_cbr_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap,
-                _ptr(level_in), _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), *_meta_ptrs(meta), _stream()))
-        level.copy_(level_out.view_as(level))
-        over, L = [], min(start, cap)                # the level before each frame, replayed from the sizes
-        for f, s in enumerate(sizes_l):
-            if s > L:
-                over.append(f)                       # (STATUS_OVER_BUDGET is set iff there are any)
-            L = min(cap, L - s + rate)
-        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], over
+        budget = self._uint64(batch_bytes, "encode_to_batch_budget: batch_bytes")
+        data, sizes_l, chosen_l, _, status = self._encode_candidates(
+            "encode_to_batch_budget", "m1v_encode_batch_budget_device", rgb, candidates, first_frame_index, (budget,))
+        return data, sizes_l, chosen_l, bool(status & _ffi.STATUS_OVER_BUDGET)
 
     def _encode_rd_batch(self, name, rule, rgb, limit, candidates, first_frame_index):
         """The two batch forms that pick by distortion: (bytes, sizes, chosen, over the limit, distortion per frame)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        cand_buf = self._candidates(candidates, name)
-        if not 0 <= int(limit) < 2 ** 64:
-            raise EncoderError(_ffi.E_ARG, f"{name}: the limit must fit uint64")
-        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
-        data, sizes_l, status = self._encode_retrying(
-            rgb, name,
-            lambda out, sizes, meta: _call(
-                "m1v_encode_rd_batch_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rule,
-                int(limit), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist), *_meta_ptrs(meta), _stream()))
+        middle = (rule, self._uint64(limit, f"{name}: the limit"))
+        data, sizes_l, chosen_l, dist_l, status = self._encode_candidates(
+            name, "m1v_encode_rd_batch_device", rgb, candidates, first_frame_index, middle, with_dist=True)
         bit = _ffi.STATUS_OVER_BUDGET if rule == _ffi.RD_BEST_IN_BUDGET else _ffi.STATUS_OVER_DISTORTION
-        return data, sizes_l, [int(c) for c in chosen[:n].cpu()], bool(status & bit), [int(d) for d in dist[:n].cpu()]
+        return data, sizes_l, chosen_l, bool(status & bit), dist_l
 
     def encode_best_in_batch_budget(self, rgb, batch_bytes, candidates, first_frame_index=0):
         """Synchronous: the whole batch within batch_bytes (the sum of its records) at the least total distortion the greedy
@@ -520,7 +465,8 @@ class Mpeg1Encoder:
 
     @staticmethod
     def _over_level(sizes_l, start, rate, cap):
-        """The frames whose record exceeds the level before them, replayed from the sizes."""
+        """The frames whose record exceeds the level before them, replayed from the sizes (STATUS_OVER_BUDGET is set iff there
+        are any)."""
         over, L = [], min(start, cap)
         for f, s in enumerate(sizes_l):
             if s > L:
@@ -528,30 +474,34 @@ class Mpeg1Encoder:
             L = min(cap, L - s + rate)
         return over
 
+    def _encode_bitrate(self, name, fn, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index, with_dist):
+        """The two bitrate encodes: (bytes, sizes, chosen, over_budget_frames, distortion per frame or None)."""
+        import torch
+        rate, cap = self._bitrate_args(name, bytes_per_frame, buffer_bytes, level)
+        level_in = level.contiguous()
+        start = int(level_in.item())
+        level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
+        data, sizes_l, chosen_l, dist_l, _ = self._encode_candidates(
+            name, fn, rgb, candidates, first_frame_index, (rate, cap, _ptr(level_in), _ptr(level_out)), with_dist)
+        level.copy_(level_out.view_as(level))
+        return data, sizes_l, chosen_l, self._over_level(sizes_l, start, rate, cap), dist_l
+
+    def encode_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
+        """Synchronous constant bitrate (a leaky bucket, include/mpeg1_hip.h m1v_encode_cbr_device): bytes_per_frame per frame
+        into a buffer of buffer_bytes.  level: CUDA int64 tensor [1], the bytes available to the next frame; each frame goes at
+        the largest of `candidates` whose record fits it, else at the smallest.  The level is advanced over the batch in place,
+        only when the call succeeds, so that consecutive calls form one stream.  Returns (bytes, sizes, chosen,
+        over_budget_frames)."""
+        return self._encode_bitrate("encode_at_bitrate", "m1v_encode_cbr_device", rgb, bytes_per_frame, buffer_bytes, candidates,
+                                    level, first_frame_index, False)[:4]
+
     def encode_best_at_bitrate(self, rgb, bytes_per_frame, buffer_bytes, candidates, level, first_frame_index=0):
         """Synchronous constant bitrate that picks by distortion (include/mpeg1_hip.h, m1v_encode_rd_cbr_device): the leaky bucket
         of encode_at_bitrate, each frame at the candidate of LEAST DISTORTION whose record fits the level (ties: the smaller
         record, then the smaller quality), else at its smallest record.  The level is advanced over the batch in place, only
         when the call succeeds.  Returns (bytes, sizes, chosen, over_budget_frames, distortion)."""
-        import torch
-        n = rgb.shape[0]
-        self._check_input(rgb)
-        rate, cap = self._bitrate_args("encode_best_at_bitrate", bytes_per_frame, buffer_bytes, level)
-        cand_buf = self._candidates(candidates, "encode_best_at_bitrate")
-        level_in = level.contiguous()
-        start = int(level_in.item())
-        level_out = torch.empty(1, dtype=torch.int64, device=level.device)   # a retry starts from the same level
-        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
-        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device)
-        data, sizes_l, _ = self._encode_retrying(
-            rgb, "encode_best_at_bitrate",
-            lambda out, sizes, meta: _call(
-                "m1v_encode_rd_cbr_device", self._h, _ptr(rgb), n, int(first_frame_index), cand_buf, len(cand_buf), rate, cap,
-                _ptr(level_in), _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist),
-                *_meta_ptrs(meta), _stream()))
-        level.copy_(level_out.view_as(level))
-        return (data, sizes_l, [int(c) for c in chosen[:n].cpu()], self._over_level(sizes_l, start, rate, cap),
-                [int(d) for d in dist[:n].cpu()])
+        return self._encode_bitrate("encode_best_at_bitrate", "m1v_encode_rd_cbr_device", rgb, bytes_per_frame, buffer_bytes,
+                                    candidates, level, first_frame_index, True)
 
     @staticmethod
     def _rd_tables(sizes, dist, status):
@@ -569,11 +519,10 @@ class Mpeg1Encoder:
         (picks, over): the candidate INDEX of every frame and whether the rule's limit was missed."""
         import torch
         sizes, dist, K, n = self._rd_tables(sizes, dist, status)
-        if not 0 <= int(limit) < 2 ** 64:
-            raise EncoderError(_ffi.E_ARG, "rd_batch_pick: the limit must fit uint64")
+        limit = self._uint64(limit, "rd_batch_pick: the limit")
         picks = torch.zeros(max(n, 1), dtype=torch.uint8, device=sizes.device)
         word = torch.zeros(1, dtype=torch.int32, device=sizes.device)
-        _call("m1v_rd_batch_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, int(rule), int(limit), _ptr(picks),
+        _call("m1v_rd_batch_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, int(rule), limit, _ptr(picks),
               None, _ptr(word), _stream())
         bits = int(word.item())
         return [int(k) for k in picks[:n].cpu()], bool(bits & (_ffi.STATUS_OVER_BUDGET | _ffi.STATUS_OVER_DISTORTION))

@@ -437,4 +437,8 @@ def test_argument_errors(torch_cuda):
     with pytest.raises(EncoderError) as ei:
         enc.encode_to_batch_budget(dev, 10 ** 6, (8, 4))
     assert ei.value.code == _ffi.E_ARG
+    for budget in (-1, 2 ** 64):                                   # a scalar budget that does not fit uint64
+        with pytest.raises(EncoderError) as ei:
+            enc.encode_to_budget(dev, budget, good)
+        assert ei.value.code == _ffi.E_ARG
     enc.close()

@@ -284,6 +284,72 @@ def test_a_profiled_call_counts_two_launches(torch_cuda, noise):
     enc.close()
 
 
+@pytest.mark.parametrize("call", ["rd", "rd_batch", "rd_cbr"])
+@pytest.mark.parametrize("stage", [1, 2, 3])
+def test_failed_call_leaves_the_encoder_correct(torch_cuda, noise, stage, call):
+    """m1v_debug_fail_encode in front of each of the three encodes that pick by distortion: the call returns E_HIP, the bitrate
+    form leaves d_level_in alone, and the same call again, a plain encode and every rule after it are the oracle's.
+    Limitation: these calls need the fused table, whose pass comes first and has the hook at all three stages, so the failure
+    is always the table's.  This pins the table's poison recovery inside these calls, not a failure in the encode behind it."""
+    from ec504_imageencoder_amd import Mpeg1Encoder, _ffi
+    from test_gpu_rd_encode import _model, _rd_device
+    torch = torch_cuda
+    n, first, K = 5, noise["first"], len(NOISE_CANDS)
+    S, D = [row[:n] for row in noise["s"]], [row[:n] for row in noise["d"]]
+    enc = Mpeg1Encoder(noise["W"], noise["H"], 12, "full", max_frames=n)
+    assert enc.path == "tiles" and enc.size_table_fused == 1
+    if stage == 2:
+        enc.set_pipelined(True)
+    dev = torch.from_numpy(noise["px"][:n]).cuda()
+
+    def records(qs):
+        recs = [noise["recs"][f, q] for f, q in enumerate(qs)]
+        return b"".join(recs), [len(r) for r in recs]
+
+    per_frame = sorted(x for row in S for x in row)[K * n // 2]
+    budget = _batch_limits(S, D, M.BEST_IN_BUDGET)[0][0]
+    rate, cap, level = _bitrate_setup(S, D)
+    out, sizes, chosen, dist, meta = _buffers(torch, enc, n, True, True)
+    lin = torch.tensor([level], dtype=torch.int64).cuda()
+    lout = torch.full((1,), -777, dtype=torch.int64, device="cuda")
+    L = _ffi.lib()
+    cbuf = (C.c_uint8 * K)(*NOISE_CANDS)
+    results = (_p(chosen), _p(out), out.numel(), _p(sizes), _p(dist), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8),
+               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    L.m1v_debug_fail_encode(stage)
+    try:
+        if call == "rd":
+            rc = L.m1v_encode_rd_device(enc._h, _p(dev), n, first, cbuf, K, M.BEST_IN_BUDGET, per_frame, None, *results)
+        elif call == "rd_batch":
+            rc = L.m1v_encode_rd_batch_device(enc._h, _p(dev), n, first, cbuf, K, M.BEST_IN_BUDGET, budget, *results)
+        else:
+            rc = L.m1v_encode_rd_cbr_device(enc._h, _p(dev), n, first, cbuf, K, rate, cap, _p(lin), _p(lout), *results)
+        assert rc == _ffi.E_HIP
+    finally:
+        L.m1v_debug_fail_encode(0)
+    enc.flush()
+    torch.cuda.synchronize()
+    assert int(lin.item()) == level
+    # the same call again
+    if call == "rd":
+        picks, over = _model(M.BEST_IN_BUDGET, S, D, [per_frame] * n)
+        got, sizes, chosen, dist, status = _rd_device(torch, enc, dev, NOISE_CANDS, M.BEST_IN_BUDGET, per_frame, first)
+    elif call == "rd_batch":
+        picks, over = M.batch_pick(S, D, M.BEST_IN_BUDGET, budget)
+        got, sizes, chosen, dist, status = _batch_device(torch, enc, dev, NOISE_CANDS, M.BEST_IN_BUDGET, budget, first)
+    else:
+        picks, over, level_out = M.bitrate_walk(S, D, rate, cap, level)
+        got, sizes, chosen, dist, status, lout = _cbr_device(torch, enc, dev, NOISE_CANDS, rate, cap, level, first)
+        assert lout == level_out
+    assert len(set(picks)) > 1 and status == (16 if over else 0)
+    assert chosen == [NOISE_CANDS[k] for k in picks] and dist == [D[k][f] for f, k in enumerate(picks)]
+    assert (got, sizes) == records([NOISE_CANDS[k] for k in picks])
+    # a plain encode, then both batch rules and the bitrate form
+    assert enc.encode_to_bytes(dev, first_frame_index=first) == records([12] * n)
+    _check_batch_and_bitrate(torch, enc, dev, NOISE_CANDS, S, D, first, records, False)
+    enc.close()
+
+
 def test_argument_errors_and_the_empty_batch(torch_cuda):
     from ec504_imageencoder_amd import EncoderError, Mpeg1Encoder, _ffi
     torch = torch_cuda
