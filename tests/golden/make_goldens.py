@@ -7,6 +7,7 @@ coefficient arrays) and the outputs the reference produced for them.  No referen
 
     python tests/golden/make_goldens.py              (everything)
     python tests/golden/make_goldens.py code_space   (only vlc_code_space.json)
+    python tests/golden/make_goldens.py geometry_space   (only geometry_space.json and profiles/r17_geometry_census.txt)
 """
 import hashlib
 import json
@@ -103,10 +104,30 @@ def code_space_goldens():
               open(os.path.join(HERE, "vlc_code_space.json"), "w"), indent=1)
 
 
+def geometry_space_goldens():
+    """geometry_space.json: the ORACLE's records over tests/geometry_space.all_members, one SHA-256 per member and content.
+    The members of even height are those tests/test_geometry_space_cpu.py compares with the reference where this file is
+    written; the reference cannot run at the odd heights, which the oracle alone defines."""
+    import geometry_space as gs
+    import oracle_ffi as orc
+    members = gs.all_members()
+    json.dump({"order": "per member and content: the records of orc.encode_frame on geometry_space.pixels(member, content) at the "
+                        "content's quality, frames 0 .. n - 1 as frame indices 17 .. 17 + n - 1, back to back",
+               "members": len(members),
+               "sha256": {gs.name(t): gs.digest(orc, t) for t in members}},
+              open(os.path.join(HERE, "geometry_space.json"), "w"), indent=1)
+    # the census that tests/test_geometry_space_cpu.py compares with: rewritten here and nowhere else
+    with open(os.path.join(os.path.dirname(os.path.dirname(HERE)), "profiles", "r17_geometry_census.txt"), "w") as fh:
+        fh.write(gs.census_text())
+
+
 def main():
     assert ref.ensure_built(), "reference sources not available"
     if sys.argv[1:] == ["code_space"]:          # only tests/golden/vlc_code_space.json
         code_space_goldens()
+        return
+    if sys.argv[1:] == ["geometry_space"]:      # only tests/golden/geometry_space.json
+        geometry_space_goldens()
         return
     rng = np.random.default_rng(504)
 
@@ -229,6 +250,9 @@ def main():
 
     # 10. the whole code space of the block coder, as hashes
     code_space_goldens()
+
+    # 11. the oracle's records over the geometry space, as hashes
+    geometry_space_goldens()
 
     for f in sorted(os.listdir(HERE)):
         print(f"{os.path.getsize(os.path.join(HERE, f)):>10}  {f}")

@@ -4,6 +4,11 @@ Covers every row of SURVEY §8(a): colour conversion (exhaustive 2^24), subsampl
 scaling, quantise+zigzag, run-length, DC/AC/EOB coding incl. the KATs listed in SURVEY §8(a) rows
 10-11, slice/macroblock headers, and the whole driver end to end (STRICT = unmodified reference,
 FULL = reference with the two loop-bound literals restored).
+
+The driver cases all have EVEN heights: at an odd height the reference corrupts its heap (glibc "malloc(): invalid size",
+exit -6, at every width tried with H in {33, 35, 47, 49} and at 105x49, 333x301, 31x47, 143x65, 255x127; DESIGN.md, "Tests: the
+geometry space"), so odd heights are outside its behaviour and nothing here runs it there.  Odd widths are fine
+(tests/test_geometry_space_cpu.py compares 33, 35 and 47 wide pictures and the even-height sizes of the geometry space).
 """
 import hashlib
 import os
