@@ -28,6 +28,17 @@ class PlaneLayout(C.Structure):
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
+SAMPLES_YUY2, SAMPLES_UYVY, SAMPLES_YVYU, SAMPLES_P010 = 0, 1, 2, 3
+SAMPLE_PRESETS = {"yuy2": SAMPLES_YUY2, "uyvy": SAMPLES_UYVY, "yvyu": SAMPLES_YVYU, "p010": SAMPLES_P010}
+
+
+class SampleLayout(C.Structure):
+    """m1v_sample_layout (include/mpeg1_hip.h): the plane layout with the distance between neighbouring luma samples."""
+    _fields_ = [(name, C.c_size_t) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "y_step", "c_step", "frame_stride")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
 _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
@@ -44,6 +55,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_debug_set_input_mode", "m1v_reserve_scratch", "m1v_scratch_bytes", "m1v_debug_set_path", "m1v_path_in_use", "m1v_debug_fail_alloc",
     "m1v_debug_fail_encode", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
     "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
+    "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -172,6 +184,12 @@ def lib():
     L.m1v_set_plane_layout.restype = C.c_int
     L.m1v_plane_layout_in_force.argtypes = [vp, C.POINTER(PlaneLayout)]
     L.m1v_plane_layout_in_force.restype = C.c_int
+    L.m1v_sample_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SampleLayout)]
+    L.m1v_sample_layout_preset.restype = C.c_int
+    L.m1v_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
+    L.m1v_set_sample_layout.restype = C.c_int
+    L.m1v_sample_layout_in_force.argtypes = [vp, C.POINTER(SampleLayout)]
+    L.m1v_sample_layout_in_force.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

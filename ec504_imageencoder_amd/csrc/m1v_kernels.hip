@@ -1259,6 +1259,7 @@ constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 
 #include "m1v_tiles.h"
 #include "m1v_planes.h"
+#include "m1v_step2.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1779,7 +1780,7 @@ struct m1v_encoder {
         uint32_t row_pitch = 0;               // bytes from a picture row to the next
         unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
         int order = M1V_ORDER_RGB;
-        uint32_t y_off = 0, cb_off = 0, cr_off = 0, y_pitch = 0, c_pitch = 0, c_step = 0;
+        uint32_t y_off = 0, cb_off = 0, cr_off = 0, y_pitch = 0, c_pitch = 0, y_step = 0, c_step = 0;
         unsigned long long extent = 0;        // bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
@@ -2014,23 +2015,23 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
-enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kTileVariants = kPlanes + 2 };
+enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kStep2 = kPlanes + 2, kTileVariants = kPlanes + 3 };
 #define M1V_PAIR(K, ...) {(const void *)&K<false, __VA_ARGS__>, (const void *)&K<true, __VA_ARGS__>}
-#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES)                                                              \
+#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES, STEP2)                                                       \
     {PACKED3, PACKED4, M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 1),                  \
      M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 1), M1V_PAIR(PLANES, M1V_TILE_RING, 1), \
-     M1V_PAIR(PLANES, M1V_TILE_RING, 2)}
+     M1V_PAIR(PLANES, M1V_TILE_RING, 2), M1V_PAIR(STEP2, M1V_TILE_RING)}
 static const struct Kernels {
     const void *tile[3][kTileVariants][2];
     const void *dense[4][2];
     const void *strips[2][2];
 } kKernels = {
     // (packed 4-channel pictures encode on the run kernels)
-    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes),
+    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes, k_encode_step2),
      M1V_TILE_FAMILY(M1V_PAIR(k_size_table_tiles, M1V_TILE_RING), M1V_PAIR(k_size_table_rgba, M1V_TILE_RING), k_size_table_surface,
-                     k_size_table_planes),
+                     k_size_table_planes, k_size_table_step2),
      M1V_TILE_FAMILY(M1V_PAIR(k_rd_table_tiles, M1V_TILE_RING), M1V_PAIR(k_rd_table_rgba, M1V_TILE_RING), k_rd_table_surface,
-                     k_rd_table_planes)},
+                     k_rd_table_planes, k_rd_table_step2)},
     {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
      {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
      {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
@@ -2056,7 +2057,7 @@ static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->q
 // chroma step to an instantiation
 static int tile_variant(const m1v_encoder *e) {
     const m1v_encoder::Layout &l = e->layout;
-    if (l.kind == LayoutKind::planes) return kPlanes + (int)l.c_step - 1;
+    if (l.kind == LayoutKind::planes) return l.y_step == 2 ? kStep2 : kPlanes + (int)l.c_step - 1;
     if (l.kind == LayoutKind::surface) return kSurface + (e->g.C == 4 ? 2 : 0) + l.order;
     return e->g.C == 4 ? kPacked4 : kPacked3;
 }

@@ -578,7 +578,9 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::planes) return fail(M1V_E_ARG, "a plane layout is in force: ask m1v_plane_layout_in_force%s");
+    if (e->layout.kind == LayoutKind::planes)
+        return fail(M1V_E_ARG, e->layout.y_step == 2 ? "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s"
+                                                      : "a plane layout is in force: ask m1v_plane_layout_in_force%s");
     if (row_pitch_bytes) *row_pitch_bytes = e->layout.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)e->layout.frame_stride;
     if (order) *order = e->layout.order;
@@ -614,25 +616,57 @@ int m1v_plane_layout_preset(int width, int height, int preset, m1v_plane_layout 
     return M1V_OK;
 }
 
-int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+int m1v_sample_layout_preset(int width, int height, int preset, m1v_sample_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (preset < M1V_SAMPLES_YUY2 || preset > M1V_SAMPLES_P010) return fail(M1V_E_ARG, "unknown sample layout preset%s");
+    if ((width | height) & 1) return fail(M1V_E_ARG, "a sample layout preset needs an even width and height%s");
+    const size_t W = (size_t)width, H = (size_t)height;
+    m1v_sample_layout l = {};
+    l.y_step = 2;
+    l.c_step = 4;
+    l.y_pitch = 2 * W;
+    if (preset == M1V_SAMPLES_P010) { // a plane of 16-bit luma words, then one of Cb, Cr word pairs: the high byte of each word
+        l.y_offset = 1;
+        l.cb_offset = 2 * W * H + 1;
+        l.cr_offset = 2 * W * H + 3;
+        l.c_pitch = 2 * W;
+        l.frame_stride = 3 * W * H;
+    } else { // groups of four bytes = two pixels; chroma from the even picture rows
+        l.y_offset = preset == M1V_SAMPLES_UYVY ? 1 : 0;
+        l.cb_offset = preset == M1V_SAMPLES_YUY2 ? 1 : (preset == M1V_SAMPLES_UYVY ? 0 : 3);
+        l.cr_offset = preset == M1V_SAMPLES_YUY2 ? 3 : (preset == M1V_SAMPLES_UYVY ? 2 : 1);
+        l.c_pitch = 4 * W;
+        l.frame_stride = 2 * W * H;
+    }
+    *out = l;
+    return M1V_OK;
+}
+
+// m1v_set_plane_layout and m1v_set_sample_layout: the checks of include/mpeg1_hip.h with the steps put in, then the reconfiguration
+static int set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
     m1v_encoder::Layout want;
     if (layout) {
         const Geometry &g = e->g;
         if (g.C != 3) return fail(M1V_E_ARG, "a plane layout needs an encoder created with 3 channels%s");
-        if (layout->c_step > 2) return fail(M1V_E_ARG, "c_step must be 1 or 2 (0 = 1)%s");
+        const unsigned long long y_step = layout->y_step ? layout->y_step : 1, step = layout->c_step ? layout->c_step : 1;
+        if (!((y_step == 1 && step <= 2) || (y_step == 2 && step == 4)))
+            return fail(M1V_E_ARG, "(y_step, c_step) must be (1, 1), (1, 2) or (2, 4) (0 = 1)%s");
+        if (step == 4 && std::max(layout->cb_offset, layout->cr_offset) - std::min(layout->cb_offset, layout->cr_offset) > 3)
+            return fail(M1V_E_ARG, "with c_step 4 the chroma offsets must lie within one 4-byte group%s");
         if (layout->frame_stride == 0) return fail(M1V_E_ARG, "a plane layout needs a frame stride%s");
-        const unsigned long long W = (unsigned long long)g.W, half = W / 2, step = layout->c_step ? layout->c_step : 1;
-        if (layout->y_pitch != 0 && layout->y_pitch < W) return fail(M1V_E_ARG, "luma pitch below the width%s");
+        const unsigned long long W = (unsigned long long)g.W, half = W / 2;
+        if (layout->y_pitch != 0 && layout->y_pitch < W * y_step) return fail(M1V_E_ARG, "luma pitch below width * y_step%s");
         if (layout->c_pitch != 0 && layout->c_pitch < half * step) return fail(M1V_E_ARG, "chroma pitch below (width / 2) * c_step%s");
-        const unsigned long long y_pitch = layout->y_pitch ? layout->y_pitch : W, c_pitch = layout->c_pitch ? layout->c_pitch : half * step;
+        const unsigned long long y_pitch = layout->y_pitch ? layout->y_pitch : W * y_step, c_pitch = layout->c_pitch ? layout->c_pitch : half * step;
         // the frame's extent: the read contract of mpeg1_hip.h (rows and row bytes of the region the encoder codes)
         const unsigned long long xe = (unsigned long long)g.n_strips * 16, ye = (unsigned long long)g.n_mbrows * 16;
         const unsigned long long limit = 1ull << 32;
         if (y_pitch >= limit || c_pitch >= limit || layout->y_offset >= limit || layout->cb_offset >= limit || layout->cr_offset >= limit)
             return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        const unsigned long long y_rows = (ye - 1) * y_pitch + (xe - 1) * y_step + 1;             // one past the last addressed luma byte
         const unsigned long long c_rows = (ye / 2 - 1) * c_pitch + (xe / 2 - 1) * step + 1; // one past a plane's last addressed byte
-        const unsigned long long extent = std::max(layout->y_offset + (ye - 1) * y_pitch + xe,
+        const unsigned long long extent = std::max(layout->y_offset + y_rows,
                                                    std::max<unsigned long long>(layout->cb_offset, layout->cr_offset) + c_rows);
         if (extent >= limit) return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
         if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
@@ -644,6 +678,7 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
         want.cr_off = (uint32_t)layout->cr_offset;
         want.y_pitch = (uint32_t)y_pitch;
         want.c_pitch = (uint32_t)c_pitch;
+        want.y_step = (uint32_t)y_step;
         want.c_step = (uint32_t)step;
         want.extent = extent;
         want.frame_stride = layout->frame_stride;
@@ -651,12 +686,36 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
     return reconfigure(e, &m1v_encoder::layout, want);
 }
 
+int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (!layout) return set_sample_layout(e, nullptr);
+    if (layout->c_step > 2) return fail(M1V_E_ARG, "c_step must be 1 or 2 (0 = 1)%s");
+    const m1v_sample_layout l = {layout->y_offset, layout->cb_offset, layout->cr_offset, layout->y_pitch, layout->c_pitch, 1, layout->c_step, layout->frame_stride};
+    return set_sample_layout(e, &l);
+}
+
+int m1v_set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    return set_sample_layout(e, layout);
+}
+
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::planes) return 0;
+    if (e->layout.y_step == 2) return fail(M1V_E_ARG, "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s");
+    if (out) {
+        const m1v_encoder::Layout &l = e->layout;
+        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.c_step, (size_t)l.frame_stride};
+    }
+    return 1;
+}
+
+int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (e->layout.kind != LayoutKind::planes) return 0;
     if (out) {
         const m1v_encoder::Layout &l = e->layout;
-        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.c_step, (size_t)l.frame_stride};
+        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.y_step, l.c_step, (size_t)l.frame_stride};
     }
     return 1;
 }

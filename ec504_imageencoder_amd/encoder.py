@@ -101,14 +101,37 @@ def plane_layout_preset(width, height, name):
                 y_pitch=W, c_pitch=W // 2 if planar else W, c_step=1 if planar else 2, frame_stride=luma * 3 // 2)
 
 
+SAMPLE_LAYOUT_FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "y_step", "c_step", "frame_stride")
+
+
+def sample_layout_preset(width, height, name):
+    """The tightly packed sample layout `name` ("yuy2", "uyvy", "yvyu", "p010") of a width x height frame as a dict of
+    SAMPLE_LAYOUT_FIELDS in bytes, as Mpeg1Encoder.set_sample_layout takes it (include/mpeg1_hip.h, m1v_sample_layout_preset,
+    whose values these are).  The packed 4:2:2 presets take chroma from the even picture rows; "p010" also serves P012 and P016
+    (the coded sample is the high byte of each 16-bit word).  Pure: no torch, no library."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if name not in _ffi.SAMPLE_PRESETS:
+        raise ValueError(f"unknown sample layout preset {name!r}")
+    if W % 2 or H % 2:
+        raise ValueError("a sample layout preset needs an even width and height")
+    if name == "p010":
+        return dict(y_offset=1, cb_offset=2 * W * H + 1, cr_offset=2 * W * H + 3, y_pitch=2 * W, c_pitch=2 * W, y_step=2, c_step=4,
+                    frame_stride=3 * W * H)
+    y, cb, cr = {"yuy2": (0, 1, 3), "uyvy": (1, 0, 2), "yvyu": (0, 3, 1)}[name]
+    return dict(y_offset=y, cb_offset=cb, cr_offset=cr, y_pitch=2 * W, c_pitch=4 * W, y_step=2, c_step=4, frame_stride=2 * W * H)
+
+
 def plane_layout_extent(layout, strips, mb_rows):
     """Bytes of a frame the plane kernels may read (the read contract of include/mpeg1_hip.h): the largest
     offset + (rows - 1) * pitch + row bytes over the three planes of the strips * 16 x mb_rows * 16 region (row bytes: up to a
-    row's last addressed byte).  layout: a dict of
-    PLANE_LAYOUT_FIELDS with no zeros (Mpeg1Encoder.plane_layout)."""
+    row's last addressed byte, (samples - 1) * step + 1).  layout: a dict of PLANE_LAYOUT_FIELDS (y_step = 1) or
+    SAMPLE_LAYOUT_FIELDS with no zeros (Mpeg1Encoder.plane_layout, Mpeg1Encoder.sample_layout)."""
     xe, ye = strips * 16, mb_rows * 16
+    luma = (ye - 1) * layout["y_pitch"] + (xe - 1) * layout.get("y_step", 1) + 1
     chroma = (ye // 2 - 1) * layout["c_pitch"] + (xe // 2 - 1) * layout["c_step"] + 1
-    return max(layout["y_offset"] + (ye - 1) * layout["y_pitch"] + xe, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
+    return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
 
 
 class Mpeg1Encoder:
@@ -134,7 +157,7 @@ class Mpeg1Encoder:
         self.frame_bytes_in = L.m1v_frame_bytes_in(self._h)
         self.blocks_per_frame = self.strips * self.mb_rows * 6
         self._layout = (0, 0, "rgb")    # what _check_input holds tensors against (set_input_layout)
-        self._planes = None             # the plane layout in force (set_plane_layout), a dict of PLANE_LAYOUT_FIELDS
+        self._planes = None             # the plane or sample layout in force (set_plane_layout, set_sample_layout), a dict
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -222,6 +245,36 @@ class Mpeg1Encoder:
         _call("m1v_set_plane_layout", self._h, c)
         self._planes = self.plane_layout
         self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+
+    def set_sample_layout(self, layout):
+        """Frames whose samples lie one or two bytes apart, encoded where they lie (include/mpeg1_hip.h, m1v_set_sample_layout;
+        3-channel encoders): packed 4:2:2 and P010 / P012 / P016 beside everything set_plane_layout takes.  layout: a preset name
+        ("yuy2", "uyvy", "yvyu", "p010"), a dict of SAMPLE_LAYOUT_FIELDS in bytes (sample_layout_preset gives one to start from;
+        missing pitches and steps default as in the header), or None = back to the default layout and its kernels.  Every call
+        then takes uint8 CUDA tensors [n, L] as after set_plane_layout.  A uint16 P010 tensor goes in as
+        frames.view(torch.uint8) (reshaped to [n, L]): the coded sample is each word's high byte, truncation, not rounding.
+        A reconfiguration: call it between batches."""
+        c = None
+        if layout is not None:
+            if isinstance(layout, str):
+                layout = sample_layout_preset(self.width, self.height, layout)
+            unknown = set(layout) - set(SAMPLE_LAYOUT_FIELDS)
+            if unknown:
+                raise ValueError(f"unknown sample layout fields {sorted(unknown)}")
+            c = C.byref(_ffi.SampleLayout(**{k: int(v) for k, v in layout.items()}))
+        _call("m1v_set_sample_layout", self._h, c)
+        self._planes = self.sample_layout
+        self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+
+    @property
+    def sample_layout(self):
+        """The plane or sample layout in force as a dict of SAMPLE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros;
+        y_step = 1 for a layout set through set_plane_layout), or None."""
+        c = _ffi.SampleLayout()
+        rc = _ffi.lib().m1v_sample_layout_in_force(self._h, C.byref(c))
+        if rc < 0:
+            raise EncoderError(rc, "m1v_sample_layout_in_force")
+        return c.as_dict() if rc == 1 else None
 
     @property
     def plane_layout(self):

@@ -443,6 +443,54 @@ int m1v_plane_layout_preset(int width, int height, int preset, m1v_plane_layout 
 int m1v_set_plane_layout(m1v_encoder *enc, const m1v_plane_layout *layout);
 int m1v_plane_layout_in_force(const m1v_encoder *enc, m1v_plane_layout *out);
 
+/* Sample layout: the plane layout with one more parameter, the distance between neighbouring luma samples.  It covers the YCbCr
+ * frames whose samples do not lie next to one another: packed 4:2:2 (YUY2, UYVY, YVYU: capture cards, cameras, hardware JPEG
+ * decoders) and P010 / P012 / P016 (10-bit and deeper hardware video decode: 16-bit little-endian words with the value in the
+ * high bits, a luma plane and one plane of Cb, Cr word pairs).  For encoders created with channels = 3.
+ *
+ * Definition.  Frame f starts at F = d_rgb + f * frame_stride; the region coded is xe x ye as above.  The macroblock at (x, y) takes
+ *     luma block k, row i, sample j       the byte at  F + y_offset + (y + 8 * (k / 2) + i) * y_pitch + (x + 8 * (k % 2) + j) * y_step
+ *     chroma plane p, row i, sample j     the byte at  F + p_offset + (y / 2 + i) * c_pitch + (x / 2 + j) * c_step
+ * and the record is the reference's frame body on those bytes, exactly as for plane layouts (y_step = 1 IS the plane layout).
+ *
+ *   m1v_sample_layout_preset(width, height, preset, &layout)   pure host arithmetic, tightly packed; y_step 2, c_step 4
+ *     M1V_SAMPLES_YUY2   groups Y0 Cb Y1 Cr: y_offset 0, cb_offset 1, cr_offset 3, y_pitch 2*W, c_pitch 4*W, stride 2*W*H
+ *     M1V_SAMPLES_UYVY   groups Cb Y0 Cr Y1: y_offset 1, cb_offset 0, cr_offset 2, the same pitches and stride
+ *     M1V_SAMPLES_YVYU   groups Y0 Cr Y1 Cb: y_offset 0, cb_offset 3, cr_offset 1, the same pitches and stride
+ *     M1V_SAMPLES_P010   y_offset 1, cb_offset 2*W*H + 1, cr_offset 2*W*H + 3, y_pitch = c_pitch = 2*W, stride 3*W*H
+ *     All four need an even width and height (M1V_E_ARG otherwise); M1V_E_ARG: unknown preset.
+ *     The packed 4:2:2 presets turn 4:2:2 into the 4:2:0 the format codes by taking chroma from the EVEN picture rows
+ *     (c_pitch = two picture rows); a caller who wants the odd rows adds y_pitch to both chroma offsets.
+ *     M1V_SAMPLES_P010 also serves P012 and P016: the bytes are the same.  The coded sample is the word's high byte, v10 >> 2 for
+ *     P010: truncation, not rounding.
+ *   m1v_set_sample_layout(enc, &layout)   NULL = back to the default layout.  The reconfiguration m1v_set_plane_layout is, and the
+ *     same code: (y_step, c_step) = (1, 1) or (1, 2) is exactly m1v_set_plane_layout (the same kernels, the same layout in force);
+ *     (2, 4) takes the tile plan behind k_encode_step2, k_size_table_step2 and k_rd_table_step2.  Everything m1v_set_plane_layout
+ *     says about replacing other layouts, the calls that work on it and the packed-only entry points holds.
+ *     M1V_E_ARG, before anything is launched or reallocated: a null encoder; channels != 3; a step pair other than (1, 1), (1, 2),
+ *     (2, 4) (0 = 1); with c_step 4, chroma offsets more than 3 bytes apart (both components of a sample pair lie in one 4-byte
+ *     group: interleaved chroma); frame_stride 0; 0 < y_pitch < width * y_step; 0 < c_pitch < (width / 2) * c_step; an offset, a
+ *     pitch or a frame extent E of 2^32 or more; frame_stride < E; an encoder that a hook has forced to the run kernels.
+ *   m1v_sample_layout_in_force(enc, &layout)   1 = a plane or sample layout is in force (layout filled with the values the kernels
+ *     use, no zeros: y_step = 1 for a layout set through m1v_set_plane_layout; may be NULL), 0 = none, < 0 = error.  While a
+ *     (2, 4) layout is in force m1v_plane_layout_in_force and m1v_input_layout return M1V_E_ARG (the message names this query).
+ * Read contract: unchanged.  Of frame f a kernel reads only bytes of [F, F + E) rounded up to the next 4-byte boundary; E is
+ * computed as above with luma row bytes (xe - 1) * y_step + 1 and chroma row bytes (xe / 2 - 1) * c_step + 1.  Bytes inside that
+ * range that the definition does not address (the low byte of every P010 word, the chroma bytes of odd rows of a 4:2:2 frame,
+ * row padding, gaps) may be read; they never influence the output. */
+typedef struct m1v_sample_layout {
+    size_t y_offset, cb_offset, cr_offset; /* bytes from the frame's base to sample (0,0) of each component        */
+    size_t y_pitch;                        /* bytes between luma rows; 0 = width * y_step                          */
+    size_t c_pitch;                        /* bytes between chroma rows of the addressing above; 0 = (width / 2) * c_step */
+    size_t y_step;                         /* bytes between neighbouring luma samples: 1 or 2; 0 = 1               */
+    size_t c_step;                         /* bytes between neighbouring samples of ONE chroma component: 1, 2 or 4; 0 = 1 */
+    size_t frame_stride;                   /* bytes between frames; never 0                                        */
+} m1v_sample_layout;
+enum { M1V_SAMPLES_YUY2 = 0, M1V_SAMPLES_UYVY = 1, M1V_SAMPLES_YVYU = 2, M1V_SAMPLES_P010 = 3 };
+int m1v_sample_layout_preset(int width, int height, int preset, m1v_sample_layout *out);
+int m1v_set_sample_layout(m1v_encoder *enc, const m1v_sample_layout *layout);
+int m1v_sample_layout_in_force(const m1v_encoder *enc, m1v_sample_layout *out);
+
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
  * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.

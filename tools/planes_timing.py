@@ -11,6 +11,10 @@ legs alternate for `--rounds` rounds and the median round is printed with the ra
                                                              DIFFER: 8-bit YCbCr -> RGB -> YCbCr is not the identity; a cost
                                                              comparison only)
           table K=8, budget K=8 on NV12          this tree | the other library's on packed RGB
+          YUY2 / P010 step                       this tree | the other library's packed RGB step, and its NV12 step where it
+                                                             has plane layouts, on the same pictures (m1v_set_sample_layout:
+                                                             samples two bytes apart; same records out)
+    --only <text>: time only the legs whose name contains <text> (several: a comma-separated list); every output is still checked
     usage: planes_timing.py --other <path to the other libencoder.so> [--w 1920 --h 1080 --n 300]
 Every plane output (records, sizes, K = 8 table) is compared with the other library's output on the RGB frames before anything
 is timed.  Also printed: the time of the encode kernel alone under m1v_profile_* for each side."""
@@ -30,6 +34,7 @@ ap.add_argument("--q", type=int, default=12)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--settle", type=int, default=60)
 ap.add_argument("--launches", type=int, default=100)
+ap.add_argument("--only", default="")
 a = ap.parse_args()
 import torch
 
@@ -42,6 +47,10 @@ assert W % 2 == 0 and H % 2 == 0
 
 class PlaneLayout(C.Structure):
     _fields_ = [(k, C.c_size_t) for k in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")]
+
+
+class SampleLayout(C.Structure):
+    _fields_ = [(k, C.c_size_t) for k in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "y_step", "c_step", "frame_stride")]
 
 
 def load(path):
@@ -62,6 +71,9 @@ def load(path):
     if hasattr(L, "m1v_set_plane_layout"):
         L.m1v_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(PlaneLayout)]
         L.m1v_set_plane_layout.argtypes = [vp, C.POINTER(PlaneLayout)]
+    if hasattr(L, "m1v_set_sample_layout"):
+        L.m1v_sample_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SampleLayout)]
+        L.m1v_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
     return L
 
 
@@ -69,7 +81,7 @@ this, other = load(os.path.join(ROOT, "ec504_imageencoder_amd", "libencoder.so")
 handles, alive = [], []
 
 
-def create(L, channels, surface=None, planes=None):
+def create(L, channels, surface=None, planes=None, samples=None):
     h = vp()
     assert L.m1v_create(C.byref(h), 0, W, H, channels, a.q, 1, N) == 0, L.m1v_last_error()
     if surface:
@@ -78,6 +90,10 @@ def create(L, channels, surface=None, planes=None):
         lay = PlaneLayout()
         assert L.m1v_plane_layout_preset(W, H, planes, C.byref(lay)) == 0, L.m1v_last_error()
         assert L.m1v_set_plane_layout(h, C.byref(lay)) == 0, L.m1v_last_error()
+    if samples is not None:
+        lay = SampleLayout()
+        assert L.m1v_sample_layout_preset(W, H, samples, C.byref(lay)) == 0, L.m1v_last_error()
+        assert L.m1v_set_sample_layout(h, C.byref(lay)) == 0, L.m1v_last_error()
     handles.append((L, h))
     return h
 
@@ -212,6 +228,33 @@ for name, preset, frames, conv in (("reference planes", 0, ref, convert_referenc
         legs.append(("table K=8 (this NV12 | other packed RGB)", table8(this, e, frames.data_ptr()), table8(other, e_rgb_other, rgb3.data_ptr())))
         legs.append(("budget K=8 (this NV12 | other packed RGB)", budget8(this, e, frames.data_ptr()), budget8(other, e_rgb_other, rgb3.data_ptr())))
 
+# ---- samples two bytes apart: the same pictures as packed 4:2:2 (chroma in the even rows; the odd rows' chroma bytes are
+#      noise) and as P010 (the sample in each word's high byte; the low bytes are noise) ----
+yuy2 = torch.randint(0, 256, (N, H, W // 2, 4), dtype=torch.uint8, device="cuda")
+yuy2.view(N, H, W, 2)[..., 0] = i420[:, :H * W].view(N, H, W)
+yuy2[:, 0::2, :, 1] = i420[:, H * W:H * W + quarter].view(N, H // 2, W // 2)
+yuy2[:, 0::2, :, 3] = i420[:, H * W + quarter:].view(N, H // 2, W // 2)
+p010 = torch.randint(0, 256, (N, H * 3 // 2 * W, 2), dtype=torch.uint8, device="cuda")
+p010[..., 1] = nv12
+torch.cuda.synchronize()
+alive += [yuy2, p010]
+e_nv12_other = create(other, 3, planes=3) if hasattr(other, "m1v_set_plane_layout") else None
+for name, preset, frames in (("YUY2", 0, yuy2), ("P010", 3, p010)):
+    e = create(this, 3, samples=preset)
+    assert this.m1v_path_in_use(e) == 1
+    same(result(plain(this, e, frames.data_ptr()), name), want_rgb, name)
+    assert torch.equal(result(table8(this, e, frames.data_ptr()), name + " table")[2], want_table), f"{name}: tables differ"
+    same(result(budget8(this, e, frames.data_ptr()), name + " budget"), want_budget, name + " budget")
+    legs.append((f"{name} step (this | other packed RGB step, same records)", plain(this, e, frames.data_ptr()),
+                 plain(other, e_rgb_other, rgb3.data_ptr())))
+    if e_nv12_other is not None:
+        legs.append((f"{name} step (this | other NV12 step, same records)", plain(this, e, frames.data_ptr()),
+                     plain(other, e_nv12_other, nv12.data_ptr())))
+    plane_legs.append((name, e, frames))
+
+if a.only:
+    legs = [leg for leg in legs if any(text in leg[0] for text in a.only.split(","))]
+    plane_legs = [leg for leg in plane_legs if any(text in leg[0] for text in a.only.split(","))]
 res = {}
 for r in range(a.rounds):
     for name, go_left, go_right in legs:
@@ -252,6 +295,6 @@ print("encode kernel alone (m1v_profile_*), us per launch:")
 print(f"    other k_encode_tiles on packed RGB  {kernel_us(other, e_rgb_other, rgb3.data_ptr()):8.1f}")
 print(f"    this  k_encode_tiles on packed RGB  {kernel_us(this, e_rgb_this, rgb3.data_ptr()):8.1f}")
 for name, e, frames in plane_legs:
-    print(f"    this  k_encode_planes on {name:<17s} {kernel_us(this, e, frames.data_ptr()):8.1f}")
+    print(f"    this  plane / sample kernel on {name:<17s} {kernel_us(this, e, frames.data_ptr()):8.1f}")
 for L, h in handles:
     L.m1v_destroy(h)
