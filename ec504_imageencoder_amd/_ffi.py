@@ -39,6 +39,17 @@ class SampleLayout(C.Structure):
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
+RGB_PLANES_RGB, RGB_PLANES_BGR, RGB_PLANES_GBR = 0, 1, 2
+RGB_PLANE_ORDERS = {"rgb": RGB_PLANES_RGB, "bgr": RGB_PLANES_BGR, "gbr": RGB_PLANES_GBR}
+
+
+class RgbPlaneLayout(C.Structure):
+    """m1v_rgb_plane_layout (include/mpeg1_hip.h): where the R, G and B bytes of a frame lie, in bytes."""
+    _fields_ = [(name, C.c_uint64) for name in ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
 _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
@@ -56,6 +67,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_debug_fail_encode", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
     "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
     "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
+    "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -190,6 +202,12 @@ def lib():
     L.m1v_set_sample_layout.restype = C.c_int
     L.m1v_sample_layout_in_force.argtypes = [vp, C.POINTER(SampleLayout)]
     L.m1v_sample_layout_in_force.restype = C.c_int
+    L.m1v_rgb_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(RgbPlaneLayout)]
+    L.m1v_rgb_plane_layout_preset.restype = C.c_int
+    L.m1v_set_rgb_plane_layout.argtypes = [vp, C.POINTER(RgbPlaneLayout)]
+    L.m1v_set_rgb_plane_layout.restype = C.c_int
+    L.m1v_rgb_plane_layout_in_force.argtypes = [vp, C.POINTER(RgbPlaneLayout)]
+    L.m1v_rgb_plane_layout_in_force.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

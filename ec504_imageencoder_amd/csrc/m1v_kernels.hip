@@ -19,6 +19,9 @@
 //   k_encode_planes, k_size_table_planes     (m1v_planes.h, the same two bodies) the tile encode and size table on planar and
 //                     semi-planar YCbCr frames (m1v_set_plane_layout: reference planes, I420 / YV12, NV12 / NV21, pitched
 //                     windows of them): no colour stage, bytes straight into the fp32 FDCT
+//   k_encode_rgb_planes, k_size_table_rgb_planes, k_rd_table_rgb_planes   (m1v_rgb_planes.h, the same bodies) the tile kernels on
+//                     planes of R, G and B bytes (m1v_set_rgb_plane_layout: NCHW uint8 tensors in any plane order): the colour
+//                     stage of the surface kernels on de-interleaved bytes
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -1260,6 +1263,7 @@ constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 #include "m1v_tiles.h"
 #include "m1v_planes.h"
 #include "m1v_step2.h"
+#include "m1v_rgb_planes.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1774,9 +1778,11 @@ struct m1v_encoder {
     // plan_for's 4-channel fused table: every hook keeps one probe per quality, the A/B reference inside one process
     bool any_hook_set() const { return forced_path >= 0 || forced_mode >= 0 || forced_T != 0; }
     // The input layout in force, no zeros.  surface (m1v_set_input_layout): the pictures are windows of a pitched surface (the
-    // surface kernels); planes (m1v_set_plane_layout): the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h)
+    // surface kernels); planes (m1v_set_plane_layout): the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h);
+    // rgb_planes (m1v_set_rgb_plane_layout): planes of R, G and B bytes (m1v_rgb_planes.h; y_off, cb_off, cr_off hold the R, G, B
+    // offsets, row_pitch the planes' common pitch)
     struct Layout {
-        enum class Kind { packed, surface, planes } kind = Kind::packed;
+        enum class Kind { packed, surface, planes, rgb_planes } kind = Kind::packed;
         uint32_t row_pitch = 0;               // bytes from a picture row to the next
         unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
         int order = M1V_ORDER_RGB;
@@ -2015,23 +2021,24 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
-enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kStep2 = kPlanes + 2, kTileVariants = kPlanes + 3 };
+enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kStep2 = kPlanes + 2, kRgbPlanes = kPlanes + 3, kTileVariants = kPlanes + 4 };
 #define M1V_PAIR(K, ...) {(const void *)&K<false, __VA_ARGS__>, (const void *)&K<true, __VA_ARGS__>}
-#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES, STEP2)                                                       \
+#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES, STEP2, RGBP)                                                      \
     {PACKED3, PACKED4, M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 1),                  \
      M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 1), M1V_PAIR(PLANES, M1V_TILE_RING, 1), \
-     M1V_PAIR(PLANES, M1V_TILE_RING, 2), M1V_PAIR(STEP2, M1V_TILE_RING)}
+     M1V_PAIR(PLANES, M1V_TILE_RING, 2), M1V_PAIR(STEP2, M1V_TILE_RING), M1V_PAIR(RGBP, M1V_TILE_RING)}
 static const struct Kernels {
     const void *tile[3][kTileVariants][2];
     const void *dense[4][2];
     const void *strips[2][2];
 } kKernels = {
     // (packed 4-channel pictures encode on the run kernels)
-    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes, k_encode_step2),
+    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes, k_encode_step2,
+                     k_encode_rgb_planes),
      M1V_TILE_FAMILY(M1V_PAIR(k_size_table_tiles, M1V_TILE_RING), M1V_PAIR(k_size_table_rgba, M1V_TILE_RING), k_size_table_surface,
-                     k_size_table_planes, k_size_table_step2),
+                     k_size_table_planes, k_size_table_step2, k_size_table_rgb_planes),
      M1V_TILE_FAMILY(M1V_PAIR(k_rd_table_tiles, M1V_TILE_RING), M1V_PAIR(k_rd_table_rgba, M1V_TILE_RING), k_rd_table_surface,
-                     k_rd_table_planes, k_rd_table_step2)},
+                     k_rd_table_planes, k_rd_table_step2, k_rd_table_rgb_planes)},
     {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
      {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
      {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
@@ -2057,6 +2064,7 @@ static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->q
 // chroma step to an instantiation
 static int tile_variant(const m1v_encoder *e) {
     const m1v_encoder::Layout &l = e->layout;
+    if (l.kind == LayoutKind::rgb_planes) return kRgbPlanes;
     if (l.kind == LayoutKind::planes) return l.y_step == 2 ? kStep2 : kPlanes + (int)l.c_step - 1;
     if (l.kind == LayoutKind::surface) return kSurface + (e->g.C == 4 ? 2 : 0) + l.order;
     return e->g.C == 4 ? kPacked4 : kPacked3;
@@ -2100,15 +2108,17 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
     a.tile_row_order = e->d_tile_order;
 }
 
-// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs; 1 = size table, 2 = rd table: their
-// table counterparts) over the grid a's TileArgs / TableArgs carries (fill_tile_grid), with a wrapped for the layout in force
-template <typename Surface, typename Planes, typename Args>
+// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs, RgbPlanes = RgbPlaneArgs; 1 = size
+// table, 2 = rd table: their table counterparts) over the grid a's TileArgs / TableArgs carries (fill_tile_grid), with a wrapped for the layout in force
+template <typename Surface, typename Planes, typename RgbPlanes, typename Args>
 static int launch_tiles(m1v_encoder *e, int family, bool narrow, Args &a, size_t grid, size_t lds, hipStream_t st) {
     const m1v_encoder::Layout &l = e->layout;
     Surface on_surface = {a, l.frame_stride, l.row_pitch};
     // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
     Planes on_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride};
-    void *arg = l.kind == LayoutKind::planes ? (void *)&on_planes
+    RgbPlanes on_rgb_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.row_pitch}, l.frame_stride};
+    void *arg = l.kind == LayoutKind::rgb_planes ? (void *)&on_rgb_planes
+                : l.kind == LayoutKind::planes ? (void *)&on_planes
                 : l.kind == LayoutKind::surface ? (void *)&on_surface : (void *)&a;
     return launch_profiled(e, kKernels.tile[family][tile_variant(e)][narrow ? 1 : 0], grid, kTileThreads,
                            arg, lds, st);
@@ -2217,7 +2227,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        rc = launch_tiles<SurfaceArgs, PlaneArgs>(e, 0, e->narrow, a, grid, p.lds_bytes, st);
+        rc = launch_tiles<SurfaceArgs, PlaneArgs, RgbPlaneArgs>(e, 0, e->narrow, a, grid, p.lds_bytes, st);
     } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
@@ -2358,8 +2368,8 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     const size_t grid = (size_t)n_frames * p.table_units;
     if (dist) {
         RdTableArgs ra = {a, e->d_dq_all, tc.frame_dist};
-        if (const int rc = launch_tiles<SurfaceRdArgs, PlaneRdArgs>(e, 2, narrow, ra, grid, p.table_lds_bytes + kRdPartWords * 4, st)) return rc;
-    } else if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs>(e, 1, narrow, a, grid, p.table_lds_bytes, st)) {
+        if (const int rc = launch_tiles<SurfaceRdArgs, PlaneRdArgs, RgbPlaneRdArgs>(e, 2, narrow, ra, grid, p.table_lds_bytes + kRdPartWords * 4, st)) return rc;
+    } else if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs, RgbPlaneTableArgs>(e, 1, narrow, a, grid, p.table_lds_bytes, st)) {
         return rc;
     }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;

@@ -310,6 +310,7 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
 // What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
 // the run kernels
 static int packed_only(const m1v_encoder *e) {
+    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "packed input only: an RGB plane layout is set (m1v_set_rgb_plane_layout)%s");
     if (e->layout.kind == LayoutKind::planes) return fail(M1V_E_ARG, "packed input only: a plane layout is set (m1v_set_plane_layout)%s");
     return e->layout.kind == LayoutKind::surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
 }
@@ -578,6 +579,7 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
     if (e->layout.kind == LayoutKind::planes)
         return fail(M1V_E_ARG, e->layout.y_step == 2 ? "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s"
                                                       : "a plane layout is in force: ask m1v_plane_layout_in_force%s");
@@ -701,6 +703,7 @@ int m1v_set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
     if (e->layout.kind != LayoutKind::planes) return 0;
     if (e->layout.y_step == 2) return fail(M1V_E_ARG, "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s");
     if (out) {
@@ -712,10 +715,68 @@ int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
 
 int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
     if (e->layout.kind != LayoutKind::planes) return 0;
     if (out) {
         const m1v_encoder::Layout &l = e->layout;
         *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.y_step, l.c_step, (size_t)l.frame_stride};
+    }
+    return 1;
+}
+
+int m1v_rgb_plane_layout_preset(int width, int height, int order, m1v_rgb_plane_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (order < M1V_RGB_PLANES_RGB || order > M1V_RGB_PLANES_GBR) return fail(M1V_E_ARG, "unknown RGB plane order%s");
+    const uint64_t plane = (uint64_t)width * (uint64_t)height;
+    // which of the three planes, in memory order, holds R, G and B
+    static const int at[3][3] = {{0, 1, 2}, {2, 1, 0}, {2, 0, 1}};
+    *out = {at[order][0] * plane, at[order][1] * plane, at[order][2] * plane, (uint64_t)width, 3 * plane};
+    return M1V_OK;
+}
+
+int m1v_set_rgb_plane_layout(m1v_encoder *e, const m1v_rgb_plane_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "an RGB plane layout needs an encoder created with 3 channels%s");
+        if (g.W & 1) return fail(M1V_E_ARG, "an RGB plane layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
+        const unsigned long long W = (unsigned long long)g.W, H = (unsigned long long)g.H, pitch = layout->row_pitch;
+        if (pitch < W) return fail(M1V_E_ARG, "row pitch below the width%s");
+        const unsigned long long off[3] = {layout->r_offset, layout->g_offset, layout->b_offset};
+        const unsigned long long limit = 1ull << 32;
+        const unsigned long long lo = std::min(off[0], std::min(off[1], off[2])), hi = std::max(off[0], std::max(off[1], off[2]));
+        if (pitch >= limit || hi >= limit || hi + (H - 1) * pitch + W >= limit)
+            return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        // Two planes may share a byte range only as a row interleave.  Row y1 of the plane at the lower offset and row y2 of the
+        // other share a byte when |d + (y2 - y1) * pitch| < W, d = the distance of the offsets = q * pitch + r: y2 - y1 = -q
+        // leaves r, y2 - y1 = -q - 1 leaves r - pitch, every other difference is further away.
+        for (int a = 0; a < 3; a++)
+            for (int b = a + 1; b < 3; b++) {
+                const unsigned long long d = off[a] < off[b] ? off[b] - off[a] : off[a] - off[b], q = d / pitch, r = d % pitch;
+                if ((r < W && q <= H - 1) || (pitch - r < W && q + 1 <= H - 1))
+                    return fail(M1V_E_ARG, "two planes share bytes (planes may interleave by rows only)%s");
+            }
+        if (layout->frame_stride < hi + (H - 1) * pitch + W - lo) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
+        if (e->run_hook_set())
+            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
+        want.kind = LayoutKind::rgb_planes;
+        want.y_off = (uint32_t)off[0];
+        want.cb_off = (uint32_t)off[1];
+        want.cr_off = (uint32_t)off[2];
+        want.row_pitch = (uint32_t)pitch;
+        want.frame_stride = layout->frame_stride;
+    }
+    return reconfigure(e, &m1v_encoder::layout, want);
+}
+
+int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::rgb_planes) return 0;
+    if (out) {
+        const m1v_encoder::Layout &l = e->layout;
+        *out = {l.y_off, l.cb_off, l.cr_off, l.row_pitch, l.frame_stride};
     }
     return 1;
 }

@@ -59,6 +59,51 @@ def surface_strides(shape, strides):
     return row_pitch, frame_stride
 
 
+RGB_PLANE_LAYOUT_FIELDS = ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")
+# which channel of an [n, C, H, W] tensor holds R, G and B, by the planes' order in memory
+_RGB_PLANE_CHANNELS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "gbr": (2, 0, 1)}
+
+
+def rgb_plane_layout_preset(width, height, name):
+    """The tightly packed RGB plane layout `name` ("rgb", "bgr", "gbr": the planes' order in memory) of a width x height frame
+    as a dict of RGB_PLANE_LAYOUT_FIELDS in bytes, as Mpeg1Encoder.set_rgb_plane_layout takes it (include/mpeg1_hip.h,
+    m1v_rgb_plane_layout_preset, whose values these are).  Pure: no torch, no library."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if name not in _RGB_PLANE_CHANNELS:
+        raise ValueError(f"unknown RGB plane order {name!r}")
+    r, g, b = _RGB_PLANE_CHANNELS[name]
+    return dict(r_offset=r * W * H, g_offset=g * W * H, b_offset=b * W * H, row_pitch=W, frame_stride=3 * W * H)
+
+
+def rgb_plane_strides(shape, strides, order="rgb"):
+    """The RGB plane layout (a dict of RGB_PLANE_LAYOUT_FIELDS in bytes, as Mpeg1Encoder.set_rgb_plane_layout takes it) of a uint8
+    [n, C, H, W] array with the given strides (in elements = bytes): a packed NCHW tensor, a window x[:, :, y0:y0+H, x0:x0+W] of a
+    larger one, three planes of a 4-plane tensor, frames with a gap.  order: "rgb", "bgr" or "gbr" = the order of the first three
+    channels, or the three channel indices of R, G and B.  Offsets count from the array's first byte.  Raises ValueError for what
+    the layout does not describe: fewer than 3 channels, bytes of a row that are not adjacent, a pitch below W.  Pure: no torch."""
+    if len(shape) != 4 or len(strides) != 4:
+        raise ValueError("frames must be [n, C, H, W]")
+    n, C, H, W = (int(x) for x in shape)
+    frame_stride, plane, row_pitch, byte = (int(x) for x in strides)
+    channels = _RGB_PLANE_CHANNELS.get(order, order) if isinstance(order, str) else tuple(int(c) for c in order)
+    if not isinstance(channels, tuple) or len(channels) != 3:
+        raise ValueError(f"unknown RGB plane order {order!r}")
+    if C < 3 or any(c < 0 or c >= C for c in channels):
+        raise ValueError(f"channels {channels} of a tensor with {C}")
+    if byte != 1:
+        raise ValueError(f"the bytes of a row must be adjacent (stride {byte})")
+    if row_pitch < W:
+        raise ValueError(f"row pitch {row_pitch} below W = {W}")
+    if plane < 0 or frame_stride < 0:
+        raise ValueError("negative strides")
+    offsets = [c * plane for c in channels]
+    if n <= 1:  # (a single frame's stride is arbitrary)
+        frame_stride = max(offsets) + (H - 1) * row_pitch + W
+    return dict(r_offset=offsets[0], g_offset=offsets[1], b_offset=offsets[2], row_pitch=row_pitch, frame_stride=frame_stride)
+
+
 def distortion_to_psnr(d, blocks):
     """The distortion d of a frame of `blocks` blocks (Mpeg1Encoder.blocks_per_frame = strips * mb_rows * 6) as a PSNR in dB:
     10 * log10(255^2 * 64 * blocks / d), the coefficient-domain squared error read as a pixel-domain one (the FDCT is scaled like
@@ -158,6 +203,7 @@ class Mpeg1Encoder:
         self.blocks_per_frame = self.strips * self.mb_rows * 6
         self._layout = (0, 0, "rgb")    # what _check_input holds tensors against (set_input_layout)
         self._planes = None             # the plane or sample layout in force (set_plane_layout, set_sample_layout), a dict
+        self._rgb_planes = None         # the RGB plane layout in force (set_rgb_plane_layout), a dict
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -173,8 +219,8 @@ class Mpeg1Encoder:
     # ---- the hot path -------------------------------------------------------------------------
     def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
-        as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes.  Asynchronous on torch's current
-        stream.
+        as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes; or, after set_rgb_plane_layout,
+        [n, C, H, W] planes of R, G and B.  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
         CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
@@ -198,6 +244,18 @@ class Mpeg1Encoder:
 
     def _check_input(self, rgb):
         import torch
+        if self._rgb_planes is not None:  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
+            want = self._rgb_planes
+            assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4, "RGB plane frames must be a CUDA uint8 tensor [n, C, H, W]"
+            assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
+            assert rgb.stride(3) == 1 and rgb.stride(2) == want["row_pitch"], \
+                f"strides {tuple(rgb.stride())} are not the RGB plane layout in force (row pitch {want['row_pitch']})"
+            assert rgb.shape[0] <= 1 or rgb.stride(0) == want["frame_stride"], \
+                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)})"
+            plane = rgb.stride(1)
+            assert all(plane > 0 and want[k] % plane == 0 and want[k] // plane < rgb.shape[1] for k in ("r_offset", "g_offset", "b_offset")), \
+                f"the plane offsets in force are not channels of this tensor (plane stride {plane})"
+            return
         if self._planes is not None:    # [n, L] bytes, frame f at row f: L covers the frame's extent, rows frame_stride apart
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 2, "plane frames must be a CUDA uint8 tensor [n, L]"
             extent = plane_layout_extent(self._planes, self.strips, self.mb_rows)
@@ -224,7 +282,7 @@ class Mpeg1Encoder:
         kernels.  A reconfiguration: call it between batches."""
         code = {"rgb": _ffi.ORDER_RGB, "bgr": _ffi.ORDER_BGR}.get(order, order)
         _call("m1v_set_input_layout", self._h, int(row_pitch), int(frame_stride), int(code))
-        self._planes = None             # one input layout is in force at a time
+        self._planes = self._rgb_planes = None  # one input layout is in force at a time
         self._layout = self.input_layout
 
     def set_plane_layout(self, layout):
@@ -243,6 +301,7 @@ class Mpeg1Encoder:
                 raise ValueError(f"unknown plane layout fields {sorted(unknown)}")
             c = C.byref(_ffi.PlaneLayout(**{k: int(v) for k, v in layout.items()}))
         _call("m1v_set_plane_layout", self._h, c)
+        self._rgb_planes = None
         self._planes = self.plane_layout
         self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
 
@@ -263,8 +322,37 @@ class Mpeg1Encoder:
                 raise ValueError(f"unknown sample layout fields {sorted(unknown)}")
             c = C.byref(_ffi.SampleLayout(**{k: int(v) for k, v in layout.items()}))
         _call("m1v_set_sample_layout", self._h, c)
+        self._rgb_planes = None
         self._planes = self.sample_layout
         self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+
+    def set_rgb_plane_layout(self, layout):
+        """Frames as planes of R, G and B bytes on the device — NCHW uint8 tensors — encoded where they lie, without a permute and
+        copy to interleaved pixels (include/mpeg1_hip.h, m1v_set_rgb_plane_layout; 3-channel encoders, even widths).  layout: a
+        plane order ("rgb", "bgr", "gbr": tightly packed, rgb_plane_layout_preset), a dict of RGB_PLANE_LAYOUT_FIELDS in bytes
+        (rgb_plane_strides derives one from a tensor's shape and strides), or None = back to the default layout and its kernels.
+        Every call then takes uint8 CUDA tensors [n, C >= 3, H, W] with those strides: a view x[:, :, y0:y0+H, x0:x0+W] of a larger
+        tensor goes in as it is.  A reconfiguration: call it between batches."""
+        c = None
+        if layout is not None:
+            if isinstance(layout, str):
+                layout = rgb_plane_layout_preset(self.width, self.height, layout)
+            if set(layout) != set(RGB_PLANE_LAYOUT_FIELDS):
+                raise ValueError(f"an RGB plane layout has the fields {RGB_PLANE_LAYOUT_FIELDS}")
+            c = C.byref(_ffi.RgbPlaneLayout(**{k: int(v) for k, v in layout.items()}))
+        _call("m1v_set_rgb_plane_layout", self._h, c)
+        self._rgb_planes = self.rgb_plane_layout
+        self._planes = None
+        self._layout = (0, 0, "rgb") if self._rgb_planes is not None else self.input_layout
+
+    @property
+    def rgb_plane_layout(self):
+        """The RGB plane layout in force as a dict of RGB_PLANE_LAYOUT_FIELDS in bytes, or None."""
+        c = _ffi.RgbPlaneLayout()
+        rc = _ffi.lib().m1v_rgb_plane_layout_in_force(self._h, C.byref(c))
+        if rc < 0:
+            raise EncoderError(rc, "m1v_rgb_plane_layout_in_force")
+        return c.as_dict() if rc == 1 else None
 
     @property
     def sample_layout(self):

@@ -491,6 +491,62 @@ int m1v_sample_layout_preset(int width, int height, int preset, m1v_sample_layou
 int m1v_set_sample_layout(m1v_encoder *enc, const m1v_sample_layout *layout);
 int m1v_sample_layout_in_force(const m1v_encoder *enc, m1v_sample_layout *out);
 
+/* RGB plane layout: frames whose R, G and B bytes lie in three planes on the device — a PyTorch image batch [n, 3, H, W] of
+ * uint8, the CHW output of a JPEG decoder, three planes of a 4-plane RGBA tensor, a sliced or as_strided view of one — encoded
+ * where they lie: no permute-and-copy to interleaved pixels in front of the encoder.  For encoders created with channels = 3.
+ * Samples are bytes: the reference's Image::data is unsigned char, and a float sample would need a rounding rule it does not have.
+ *
+ * Definition.  Frame f starts at F = d_rgb + f * frame_stride.  Component c (R, G, B) of pixel (x, y) is the byte at
+ *     F + c_offset + y * row_pitch + x
+ * and the record of a frame is, byte for byte, the record the packed calls give for the interleaved picture [y][x] = (R, G, B) of
+ * those bytes: the reference's whole frame body, colour conversion included; the same headers, first_frame_index, status bits,
+ * per-frame quality and sizes.  Any byte alignment of the pointer, the offsets, the pitch and the stride is accepted.  The three
+ * offsets are independent: R,G,B, B,G,R and G,B,R plane orders, three planes of a 4-plane tensor (the fourth is never read),
+ * pitched windows of larger planes and planes interleaved by rows (row_pitch = 3 * width, offsets 0, width, 2 * width) are all
+ * layouts.
+ *
+ *   m1v_rgb_plane_layout_preset(width, height, order, &layout)   pure host arithmetic (no encoder, no device): three tightly packed
+ *     planes of width * height bytes, row_pitch = width, frame_stride = 3 * width * height, in memory order
+ *     M1V_RGB_PLANES_RGB   R, G, B: offsets 0, W*H, 2*W*H
+ *     M1V_RGB_PLANES_BGR   B, G, R: r_offset 2*W*H, g_offset W*H, b_offset 0
+ *     M1V_RGB_PLANES_GBR   G, B, R: r_offset 2*W*H, g_offset 0, b_offset W*H
+ *     M1V_E_ARG: a null out, width or height <= 0, an unknown order.
+ *   m1v_set_rgb_plane_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like m1v_set_input_layout (call it
+ *     between batches; buffers are allocated first and swapped in on success, so a failed call leaves the encoder as it was).  The
+ *     encoder takes the tile plan (m1v_path_in_use and m1v_size_table_fused are 1) behind k_encode_rgb_planes,
+ *     k_size_table_rgb_planes and k_rd_table_rgb_planes.  ONE input layout is in force at a time: each of m1v_set_input_layout,
+ *     m1v_set_plane_layout, m1v_set_sample_layout and m1v_set_rgb_plane_layout replaces what another has set, and each one's default
+ *     (NULL; 0, 0, M1V_ORDER_RGB) restores the default plan.  While an RGB plane layout is in force m1v_input_layout,
+ *     m1v_plane_layout_in_force and m1v_sample_layout_in_force return M1V_E_ARG.  Every *_device encode, probe, size-table,
+ *     rd-table, budget, batch-budget and bitrate call (by size and by distortion), pipelined mode, m1v_reserve_scratch,
+ *     m1v_debug_set_lds_words and m1v_delivery_* work on it.
+ *     M1V_E_ARG, before anything is launched or reallocated: a null encoder; channels != 3; an odd width (the reference addresses
+ *     its chroma plane with stride width / 2: with an odd width a chroma block row straddles two picture rows); row_pitch < width;
+ *     (largest offset) + (height - 1) * row_pitch + width >= 2^32 (offsets inside a frame are 32-bit); two planes that share an
+ *     addressed byte (their ranges may overlap as a row interleave only); frame_stride below the bytes from the smallest offset to
+ *     the end of the last plane's range; an encoder that a hook has forced to the run kernels (those hooks return M1V_E_ARG on an
+ *     encoder with an RGB plane layout).
+ *     Packed only: m1v_coefficients_device, m1v_convert_device, m1v_encode_host, m1v_encode_planes_host and m1v_convert_host
+ *     return M1V_E_ARG while an RGB plane layout is set.
+ *   m1v_rgb_plane_layout_in_force(enc, &layout)   1 = an RGB plane layout is in force (layout filled with the values the kernels
+ *     use; may be NULL), 0 = another layout or none, < 0 = error.
+ * Read contract: of frame f a kernel reads only bytes of the three ranges [F + c_offset, F + c_offset + (height - 1) * row_pitch +
+ * width), each rounded up to the next 4-byte boundary.  The kernels fetch 16-byte units: a luma unit is one strip's 16 addressed
+ * bytes of one plane; a chroma unit is the 8 + 8 pixels of two neighbouring strips, and where a tile column ends with an odd strip
+ * it runs 8 bytes past the half row it belongs to, in one of the first height / 4 rows of the range.  Bytes outside the three ranges
+ * (a fourth plane, what lies in front of the first and behind the last frame, gaps between frames) are never read; bytes inside a
+ * range that the definition does not address (row padding, another plane's rows of a row interleave) may be read and never
+ * influence the output. */
+typedef struct m1v_rgb_plane_layout {
+    uint64_t r_offset, g_offset, b_offset; /* bytes from the frame's base to pixel (0,0) of each plane                */
+    uint64_t row_pitch;                    /* bytes between picture rows, the same in the three planes; >= width      */
+    uint64_t frame_stride;                 /* bytes between frames                                                    */
+} m1v_rgb_plane_layout;
+enum { M1V_RGB_PLANES_RGB = 0, M1V_RGB_PLANES_BGR = 1, M1V_RGB_PLANES_GBR = 2 }; /* the planes' order in memory */
+int m1v_rgb_plane_layout_preset(int width, int height, int order, m1v_rgb_plane_layout *out);
+int m1v_set_rgb_plane_layout(m1v_encoder *enc, const m1v_rgb_plane_layout *layout);
+int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *out);
+
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
  * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.
@@ -597,7 +653,7 @@ int m1v_debug_set_lds_words(m1v_encoder *enc, int words);
 int m1v_debug_set_path(m1v_encoder *enc, int path);
 int m1v_path_in_use(const m1v_encoder *enc); /* 1 = tiles, 0 = runs */
 /* Test hook: the nth device allocation made from now on by a reconfiguration (m1v_reserve_scratch, m1v_set_pipelined, m1v_set_input_layout,
- * the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
+ * m1v_set_plane_layout, m1v_set_sample_layout, m1v_set_rgb_plane_layout, the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
  * M1V_E_HIP and leaves the encoder exactly as it was.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
 void m1v_debug_fail_alloc(int nth);
 /* Test hook: the next m1v_encode_device that reaches `stage` returns M1V_E_HIP there, as a failed HIP call would: 1 = after
