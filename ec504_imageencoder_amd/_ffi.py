@@ -21,34 +21,32 @@ PLANES_REFERENCE, PLANES_I420, PLANES_YV12, PLANES_NV12, PLANES_NV21 = 0, 1, 2, 
 PLANE_PRESETS = {"reference": PLANES_REFERENCE, "i420": PLANES_I420, "yv12": PLANES_YV12, "nv12": PLANES_NV12, "nv21": PLANES_NV21}
 
 
-class PlaneLayout(C.Structure):
-    """m1v_plane_layout (include/mpeg1_hip.h): where the Y, Cb and Cr samples of a frame lie, in bytes."""
-    _fields_ = [(name, C.c_size_t) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")]
+class _Layout(C.Structure):
+    """What the layout structs of include/mpeg1_hip.h share: every field is a count of bytes."""
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class PlaneLayout(_Layout):
+    """m1v_plane_layout (include/mpeg1_hip.h): where the Y, Cb and Cr samples of a frame lie, in bytes."""
+    _fields_ = [(name, C.c_size_t) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")]
 
 SAMPLES_YUY2, SAMPLES_UYVY, SAMPLES_YVYU, SAMPLES_P010 = 0, 1, 2, 3
 SAMPLE_PRESETS = {"yuy2": SAMPLES_YUY2, "uyvy": SAMPLES_UYVY, "yvyu": SAMPLES_YVYU, "p010": SAMPLES_P010}
 
 
-class SampleLayout(C.Structure):
+class SampleLayout(_Layout):
     """m1v_sample_layout (include/mpeg1_hip.h): the plane layout with the distance between neighbouring luma samples."""
     _fields_ = [(name, C.c_size_t) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "y_step", "c_step", "frame_stride")]
-
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 RGB_PLANES_RGB, RGB_PLANES_BGR, RGB_PLANES_GBR = 0, 1, 2
 RGB_PLANE_ORDERS = {"rgb": RGB_PLANES_RGB, "bgr": RGB_PLANES_BGR, "gbr": RGB_PLANES_GBR}
 
 
-class RgbPlaneLayout(C.Structure):
+class RgbPlaneLayout(_Layout):
     """m1v_rgb_plane_layout (include/mpeg1_hip.h): where the R, G and B bytes of a frame lie, in bytes."""
     _fields_ = [(name, C.c_uint64) for name in ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")]
-
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 _u8p = C.POINTER(C.c_uint8)
 

@@ -1709,8 +1709,8 @@ __global__ __launch_bounds__(256) void k_synth(uint8_t *rgb, unsigned long long 
 // ------------------------------------------------------------------------------------------------
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, const char *detail = "") {
-    snprintf(g_err, sizeof g_err, fmt, detail);
+int fail(int code, const char *fmt, const char *detail = "", const char *detail2 = "") {
+    snprintf(g_err, sizeof g_err, fmt, detail, detail2);
     return code;
 }
 #define HIP_TRY(expr)                                                                              \
@@ -1777,17 +1777,16 @@ struct m1v_encoder {
     bool run_hook_set() const { return runs_by_path_or_mode() || forced_T > 0; }
     // plan_for's 4-channel fused table: every hook keeps one probe per quality, the A/B reference inside one process
     bool any_hook_set() const { return forced_path >= 0 || forced_mode >= 0 || forced_T != 0; }
-    // The input layout in force, no zeros.  surface (m1v_set_input_layout): the pictures are windows of a pitched surface (the
-    // surface kernels); planes (m1v_set_plane_layout): the frames are Y, Cb, Cr planes (the plane kernels, m1v_planes.h);
-    // rgb_planes (m1v_set_rgb_plane_layout): planes of R, G and B bytes (m1v_rgb_planes.h; y_off, cb_off, cr_off hold the R, G, B
-    // offsets, row_pitch the planes' common pitch)
+    // The input layout in force, no zeros: its kind, the frame stride every kind but packed has, and one member per kind.  Only the
+    // member of the kind in force is set and read (layout_facts: how messages name a kind, its setter and its getter).
     struct Layout {
-        enum class Kind { packed, surface, planes, rgb_planes } kind = Kind::packed;
-        uint32_t row_pitch = 0;               // bytes from a picture row to the next
-        unsigned long long frame_stride = 0;  // bytes from a frame's first pixel to the next frame's
-        int order = M1V_ORDER_RGB;
-        uint32_t y_off = 0, cb_off = 0, cr_off = 0, y_pitch = 0, c_pitch = 0, y_step = 0, c_step = 0;
-        unsigned long long extent = 0;        // bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
+        enum class Kind { packed, surface, samples, rgb_planes } kind = Kind::packed;
+        unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
+        struct Surface { uint32_t row_pitch; int order; } surface = {}; // m1v_set_input_layout: windows of a pitched surface, M1V_ORDER_* pixels
+        // m1v_set_plane_layout (y_step 1), m1v_set_sample_layout: Y, Cb, Cr samples where they lie (m1v_planes.h, m1v_step2.h);
+        // extent: bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
+        struct Samples { uint32_t y_off, cb_off, cr_off, y_pitch, c_pitch, y_step, c_step; unsigned long long extent; } samples = {};
+        RgbPlaneFrontArgs rgb_planes = {}; // m1v_set_rgb_plane_layout: planes of R, G and B bytes, as their kernels take them (m1v_rgb_planes.h)
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
@@ -2017,35 +2016,41 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 
 // Every kernel that takes dynamic LDS: the launches pick from it (tile_variant, run_kernel) and m1v_create raises the limit of
 // each.  [narrow staging] last; a null entry is a variant that does not exist.
-//   tile[encode | size table | rd table][tile_variant()]: the tile-shaped kernels of every input layout
+//   tile[TileFamily::row][tile_variant()]: the tile-shaped kernels of every input layout, each filled in beside its name
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
-enum { kPacked3, kPacked4, kSurface, kPlanes = kSurface + 4, kStep2 = kPlanes + 2, kRgbPlanes = kPlanes + 3, kTileVariants = kPlanes + 4 };
-#define M1V_PAIR(K, ...) {(const void *)&K<false, __VA_ARGS__>, (const void *)&K<true, __VA_ARGS__>}
-#define M1V_TILE_FAMILY(PACKED3, PACKED4, SURFACE, PLANES, STEP2, RGBP)                                                      \
-    {PACKED3, PACKED4, M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 3, 1),                  \
-     M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 0), M1V_PAIR(SURFACE, M1V_TILE_RING, 4, 1), M1V_PAIR(PLANES, M1V_TILE_RING, 1), \
-     M1V_PAIR(PLANES, M1V_TILE_RING, 2), M1V_PAIR(STEP2, M1V_TILE_RING), M1V_PAIR(RGBP, M1V_TILE_RING)}
-static const struct Kernels {
-    const void *tile[3][kTileVariants][2];
-    const void *dense[4][2];
-    const void *strips[2][2];
-} kKernels = {
-    // (packed 4-channel pictures encode on the run kernels)
-    {M1V_TILE_FAMILY(M1V_PAIR(k_encode_tiles, M1V_TILE_RING), {}, k_encode_surface, k_encode_planes, k_encode_step2,
-                     k_encode_rgb_planes),
-     M1V_TILE_FAMILY(M1V_PAIR(k_size_table_tiles, M1V_TILE_RING), M1V_PAIR(k_size_table_rgba, M1V_TILE_RING), k_size_table_surface,
-                     k_size_table_planes, k_size_table_step2, k_size_table_rgb_planes),
-     M1V_TILE_FAMILY(M1V_PAIR(k_rd_table_tiles, M1V_TILE_RING), M1V_PAIR(k_rd_table_rgba, M1V_TILE_RING), k_rd_table_surface,
-                     k_rd_table_planes, k_rd_table_step2, k_rd_table_rgb_planes)},
-    {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
-     {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
-     {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
-     {(const void *)&k_encode_dense<3, false>, (const void *)&k_encode_dense<3, true>}},
-    {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
-     {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
-#undef M1V_TILE_FAMILY
+enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kTileVariants };
+enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
+struct Kernels { const void *tile[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
+// K<wide>, K<narrow> with the tile ring and the variant's own template arguments behind it
+#define M1V_PAIR(DST, K, ...) ((DST)[0] = (const void *)&K<false, M1V_TILE_RING, ##__VA_ARGS__>, (DST)[1] = (const void *)&K<true, M1V_TILE_RING, ##__VA_ARGS__>)
+// one variant's encode, size-table and rd-table kernels: k_encode_<NAME>, k_size_table_<NAME>, k_rd_table_<NAME>
+#define M1V_TILE_VARIANT(V, NAME, ...)                                                                                            \
+    (M1V_PAIR(k.tile[kEncode][V], k_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.tile[kSizeTable][V], k_size_table_##NAME, ##__VA_ARGS__), \
+     M1V_PAIR(k.tile[kRdTable][V], k_rd_table_##NAME, ##__VA_ARGS__))
+static const Kernels kKernels = [] {
+    Kernels k = {{},
+                 {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
+                  {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
+                  {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
+                  {(const void *)&k_encode_dense<3, false>, (const void *)&k_encode_dense<3, true>}},
+                 {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
+                  {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
+    M1V_TILE_VARIANT(kPacked3, tiles);
+    M1V_PAIR(k.tile[kSizeTable][kPacked4], k_size_table_rgba); // (packed 4-channel pictures encode on the run kernels)
+    M1V_PAIR(k.tile[kRdTable][kPacked4], k_rd_table_rgba);
+    M1V_TILE_VARIANT(kSurfaceRgb3, surface, 3, M1V_ORDER_RGB);
+    M1V_TILE_VARIANT(kSurfaceBgr3, surface, 3, M1V_ORDER_BGR);
+    M1V_TILE_VARIANT(kSurfaceRgb4, surface, 4, M1V_ORDER_RGB);
+    M1V_TILE_VARIANT(kSurfaceBgr4, surface, 4, M1V_ORDER_BGR);
+    M1V_TILE_VARIANT(kPlanes, planes, 1);
+    M1V_TILE_VARIANT(kPlanesPaired, planes, 2);
+    M1V_TILE_VARIANT(kStep2, step2);
+    M1V_TILE_VARIANT(kRgbPlanes, rgb_planes);
+    return k;
+}();
+#undef M1V_TILE_VARIANT
 #undef M1V_PAIR
 
 // defined in m1v_runtime.h
@@ -2061,13 +2066,16 @@ static bool fast_path(const m1v_encoder *e, const uint8_t *d_rgb) {
 static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->qf, 1), 100); }
 
 // The tile-shaped kernels' variant for the layout in force (Kernels::tile): the one place that maps channels, byte order and
-// chroma step to an instantiation
-static int tile_variant(const m1v_encoder *e) {
+// sample steps to an instantiation
+static TileVariant tile_variant(const m1v_encoder *e) {
     const m1v_encoder::Layout &l = e->layout;
-    if (l.kind == LayoutKind::rgb_planes) return kRgbPlanes;
-    if (l.kind == LayoutKind::planes) return l.y_step == 2 ? kStep2 : kPlanes + (int)l.c_step - 1;
-    if (l.kind == LayoutKind::surface) return kSurface + (e->g.C == 4 ? 2 : 0) + l.order;
-    return e->g.C == 4 ? kPacked4 : kPacked3;
+    const bool four = e->g.C == 4;
+    switch (l.kind) {
+    case LayoutKind::rgb_planes: return kRgbPlanes;
+    case LayoutKind::samples: return l.samples.y_step == 2 ? kStep2 : (l.samples.c_step == 2 ? kPlanesPaired : kPlanes);
+    case LayoutKind::surface: return l.surface.order == M1V_ORDER_BGR ? (four ? kSurfaceBgr4 : kSurfaceBgr3) : (four ? kSurfaceRgb4 : kSurfaceRgb3);
+    case LayoutKind::packed: return four ? kPacked4 : kPacked3;
+    }
 }
 
 // the run kernel (plan: dense or strips) for this input pointer
@@ -2108,20 +2116,27 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
     a.tile_row_order = e->d_tile_order;
 }
 
-// The tile-shaped kernel of `family` (0 = encode: Surface = SurfaceArgs, Planes = PlaneArgs, RgbPlanes = RgbPlaneArgs; 1 = size
-// table, 2 = rd table: their table counterparts) over the grid a's TileArgs / TableArgs carries (fill_tile_grid), with a wrapped for the layout in force
-template <typename Surface, typename Planes, typename RgbPlanes, typename Args>
-static int launch_tiles(m1v_encoder *e, int family, bool narrow, Args &a, size_t grid, size_t lds, hipStream_t st) {
+// What a tile-shaped kernel's base arguments are wrapped in for each layout kind, and their row of Kernels::tile
+template <typename Base> struct TileFamily;
+template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; };
+template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; };
+template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; };
+
+// The tile-shaped kernel of a's family over the grid a carries (fill_tile_grid), with a wrapped for the layout in force
+template <typename Args>
+static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_t lds, hipStream_t st) {
+    using Family = TileFamily<Args>;
     const m1v_encoder::Layout &l = e->layout;
-    Surface on_surface = {a, l.frame_stride, l.row_pitch};
-    // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
-    Planes on_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, (uint32_t)(((l.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride};
-    RgbPlanes on_rgb_planes = {a, {l.y_off, l.cb_off, l.cr_off, l.row_pitch}, l.frame_stride};
-    void *arg = l.kind == LayoutKind::rgb_planes ? (void *)&on_rgb_planes
-                : l.kind == LayoutKind::planes ? (void *)&on_planes
-                : l.kind == LayoutKind::surface ? (void *)&on_surface : (void *)&a;
-    return launch_profiled(e, kKernels.tile[family][tile_variant(e)][narrow ? 1 : 0], grid, kTileThreads,
-                           arg, lds, st);
+    const void *kernel = kKernels.tile[Family::row][tile_variant(e)][narrow ? 1 : 0];
+    auto launch = [&](auto &&arg) { return launch_profiled(e, kernel, grid, kTileThreads, &arg, lds, st); };
+    const m1v_encoder::Layout::Samples &s = l.samples;
+    switch (l.kind) {
+    case LayoutKind::surface: return launch(typename Family::Surface{a, l.frame_stride, l.surface.row_pitch});
+    case LayoutKind::samples: // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
+        return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride});
+    case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, l.frame_stride});
+    case LayoutKind::packed: return launch(a);
+    }
 }
 
 // From its construction on, an error return leaves counters half used: the flag tells the next call to clear them first
@@ -2227,7 +2242,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         a.luma_region = p.luma_region;
         a.chroma_region = p.chroma_region;
         a.stamps = e->d_stamps;
-        rc = launch_tiles<SurfaceArgs, PlaneArgs, RgbPlaneArgs>(e, 0, e->narrow, a, grid, p.lds_bytes, st);
+        rc = launch_tiles(e, e->narrow, a, grid, p.lds_bytes, st);
     } else if (p.producer == Producer::dense) {
         DenseArgs a;
         a.g = g;
@@ -2368,8 +2383,8 @@ static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
     const size_t grid = (size_t)n_frames * p.table_units;
     if (dist) {
         RdTableArgs ra = {a, e->d_dq_all, tc.frame_dist};
-        if (const int rc = launch_tiles<SurfaceRdArgs, PlaneRdArgs, RgbPlaneRdArgs>(e, 2, narrow, ra, grid, p.table_lds_bytes + kRdPartWords * 4, st)) return rc;
-    } else if (const int rc = launch_tiles<SurfaceTableArgs, PlaneTableArgs, RgbPlaneTableArgs>(e, 1, narrow, a, grid, p.table_lds_bytes, st)) {
+        if (const int rc = launch_tiles(e, narrow, ra, grid, p.table_lds_bytes + kRdPartWords * 4, st)) return rc;
+    } else if (const int rc = launch_tiles(e, narrow, a, grid, p.table_lds_bytes, st)) {
         return rc;
     }
     if (fail_encode_at(2) != M1V_OK) return M1V_E_HIP;

@@ -307,12 +307,40 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
     return rc;
 }
 
+// How messages name a layout kind, its setter and its getter.  two_apart: a sample layout with y_step 2, which the getters name
+// for what it is (m1v_plane_layout cannot hold it)
+struct LayoutFacts { const char *name, *setter, *getter; };
+static LayoutFacts layout_facts(LayoutKind kind, bool two_apart = false) {
+    switch (kind) {
+    case LayoutKind::surface: return {"a surface layout", "m1v_set_input_layout", "m1v_input_layout"};
+    case LayoutKind::samples:
+        if (two_apart) return {"a layout with samples two bytes apart", "m1v_set_sample_layout", "m1v_sample_layout_in_force"};
+        return {"a plane layout", "m1v_set_plane_layout", "m1v_plane_layout_in_force"};
+    case LayoutKind::rgb_planes: return {"an RGB plane layout", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force"};
+    case LayoutKind::packed: return {"packed input", "m1v_set_input_layout", "m1v_input_layout"}; // (the surface layout's default)
+    }
+}
+
 // What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
 // the run kernels
 static int packed_only(const m1v_encoder *e) {
-    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "packed input only: an RGB plane layout is set (m1v_set_rgb_plane_layout)%s");
-    if (e->layout.kind == LayoutKind::planes) return fail(M1V_E_ARG, "packed input only: a plane layout is set (m1v_set_plane_layout)%s");
-    return e->layout.kind == LayoutKind::surface ? fail(M1V_E_ARG, "packed input only: a surface layout is set (m1v_set_input_layout)%s") : M1V_OK;
+    if (!e->layout.tiles_only()) return M1V_OK;
+    const LayoutFacts f = layout_facts(e->layout.kind);
+    return fail(M1V_E_ARG, "packed input only: %s is set (%s)", f.name, f.setter);
+}
+
+// A getter that cannot describe the layout in force names the one that can
+static int ask_its_getter(const m1v_encoder *e) {
+    const LayoutFacts f = layout_facts(e->layout.kind, e->layout.kind == LayoutKind::samples && e->layout.samples.y_step == 2);
+    return fail(M1V_E_ARG, "%s is in force: ask %s", f.name, f.getter);
+}
+
+// The shared tail of the layout setters, behind their argument checks: a layout of the tile kernels and a hook that forces the run
+// kernels refuse each other; then the new plan, or the layout that was in force
+static int apply_layout(m1v_encoder *e, const m1v_encoder::Layout &want) {
+    if (want.tiles_only() && e->run_hook_set())
+        return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
+    return reconfigure(e, &m1v_encoder::layout, want);
 }
 
 extern "C" {
@@ -568,24 +596,20 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
             return fail(M1V_E_ARG, "a window of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
         const unsigned long long extent = (unsigned long long)(g.H - 1) * pitch + row;
         if (frame_stride_bytes != 0 && frame_stride_bytes < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's window spans%s");
-        if (e->run_hook_set())
-            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
-        want.row_pitch = (uint32_t)pitch;
+        want.surface = {(uint32_t)pitch, order};
         want.frame_stride = frame_stride_bytes ? frame_stride_bytes : (unsigned long long)g.H * pitch;
-        want.order = order;
     }
-    return reconfigure(e, &m1v_encoder::layout, want);
+    return apply_layout(e, want);
 }
 
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
-    if (e->layout.kind == LayoutKind::planes)
-        return fail(M1V_E_ARG, e->layout.y_step == 2 ? "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s"
-                                                      : "a plane layout is in force: ask m1v_plane_layout_in_force%s");
-    if (row_pitch_bytes) *row_pitch_bytes = e->layout.row_pitch;
-    if (frame_stride_bytes) *frame_stride_bytes = (size_t)e->layout.frame_stride;
-    if (order) *order = e->layout.order;
+    const m1v_encoder::Layout &l = e->layout;
+    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    const m1v_encoder::Layout::Surface s = l.kind == LayoutKind::surface ? l.surface : m1v_encoder::Layout::Surface{0, M1V_ORDER_RGB};
+    if (row_pitch_bytes) *row_pitch_bytes = s.row_pitch;
+    if (frame_stride_bytes) *frame_stride_bytes = (size_t)l.frame_stride;
+    if (order) *order = s.order;
     return M1V_OK;
 }
 
@@ -645,8 +669,9 @@ int m1v_sample_layout_preset(int width, int height, int preset, m1v_sample_layou
     return M1V_OK;
 }
 
-// m1v_set_plane_layout and m1v_set_sample_layout: the checks of include/mpeg1_hip.h with the steps put in, then the reconfiguration
-static int set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
+// (m1v_set_plane_layout too: the checks of include/mpeg1_hip.h with the steps put in, then the reconfiguration)
+int m1v_set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
     m1v_encoder::Layout want;
     if (layout) {
         const Geometry &g = e->g;
@@ -672,55 +697,38 @@ static int set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
                                                    std::max<unsigned long long>(layout->cb_offset, layout->cr_offset) + c_rows);
         if (extent >= limit) return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
         if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
-        if (e->run_hook_set())
-            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
-        want.kind = LayoutKind::planes;
-        want.y_off = (uint32_t)layout->y_offset;
-        want.cb_off = (uint32_t)layout->cb_offset;
-        want.cr_off = (uint32_t)layout->cr_offset;
-        want.y_pitch = (uint32_t)y_pitch;
-        want.c_pitch = (uint32_t)c_pitch;
-        want.y_step = (uint32_t)y_step;
-        want.c_step = (uint32_t)step;
-        want.extent = extent;
+        want.kind = LayoutKind::samples;
+        want.samples = {(uint32_t)layout->y_offset, (uint32_t)layout->cb_offset, (uint32_t)layout->cr_offset, (uint32_t)y_pitch,
+                        (uint32_t)c_pitch, (uint32_t)y_step, (uint32_t)step, extent};
         want.frame_stride = layout->frame_stride;
     }
-    return reconfigure(e, &m1v_encoder::layout, want);
+    return apply_layout(e, want);
 }
 
 int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (!layout) return set_sample_layout(e, nullptr);
+    if (!layout) return m1v_set_sample_layout(e, nullptr);
     if (layout->c_step > 2) return fail(M1V_E_ARG, "c_step must be 1 or 2 (0 = 1)%s");
     const m1v_sample_layout l = {layout->y_offset, layout->cb_offset, layout->cr_offset, layout->y_pitch, layout->c_pitch, 1, layout->c_step, layout->frame_stride};
-    return set_sample_layout(e, &l);
-}
-
-int m1v_set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    return set_sample_layout(e, layout);
+    return m1v_set_sample_layout(e, &l);
 }
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
-    if (e->layout.kind != LayoutKind::planes) return 0;
-    if (e->layout.y_step == 2) return fail(M1V_E_ARG, "a layout with samples two bytes apart is in force: ask m1v_sample_layout_in_force%s");
-    if (out) {
-        const m1v_encoder::Layout &l = e->layout;
-        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.c_step, (size_t)l.frame_stride};
-    }
+    if (e->layout.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    if (e->layout.kind != LayoutKind::samples) return 0;
+    const m1v_encoder::Layout::Samples &s = e->layout.samples;
+    if (s.y_step == 2) return ask_its_getter(e);
+    if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.c_step, (size_t)e->layout.frame_stride};
     return 1;
 }
 
 int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes) return fail(M1V_E_ARG, "an RGB plane layout is in force: ask m1v_rgb_plane_layout_in_force%s");
-    if (e->layout.kind != LayoutKind::planes) return 0;
-    if (out) {
-        const m1v_encoder::Layout &l = e->layout;
-        *out = {l.y_off, l.cb_off, l.cr_off, l.y_pitch, l.c_pitch, l.y_step, l.c_step, (size_t)l.frame_stride};
-    }
+    if (e->layout.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    if (e->layout.kind != LayoutKind::samples) return 0;
+    const m1v_encoder::Layout::Samples &s = e->layout.samples;
+    if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.y_step, s.c_step, (size_t)e->layout.frame_stride};
     return 1;
 }
 
@@ -759,25 +767,18 @@ int m1v_set_rgb_plane_layout(m1v_encoder *e, const m1v_rgb_plane_layout *layout)
                     return fail(M1V_E_ARG, "two planes share bytes (planes may interleave by rows only)%s");
             }
         if (layout->frame_stride < hi + (H - 1) * pitch + W - lo) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
-        if (e->run_hook_set())
-            return fail(M1V_E_ARG, "a debug hook has forced this encoder to the run kernels, which take packed input only%s");
         want.kind = LayoutKind::rgb_planes;
-        want.y_off = (uint32_t)off[0];
-        want.cb_off = (uint32_t)off[1];
-        want.cr_off = (uint32_t)off[2];
-        want.row_pitch = (uint32_t)pitch;
+        want.rgb_planes = {(uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2], (uint32_t)pitch};
         want.frame_stride = layout->frame_stride;
     }
-    return reconfigure(e, &m1v_encoder::layout, want);
+    return apply_layout(e, want);
 }
 
 int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (e->layout.kind != LayoutKind::rgb_planes) return 0;
-    if (out) {
-        const m1v_encoder::Layout &l = e->layout;
-        *out = {l.y_off, l.cb_off, l.cr_off, l.row_pitch, l.frame_stride};
-    }
+    const RgbPlaneFrontArgs &p = e->layout.rgb_planes;
+    if (out) *out = {p.r_off, p.g_off, p.b_off, p.row_pitch, e->layout.frame_stride};
     return 1;
 }
 

@@ -201,9 +201,7 @@ class Mpeg1Encoder:
         self.frame_bound = L.m1v_frame_bound(self._h)
         self.frame_bytes_in = L.m1v_frame_bytes_in(self._h)
         self.blocks_per_frame = self.strips * self.mb_rows * 6
-        self._layout = (0, 0, "rgb")    # what _check_input holds tensors against (set_input_layout)
-        self._planes = None             # the plane or sample layout in force (set_plane_layout, set_sample_layout), a dict
-        self._rgb_planes = None         # the RGB plane layout in force (set_rgb_plane_layout), a dict
+        self._refresh_input()
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -242,10 +240,17 @@ class Mpeg1Encoder:
             _call("m1v_encode_quality_device", self._h, _ptr(rgb), n, int(first_frame_index), _ptr(q), *results)
         return out, sizes, meta
 
+    def _refresh_input(self):
+        """What _check_input holds tensors against: (the property that describes the input layout in force, its value), asked of
+        the library in the order in which its getters cannot fail.  sample_layout also holds a plane layout (y_step 1);
+        input_layout is never None: all zeros = packed frames."""
+        kinds = ("rgb_plane_layout", "sample_layout", "input_layout")
+        self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
+
     def _check_input(self, rgb):
         import torch
-        if self._rgb_planes is not None:  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
-            want = self._rgb_planes
+        kind, want = self._input
+        if kind == "rgb_plane_layout":  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4, "RGB plane frames must be a CUDA uint8 tensor [n, C, H, W]"
             assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
             assert rgb.stride(3) == 1 and rgb.stride(2) == want["row_pitch"], \
@@ -256,15 +261,15 @@ class Mpeg1Encoder:
             assert all(plane > 0 and want[k] % plane == 0 and want[k] // plane < rgb.shape[1] for k in ("r_offset", "g_offset", "b_offset")), \
                 f"the plane offsets in force are not channels of this tensor (plane stride {plane})"
             return
-        if self._planes is not None:    # [n, L] bytes, frame f at row f: L covers the frame's extent, rows frame_stride apart
+        if kind == "sample_layout":     # [n, L] bytes, frame f at row f: L covers the frame's extent, rows frame_stride apart
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 2, "plane frames must be a CUDA uint8 tensor [n, L]"
-            extent = plane_layout_extent(self._planes, self.strips, self.mb_rows)
+            extent = plane_layout_extent(want, self.strips, self.mb_rows)
             assert rgb.shape[0] == 0 or (rgb.stride(1) == 1 and rgb.shape[1] >= extent), \
                 f"a frame's row must be contiguous and hold the {extent} bytes its planes span"
-            assert rgb.shape[0] <= 1 or rgb.stride(0) == self._planes["frame_stride"], \
-                f"frames must lie {self._planes['frame_stride']} bytes apart (stride {rgb.stride(0)})"
+            assert rgb.shape[0] <= 1 or rgb.stride(0) == want["frame_stride"], \
+                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)})"
             return
-        row_pitch, frame_stride, _ = self._layout
+        row_pitch, frame_stride, _ = want
         if row_pitch == 0:      # the default layout: packed frames
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous()
             assert rgb.numel() == rgb.shape[0] * self.frame_bytes_in
@@ -282,8 +287,21 @@ class Mpeg1Encoder:
         kernels.  A reconfiguration: call it between batches."""
         code = {"rgb": _ffi.ORDER_RGB, "bgr": _ffi.ORDER_BGR}.get(order, order)
         _call("m1v_set_input_layout", self._h, int(row_pitch), int(frame_stride), int(code))
-        self._planes = self._rgb_planes = None  # one input layout is in force at a time
-        self._layout = self.input_layout
+        self._refresh_input()   # one input layout is in force at a time
+
+    def _set_layout(self, what, layout, preset, struct, fields, exact=False):
+        """m1v_set_<what>_layout with `layout`: a preset name, a dict of `fields` (exact: of all of them), or None."""
+        c = None
+        if layout is not None:
+            if isinstance(layout, str):
+                layout = preset(self.width, self.height, layout)
+            if exact and set(layout) != set(fields):
+                raise ValueError(f"an RGB plane layout has the fields {fields}")
+            if set(layout) - set(fields):
+                raise ValueError(f"unknown {what} layout fields {sorted(set(layout) - set(fields))}")
+            c = C.byref(struct(**{k: int(v) for k, v in layout.items()}))
+        _call(f"m1v_set_{what}_layout", self._h, c)
+        self._refresh_input()
 
     def set_plane_layout(self, layout):
         """Frames as Y, Cb, Cr planes on the device, encoded without a colour conversion (include/mpeg1_hip.h,
@@ -292,18 +310,7 @@ class Mpeg1Encoder:
         header), or None = back to the default layout and its kernels.  Every call then takes uint8 CUDA tensors [n, L] whose
         rows are the frames: L >= the bytes a frame's planes span, rows frame_stride apart — convert(rgb).view(n, -1) and
         torch.as_strided views go in as they are.  A reconfiguration: call it between batches."""
-        c = None
-        if layout is not None:
-            if isinstance(layout, str):
-                layout = plane_layout_preset(self.width, self.height, layout)
-            unknown = set(layout) - set(PLANE_LAYOUT_FIELDS)
-            if unknown:
-                raise ValueError(f"unknown plane layout fields {sorted(unknown)}")
-            c = C.byref(_ffi.PlaneLayout(**{k: int(v) for k, v in layout.items()}))
-        _call("m1v_set_plane_layout", self._h, c)
-        self._rgb_planes = None
-        self._planes = self.plane_layout
-        self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+        self._set_layout("plane", layout, plane_layout_preset, _ffi.PlaneLayout, PLANE_LAYOUT_FIELDS)
 
     def set_sample_layout(self, layout):
         """Frames whose samples lie one or two bytes apart, encoded where they lie (include/mpeg1_hip.h, m1v_set_sample_layout;
@@ -313,18 +320,7 @@ class Mpeg1Encoder:
         then takes uint8 CUDA tensors [n, L] as after set_plane_layout.  A uint16 P010 tensor goes in as
         frames.view(torch.uint8) (reshaped to [n, L]): the coded sample is each word's high byte, truncation, not rounding.
         A reconfiguration: call it between batches."""
-        c = None
-        if layout is not None:
-            if isinstance(layout, str):
-                layout = sample_layout_preset(self.width, self.height, layout)
-            unknown = set(layout) - set(SAMPLE_LAYOUT_FIELDS)
-            if unknown:
-                raise ValueError(f"unknown sample layout fields {sorted(unknown)}")
-            c = C.byref(_ffi.SampleLayout(**{k: int(v) for k, v in layout.items()}))
-        _call("m1v_set_sample_layout", self._h, c)
-        self._rgb_planes = None
-        self._planes = self.sample_layout
-        self._layout = (0, 0, "rgb") if self._planes is not None else self.input_layout
+        self._set_layout("sample", layout, sample_layout_preset, _ffi.SampleLayout, SAMPLE_LAYOUT_FIELDS)
 
     def set_rgb_plane_layout(self, layout):
         """Frames as planes of R, G and B bytes on the device — NCHW uint8 tensors — encoded where they lie, without a permute and
@@ -333,45 +329,31 @@ class Mpeg1Encoder:
         (rgb_plane_strides derives one from a tensor's shape and strides), or None = back to the default layout and its kernels.
         Every call then takes uint8 CUDA tensors [n, C >= 3, H, W] with those strides: a view x[:, :, y0:y0+H, x0:x0+W] of a larger
         tensor goes in as it is.  A reconfiguration: call it between batches."""
-        c = None
-        if layout is not None:
-            if isinstance(layout, str):
-                layout = rgb_plane_layout_preset(self.width, self.height, layout)
-            if set(layout) != set(RGB_PLANE_LAYOUT_FIELDS):
-                raise ValueError(f"an RGB plane layout has the fields {RGB_PLANE_LAYOUT_FIELDS}")
-            c = C.byref(_ffi.RgbPlaneLayout(**{k: int(v) for k, v in layout.items()}))
-        _call("m1v_set_rgb_plane_layout", self._h, c)
-        self._rgb_planes = self.rgb_plane_layout
-        self._planes = None
-        self._layout = (0, 0, "rgb") if self._rgb_planes is not None else self.input_layout
+        self._set_layout("rgb_plane", layout, rgb_plane_layout_preset, _ffi.RgbPlaneLayout, RGB_PLANE_LAYOUT_FIELDS, exact=True)
+
+    def _in_force(self, name, struct):
+        """The C getter `name` of a layout `struct`: the layout in force as a dict, or None where another kind is."""
+        c = struct()
+        rc = getattr(_ffi.lib(), name)(self._h, C.byref(c))
+        if rc < 0:
+            raise EncoderError(rc, name)
+        return c.as_dict() if rc == 1 else None
 
     @property
     def rgb_plane_layout(self):
         """The RGB plane layout in force as a dict of RGB_PLANE_LAYOUT_FIELDS in bytes, or None."""
-        c = _ffi.RgbPlaneLayout()
-        rc = _ffi.lib().m1v_rgb_plane_layout_in_force(self._h, C.byref(c))
-        if rc < 0:
-            raise EncoderError(rc, "m1v_rgb_plane_layout_in_force")
-        return c.as_dict() if rc == 1 else None
+        return self._in_force("m1v_rgb_plane_layout_in_force", _ffi.RgbPlaneLayout)
 
     @property
     def sample_layout(self):
         """The plane or sample layout in force as a dict of SAMPLE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros;
         y_step = 1 for a layout set through set_plane_layout), or None."""
-        c = _ffi.SampleLayout()
-        rc = _ffi.lib().m1v_sample_layout_in_force(self._h, C.byref(c))
-        if rc < 0:
-            raise EncoderError(rc, "m1v_sample_layout_in_force")
-        return c.as_dict() if rc == 1 else None
+        return self._in_force("m1v_sample_layout_in_force", _ffi.SampleLayout)
 
     @property
     def plane_layout(self):
         """The plane layout in force as a dict of PLANE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros), or None."""
-        c = _ffi.PlaneLayout()
-        rc = _ffi.lib().m1v_plane_layout_in_force(self._h, C.byref(c))
-        if rc < 0:
-            raise EncoderError(rc, "m1v_plane_layout_in_force")
-        return c.as_dict() if rc == 1 else None
+        return self._in_force("m1v_plane_layout_in_force", _ffi.PlaneLayout)
 
     @property
     def input_layout(self):
