@@ -1782,6 +1782,9 @@ struct m1v_encoder {
     struct Layout {
         enum class Kind { packed, surface, samples, rgb_planes } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
+        // m1v_set_frame_table: d_rgb is a device array of one 64-bit frame address per frame; frame_stride is kept and unused.
+        // Part of the record, so every setter's fresh record turns it off and a failed setter leaves it as it was.
+        bool frame_table = false;
         struct Surface { uint32_t row_pitch; int order; } surface = {}; // m1v_set_input_layout: windows of a pitched surface, M1V_ORDER_* pixels
         // m1v_set_plane_layout (y_step 1), m1v_set_sample_layout: Y, Cb, Cr samples where they lie (m1v_planes.h, m1v_step2.h);
         // extent: bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
@@ -2017,27 +2020,32 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 // Every kernel that takes dynamic LDS: the launches pick from it (tile_variant, run_kernel) and m1v_create raises the limit of
 // each.  [narrow staging] last; a null entry is a variant that does not exist.
 //   tile[TileFamily::row][tile_variant()]: the tile-shaped kernels of every input layout, each filled in beside its name
+//   table[...][...]: their kt_* twins of a frame table (m1v_set_frame_table); null for the packed variants, which take none
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
 enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kTileVariants };
 enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
-struct Kernels { const void *tile[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
+struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
 // K<wide>, K<narrow> with the tile ring and the variant's own template arguments behind it
 #define M1V_PAIR(DST, K, ...) ((DST)[0] = (const void *)&K<false, M1V_TILE_RING, ##__VA_ARGS__>, (DST)[1] = (const void *)&K<true, M1V_TILE_RING, ##__VA_ARGS__>)
-// one variant's encode, size-table and rd-table kernels: k_encode_<NAME>, k_size_table_<NAME>, k_rd_table_<NAME>
+// one layout variant's encode, size-table and rd-table kernels: k_encode_<NAME>, k_size_table_<NAME>, k_rd_table_<NAME>, and kt_* of each
 #define M1V_TILE_VARIANT(V, NAME, ...)                                                                                            \
     (M1V_PAIR(k.tile[kEncode][V], k_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.tile[kSizeTable][V], k_size_table_##NAME, ##__VA_ARGS__), \
-     M1V_PAIR(k.tile[kRdTable][V], k_rd_table_##NAME, ##__VA_ARGS__))
+     M1V_PAIR(k.tile[kRdTable][V], k_rd_table_##NAME, ##__VA_ARGS__),                                                             \
+     M1V_PAIR(k.table[kEncode][V], kt_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.table[kSizeTable][V], kt_size_table_##NAME, ##__VA_ARGS__), \
+     M1V_PAIR(k.table[kRdTable][V], kt_rd_table_##NAME, ##__VA_ARGS__))
 static const Kernels kKernels = [] {
-    Kernels k = {{},
+    Kernels k = {{}, {},
                  {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
                   {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
                   {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
                   {(const void *)&k_encode_dense<3, false>, (const void *)&k_encode_dense<3, true>}},
                  {{(const void *)&k_encode_strips<false>, (const void *)&k_encode_strips<false>},
                   {(const void *)&k_encode_strips<true>, (const void *)&k_encode_strips<true>}}};
-    M1V_TILE_VARIANT(kPacked3, tiles);
+    M1V_PAIR(k.tile[kEncode][kPacked3], k_encode_tiles); // (the packed kernels have no frame-table twins)
+    M1V_PAIR(k.tile[kSizeTable][kPacked3], k_size_table_tiles);
+    M1V_PAIR(k.tile[kRdTable][kPacked3], k_rd_table_tiles);
     M1V_PAIR(k.tile[kSizeTable][kPacked4], k_size_table_rgba); // (packed 4-channel pictures encode on the run kernels)
     M1V_PAIR(k.tile[kRdTable][kPacked4], k_rd_table_rgba);
     M1V_TILE_VARIANT(kSurfaceRgb3, surface, 3, M1V_ORDER_RGB);
@@ -2127,16 +2135,25 @@ template <typename Args>
 static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_t lds, hipStream_t st) {
     using Family = TileFamily<Args>;
     const m1v_encoder::Layout &l = e->layout;
-    const void *kernel = kKernels.tile[Family::row][tile_variant(e)][narrow ? 1 : 0];
+    // (a frame table has the kt_* twin of the variant's kernel, which reads a.rgb as the table and not the stride: frame_table_entry)
+    const void *kernel = (l.frame_table ? kKernels.table : kKernels.tile)[Family::row][tile_variant(e)][narrow ? 1 : 0];
     auto launch = [&](auto &&arg) { return launch_profiled(e, kernel, grid, kTileThreads, &arg, lds, st); };
     const m1v_encoder::Layout::Samples &s = l.samples;
+    const unsigned long long stride = l.frame_stride;
     switch (l.kind) {
-    case LayoutKind::surface: return launch(typename Family::Surface{a, l.frame_stride, l.surface.row_pitch});
+    case LayoutKind::surface: return launch(typename Family::Surface{a, stride, l.surface.row_pitch});
     case LayoutKind::samples: // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
-        return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, l.frame_stride});
-    case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, l.frame_stride});
+        return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, stride});
+    case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, stride});
     case LayoutKind::packed: return launch(a);
     }
+}
+
+// With a frame table on, d_rgb is read as 64-bit words by a scalar load: refused here, in front of every launch, when misaligned
+static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
+    if (e->layout.frame_table && ((uintptr_t)d_rgb & 7) != 0)
+        return fail(M1V_E_ARG, "a frame table is on (m1v_set_frame_table): d_rgb is an array of 64-bit frame addresses and must be 8-byte aligned%s");
+    return M1V_OK;
 }
 
 // From its construction on, an error return leaves counters half used: the flag tells the next call to clear them first
@@ -2187,6 +2204,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
                         const EncodeOut &o, void *stream) {
     if (!e || (!d_rgb && n_frames > 0) || (!o.out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
     if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (const int rc = check_frame_table(e, d_rgb)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));
     m1v_encoder::Batch &bt = e->batch[e->pipelined ? (e->calls++ & 1u) : 0];
@@ -2360,6 +2378,7 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
 // dist != null: the rd table (the k_rd_table_* kernels and k_rd_table_sizes in their places), dist[k * stride + frame] beside the sizes.
 static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,
                             unsigned long long *sizes, unsigned long long *dist, size_t stride, uint32_t *status, hipStream_t st) {
+    if (const int rc = check_frame_table(e, d_rgb)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     m1v_encoder::TableCounters &tc = e->table;
     const Plan &p = e->plan;

@@ -183,8 +183,8 @@ struct PlaneTableArgs {
 };
 
 // the bodies' input-layout names: the frame base is taken as for a surface (base + frame * frame_stride, default rounding mode)
-#define M1V_PLANE_INPUT                                                                            \
-    constexpr bool SURFACE = true;                                                                 \
+#define M1V_PLANE_INPUT(TABLE)                                                                     \
+    constexpr bool SURFACE = true, FRAME_TABLE = TABLE;                                            \
     constexpr int BPP = 3, ORDER = 0;                                                              \
     constexpr uint32_t row_pitch = 0;                                                              \
     const unsigned long long frame_stride = pa.frame_stride;                                       \
@@ -196,14 +196,14 @@ struct PlaneTableArgs {
 template <bool STAGE8, int R, int CSTEP>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
 void k_encode_planes(PlaneArgs pa) {
-    M1V_PLANE_INPUT;
+    M1V_PLANE_INPUT(false);
     const TileArgs &a = pa.t;
 #include "m1v_encode_tile_body.h"
 }
 
 template <bool STAGE8, int R, int CSTEP>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_planes(PlaneTableArgs pa) {
-    M1V_PLANE_INPUT;
+    M1V_PLANE_INPUT(false);
     const TableArgs &a = pa.t;
     M1V_SIZES_ONLY;
 #include "m1v_size_table_body.h"
@@ -216,7 +216,31 @@ struct PlaneRdArgs {
 };
 template <bool STAGE8, int R, int CSTEP>
 __global__ __launch_bounds__(kTileThreads) void k_rd_table_planes(PlaneRdArgs pa) {
-    M1V_PLANE_INPUT;
+    M1V_PLANE_INPUT(false);
+    M1V_RD_INPUT(pa.t);
+#include "m1v_size_table_body.h"
+}
+
+// The same three of a frame table (m1v_set_frame_table): pa.t.rgb holds one 64-bit frame address per frame, pa.frame_stride is not read
+template <bool STAGE8, int R, int CSTEP>
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
+void kt_encode_planes(PlaneArgs pa) {
+    M1V_PLANE_INPUT(true);
+    const TileArgs &a = pa.t;
+#include "m1v_encode_tile_body.h"
+}
+
+template <bool STAGE8, int R, int CSTEP>
+__global__ __launch_bounds__(kTileThreads) void kt_size_table_planes(PlaneTableArgs pa) {
+    M1V_PLANE_INPUT(true);
+    const TableArgs &a = pa.t;
+    M1V_SIZES_ONLY;
+#include "m1v_size_table_body.h"
+}
+
+template <bool STAGE8, int R, int CSTEP>
+__global__ __launch_bounds__(kTileThreads) void kt_rd_table_planes(PlaneRdArgs pa) {
+    M1V_PLANE_INPUT(true);
     M1V_RD_INPUT(pa.t);
 #include "m1v_size_table_body.h"
 }

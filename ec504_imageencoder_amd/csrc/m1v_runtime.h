@@ -782,6 +782,18 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *ou
     return 1;
 }
 
+// The frame table is a flag of the layout record in force: no plan, no allocation, nothing queued
+int m1v_set_frame_table(m1v_encoder *e, int enable) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (enable && !e->layout.tiles_only())
+        return fail(M1V_E_ARG, "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
+                               "m1v_set_input_layout(enc, width * channels, 0, order)%s");
+    e->layout.frame_table = enable != 0;
+    return M1V_OK;
+}
+
+int m1v_frame_table(const m1v_encoder *e) { return e ? (e->layout.frame_table ? 1 : 0) : -1; }
+
 int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }
 
 int m1v_size_table_fused(const m1v_encoder *e) { return e ? (e->plan.table_units ? 1 : 0) : -1; }

@@ -317,12 +317,21 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
 #endif
 // the input layout of the packed kernels, for the kernel bodies that are shared with the surface kernels as headers
 #define M1V_PACKED_INPUT                                                                           \
-    constexpr bool SURFACE = false;                                                                \
+    constexpr bool SURFACE = false, FRAME_TABLE = false;                                           \
     constexpr int ORDER = 0;                                                                       \
     constexpr uint32_t row_pitch = 0;                                                              \
     constexpr unsigned long long frame_stride = 0
 // the front half the kernel bodies call (m1v_planes.h puts its own in this place for the plane kernels)
 #define M1V_FRONT_HALF tile_pixel_rows
+
+// The frame base in the kt_* kernels, the instantiations of a frame table (m1v_set_frame_table; FRAME_TABLE in the bodies) beside
+// every kernel that takes a layout: `rgb` is a device array of one 64-bit address per frame, and the layout's frame_stride is not
+// read.  `frame` is workgroup-uniform (frame_unit_of on blockIdx.x), so this is one 8-byte scalar load where the k_* kernels have a
+// scalar multiply-add.  The table has kernels of its own, not a runtime select in the k_* kernels: with the select the stride
+// encodes of two layouts measured outside their A/A spread against the parent's (DESIGN.md "Frame tables").
+__device__ __forceinline__ const uint8_t *frame_table_entry(const uint8_t *rgb, int frame) {
+    return reinterpret_cast<const uint8_t *>(static_cast<uintptr_t>(reinterpret_cast<const unsigned long long *>(rgb)[frame]));
+}
 #ifndef M1V_TILE_WAVES_PER_EU
 #define M1V_TILE_WAVES_PER_EU 5
 #endif
@@ -495,7 +504,17 @@ struct SurfaceArgs {
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
 void k_encode_surface(SurfaceArgs sa) {
-    constexpr bool SURFACE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    const TileArgs &a = sa.t;
+    const uint32_t row_pitch = sa.row_pitch;
+    const unsigned long long frame_stride = sa.frame_stride;
+#include "m1v_encode_tile_body.h"
+}
+// ... and of a frame table (m1v_set_frame_table): sa.t.rgb holds one 64-bit frame address per frame, sa.frame_stride is not read
+template <bool STAGE8, int R, int BPP, int ORDER>
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
+void kt_encode_surface(SurfaceArgs sa) {
+    constexpr bool SURFACE = true, FRAME_TABLE = true;
     const TileArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -634,7 +653,17 @@ struct SurfaceTableArgs {
 };
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_surface(SurfaceTableArgs sa) {
-    constexpr bool SURFACE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    const TableArgs &a = sa.t;
+    const uint32_t row_pitch = sa.row_pitch;
+    const unsigned long long frame_stride = sa.frame_stride;
+    M1V_SIZES_ONLY;
+#include "m1v_size_table_body.h"
+}
+// (of a frame table)
+template <bool STAGE8, int R, int BPP, int ORDER>
+__global__ __launch_bounds__(kTileThreads) void kt_size_table_surface(SurfaceTableArgs sa) {
+    constexpr bool SURFACE = true, FRAME_TABLE = true;
     const TableArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -704,7 +733,16 @@ struct SurfaceRdArgs {
 };
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void k_rd_table_surface(SurfaceRdArgs sa) {
-    constexpr bool SURFACE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    const uint32_t row_pitch = sa.row_pitch;
+    const unsigned long long frame_stride = sa.frame_stride;
+    M1V_RD_INPUT(sa.t);
+#include "m1v_size_table_body.h"
+}
+// (of a frame table)
+template <bool STAGE8, int R, int BPP, int ORDER>
+__global__ __launch_bounds__(kTileThreads) void kt_rd_table_surface(SurfaceRdArgs sa) {
+    constexpr bool SURFACE = true, FRAME_TABLE = true;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
     M1V_RD_INPUT(sa.t);

@@ -68,7 +68,8 @@ class HostDelivery:
         return host.value, int(nbytes.value), sizes.value
 
     def step(self, rgb, first_frame_index=0):
-        """Encode `rgb` (device-resident) on the current stream; the batch before it starts travelling behind it."""
+        """Encode `rgb` (device-resident; while the encoder's frame table is on, what enc.frames() returned or an int64 CUDA tensor
+        of frame addresses) on the current stream; the batch before it starts travelling behind it."""
         self._keep.append(rgb)
         n = int(rgb.shape[0])
         slot = _ffi.lib().m1v_delivery_step(self._h, _ptr(rgb), n, int(first_frame_index), _stream())

@@ -179,6 +179,23 @@ def plane_layout_extent(layout, strips, mb_rows):
     return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
 
 
+class FrameTable:
+    """A batch whose frames lie at separate device addresses (Mpeg1Encoder.frames, Mpeg1Encoder.set_frame_table): `table` is the
+    int64 CUDA tensor [n] of the frames' base addresses, which the kernels read on the stream; `frames` keeps the tensors it
+    names alive.  Stands where the methods of Mpeg1Encoder and HostDelivery.step take `rgb`: they read shape[0], device and
+    data_ptr() of it."""
+
+    def __init__(self, table, frames=()):
+        self.table, self.frames = table, tuple(frames)
+        self.shape, self.device = (int(table.shape[0]),), table.device
+
+    def data_ptr(self):
+        return self.table.data_ptr()
+
+    def __len__(self):
+        return self.shape[0]
+
+
 class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
@@ -218,7 +235,8 @@ class Mpeg1Encoder:
     def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
         as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes; or, after set_rgb_plane_layout,
-        [n, C, H, W] planes of R, G and B.  Asynchronous on torch's current stream.
+        [n, C, H, W] planes of R, G and B; or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
+        addresses (this holds for every method that takes rgb).  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
         CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
@@ -246,9 +264,16 @@ class Mpeg1Encoder:
         input_layout is never None: all zeros = packed frames."""
         kinds = ("rgb_plane_layout", "sample_layout", "input_layout")
         self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
+        self._table_on = self.frame_table   # (every successful layout setter turns the frame table off)
 
     def _check_input(self, rgb):
         import torch
+        if self._table_on:  # a frame table: what frames() made, or the caller's own int64 addresses [n]
+            assert isinstance(rgb, FrameTable) or (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.int64
+                                                   and rgb.dim() == 1 and rgb.is_contiguous()), \
+                "a frame table is on: pass frames([...]) or a contiguous CUDA int64 tensor [n] of frame addresses"
+            return
+        assert not isinstance(rgb, FrameTable), "a FrameTable needs set_frame_table()"
         kind, want = self._input
         if kind == "rgb_plane_layout":  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4, "RGB plane frames must be a CUDA uint8 tensor [n, C, H, W]"
@@ -330,6 +355,40 @@ class Mpeg1Encoder:
         Every call then takes uint8 CUDA tensors [n, C >= 3, H, W] with those strides: a view x[:, :, y0:y0+H, x0:x0+W] of a larger
         tensor goes in as it is.  A reconfiguration: call it between batches."""
         self._set_layout("rgb_plane", layout, rgb_plane_layout_preset, _ffi.RgbPlaneLayout, RGB_PLANE_LAYOUT_FIELDS, exact=True)
+
+    def set_frame_table(self, enable=True):
+        """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
+        method takes, in the place of `rgb`, what frames() returns or a contiguous CUDA int64 tensor [n] of the frames' base
+        addresses, which only the kernels read, on the stream.  Needs a surface, plane, sample or RGB plane layout in force (packed
+        frames: set_input_layout(width * channels) first); every layout setter turns it off again.  Not a reconfiguration:
+        nothing is allocated or waited for."""
+        _call("m1v_set_frame_table", self._h, 1 if enable else 0)
+        self._table_on = self.frame_table
+
+    @property
+    def frame_table(self):
+        """True while a frame table is on (set_frame_table)."""
+        return _ffi.lib().m1v_frame_table(self._h) == 1
+
+    def frames(self, tensors):
+        """A FrameTable of `tensors`: one CUDA uint8 tensor per frame, each what the layout in force takes as a batch of one
+        without its leading dimension ([H, W, C] with the row pitch in force; [L] bytes of planes or samples; [C, H, W] planes of
+        R, G and B) — separate allocations, views of a pool, the same tensor more than once, in any order.  Checks each as a batch
+        of one, uploads their addresses (a host-to-device copy on the current stream) and keeps the tensors alive with the
+        result.  For the calls made while set_frame_table() is on."""
+        import torch
+        tensors = list(tensors)
+        assert tensors, "frames() needs at least one frame"
+        assert self._input != ("input_layout", (0, 0, "rgb")), "a frame table needs a layout: set_input_layout(width * channels) for packed frames"
+        on, self._table_on = self._table_on, False
+        try:
+            for t in tensors:
+                self._check_input(t.unsqueeze(0))
+        finally:
+            self._table_on = on
+        assert all(t.device == tensors[0].device for t in tensors), "the frames of a table lie on one device"
+        table = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(tensors[0].device)
+        return FrameTable(table, tensors)
 
     def _in_force(self, name, struct):
         """The C getter `name` of a layout `struct`: the layout in force as a dict, or None where another kind is."""

@@ -547,6 +547,42 @@ int m1v_rgb_plane_layout_preset(int width, int height, int order, m1v_rgb_plane_
 int m1v_set_rgb_plane_layout(m1v_encoder *enc, const m1v_rgb_plane_layout *layout);
 int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *out);
 
+/* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
+ * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
+ * contiguous batch in front of the encoder.
+ *
+ * Definition.  While the table is on, the d_rgb argument of every *_device call and of m1v_delivery_step is a device array of
+ * uint64_t[n_frames] that holds the device address of each frame's base F; it is no longer the first frame's first byte, and frame
+ * f no longer starts at d_rgb + f * frame_stride.  Everything else the layout in force defines — offsets, pitches, steps, byte
+ * order, the read contract — applies to each F exactly as it does without a table.  Frame f of the table is frame
+ * first_frame_index + f of the stream.  Entries may repeat an address, appear in any memory order and point into different
+ * allocations; any byte alignment of an entry is accepted, as any pointer, pitch and stride are without a table.
+ *
+ *   m1v_set_frame_table(enc, enable)   M1V_OK, or M1V_E_ARG: a null encoder; enable != 0 on the default packed layout.  The table
+ *     needs a layout served by the tile kernels in force (m1v_set_input_layout, m1v_set_plane_layout, m1v_set_sample_layout,
+ *     m1v_set_rgb_plane_layout); packed frames go through a table after m1v_set_input_layout(enc, width * channels, 0, order), the
+ *     way a packed buffer reaches the surface kernels.  The packed tile kernels and the run kernels take no table.
+ *     The flag is part of the layout in force: every successful layout setter, those that restore the default included, turns it
+ *     off; a setter that fails leaves it as it was, like everything else.  Not a reconfiguration: nothing is allocated, waited for
+ *     or queued, and the plan does not change.  m1v_path_in_use, m1v_size_table_fused and the layout getters answer as before; the
+ *     layout's frame_stride is kept and reported, and unused while the table is on.
+ *   m1v_frame_table(enc)   1 = on, 0 = off, -1 = a null encoder.
+ * Served: m1v_encode_device, m1v_encode_quality_device, m1v_frame_sizes_device, m1v_frame_size_table_device,
+ * m1v_frame_rd_table_device, the budget, batch-budget and bitrate calls by size and by distortion, pipelined mode, and
+ * m1v_delivery_step with its scratch retry, which reads the table again.
+ * When the table is read: only the kernels read it, on the stream, and only entries [0, n_frames).  A caller may fill it with work
+ * queued on the same stream in front of the call, with no host wait.  The table and the frames it names must stay valid as long
+ * as d_rgb must without a table; for a delivery step that is until the batch's copy has started.
+ * Errors: M1V_E_ARG before anything is launched when the table pointer is not 8-byte aligned (the kernels load an entry as one
+ * 64-bit word); the null and n_frames checks are those of every call.  The entries are not validated and cannot be: an entry that
+ * is not a device address of the encoder's device is undefined behaviour, exactly as a bad d_rgb is without a table.
+ * Read contract: unchanged per frame — the range or ranges the layout defines, relative to that frame's F, each rounded up to the
+ * next 4-byte boundary; of the table, entries [0, n_frames).
+ * Not covered: separate pointers per plane of one frame (Y, Cb and Cr, or R, G and B, in three allocations).  The kernels address
+ * a frame as one scalar base plus 32-bit lane offsets, and the plane kernels clamp their loads relative to that base. */
+int m1v_set_frame_table(m1v_encoder *enc, int enable);
+int m1v_frame_table(const m1v_encoder *enc);
+
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
  * the failed call's outputs are undefined, and the next call on the same encoder and stream is exact again.
