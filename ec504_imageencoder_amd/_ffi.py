@@ -66,7 +66,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
     "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
     "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
-    "m1v_set_frame_table", "m1v_frame_table",
+    "m1v_set_frame_table", "m1v_frame_table", "m1v_set_plane_table", "m1v_plane_table",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
 DELIVERY_NONE = 2
@@ -211,6 +211,10 @@ def lib():
     L.m1v_set_frame_table.restype = C.c_int
     L.m1v_frame_table.argtypes = [vp]
     L.m1v_frame_table.restype = C.c_int
+    L.m1v_set_plane_table.argtypes = [vp, C.c_int]
+    L.m1v_set_plane_table.restype = C.c_int
+    L.m1v_plane_table.argtypes = [vp]
+    L.m1v_plane_table.restype = C.c_int
     L.m1v_debug_fail_alloc.argtypes = [C.c_int]
     L.m1v_debug_fail_alloc.restype = None
     L.m1v_debug_fail_encode.argtypes = [C.c_int]

@@ -1,7 +1,7 @@
 // ec504_imageencoder_amd/csrc/m1v_encode_tile_body.h — the body of k_encode_tiles and k_encode_surface (m1v_tiles.h), included
 // inside each kernel (a shared inline function would do, but the compiler may then number the registers of k_encode_tiles
 // differently: its code stays the parent's instruction for instruction this way).  In scope: STAGE8, R (template parameters),
-// TileArgs a, and the input layout: BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows), FRAME_TABLE.  The front
+// TileArgs a, and the input layout: BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows), FRAME_TABLE, PLANE_TABLE.  The front
 // half is named by the macro M1V_FRONT_HALF: tile_pixel_rows, or PlaneFront::run for the plane kernels (m1v_planes.h).
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const Geometry &g = a.g;
@@ -26,7 +26,8 @@
     int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
     // (a surface kernel stays in the default rounding mode: the integer row pass, as the size-table kernels)
     const uint8_t *fbase;
-    if constexpr (SURFACE && FRAME_TABLE) fbase = frame_table_entry(a.rgb, frame); // (the kt_* kernels: a.rgb is the frame table)
+    if constexpr (SURFACE && PLANE_TABLE) fbase = plane_table_row(a.rgb, frame); // (the kp_* kernels: the frame's three entries of the plane table)
+    else if constexpr (SURFACE && FRAME_TABLE) fbase = frame_table_entry(a.rgb, frame); // (the kt_* kernels: a.rgb is the frame table)
     else if constexpr (SURFACE) fbase = a.rgb + (unsigned long long)frame * frame_stride;
     else fbase = pixel_stage_rounds_down(a.rgb + (unsigned long long)frame * g.frame_bytes, s0, m0);
     const unsigned long long tile_index = (unsigned long long)frame * a.tiles_per_frame + tile;

@@ -1782,9 +1782,10 @@ struct m1v_encoder {
     struct Layout {
         enum class Kind { packed, surface, samples, rgb_planes } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
-        // m1v_set_frame_table: d_rgb is a device array of one 64-bit frame address per frame; frame_stride is kept and unused.
-        // Part of the record, so every setter's fresh record turns it off and a failed setter leaves it as it was.
-        bool frame_table = false;
+        // m1v_set_frame_table / m1v_set_plane_table: d_rgb is a device array of one 64-bit address per frame, or of three (one per
+        // plane); frame_stride is kept and unused.  Part of the record, so every setter's fresh record turns tables off and a
+        // failed setter leaves the mode as it was.
+        enum class Table { off, frames, planes } table = Table::off;
         struct Surface { uint32_t row_pitch; int order; } surface = {}; // m1v_set_input_layout: windows of a pitched surface, M1V_ORDER_* pixels
         // m1v_set_plane_layout (y_step 1), m1v_set_sample_layout: Y, Cb, Cr samples where they lie (m1v_planes.h, m1v_step2.h);
         // extent: bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
@@ -1857,6 +1858,7 @@ struct m1v_encoder {
 };
 
 using LayoutKind = m1v_encoder::Layout::Kind;
+using TableMode = m1v_encoder::Layout::Table;
 
 // The order in which a frame's tile rows are processed.  Tile row R (macroblock rows 4R..4R+3) reads its luma from picture
 // rows [64R, 64R+64) and — the chroma quirk, encoder.h:347-348 — its chroma from rows [16R, 16R+16), i.e. from one quarter of
@@ -2026,7 +2028,8 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   every level wide.
 enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kTileVariants };
 enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
-struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
+//   planes[...][...]: their kp_* twins of a plane table (m1v_set_plane_table); kPlanes, kPlanesPaired and kRgbPlanes only
+struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows][kTileVariants][2], *planes[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
 // K<wide>, K<narrow> with the tile ring and the variant's own template arguments behind it
 #define M1V_PAIR(DST, K, ...) ((DST)[0] = (const void *)&K<false, M1V_TILE_RING, ##__VA_ARGS__>, (DST)[1] = (const void *)&K<true, M1V_TILE_RING, ##__VA_ARGS__>)
 // one layout variant's encode, size-table and rd-table kernels: k_encode_<NAME>, k_size_table_<NAME>, k_rd_table_<NAME>, and kt_* of each
@@ -2035,8 +2038,12 @@ struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows
      M1V_PAIR(k.tile[kRdTable][V], k_rd_table_##NAME, ##__VA_ARGS__),                                                             \
      M1V_PAIR(k.table[kEncode][V], kt_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.table[kSizeTable][V], kt_size_table_##NAME, ##__VA_ARGS__), \
      M1V_PAIR(k.table[kRdTable][V], kt_rd_table_##NAME, ##__VA_ARGS__))
+// ... and its kp_* kernels of a plane table
+#define M1V_PLANE_TABLE_VARIANT(V, NAME, ...)                                                                                     \
+    (M1V_PAIR(k.planes[kEncode][V], kp_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.planes[kSizeTable][V], kp_size_table_##NAME, ##__VA_ARGS__), \
+     M1V_PAIR(k.planes[kRdTable][V], kp_rd_table_##NAME, ##__VA_ARGS__))
 static const Kernels kKernels = [] {
-    Kernels k = {{}, {},
+    Kernels k = {{}, {}, {},
                  {{(const void *)&k_encode_dense<0, false>, (const void *)&k_encode_dense<0, true>},
                   {(const void *)&k_encode_dense<1, false>, (const void *)&k_encode_dense<1, true>},
                   {(const void *)&k_encode_dense<2, false>, (const void *)&k_encode_dense<2, true>},
@@ -2056,8 +2063,12 @@ static const Kernels kKernels = [] {
     M1V_TILE_VARIANT(kPlanesPaired, planes, 2);
     M1V_TILE_VARIANT(kStep2, step2);
     M1V_TILE_VARIANT(kRgbPlanes, rgb_planes);
+    M1V_PLANE_TABLE_VARIANT(kPlanes, planes, 1);
+    M1V_PLANE_TABLE_VARIANT(kPlanesPaired, planes, 2);
+    M1V_PLANE_TABLE_VARIANT(kRgbPlanes, rgb_planes);
     return k;
 }();
+#undef M1V_PLANE_TABLE_VARIANT
 #undef M1V_TILE_VARIANT
 #undef M1V_PAIR
 
@@ -2136,10 +2147,22 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
     using Family = TileFamily<Args>;
     const m1v_encoder::Layout &l = e->layout;
     // (a frame table has the kt_* twin of the variant's kernel, which reads a.rgb as the table and not the stride: frame_table_entry)
-    const void *kernel = (l.frame_table ? kKernels.table : kKernels.tile)[Family::row][tile_variant(e)][narrow ? 1 : 0];
+    // (a plane table has the kp_* twin, which reads a.rgb as three addresses per frame: plane_table_row, PlaneBases)
+    const auto &rows = l.table == TableMode::planes ? kKernels.planes : (l.table == TableMode::frames ? kKernels.table : kKernels.tile);
+    const void *kernel = rows[Family::row][tile_variant(e)][narrow ? 1 : 0];
+    if (!kernel) return fail(M1V_E_ARG, "no kernel serves the table mode in force with this layout%s"); // (m1v_set_plane_table refuses those layouts)
     auto launch = [&](auto &&arg) { return launch_profiled(e, kernel, grid, kTileThreads, &arg, lds, st); };
     const m1v_encoder::Layout::Samples &s = l.samples;
     const unsigned long long stride = l.frame_stride;
+    if (l.table == TableMode::planes) {
+        if (l.kind == LayoutKind::rgb_planes) return launch(RgbPlanePtrArgs<Args>{a, l.rgb_planes});
+        // one limit per chroma plane, relative to its own pointer: the last offset at which a 16-byte unit may start, from the
+        // plane's extent E_p = p_off + (rows - 1) * c_pitch + row bytes (the read contract of mpeg1_hip.h), rounded up to whole dwords
+        const unsigned long long xe = (unsigned long long)e->g.n_strips * 16, ye = (unsigned long long)e->g.n_mbrows * 16;
+        const unsigned long long c_rows = (ye / 2 - 1) * s.c_pitch + (xe / 2 - 1) * s.c_step + 1;
+        auto lim = [&](uint32_t off) { return (uint32_t)(((off + c_rows + 3ull) & ~3ull) - 16ull); };
+        return launch(PlanePtrArgs<Args>{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, lim(s.cb_off), lim(s.cr_off)}});
+    }
     switch (l.kind) {
     case LayoutKind::surface: return launch(typename Family::Surface{a, stride, l.surface.row_pitch});
     case LayoutKind::samples: // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
@@ -2149,11 +2172,12 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
     }
 }
 
-// With a frame table on, d_rgb is read as 64-bit words by a scalar load: refused here, in front of every launch, when misaligned
+// With a frame or plane table on, d_rgb is read as 64-bit words by scalar loads: refused here, in front of every launch, when misaligned
 static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
-    if (e->layout.frame_table && ((uintptr_t)d_rgb & 7) != 0)
-        return fail(M1V_E_ARG, "a frame table is on (m1v_set_frame_table): d_rgb is an array of 64-bit frame addresses and must be 8-byte aligned%s");
-    return M1V_OK;
+    if (e->layout.table == TableMode::off || ((uintptr_t)d_rgb & 7) == 0) return M1V_OK;
+    if (e->layout.table == TableMode::planes)
+        return fail(M1V_E_ARG, "a plane table is on (m1v_set_plane_table): d_rgb is an array of three 64-bit plane addresses per frame and must be 8-byte aligned%s");
+    return fail(M1V_E_ARG, "a frame table is on (m1v_set_frame_table): d_rgb is an array of 64-bit frame addresses and must be 8-byte aligned%s");
 }
 
 // From its construction on, an error return leaves counters half used: the flag tells the next call to clear them first

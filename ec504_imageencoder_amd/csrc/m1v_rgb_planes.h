@@ -172,7 +172,7 @@ struct RgbPlaneRdArgs {
 
 // the bodies' input-layout names: the frame base is taken as for a surface (base + frame * frame_stride, default rounding mode)
 #define M1V_RGB_PLANES_INPUT(TABLE)                                                                \
-    constexpr bool SURFACE = true, FRAME_TABLE = TABLE;                                            \
+    constexpr bool SURFACE = true, FRAME_TABLE = TABLE, PLANE_TABLE = false;                       \
     constexpr int BPP = 3, ORDER = 0;                                                              \
     constexpr uint32_t row_pitch = 0;                                                              \
     const unsigned long long frame_stride = pa.frame_stride;                                       \
@@ -224,6 +224,135 @@ __global__ __launch_bounds__(kTileThreads) void kt_size_table_rgb_planes(RgbPlan
 template <bool STAGE8, int R>
 __global__ __launch_bounds__(kTileThreads) void kt_rd_table_rgb_planes(RgbPlaneRdArgs pa) {
     M1V_RGB_PLANES_INPUT(true);
+    M1V_RD_INPUT(pa.t);
+#include "m1v_size_table_body.h"
+}
+
+// ---- plane table (m1v_set_plane_table, include/mpeg1_hip.h "Plane table"): one pointer per plane, the kp_* kernels ----
+// RgbPlaneFront with every offset relative to its own plane's pointer.  A struct of its own beside RgbPlaneFront, not a parameter
+// of it: the k_* and kt_* kernels stay the parent's device code text for text this way.
+// `fbase` is the address of the frame's three table entries (R, G, B; plane_table_row), loaded with scalar loads.  The first
+// instruction of a row-step reads R in lanes 0-31 and G in lanes 32-63, so it takes one 64-bit address per lane
+// (global_load_lds_dwordx4 v[lo:hi], off): the lane's plane pointer + offset, kept in two registers, plus the row-step's uniform
+// offset.  The second reads B alone and stays on a scalar base, the B pointer, 1024 lower as before.  The vmcnt sequence is
+// RgbPlaneFront's.  Rejected: two scalar-base instructions under EXEC halves, three instructions per row-step and another vmcnt
+// sequence.  There is no clamp in this front half: the one unit that runs past its addressed bytes ends in one of the first
+// H / 4 rows of its own plane's range (the read contract above), so the argument already was per plane.
+struct RgbPlanePtrFront {
+    RgbPlaneFrontArgs p;
+
+    template <int R, int KEEP, bool DOWN, int BPP, bool SURFACE, int ORDER, typename First, typename Meanwhile>
+    __device__ __forceinline__ void run(const Geometry &g, const uint8_t *fbase, uint32_t ring, int wave, int lane, int s0, int m0,
+                                        int strips_here, int comp, First first, Meanwhile meanwhile, RowStore<KEEP> &rows,
+                                        uint32_t = 0) const {
+        static_assert(!DOWN, "the RGB plane kernels stay in the default rounding mode");
+        (void)comp;
+        constexpr uint32_t kSlot = 2048, kPlane = 512;
+        const bool chroma = wave == 2;
+        auto uniform = [](uint32_t v) { // an opaque scalar, as in tile_pixel_rows
+            asm volatile("" : "+s"(v));
+            return v;
+        };
+        const PlaneBases bases = PlaneBases::load(fbase);
+        const uint32_t L = (uint32_t)lane;
+        // the four row offsets a wave's lanes choose from (uniform), as in RgbPlaneFront
+        auto row_off = [&](uint32_t k) {
+            if (!chroma) {
+                const uint32_t mb = (uint32_t)min(m0 + 2 * wave + (int)(k >> 1), g.n_mbrows - 1);
+                return (mb * 16u + (k & 1u) * 8u) * p.row_pitch + (uint32_t)s0 * 16u;
+            }
+            const uint32_t mb = (uint32_t)min(m0 + (int)k, g.n_mbrows - 1);
+            return mb * 4u * p.row_pitch + (uint32_t)s0 * 8u;
+        };
+        const uint32_t r0 = uniform(row_off(0)), r1 = uniform(row_off(1)), r2 = uniform(row_off(2)), r3 = uniform(row_off(3));
+        // ---- the lane's 16-byte units of row-step 0: the first instruction's as an address, the second's as an offset from the B pointer ----
+        const uint32_t sh = chroma ? 2u : 3u;                                                  // uniform
+        const uint32_t vw = chroma ? (((uint32_t)strips_here * 8u + 15u) & ~15u) : (uint32_t)strips_here * 16u; // bytes of a row fetched
+        const uint32_t k = (L >> sh) & 3u;
+        const uint32_t in_plane = (k == 0 ? r0 : (k == 1 ? r1 : (k == 2 ? r2 : r3))) + min((L & ((1u << sh) - 1u)) * 16u, vw - 16u);
+        const unsigned long long addr_a = (L >= 32u ? bases.p[1] + p.g_off : bases.p[0] + p.r_off) + in_plane;
+        const uint32_t voff_b = p.b_off + in_plane;
+        const uint8_t *b_base = reinterpret_cast<const uint8_t *>(static_cast<uintptr_t>(bases.p[2]));
+        // ---- the lane's 8 bytes of R inside slot 0; G and B lie kPlane and 2 kPlane further ----
+        const uint32_t lane_row = ring + ((chroma ? L & 31u : L) << 3);
+        // row-step r lies (r >> 1) * step2 + (r & 1) * step1 behind row-step 0 (uniform; r is a constant of the unrolled loop)
+        const uint32_t step2 = chroma ? p.row_pitch : 2u * p.row_pitch, step1 = chroma ? (uint32_t)g.half_w : p.row_pitch;
+        auto issue_row = [&](int r) { // row-step r -> slot r % R.  M0 is set once: the second instruction's offset:1024 moves its LDS
+                                      // address AND its source address, so its base is 1024 lower (tile_pixel_rows)
+            const unsigned long long off = (unsigned long long)(r >> 1) * step2 + (unsigned long long)(r & 1) * step1;
+            const uint32_t dst = ring + (uint32_t)(r % R) * kSlot;
+            uint32_t keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %1, off\n\tglobal_load_lds_dwordx4 %2, %4 offset:1024\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep)
+                         : "v"(addr_a + off), "v"(voff_b), "s"(dst), "s"(b_base + off - 1024));
+        };
+
+        first();
+#pragma unroll
+        for (int r = 0; r < R; r++) issue_row(r);
+        meanwhile();
+
+        // ---- rows out of the ring as they land, the freed slot refilled with row i + R ----
+        const CompCoefF kf = comp_coef_wave(!chroma, lane);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int newest = (i - 1 + R < 7) ? (i - 1 + R) : 7; // newest row-step requested so far
+            const int behind = newest - i;                         // row-steps that may still be in flight: two instructions each
+            if (behind == 0) wait_vm<0>(); else if (behind == 1) wait_vm<2>(); else if (behind == 2) wait_vm<4>();
+            else if (behind == 3) wait_vm<6>(); else if (behind == 4) wait_vm<8>(); else if (behind == 5) wait_vm<10>();
+            else if (behind == 6) wait_vm<12>(); else wait_vm<14>();
+            unsigned long long cr, cg, cb;
+            asm volatile("ds_read_b64 %0, %3\n\tds_read_b64 %1, %3 offset:%4\n\tds_read_b64 %2, %3 offset:%5\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(cr), "=&v"(cg), "=&v"(cb)
+                         : "v"(lane_row + (uint32_t)(i % R) * kSlot), "n"(kPlane), "n"(2 * kPlane));
+            if (i + R < 8) issue_row(i + R);
+            RowPlanes v;
+            v.d[0] = (uint32_t)cr; v.d[1] = (uint32_t)(cr >> 32);
+            v.d[2] = (uint32_t)cg; v.d[3] = (uint32_t)(cg >> 32);
+            v.d[4] = (uint32_t)cb; v.d[5] = (uint32_t)(cb >> 32);
+            float px[8];
+            convert_row_planes(v, kf, px);
+            float ro[8];
+            m1vf::fdct_row_f<float, false>(px, ro);
+            rows.put(i, ro);
+        }
+    }
+};
+
+// pa.t.rgb holds three 64-bit plane addresses per frame; there is no frame stride
+template <typename Base>
+struct RgbPlanePtrArgs {
+    Base t;
+    RgbPlaneFrontArgs pl;
+};
+#define M1V_RGB_PLANE_PTR_INPUT                                                                    \
+    constexpr bool SURFACE = true, FRAME_TABLE = false, PLANE_TABLE = true;                        \
+    constexpr int BPP = 3, ORDER = 0;                                                              \
+    constexpr uint32_t row_pitch = 0;                                                              \
+    constexpr unsigned long long frame_stride = 0;                                                 \
+    const RgbPlanePtrFront rgb_plane_front = {pa.pl}
+
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
+void kp_encode_rgb_planes(RgbPlanePtrArgs<TileArgs> pa) {
+    M1V_RGB_PLANE_PTR_INPUT;
+    const TileArgs &a = pa.t;
+#include "m1v_encode_tile_body.h"
+}
+
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void kp_size_table_rgb_planes(RgbPlanePtrArgs<TableArgs> pa) {
+    M1V_RGB_PLANE_PTR_INPUT;
+    const TableArgs &a = pa.t;
+    M1V_SIZES_ONLY;
+#include "m1v_size_table_body.h"
+}
+
+template <bool STAGE8, int R>
+__global__ __launch_bounds__(kTileThreads) void kp_rd_table_rgb_planes(RgbPlanePtrArgs<RdTableArgs> pa) {
+    M1V_RGB_PLANE_PTR_INPUT;
     M1V_RD_INPUT(pa.t);
 #include "m1v_size_table_body.h"
 }

@@ -782,17 +782,37 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *ou
     return 1;
 }
 
-// The frame table is a flag of the layout record in force: no plan, no allocation, nothing queued
+// The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (enable && !e->layout.tiles_only())
         return fail(M1V_E_ARG, "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
                                "m1v_set_input_layout(enc, width * channels, 0, order)%s");
-    e->layout.frame_table = enable != 0;
+    e->layout.table = enable ? TableMode::frames : TableMode::off;
     return M1V_OK;
 }
 
-int m1v_frame_table(const m1v_encoder *e) { return e ? (e->layout.frame_table ? 1 : 0) : -1; }
+int m1v_frame_table(const m1v_encoder *e) { return e ? (e->layout.table == TableMode::frames ? 1 : 0) : -1; }
+
+// The plane table is another value of the same field: each setter selects its own mode, either turns tables off
+int m1v_set_plane_table(m1v_encoder *e, int enable) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (enable) {
+        const m1v_encoder::Layout &l = e->layout;
+        if (l.kind == LayoutKind::packed)
+            return fail(M1V_E_ARG, "a plane table needs a plane layout (m1v_set_plane_layout) or an RGB plane layout (m1v_set_rgb_plane_layout): "
+                                   "packed pixels have no planes%s");
+        if (l.kind == LayoutKind::surface)
+            return fail(M1V_E_ARG, "a surface layout has one plane: m1v_set_frame_table serves it%s");
+        if (l.kind == LayoutKind::samples && l.samples.y_step == 2)
+            return fail(M1V_E_ARG, "a plane table does not serve a (2, 4) sample layout: packed 4:2:2 has no planes, and P010 with separate "
+                                   "Y and UV pointers is not covered%s");
+    }
+    e->layout.table = enable ? TableMode::planes : TableMode::off;
+    return M1V_OK;
+}
+
+int m1v_plane_table(const m1v_encoder *e) { return e ? (e->layout.table == TableMode::planes ? 1 : 0) : -1; }
 
 int m1v_path_in_use(const m1v_encoder *e) { return e ? (e->plan.producer == Producer::tiles ? 1 : 0) : -1; }
 

@@ -1,6 +1,6 @@
 // ec504_imageencoder_amd/csrc/m1v_size_table_body.h — the body of k_size_table_tiles, k_size_table_rgba and k_size_table_surface
 // (m1v_tiles.h), included inside each kernel.  In scope: STAGE8, R (template parameters), TableArgs a, and the input layout:
-// BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows), FRAME_TABLE; M1V_FRONT_HALF names the front half (as in
+// BPP (bytes per pixel), SURFACE, ORDER, row_pitch, frame_stride (tile_pixel_rows), FRAME_TABLE, PLANE_TABLE; M1V_FRONT_HALF names the front half (as in
 // m1v_encode_tile_body.h).
 // RD (a constant in scope) = true makes it the body of the k_rd_table_* kernels: the same sizes plus the distortion of every
 // frame and quality into rd_dist[k][frame], with rd_dq = the divisors of every quality in the index order of rq_all (M1V_SIZES_ONLY
@@ -25,7 +25,8 @@
     const int tr = (int)a.tile_row_order[tk];
     const int s0 = tc * kTileStrips, m0 = tr * kTileMbRows;
     const uint8_t *fbase;
-    if constexpr (SURFACE && FRAME_TABLE) fbase = frame_table_entry(a.rgb, frame); // (the kt_* kernels: a.rgb is the frame table)
+    if constexpr (SURFACE && PLANE_TABLE) fbase = plane_table_row(a.rgb, frame); // (the kp_* kernels: the frame's three entries of the plane table)
+    else if constexpr (SURFACE && FRAME_TABLE) fbase = frame_table_entry(a.rgb, frame); // (the kt_* kernels: a.rgb is the frame table)
     else fbase = a.rgb + (unsigned long long)frame * (SURFACE ? frame_stride : g.frame_bytes);
     auto owner = [&](int ln, int &j, int &m, int &blk) {
         if (!chroma) {

@@ -141,7 +141,7 @@ struct Step2Front {
 
 // the bodies' input-layout names, as M1V_PLANE_INPUT
 #define M1V_STEP2_INPUT(TABLE)                                                                     \
-    constexpr bool SURFACE = true, FRAME_TABLE = TABLE;                                            \
+    constexpr bool SURFACE = true, FRAME_TABLE = TABLE, PLANE_TABLE = false;                       \
     constexpr int BPP = 3, ORDER = 0;                                                              \
     constexpr uint32_t row_pitch = 0;                                                              \
     const unsigned long long frame_stride = pa.frame_stride;                                       \

@@ -317,7 +317,7 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
 #endif
 // the input layout of the packed kernels, for the kernel bodies that are shared with the surface kernels as headers
 #define M1V_PACKED_INPUT                                                                           \
-    constexpr bool SURFACE = false, FRAME_TABLE = false;                                           \
+    constexpr bool SURFACE = false, FRAME_TABLE = false, PLANE_TABLE = false;                      \
     constexpr int ORDER = 0;                                                                       \
     constexpr uint32_t row_pitch = 0;                                                              \
     constexpr unsigned long long frame_stride = 0
@@ -331,6 +331,29 @@ __device__ __forceinline__ int columns_to_stage(const RowStore<KEEP> &rows, cons
 // encodes of two layouts measured outside their A/A spread against the parent's (DESIGN.md "Frame tables").
 __device__ __forceinline__ const uint8_t *frame_table_entry(const uint8_t *rgb, int frame) {
     return reinterpret_cast<const uint8_t *>(static_cast<uintptr_t>(reinterpret_cast<const unsigned long long *>(rgb)[frame]));
+}
+// The kp_* kernels, the instantiations of a plane table (m1v_set_plane_table; PLANE_TABLE in the bodies) beside the plane and RGB
+// plane kernels: `rgb` is a device array uint64_t[n_frames][3] of one address per plane.  The body hands the front half the
+// address of the frame's row of the table in the place of the frame base; PlaneBases::load turns it into the three plane
+// addresses with scalar loads (the row's address is workgroup-uniform).  Kernels of their own for the reason above.
+__device__ __forceinline__ const uint8_t *plane_table_row(const uint8_t *rgb, int frame) { return rgb + (unsigned long long)frame * 24ull; }
+struct PlaneBases {
+    unsigned long long p[3]; // Y, Cb, Cr or R, G, B
+    static __device__ __forceinline__ PlaneBases load(const uint8_t *row) {
+        // (written out: left to the compiler, the loads of the RGB plane kernels became vector loads and the B pointer a VGPR pair)
+        unsigned long long p0, p1, p2;
+        asm volatile("s_load_dwordx2 %0, %3, 0x0\n\ts_load_dwordx2 %1, %3, 0x8\n\ts_load_dwordx2 %2, %3, 0x10\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(p0), "=&s"(p1), "=&s"(p2)
+                     : "s"(row));
+        return {{p0, p1, p2}};
+    }
+};
+// dma16 from one 64-bit address per lane (no scalar base): where one wave instruction reads two planes of a plane table
+__device__ __forceinline__ void dma16_at(unsigned long long vaddr, uint32_t ldsdst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(vaddr), "s"(ldsdst));
 }
 #ifndef M1V_TILE_WAVES_PER_EU
 #define M1V_TILE_WAVES_PER_EU 5
@@ -504,7 +527,7 @@ struct SurfaceArgs {
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
 void k_encode_surface(SurfaceArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    constexpr bool SURFACE = true, FRAME_TABLE = false, PLANE_TABLE = false;
     const TileArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -514,7 +537,7 @@ void k_encode_surface(SurfaceArgs sa) {
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(M1V_TILE_WAVES_PER_EU, M1V_TILE_WAVES_PER_EU)))
 void kt_encode_surface(SurfaceArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = true, PLANE_TABLE = false;
     const TileArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -653,7 +676,7 @@ struct SurfaceTableArgs {
 };
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void k_size_table_surface(SurfaceTableArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    constexpr bool SURFACE = true, FRAME_TABLE = false, PLANE_TABLE = false;
     const TableArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -663,7 +686,7 @@ __global__ __launch_bounds__(kTileThreads) void k_size_table_surface(SurfaceTabl
 // (of a frame table)
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void kt_size_table_surface(SurfaceTableArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = true, PLANE_TABLE = false;
     const TableArgs &a = sa.t;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
@@ -733,7 +756,7 @@ struct SurfaceRdArgs {
 };
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void k_rd_table_surface(SurfaceRdArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = false;
+    constexpr bool SURFACE = true, FRAME_TABLE = false, PLANE_TABLE = false;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
     M1V_RD_INPUT(sa.t);
@@ -742,7 +765,7 @@ __global__ __launch_bounds__(kTileThreads) void k_rd_table_surface(SurfaceRdArgs
 // (of a frame table)
 template <bool STAGE8, int R, int BPP, int ORDER>
 __global__ __launch_bounds__(kTileThreads) void kt_rd_table_surface(SurfaceRdArgs sa) {
-    constexpr bool SURFACE = true, FRAME_TABLE = true;
+    constexpr bool SURFACE = true, FRAME_TABLE = true, PLANE_TABLE = false;
     const uint32_t row_pitch = sa.row_pitch;
     const unsigned long long frame_stride = sa.frame_stride;
     M1V_RD_INPUT(sa.t);

@@ -236,7 +236,8 @@ class Mpeg1Encoder:
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
         as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes; or, after set_rgb_plane_layout,
         [n, C, H, W] planes of R, G and B; or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
-        addresses (this holds for every method that takes rgb).  Asynchronous on torch's current stream.
+        addresses; or, after set_plane_table, what plane_frames() returns or an int64 CUDA tensor [n, 3] of plane addresses
+        (this holds for every method that takes rgb).  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
         CUDA uint8 tensor); an entry outside that range sets STATUS_QUALITY in meta[1] and the output is undefined.
         Returns (out, sizes, meta): out uint8[cap] frame records back to back, sizes uint64-as-int64[n],
@@ -264,10 +265,17 @@ class Mpeg1Encoder:
         input_layout is never None: all zeros = packed frames."""
         kinds = ("rgb_plane_layout", "sample_layout", "input_layout")
         self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
-        self._table_on = self.frame_table   # (every successful layout setter turns the frame table off)
+        self._table_on = self.frame_table   # (every successful layout setter turns the tables off)
+        self._planes_on = self.plane_table
 
     def _check_input(self, rgb):
         import torch
+        if self._planes_on:  # a plane table: what plane_frames() made, or the caller's own int64 addresses [n, 3]
+            assert (isinstance(rgb, FrameTable) and tuple(rgb.table.shape[1:]) == (3,)) or \
+                (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.int64 and rgb.dim() == 2
+                 and rgb.shape[1] == 3 and rgb.is_contiguous()), \
+                "a plane table is on: pass plane_frames([...]) or a contiguous CUDA int64 tensor [n, 3] of plane addresses"
+            return
         if self._table_on:  # a frame table: what frames() made, or the caller's own int64 addresses [n]
             assert isinstance(rgb, FrameTable) or (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.int64
                                                    and rgb.dim() == 1 and rgb.is_contiguous()), \
@@ -363,7 +371,58 @@ class Mpeg1Encoder:
         frames: set_input_layout(width * channels) first); every layout setter turns it off again.  Not a reconfiguration:
         nothing is allocated or waited for."""
         _call("m1v_set_frame_table", self._h, 1 if enable else 0)
-        self._table_on = self.frame_table
+        self._table_on, self._planes_on = self.frame_table, self.plane_table   # (each mode replaces the other)
+
+    def set_plane_table(self, enable=True):
+        """Batches whose frames' planes lie at separate device addresses (include/mpeg1_hip.h, m1v_set_plane_table): while on,
+        every method takes, in the place of `rgb`, what plane_frames() returns or a contiguous CUDA int64 tensor [n, 3] of plane
+        addresses (Y, Cb, Cr or R, G, B), which only the kernels read, on the stream.  Needs a plane layout (set_plane_layout) or
+        an RGB plane layout in force, which applies to each plane relative to its own pointer; replaces a frame table; every
+        layout setter turns it off again.  Not a reconfiguration: nothing is allocated or waited for."""
+        _call("m1v_set_plane_table", self._h, 1 if enable else 0)
+        self._table_on, self._planes_on = self.frame_table, self.plane_table
+
+    @property
+    def plane_table(self):
+        """True while a plane table is on (set_plane_table)."""
+        return _ffi.lib().m1v_plane_table(self._h) == 1
+
+    def plane_frames(self, planes):
+        """A FrameTable of `planes`: per frame one tuple of three CUDA uint8 tensors, (Y, Cb, Cr) under a plane layout — Y
+        [rows, >= coded width] or flat, chroma likewise; both chroma members may be the same NV12 UV tensor — or (R, G, B) [H, W]
+        under an RGB plane layout.  A Y, Cb or Cr tensor starts at its plane's pointer, so the layout's offset of that plane lies
+        inside it (0 for planes that are allocations of their own); an R, G or B tensor is the plane itself, and the table holds
+        its address less the layout's offset, as the read contract of RGB planes allows.  Checks that each plane has unit stride along a row, the row pitch of the layout in force and
+        room for the bytes the layout addresses from its pointer, and that all lie on one device; uploads the int64 [n, 3] table of
+        their addresses (a host-to-device copy on the current stream) and keeps the tensors alive with the result.  For the calls
+        made while set_plane_table() is on."""
+        import torch
+        planes = [tuple(f) for f in planes]
+        assert planes and all(len(f) == 3 for f in planes), "plane_frames() needs at least one frame of three planes"
+        kind, want = self._input
+        assert kind in ("rgb_plane_layout", "sample_layout") and want.get("y_step", 1) == 1, \
+            "a plane table needs a plane layout or an RGB plane layout in force"
+        xe, ye = self.strips * 16, self.mb_rows * 16
+        back = [0, 0, 0]    # how far in front of the tensor's first byte the plane's pointer stands
+        if kind == "rgb_plane_layout":  # a plane's range starts at its offset: the tensor is the plane, its pointer lies c_offset in front
+            back = [want[k] for k in ("r_offset", "g_offset", "b_offset")]
+            need = [(want["row_pitch"], (self.height - 1) * want["row_pitch"] + self.width)] * 3
+        else:
+            chroma = (ye // 2 - 1) * want["c_pitch"] + (xe // 2 - 1) * want["c_step"] + 1
+            need = [(want["y_pitch"], want["y_offset"] + (ye - 1) * want["y_pitch"] + xe),
+                    (want["c_pitch"], want["cb_offset"] + chroma), (want["c_pitch"], want["cr_offset"] + chroma)]
+        flat = [t for f in planes for t in f]
+        for f in planes:
+            for t, (pitch, extent) in zip(f, need):
+                assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() in (1, 2), \
+                    "a plane must be a CUDA uint8 tensor [rows, row bytes] or [bytes]"
+                assert t.stride(-1) == 1 and (t.dim() == 1 or t.shape[0] <= 1 or t.stride(0) == pitch), \
+                    f"strides {tuple(t.stride())} are not the row pitch in force ({pitch})"
+                span = t.shape[0] if t.dim() == 1 else (t.shape[0] - 1) * pitch + t.shape[1]
+                assert span >= extent, f"a plane of {span} bytes cannot hold the {extent} bytes the layout addresses from its pointer"
+        assert all(t.device == flat[0].device for t in flat), "the planes of a table lie on one device"
+        table = torch.tensor([[t.data_ptr() - b for t, b in zip(f, back)] for f in planes], dtype=torch.int64).to(flat[0].device)
+        return FrameTable(table, flat)
 
     @property
     def frame_table(self):

@@ -578,10 +578,52 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *
  * is not a device address of the encoder's device is undefined behaviour, exactly as a bad d_rgb is without a table.
  * Read contract: unchanged per frame — the range or ranges the layout defines, relative to that frame's F, each rounded up to the
  * next 4-byte boundary; of the table, entries [0, n_frames).
- * Not covered: separate pointers per plane of one frame (Y, Cb and Cr, or R, G and B, in three allocations).  The kernels address
- * a frame as one scalar base plus 32-bit lane offsets, and the plane kernels clamp their loads relative to that base. */
+ * Separate pointers per plane of one frame (Y, Cb and Cr, or R, G and B, in three allocations) are the plane table below.
+ * Not covered by either table: P010 planes behind separate Y and UV pointers (a (2, 4) sample layout takes a frame table only), and
+ * the host-buffer entry points (m1v_encode_host, m1v_encode_planes_host), which take no table. */
 int m1v_set_frame_table(m1v_encoder *enc, int enable);
 int m1v_frame_table(const m1v_encoder *enc);
+
+/* Plane table: a batch whose frames' planes lie at separate device addresses — AVFrame::data[0..2] with linesize[], the Y pointer
+ * and the UV pointer of a decoder's NV12 surface, three separately allocated tensors of a colour-space stage, the r, g, b =
+ * x.unbind(1) planes of tensors that were never one allocation — encoded where they lie: no copy of the planes into one frame.
+ *
+ * Definition.  While the plane table is on, the d_rgb argument of every *_device call and of m1v_delivery_step is a device array of
+ * uint64_t[n_frames][3]: entry [f][p] is the device address P of plane p of frame f, in the order Y, Cb, Cr under a plane layout
+ * and R, G, B under an RGB plane layout.  The layout in force applies to each plane relative to its own pointer: sample (0, 0) of
+ * plane p lies at P + p_offset, and the pitches, c_step, the chroma quirk, the record, its headers, first_frame_index, the status
+ * bits and per-frame quality are exactly those without a table.  NV12 and NV21 need no format of their own: [f][1] and [f][2] both
+ * hold the UV plane's pointer under chroma offsets 0 and 1 (1 and 0), or [f][2] = [f][1] + 1 under offsets 0 and 0.  Entries may
+ * repeat, alias, come in any memory order and point into different allocations; any byte alignment of an entry is accepted.  The
+ * layout's frame_stride is kept and reported, and unused, as with a frame table.
+ *
+ *   m1v_set_plane_table(enc, enable)   M1V_OK, or M1V_E_ARG with a message that names the reason: a null encoder; enable != 0 on
+ *     the packed layout (no planes), on a surface layout (one plane: a frame table serves it), or on a (2, 4) sample layout (packed
+ *     4:2:2 has no planes; P010 behind separate Y and UV pointers is not covered).  Served layouts: m1v_set_plane_layout, which is
+ *     the sample steps (1, 1) and (1, 2), and m1v_set_rgb_plane_layout.
+ *     The table mode is one field of the layout in force: off, frames or planes.  m1v_set_frame_table and m1v_set_plane_table with
+ *     enable != 0 each select their own mode, replacing the other; either of them with 0 turns tables off.  Every successful layout
+ *     setter turns tables off; a setter that fails leaves the mode as it was.  Not a reconfiguration: nothing is allocated, waited
+ *     for or queued, and the plan does not change.
+ *   m1v_plane_table(enc)   1 = the plane table is on, 0 = off or a frame table, -1 = a null encoder.  (m1v_frame_table answers 1 in
+ *     frame mode only.)
+ * Served: every call a frame table serves, m1v_delivery_step's scratch retry included, which passes the pointer on again.
+ * When the table is read: only the kernels read it, on the stream, and only entries [0, n_frames)[0, 3).  A caller may fill it
+ * with work queued on the same stream directly in front of the call.  The host's one check is that d_rgb is 8-byte aligned:
+ * M1V_E_ARG in front of every launch otherwise.  The entries are not validated, as a frame table's are not.
+ * Read contract, per plane.  Of plane p of frame f only bytes of [P, P + E_p), rounded up to the next 4-byte boundary, are read:
+ *     E_p = p_offset + (rows_p - 1) * pitch_p + row_bytes_p
+ * with the rows and row bytes of the contracts above: ye rows of xe bytes for Y, ye / 2 rows of (xe / 2 - 1) * c_step + 1 bytes for
+ * Cb and Cr (xe, ye = the coded region); for an RGB plane layout the layout's own range per plane, relative to P: [P + c_offset,
+ * P + c_offset + (height - 1) * row_pitch + width).  No byte outside the three ranges is read, and bytes inside a range that the
+ * definition does not address never influence the output.  Each chroma plane is held to its own range: where the single-base
+ * kernels move a 16-byte unit back at the end of the frame's extent, these move it back at the end of its own plane's (a 16 x 16
+ * I420 picture has chroma planes of 64 bytes, and the last unit of each still starts and ends inside them).  With [f][2] =
+ * [f][1] + 1 the rounding is relative to that pointer: the Cr range of a tightly packed NV12 plane then ends one byte behind the
+ * plane, which the two-offset form avoids.
+ * Not covered: P010 planes; the host-buffer entry points. */
+int m1v_set_plane_table(m1v_encoder *enc, int enable);
+int m1v_plane_table(const m1v_encoder *enc);
 
 /* An encoder is driven from ONE stream.  Every call adds into one of two internal counter sets, and the assembly kernel of
  * call k clears the set that call k + 1 adds into; calls on different streams would race on them.  After an error return
