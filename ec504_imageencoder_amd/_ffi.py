@@ -48,6 +48,19 @@ class RgbPlaneLayout(_Layout):
     """m1v_rgb_plane_layout (include/mpeg1_hip.h): where the R, G and B bytes of a frame lie, in bytes."""
     _fields_ = [(name, C.c_uint64) for name in ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")]
 
+SAMPLE_F16, SAMPLE_BF16, SAMPLE_F32 = 0, 1, 2
+FLOAT_SAMPLES = {"float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16, "float32": SAMPLE_F32}
+FLOAT_SAMPLE_BYTES = {SAMPLE_F16: 2, SAMPLE_BF16: 2, SAMPLE_F32: 4}
+RANGE_UNIT, RANGE_BYTE = 0, 1
+FLOAT_RANGES = {"unit": RANGE_UNIT, "byte": RANGE_BYTE}
+
+
+class FloatPlaneLayout(_Layout):
+    """m1v_float_plane_layout (include/mpeg1_hip.h): where the float R, G and B samples of a frame lie, in bytes, their type
+    (SAMPLE_*) and their value range (RANGE_*)."""
+    _fields_ = [(name, C.c_uint64) for name in ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")] + \
+               [("sample", C.c_int32), ("range", C.c_int32)]
+
 _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
@@ -66,6 +79,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
     "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
     "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
+    "m1v_float_plane_layout_preset", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force", "m1v_float_planes_to_bytes_device",
     "m1v_set_frame_table", "m1v_frame_table", "m1v_set_plane_table", "m1v_plane_table",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
@@ -207,6 +221,14 @@ def lib():
     L.m1v_set_rgb_plane_layout.restype = C.c_int
     L.m1v_rgb_plane_layout_in_force.argtypes = [vp, C.POINTER(RgbPlaneLayout)]
     L.m1v_rgb_plane_layout_in_force.restype = C.c_int
+    L.m1v_float_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FloatPlaneLayout)]
+    L.m1v_float_plane_layout_preset.restype = C.c_int
+    L.m1v_set_float_plane_layout.argtypes = [vp, C.POINTER(FloatPlaneLayout)]
+    L.m1v_set_float_plane_layout.restype = C.c_int
+    L.m1v_float_plane_layout_in_force.argtypes = [vp, C.POINTER(FloatPlaneLayout)]
+    L.m1v_float_plane_layout_in_force.restype = C.c_int
+    L.m1v_float_planes_to_bytes_device.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.m1v_float_planes_to_bytes_device.restype = C.c_int
     L.m1v_set_frame_table.argtypes = [vp, C.c_int]
     L.m1v_set_frame_table.restype = C.c_int
     L.m1v_frame_table.argtypes = [vp]

@@ -22,6 +22,9 @@
 //   k_encode_rgb_planes, k_size_table_rgb_planes, k_rd_table_rgb_planes   (m1v_rgb_planes.h, the same bodies) the tile kernels on
 //                     planes of R, G and B bytes (m1v_set_rgb_plane_layout: NCHW uint8 tensors in any plane order): the colour
 //                     stage of the surface kernels on de-interleaved bytes
+//   k_encode_float_planes, k_size_table_float_planes, k_rd_table_float_planes   (m1v_float_planes.h, the same bodies) the tile
+//                     kernels on planes of fp16, bf16 or fp32 samples of R, G and B (m1v_set_float_plane_layout: NCHW float
+//                     tensors): each sample becomes a byte by one rule (float_sample_to_byte), then the stage above
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -1264,6 +1267,7 @@ constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 #include "m1v_planes.h"
 #include "m1v_step2.h"
 #include "m1v_rgb_planes.h"
+#include "m1v_float_planes.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1780,7 +1784,7 @@ struct m1v_encoder {
     // The input layout in force, no zeros: its kind, the frame stride every kind but packed has, and one member per kind.  Only the
     // member of the kind in force is set and read (layout_facts: how messages name a kind, its setter and its getter).
     struct Layout {
-        enum class Kind { packed, surface, samples, rgb_planes } kind = Kind::packed;
+        enum class Kind { packed, surface, samples, rgb_planes, float_planes } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
         // m1v_set_frame_table / m1v_set_plane_table: d_rgb is a device array of one 64-bit address per frame, or of three (one per
         // plane); frame_stride is kept and unused.  Part of the record, so every setter's fresh record turns tables off and a
@@ -1791,6 +1795,9 @@ struct m1v_encoder {
         // extent: bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
         struct Samples { uint32_t y_off, cb_off, cr_off, y_pitch, c_pitch, y_step, c_step; unsigned long long extent; } samples = {};
         RgbPlaneFrontArgs rgb_planes = {}; // m1v_set_rgb_plane_layout: planes of R, G and B bytes, as their kernels take them (m1v_rgb_planes.h)
+        // m1v_set_float_plane_layout: planes of fp16, bf16 or fp32 samples of R, G and B, as their kernels take them
+        // (m1v_float_planes.h), with the M1V_SAMPLE_* and M1V_RANGE_* values they were set with
+        struct FloatPlanes { FloatPlaneFrontArgs front; int sample, range; } float_planes = {};
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
@@ -2026,7 +2033,8 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   dense, strips [input mode]: the pixel loads of the run kernels (load_block_rows): 1 = aligned rows, 2 = any row offset in an
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
-enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kTileVariants };
+enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kFloatPlanesF16, kFloatPlanesBf16,
+                   kFloatPlanesF32, kTileVariants };
 enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
 //   planes[...][...]: their kp_* twins of a plane table (m1v_set_plane_table); kPlanes, kPlanesPaired and kRgbPlanes only
 struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows][kTileVariants][2], *planes[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
@@ -2038,6 +2046,10 @@ struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows
      M1V_PAIR(k.tile[kRdTable][V], k_rd_table_##NAME, ##__VA_ARGS__),                                                             \
      M1V_PAIR(k.table[kEncode][V], kt_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.table[kSizeTable][V], kt_size_table_##NAME, ##__VA_ARGS__), \
      M1V_PAIR(k.table[kRdTable][V], kt_rd_table_##NAME, ##__VA_ARGS__))
+// the float plane kernels of one sample type: no kt_* or kp_* twins (float frames and planes behind tables are not covered)
+#define M1V_FLOAT_VARIANT(V, T)                                                                                                   \
+    (M1V_PAIR(k.tile[kEncode][V], k_encode_float_planes, T), M1V_PAIR(k.tile[kSizeTable][V], k_size_table_float_planes, T),      \
+     M1V_PAIR(k.tile[kRdTable][V], k_rd_table_float_planes, T))
 // ... and its kp_* kernels of a plane table
 #define M1V_PLANE_TABLE_VARIANT(V, NAME, ...)                                                                                     \
     (M1V_PAIR(k.planes[kEncode][V], kp_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.planes[kSizeTable][V], kp_size_table_##NAME, ##__VA_ARGS__), \
@@ -2066,8 +2078,12 @@ static const Kernels kKernels = [] {
     M1V_PLANE_TABLE_VARIANT(kPlanes, planes, 1);
     M1V_PLANE_TABLE_VARIANT(kPlanesPaired, planes, 2);
     M1V_PLANE_TABLE_VARIANT(kRgbPlanes, rgb_planes);
+    M1V_FLOAT_VARIANT(kFloatPlanesF16, F16Sample);
+    M1V_FLOAT_VARIANT(kFloatPlanesBf16, Bf16Sample);
+    M1V_FLOAT_VARIANT(kFloatPlanesF32, F32Sample);
     return k;
 }();
+#undef M1V_FLOAT_VARIANT
 #undef M1V_PLANE_TABLE_VARIANT
 #undef M1V_TILE_VARIANT
 #undef M1V_PAIR
@@ -2091,6 +2107,8 @@ static TileVariant tile_variant(const m1v_encoder *e) {
     const bool four = e->g.C == 4;
     switch (l.kind) {
     case LayoutKind::rgb_planes: return kRgbPlanes;
+    case LayoutKind::float_planes:
+        return l.float_planes.sample == M1V_SAMPLE_F32 ? kFloatPlanesF32 : (l.float_planes.sample == M1V_SAMPLE_BF16 ? kFloatPlanesBf16 : kFloatPlanesF16);
     case LayoutKind::samples: return l.samples.y_step == 2 ? kStep2 : (l.samples.c_step == 2 ? kPlanesPaired : kPlanes);
     case LayoutKind::surface: return l.surface.order == M1V_ORDER_BGR ? (four ? kSurfaceBgr4 : kSurfaceBgr3) : (four ? kSurfaceRgb4 : kSurfaceRgb3);
     case LayoutKind::packed: return four ? kPacked4 : kPacked3;
@@ -2137,9 +2155,9 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
 
 // What a tile-shaped kernel's base arguments are wrapped in for each layout kind, and their row of Kernels::tile
 template <typename Base> struct TileFamily;
-template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; };
-template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; };
-template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; };
+template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; using FloatPlanes = FloatPlaneArgs; };
+template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; using FloatPlanes = FloatPlaneTableArgs; };
+template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; using FloatPlanes = FloatPlaneRdArgs; };
 
 // The tile-shaped kernel of a's family over the grid a carries (fill_tile_grid), with a wrapped for the layout in force
 template <typename Args>
@@ -2168,12 +2186,16 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
     case LayoutKind::samples: // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
         return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, stride});
     case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, stride});
+    case LayoutKind::float_planes: return launch(typename Family::FloatPlanes{a, l.float_planes.front, stride});
     case LayoutKind::packed: return launch(a);
     }
 }
 
-// With a frame or plane table on, d_rgb is read as 64-bit words by scalar loads: refused here, in front of every launch, when misaligned
+// With a frame or plane table on, d_rgb is read as 64-bit words by scalar loads: refused here, in front of every launch, when misaligned.
+// So are float planes whose samples would not be naturally aligned (a float plane layout has no table mode).
 static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
+    if (e->layout.kind == LayoutKind::float_planes && ((uintptr_t)d_rgb & (e->layout.float_planes.sample == M1V_SAMPLE_F32 ? 3u : 1u)) != 0)
+        return fail(M1V_E_ARG, "a float plane layout is in force (m1v_set_float_plane_layout): d_rgb must be a multiple of the sample size%s");
     if (e->layout.table == TableMode::off || ((uintptr_t)d_rgb & 7) == 0) return M1V_OK;
     if (e->layout.table == TableMode::planes)
         return fail(M1V_E_ARG, "a plane table is on (m1v_set_plane_table): d_rgb is an array of three 64-bit plane addresses per frame and must be 8-byte aligned%s");

@@ -317,6 +317,7 @@ static LayoutFacts layout_facts(LayoutKind kind, bool two_apart = false) {
         if (two_apart) return {"a layout with samples two bytes apart", "m1v_set_sample_layout", "m1v_sample_layout_in_force"};
         return {"a plane layout", "m1v_set_plane_layout", "m1v_plane_layout_in_force"};
     case LayoutKind::rgb_planes: return {"an RGB plane layout", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force"};
+    case LayoutKind::float_planes: return {"a float plane layout", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force"};
     case LayoutKind::packed: return {"packed input", "m1v_set_input_layout", "m1v_input_layout"}; // (the surface layout's default)
     }
 }
@@ -605,7 +606,7 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     const m1v_encoder::Layout &l = e->layout;
-    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes || l.kind == LayoutKind::float_planes) return ask_its_getter(e);
     const m1v_encoder::Layout::Surface s = l.kind == LayoutKind::surface ? l.surface : m1v_encoder::Layout::Surface{0, M1V_ORDER_RGB};
     if (row_pitch_bytes) *row_pitch_bytes = s.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)l.frame_stride;
@@ -715,7 +716,7 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes) return ask_its_getter(e);
     if (e->layout.kind != LayoutKind::samples) return 0;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (s.y_step == 2) return ask_its_getter(e);
@@ -725,7 +726,7 @@ int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
 
 int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes) return ask_its_getter(e);
+    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes) return ask_its_getter(e);
     if (e->layout.kind != LayoutKind::samples) return 0;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.y_step, s.c_step, (size_t)e->layout.frame_stride};
@@ -743,6 +744,27 @@ int m1v_rgb_plane_layout_preset(int width, int height, int order, m1v_rgb_plane_
     return M1V_OK;
 }
 
+// What three planes of `row` bytes per picture row (width bytes, or width * S of a float layout) must satisfy, behind the check of
+// the pitch: the frame below 4 GiB, no shared bytes, a frame stride that covers them
+static int three_planes_fit(const unsigned long long off[3], unsigned long long pitch, unsigned long long row, unsigned long long H,
+                            unsigned long long frame_stride) {
+    const unsigned long long limit = 1ull << 32;
+    const unsigned long long lo = std::min(off[0], std::min(off[1], off[2])), hi = std::max(off[0], std::max(off[1], off[2]));
+    if (pitch >= limit || hi >= limit || hi + (H - 1) * pitch + row >= limit)
+        return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+    // Two planes may share a byte range only as a row interleave.  Row y1 of the plane at the lower offset and row y2 of the
+    // other share a byte when |d + (y2 - y1) * pitch| < row, d = the distance of the offsets = q * pitch + r: y2 - y1 = -q
+    // leaves r, y2 - y1 = -q - 1 leaves r - pitch, every other difference is further away.
+    for (int a = 0; a < 3; a++)
+        for (int b = a + 1; b < 3; b++) {
+            const unsigned long long d = off[a] < off[b] ? off[b] - off[a] : off[a] - off[b], q = d / pitch, r = d % pitch;
+            if ((r < row && q <= H - 1) || (pitch - r < row && q + 1 <= H - 1))
+                return fail(M1V_E_ARG, "two planes share bytes (planes may interleave by rows only)%s");
+        }
+    if (frame_stride < hi + (H - 1) * pitch + row - lo) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
+    return M1V_OK;
+}
+
 int m1v_set_rgb_plane_layout(m1v_encoder *e, const m1v_rgb_plane_layout *layout) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     m1v_encoder::Layout want;
@@ -750,23 +772,10 @@ int m1v_set_rgb_plane_layout(m1v_encoder *e, const m1v_rgb_plane_layout *layout)
         const Geometry &g = e->g;
         if (g.C != 3) return fail(M1V_E_ARG, "an RGB plane layout needs an encoder created with 3 channels%s");
         if (g.W & 1) return fail(M1V_E_ARG, "an RGB plane layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
-        const unsigned long long W = (unsigned long long)g.W, H = (unsigned long long)g.H, pitch = layout->row_pitch;
+        const unsigned long long W = (unsigned long long)g.W, pitch = layout->row_pitch;
         if (pitch < W) return fail(M1V_E_ARG, "row pitch below the width%s");
         const unsigned long long off[3] = {layout->r_offset, layout->g_offset, layout->b_offset};
-        const unsigned long long limit = 1ull << 32;
-        const unsigned long long lo = std::min(off[0], std::min(off[1], off[2])), hi = std::max(off[0], std::max(off[1], off[2]));
-        if (pitch >= limit || hi >= limit || hi + (H - 1) * pitch + W >= limit)
-            return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
-        // Two planes may share a byte range only as a row interleave.  Row y1 of the plane at the lower offset and row y2 of the
-        // other share a byte when |d + (y2 - y1) * pitch| < W, d = the distance of the offsets = q * pitch + r: y2 - y1 = -q
-        // leaves r, y2 - y1 = -q - 1 leaves r - pitch, every other difference is further away.
-        for (int a = 0; a < 3; a++)
-            for (int b = a + 1; b < 3; b++) {
-                const unsigned long long d = off[a] < off[b] ? off[b] - off[a] : off[a] - off[b], q = d / pitch, r = d % pitch;
-                if ((r < W && q <= H - 1) || (pitch - r < W && q + 1 <= H - 1))
-                    return fail(M1V_E_ARG, "two planes share bytes (planes may interleave by rows only)%s");
-            }
-        if (layout->frame_stride < hi + (H - 1) * pitch + W - lo) return fail(M1V_E_ARG, "frame stride below the bytes a frame's planes span%s");
+        if (const int rc = three_planes_fit(off, pitch, W, (unsigned long long)g.H, layout->frame_stride)) return rc;
         want.kind = LayoutKind::rgb_planes;
         want.rgb_planes = {(uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2], (uint32_t)pitch};
         want.frame_stride = layout->frame_stride;
@@ -782,9 +791,81 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *ou
     return 1;
 }
 
+// bytes of a sample of M1V_SAMPLE_*; 0 = unknown
+static unsigned long long float_sample_bytes(int sample) {
+    return sample == M1V_SAMPLE_F16 || sample == M1V_SAMPLE_BF16 ? 2 : (sample == M1V_SAMPLE_F32 ? 4 : 0);
+}
+
+int m1v_float_plane_layout_preset(int width, int height, int order, int sample, int range, m1v_float_plane_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    const uint64_t S = float_sample_bytes(sample);
+    if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
+    if (range != M1V_RANGE_UNIT && range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+    m1v_rgb_plane_layout bytes;
+    if (const int rc = m1v_rgb_plane_layout_preset(width, height, order, &bytes)) return rc;
+    *out = {bytes.r_offset * S, bytes.g_offset * S, bytes.b_offset * S, bytes.row_pitch * S, bytes.frame_stride * S, sample, range};
+    return M1V_OK;
+}
+
+int m1v_set_float_plane_layout(m1v_encoder *e, const m1v_float_plane_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a float plane layout needs an encoder created with 3 channels%s");
+        if (g.W & 1) return fail(M1V_E_ARG, "a float plane layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
+        const unsigned long long S = float_sample_bytes(layout->sample);
+        if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
+        if (layout->range != M1V_RANGE_UNIT && layout->range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+        const unsigned long long row = (unsigned long long)g.W * S, pitch = layout->row_pitch;
+        const unsigned long long off[3] = {layout->r_offset, layout->g_offset, layout->b_offset};
+        if ((off[0] | off[1] | off[2] | pitch | layout->frame_stride) % S)
+            return fail(M1V_E_ARG, "offsets, row pitch and frame stride must be multiples of the sample size (%s bytes)", S == 2 ? "2" : "4");
+        if (pitch < row) return fail(M1V_E_ARG, "row pitch below width * sample size%s");
+        if (const int rc = three_planes_fit(off, pitch, row, (unsigned long long)g.H, layout->frame_stride)) return rc;
+        want.kind = LayoutKind::float_planes;
+        want.float_planes = {{(uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2], (uint32_t)pitch, layout->range == M1V_RANGE_UNIT ? 255.0f : 1.0f},
+                             layout->sample, layout->range};
+        want.frame_stride = layout->frame_stride;
+    }
+    return apply_layout(e, want);
+}
+
+int m1v_float_plane_layout_in_force(const m1v_encoder *e, m1v_float_plane_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::float_planes) return 0;
+    const m1v_encoder::Layout::FloatPlanes &f = e->layout.float_planes;
+    if (out) *out = {f.front.r_off, f.front.g_off, f.front.b_off, f.front.row_pitch, e->layout.frame_stride, f.sample, f.range};
+    return 1;
+}
+
+int m1v_float_planes_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::float_planes) return fail(M1V_E_ARG, "m1v_float_planes_to_bytes_device needs a float plane layout in force (m1v_set_float_plane_layout)%s");
+    if (n_frames < 0 || ((!d_frames || !d_bytes) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
+    if (const int rc = check_frame_table(e, static_cast<const uint8_t *>(d_frames))) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const m1v_encoder::Layout::FloatPlanes &f = e->layout.float_planes;
+    const void *kernel = f.sample == M1V_SAMPLE_F32 ? (const void *)&k_float_planes_to_bytes<F32Sample>
+                         : (f.sample == M1V_SAMPLE_BF16 ? (const void *)&k_float_planes_to_bytes<Bf16Sample> : (const void *)&k_float_planes_to_bytes<F16Sample>);
+    const unsigned pairs = (unsigned)e->g.W / 2u * (unsigned)e->g.H;
+    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
+        const int n = std::min(n_frames - done, 65535);
+        FloatBytesArgs a = {static_cast<const uint8_t *>(d_frames) + (unsigned long long)done * e->layout.frame_stride,
+                            d_bytes + (unsigned long long)done * 3ull * (unsigned)e->g.W * (unsigned)e->g.H, f.front, e->layout.frame_stride,
+                            (uint32_t)e->g.W, (uint32_t)e->g.H};
+        void *args[] = {&a};
+        HIP_TRY(hipLaunchKernel(kernel, dim3((pairs + 255u) / 256u, (unsigned)n, 3u), dim3(256u), args, 0, (hipStream_t)stream));
+    }
+    return M1V_OK;
+}
+
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (enable && e->layout.kind == LayoutKind::float_planes)
+        return fail(M1V_E_ARG, "a frame table does not serve a float plane layout (m1v_set_float_plane_layout): float frames behind a "
+                               "table are not covered%s");
     if (enable && !e->layout.tiles_only())
         return fail(M1V_E_ARG, "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
                                "m1v_set_input_layout(enc, width * channels, 0, order)%s");
@@ -804,6 +885,9 @@ int m1v_set_plane_table(m1v_encoder *e, int enable) {
                                    "packed pixels have no planes%s");
         if (l.kind == LayoutKind::surface)
             return fail(M1V_E_ARG, "a surface layout has one plane: m1v_set_frame_table serves it%s");
+        if (l.kind == LayoutKind::float_planes)
+            return fail(M1V_E_ARG, "a plane table does not serve a float plane layout (m1v_set_float_plane_layout): float planes behind "
+                                   "separate pointers are not covered%s");
         if (l.kind == LayoutKind::samples && l.samples.y_step == 2)
             return fail(M1V_E_ARG, "a plane table does not serve a (2, 4) sample layout: packed 4:2:2 has no planes, and P010 with separate "
                                    "Y and UV pointers is not covered%s");

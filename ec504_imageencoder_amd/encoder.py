@@ -104,6 +104,46 @@ def rgb_plane_strides(shape, strides, order="rgb"):
     return dict(r_offset=offsets[0], g_offset=offsets[1], b_offset=offsets[2], row_pitch=row_pitch, frame_stride=frame_stride)
 
 
+FLOAT_PLANE_LAYOUT_FIELDS = RGB_PLANE_LAYOUT_FIELDS + ("sample", "range")
+
+
+def _float_sample(dtype):
+    """The SAMPLE_* code of "float16", "bfloat16", "float32" or the torch dtype of that name (no torch needed)."""
+    name = dtype if isinstance(dtype, str) else str(dtype).rsplit(".", 1)[-1]
+    if name not in _ffi.FLOAT_SAMPLES:
+        raise ValueError(f"a float plane layout takes float16, bfloat16 or float32 samples, not {dtype!r}")
+    return _ffi.FLOAT_SAMPLES[name]
+
+
+def _float_range(range):
+    if range not in _ffi.FLOAT_RANGES:
+        raise ValueError(f"unknown range {range!r}: \"unit\" (0.0 ... 1.0) or \"byte\" (0 ... 255)")
+    return _ffi.FLOAT_RANGES[range]
+
+
+def float_plane_layout_preset(width, height, order, dtype, range="unit"):
+    """The tightly packed float plane layout of a width x height frame as a dict of FLOAT_PLANE_LAYOUT_FIELDS (bytes, and the
+    SAMPLE_* / RANGE_* codes), as Mpeg1Encoder.set_float_plane_layout takes it (include/mpeg1_hip.h,
+    m1v_float_plane_layout_preset, whose values these are).  order: "rgb", "bgr", "gbr" = the planes' order in memory; dtype:
+    "float16", "bfloat16", "float32" or the torch dtype; range: "unit" (samples 0.0 ... 1.0) or "byte" (0 ... 255).  Pure."""
+    sample = _float_sample(dtype)
+    S = _ffi.FLOAT_SAMPLE_BYTES[sample]
+    layout = {k: v * S for k, v in rgb_plane_layout_preset(width, height, order).items()}
+    return dict(layout, sample=sample, range=_float_range(range))
+
+
+def float_plane_strides(shape, strides, dtype, order="rgb", range="unit"):
+    """The float plane layout (a dict of FLOAT_PLANE_LAYOUT_FIELDS, as Mpeg1Encoder.set_float_plane_layout takes it) of a float
+    [n, C, H, W] array with the given strides in elements, as torch gives them: a packed NCHW tensor, a window
+    x[:, :, y0:y0+H, x0:x0+W] of a larger one, three planes of a 4-plane tensor.  dtype, order and range as in
+    float_plane_layout_preset; order may also be the three channel indices of R, G and B.  Raises ValueError for what
+    rgb_plane_strides refuses.  Pure: no torch."""
+    sample = _float_sample(dtype)
+    S = _ffi.FLOAT_SAMPLE_BYTES[sample]
+    layout = {k: v * S for k, v in rgb_plane_strides(shape, strides, order).items()}
+    return dict(layout, sample=sample, range=_float_range(range))
+
+
 def distortion_to_psnr(d, blocks):
     """The distortion d of a frame of `blocks` blocks (Mpeg1Encoder.blocks_per_frame = strips * mb_rows * 6) as a PSNR in dB:
     10 * log10(255^2 * 64 * blocks / d), the coefficient-domain squared error read as a pixel-domain one (the FDCT is scaled like
@@ -199,6 +239,9 @@ class FrameTable:
 class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
+    Input: packed uint8 frames by default; the set_*_layout methods put surfaces, YCbCr planes, planes of R, G and B bytes, or
+    planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32) in their place.
+
     mode: "strict" = the 96x144 region the unmodified reference encodes (encoder.h:238,248),
           "full"   = every macroblock (the reference with its loop bounds restored).
     """
@@ -235,7 +278,8 @@ class Mpeg1Encoder:
     def encode(self, rgb, first_frame_index=0, out=None, sizes=None, meta=None, quality=None):
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
         as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes; or, after set_rgb_plane_layout,
-        [n, C, H, W] planes of R, G and B; or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
+        [n, C, H, W] planes of R, G and B; or, after set_float_plane_layout, a float16, bfloat16 or float32 tensor [n, C, H, W] of
+        the layout's dtype (a uint8 tensor is then refused, as a float tensor is under every other layout); or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
         addresses; or, after set_plane_table, what plane_frames() returns or an int64 CUDA tensor [n, 3] of plane addresses
         (this holds for every method that takes rgb).  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
@@ -263,7 +307,7 @@ class Mpeg1Encoder:
         """What _check_input holds tensors against: (the property that describes the input layout in force, its value), asked of
         the library in the order in which its getters cannot fail.  sample_layout also holds a plane layout (y_step 1);
         input_layout is never None: all zeros = packed frames."""
-        kinds = ("rgb_plane_layout", "sample_layout", "input_layout")
+        kinds = ("float_plane_layout", "rgb_plane_layout", "sample_layout", "input_layout")
         self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
         self._table_on = self.frame_table   # (every successful layout setter turns the tables off)
         self._planes_on = self.plane_table
@@ -283,6 +327,23 @@ class Mpeg1Encoder:
             return
         assert not isinstance(rgb, FrameTable), "a FrameTable needs set_frame_table()"
         kind, want = self._input
+        if kind == "float_plane_layout":  # [n, C, H, W] of the layout's dtype: strides in elements, times S = the layout's bytes
+            dtype = {_ffi.SAMPLE_F16: torch.float16, _ffi.SAMPLE_BF16: torch.bfloat16, _ffi.SAMPLE_F32: torch.float32}[want["sample"]]
+            S = _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
+            assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
+                f"the float plane layout in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+            assert rgb.is_cuda and rgb.dim() == 4, "float plane frames must be a CUDA tensor [n, C, H, W]"
+            assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
+            assert rgb.stride(3) == 1 and rgb.stride(2) * S == want["row_pitch"], \
+                f"strides {tuple(rgb.stride())} are not the float plane layout in force (row pitch {want['row_pitch']} bytes)"
+            assert rgb.shape[0] <= 1 or rgb.stride(0) * S == want["frame_stride"], \
+                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)} elements)"
+            plane = rgb.stride(1) * S
+            assert all(plane > 0 and want[k] % plane == 0 and want[k] // plane < rgb.shape[1] for k in ("r_offset", "g_offset", "b_offset")), \
+                f"the plane offsets in force are not channels of this tensor (plane stride {plane} bytes)"
+            return
+        assert not (isinstance(rgb, torch.Tensor) and rgb.dtype.is_floating_point), \
+            f"the layout in force takes torch.uint8 tensors, not {rgb.dtype} (float planes: set_float_plane_layout)"
         if kind == "rgb_plane_layout":  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4, "RGB plane frames must be a CUDA uint8 tensor [n, C, H, W]"
             assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
@@ -363,6 +424,37 @@ class Mpeg1Encoder:
         Every call then takes uint8 CUDA tensors [n, C >= 3, H, W] with those strides: a view x[:, :, y0:y0+H, x0:x0+W] of a larger
         tensor goes in as it is.  A reconfiguration: call it between batches."""
         self._set_layout("rgb_plane", layout, rgb_plane_layout_preset, _ffi.RgbPlaneLayout, RGB_PLANE_LAYOUT_FIELDS, exact=True)
+
+    def set_float_plane_layout(self, layout):
+        """Frames as planes of float R, G and B samples on the device — NCHW float16, bfloat16 or float32 tensors, a model's output
+        — encoded where they lie, without x.mul(255).round().clamp(0, 255).to(torch.uint8) in front (include/mpeg1_hip.h,
+        m1v_set_float_plane_layout, which defines the byte of a sample: one fp32 multiplication by 255 or 1, ties to even, NaN and
+        negatives 0, above 255 255; 3-channel encoders, even widths).  layout: a dict of FLOAT_PLANE_LAYOUT_FIELDS
+        (float_plane_layout_preset, or float_plane_strides from a tensor's shape and strides), or None = back to the default
+        layout and its kernels.  Every call then takes CUDA tensors [n, C >= 3, H, W] of exactly that dtype with those strides: a
+        view x[:, :, y0:y0+H, x0:x0+W] and three planes of a 4-plane tensor go in as they are; a uint8 tensor is refused.  Frame
+        and plane tables do not serve it.  A reconfiguration: call it between batches."""
+        c = None
+        if layout is not None:
+            if set(layout) != set(FLOAT_PLANE_LAYOUT_FIELDS):
+                raise ValueError(f"a float plane layout has the fields {FLOAT_PLANE_LAYOUT_FIELDS}")
+            c = C.byref(_ffi.FloatPlaneLayout(**{k: int(v) for k, v in layout.items()}))
+        _call("m1v_set_float_plane_layout", self._h, c)
+        self._refresh_input()
+
+    def float_planes_to_bytes(self, x, out=None):
+        """The bytes the encoder codes for the float tensor x under the float plane layout in force (include/mpeg1_hip.h,
+        m1v_float_planes_to_bytes_device: the kernels' own conversion function): a uint8 CUDA tensor [n, 3, H, W] in R, G, B
+        order, what set_rgb_plane_layout("rgb") takes.  Asynchronous on torch's current stream."""
+        import torch
+        assert self._input[0] == "float_plane_layout", "float_planes_to_bytes() needs a float plane layout in force (set_float_plane_layout)"
+        self._check_input(x)
+        n = x.shape[0]
+        if out is None:
+            out = torch.empty((n, 3, self.height, self.width), dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, 3, self.height, self.width)
+        _call("m1v_float_planes_to_bytes_device", self._h, _ptr(x), n, _ptr(out), _stream())
+        return out
 
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
@@ -456,6 +548,11 @@ class Mpeg1Encoder:
         if rc < 0:
             raise EncoderError(rc, name)
         return c.as_dict() if rc == 1 else None
+
+    @property
+    def float_plane_layout(self):
+        """The float plane layout in force as a dict of FLOAT_PLANE_LAYOUT_FIELDS (bytes; sample and range codes), or None."""
+        return self._in_force("m1v_float_plane_layout_in_force", _ffi.FloatPlaneLayout)
 
     @property
     def rgb_plane_layout(self):

@@ -494,7 +494,8 @@ int m1v_sample_layout_in_force(const m1v_encoder *enc, m1v_sample_layout *out);
 /* RGB plane layout: frames whose R, G and B bytes lie in three planes on the device — a PyTorch image batch [n, 3, H, W] of
  * uint8, the CHW output of a JPEG decoder, three planes of a 4-plane RGBA tensor, a sliced or as_strided view of one — encoded
  * where they lie: no permute-and-copy to interleaved pixels in front of the encoder.  For encoders created with channels = 3.
- * Samples are bytes: the reference's Image::data is unsigned char, and a float sample would need a rounding rule it does not have.
+ * Samples are bytes: the reference's Image::data is unsigned char.  Float samples are the float plane layout below, which writes
+ * down the rounding rule the reference does not have.
  *
  * Definition.  Frame f starts at F = d_rgb + f * frame_stride.  Component c (R, G, B) of pixel (x, y) is the byte at
  *     F + c_offset + y * row_pitch + x
@@ -547,6 +548,77 @@ int m1v_rgb_plane_layout_preset(int width, int height, int order, m1v_rgb_plane_
 int m1v_set_rgb_plane_layout(m1v_encoder *enc, const m1v_rgb_plane_layout *layout);
 int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *out);
 
+/* Float plane layout: frames whose R, G and B samples are floating-point numbers in three planes on the device — a PyTorch tensor
+ * [n, 3, H, W] of float16, bfloat16 or float32 as a model, a colour-space stage or an augmentation pipeline produces it, three
+ * planes of a 4-plane tensor, a sliced view of one — encoded where they lie: no x.mul(255).round().clamp(0, 255).to(uint8) in
+ * front of the encoder.  For encoders created with channels = 3.
+ *
+ * Definition.  A float plane layout describes three planes of samples of one type, S bytes each: S = 2 for fp16 (IEEE binary16)
+ * and bf16, S = 4 for fp32.  Frame f starts at F = d_rgb + f * frame_stride, and component c (R, G, B) of pixel (x, y) is the
+ * sample at
+ *     F + c_offset + y * row_pitch + x * S
+ * (all quantities in bytes).  The byte of a sample is
+ *     f = the sample converted to fp32                (exact for all three types)
+ *     t = f * scale     one fp32 multiplication, rounded to nearest even; scale = 255.0f (M1V_RANGE_UNIT: samples 0.0 ... 1.0) or
+ *                       1.0f (M1V_RANGE_BYTE: samples 0 ... 255)
+ *     r = t rounded to an integer, ties to even
+ *     byte = 0 if r is NaN or r < 0;  255 if r > 255;  else r
+ * In numpy: np.clip(np.where(np.isnan(t), 0, np.rint(t)), 0, 255) with t = x.astype(np.float32) * np.float32(scale).  It follows
+ * that -0.0, every denormal and every negative value give 0, +inf gives 255, -inf and every NaN (quiet or signalling, either
+ * sign, any payload) give 0; flushing denormals cannot change a result, since every denormal, flushed or not, rounds to 0; and no
+ * status bit is set for any sample value.  fp32 arithmetic because it is what a caller's own x.float() * 255 does and because
+ * the product of an fp16 or bf16 sample and 255 is exact in it; ties to even because it is the default rounding of IEEE 754,
+ * of torch.round and of np.rint.  The neighbours of this rule (the product rounded in fp16, the product taken in double,
+ * floor(x * 255 + 0.5), ties away from zero, truncation) all differ from it on inputs that exist; tests/test_float_planes_cpu.py
+ * counts them.
+ * The record of a frame is then exactly what m1v_set_rgb_plane_layout gives for those bytes, which is the packed calls' record for
+ * the interleaved picture [y][x] = (R, G, B): the same colour arithmetic, chroma quirk, headers, first_frame_index, per-frame
+ * quality, sizes and status bits.  The three offsets are independent, as those of an RGB plane layout.
+ *
+ *   m1v_float_plane_layout_preset(width, height, order, sample, range, &layout)   pure host arithmetic: three tightly packed planes
+ *     of width * height samples in the memory order M1V_RGB_PLANES_RGB / _BGR / _GBR, row_pitch = width * S, frame_stride = 3 *
+ *     width * height * S.  M1V_E_ARG: a null out, width or height <= 0, an unknown order, sample or range.
+ *   m1v_set_float_plane_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like the other layout setters:
+ *     it replaces whichever layout is in force, turns tables off, and a failed call leaves the layout and the table mode as they
+ *     were.  The encoder takes the tile plan behind k_encode_float_planes, k_size_table_float_planes and k_rd_table_float_planes.
+ *     While it is in force m1v_input_layout, m1v_plane_layout_in_force, m1v_sample_layout_in_force return M1V_E_ARG ("ask
+ *     m1v_float_plane_layout_in_force") and m1v_rgb_plane_layout_in_force returns 0.
+ *     M1V_E_ARG with a message that names the reason, before anything is launched or reallocated: a null encoder; channels != 3;
+ *     an odd width; an unknown sample or range; an offset, row_pitch or frame_stride that is not a multiple of S; row_pitch <
+ *     width * S; (largest offset) + (height - 1) * row_pitch + width * S >= 2^32 (offsets inside a frame are 32-bit); two planes
+ *     that share bytes other than as a row interleave; frame_stride below the bytes the planes span; an encoder that a hook has
+ *     forced to the run kernels.
+ *     Served: every call that takes d_rgb and serves an RGB plane layout — m1v_encode_device, m1v_encode_quality_device,
+ *     m1v_frame_sizes_device, m1v_frame_size_table_device, m1v_frame_rd_table_device, the budget, rd, batch-budget and bitrate
+ *     encodes, pipelined mode and m1v_delivery_step.  Each returns M1V_E_ARG in front of every launch when d_rgb is not a multiple
+ *     of S.  The packed-only calls refuse it as they refuse every other layout.  m1v_set_frame_table and m1v_set_plane_table
+ *     return M1V_E_ARG while it is in force.
+ *   m1v_float_plane_layout_in_force(enc, &layout)   1 = a float plane layout is in force (layout filled; may be NULL), 0 = another
+ *     layout or none, < 0 = error.
+ *   m1v_float_planes_to_bytes_device(enc, d_frames, n_frames, d_bytes, stream)   the bytes the encoder codes for these samples,
+ *     by the same device function: d_bytes is uint8 [n_frames][3][height][width] in R, G, B order, tightly packed — what
+ *     m1v_set_rgb_plane_layout with the M1V_RGB_PLANES_RGB preset takes.  Needs the float layout in force (M1V_E_ARG otherwise, and
+ *     for null pointers, n_frames < 0 and a misaligned d_frames); asynchronous on `stream`.  A caller sees which bytes were coded;
+ *     the record alone cannot show them, since most single +-1 changes of a byte leave a record unchanged.
+ * Read contract: of frame f only bytes of the three ranges [F + c_offset, F + c_offset + (height - 1) * row_pitch + width * S) are
+ * read, and of those only addressed samples: every load of the kernels is 8 addressed samples of one row.  Row padding, a fourth
+ * plane, gaps between frames and whatever lies in front of and behind the batch are never read.
+ * Not covered: float frames behind a frame table and float planes behind a plane table; channels-last float tensors; float
+ * YCbCr; value ranges other than the two named; the host-buffer entry points. */
+typedef struct m1v_float_plane_layout {
+    uint64_t r_offset, g_offset, b_offset; /* bytes from the frame's base to pixel (0,0) of each plane; multiples of S       */
+    uint64_t row_pitch;                    /* bytes between picture rows, the same in the three planes; >= width * S         */
+    uint64_t frame_stride;                 /* bytes between frames                                                           */
+    int32_t sample;                        /* M1V_SAMPLE_*                                                                   */
+    int32_t range;                         /* M1V_RANGE_*                                                                    */
+} m1v_float_plane_layout;
+enum { M1V_SAMPLE_F16 = 0, M1V_SAMPLE_BF16 = 1, M1V_SAMPLE_F32 = 2 };
+enum { M1V_RANGE_UNIT = 0, M1V_RANGE_BYTE = 1 };
+int m1v_float_plane_layout_preset(int width, int height, int order, int sample, int range, m1v_float_plane_layout *out);
+int m1v_set_float_plane_layout(m1v_encoder *enc, const m1v_float_plane_layout *layout);
+int m1v_float_plane_layout_in_force(const m1v_encoder *enc, m1v_float_plane_layout *out);
+int m1v_float_planes_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
+
 /* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
  * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
  * contiguous batch in front of the encoder.
@@ -560,7 +632,7 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *
  *
  *   m1v_set_frame_table(enc, enable)   M1V_OK, or M1V_E_ARG: a null encoder; enable != 0 on the default packed layout.  The table
  *     needs a layout served by the tile kernels in force (m1v_set_input_layout, m1v_set_plane_layout, m1v_set_sample_layout,
- *     m1v_set_rgb_plane_layout); packed frames go through a table after m1v_set_input_layout(enc, width * channels, 0, order), the
+ *     m1v_set_rgb_plane_layout; not m1v_set_float_plane_layout, which takes no table); packed frames go through a table after m1v_set_input_layout(enc, width * channels, 0, order), the
  *     way a packed buffer reaches the surface kernels.  The packed tile kernels and the run kernels take no table.
  *     The flag is part of the layout in force: every successful layout setter, those that restore the default included, turns it
  *     off; a setter that fails leaves it as it was, like everything else.  Not a reconfiguration: nothing is allocated, waited for
@@ -579,7 +651,8 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *
  * Read contract: unchanged per frame — the range or ranges the layout defines, relative to that frame's F, each rounded up to the
  * next 4-byte boundary; of the table, entries [0, n_frames).
  * Separate pointers per plane of one frame (Y, Cb and Cr, or R, G and B, in three allocations) are the plane table below.
- * Not covered by either table: P010 planes behind separate Y and UV pointers (a (2, 4) sample layout takes a frame table only), and
+ * Not covered by either table: P010 planes behind separate Y and UV pointers (a (2, 4) sample layout takes a frame table only),
+ * float frames and float planes (m1v_set_float_plane_layout: both setters return M1V_E_ARG while it is in force), and
  * the host-buffer entry points (m1v_encode_host, m1v_encode_planes_host), which take no table. */
 int m1v_set_frame_table(m1v_encoder *enc, int enable);
 int m1v_frame_table(const m1v_encoder *enc);
@@ -621,7 +694,7 @@ int m1v_frame_table(const m1v_encoder *enc);
  * I420 picture has chroma planes of 64 bytes, and the last unit of each still starts and ends inside them).  With [f][2] =
  * [f][1] + 1 the rounding is relative to that pointer: the Cr range of a tightly packed NV12 plane then ends one byte behind the
  * plane, which the two-offset form avoids.
- * Not covered: P010 planes; the host-buffer entry points. */
+ * Not covered: P010 planes; float planes (m1v_set_float_plane_layout); the host-buffer entry points. */
 int m1v_set_plane_table(m1v_encoder *enc, int enable);
 int m1v_plane_table(const m1v_encoder *enc);
 
@@ -731,7 +804,7 @@ int m1v_debug_set_lds_words(m1v_encoder *enc, int words);
 int m1v_debug_set_path(m1v_encoder *enc, int path);
 int m1v_path_in_use(const m1v_encoder *enc); /* 1 = tiles, 0 = runs */
 /* Test hook: the nth device allocation made from now on by a reconfiguration (m1v_reserve_scratch, m1v_set_pipelined, m1v_set_input_layout,
- * m1v_set_plane_layout, m1v_set_sample_layout, m1v_set_rgb_plane_layout, the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
+ * m1v_set_plane_layout, m1v_set_sample_layout, m1v_set_rgb_plane_layout, m1v_set_float_plane_layout, the m1v_debug_set_* hooks) fails as if the device were out of memory; 0 = off.  A failed reconfiguration returns
  * M1V_E_HIP and leaves the encoder exactly as it was.  Inert unless the process runs with EC504_DEBUG_HOOKS=1. */
 void m1v_debug_fail_alloc(int nth);
 /* Test hook: the next m1v_encode_device that reaches `stage` returns M1V_E_HIP there, as a failed HIP call would: 1 = after
