@@ -22,8 +22,9 @@ tests/code_space.py enumerates what a block can code; this module enumerates whe
            member of it is at a height the reference cannot confirm.  These six are odd widths at even heights: the CPU tests
            compare the oracle with the reference there, the GPU tests the device with the oracle.
 
-Families that restrict the size take the nearest size below: surfaces W & ~1, the 4:2:0 plane presets W & ~1 and H & ~1 (the
-number of strips and macroblock rows stays).
+Families that restrict the size take the nearest size below: surfaces, RGB planes and float planes W & ~1, the 4:2:0 plane
+presets and the packed 4:2:2 / P010 sample presets W & ~1 and H & ~1 (the number of strips and macroblock rows stays); a family
+behind a frame table (kt-) or a plane table (kp-) inherits the rule of the family behind the prefix.
 
 The content is noise from a counter-based generator written out here (splitmix64 of seed and index: no PIL, no numpy Generator,
 nothing of the reference), full range for quality 12 and of amplitude 20 around mid-grey for quality 90.  The census mirrors the
@@ -93,10 +94,13 @@ def name(t):
 
 
 def restricted(t, family):
-    """The member at the nearest size below that the family takes."""
-    if family.startswith("surface-"):
+    """The member at the nearest size below that the family takes; a family behind a frame table (kt-) or a plane table (kp-)
+    takes what the family behind the prefix takes."""
+    if family.startswith(("kt-", "kp-")):
+        family = family[3:]
+    if family.startswith(("surface-", "rgbplanes-", "float16-", "bfloat16-", "float32-")):
         return t._replace(W=t.W & ~1)
-    if family in ("planes-i420", "planes-nv12", "planes-yv12", "planes-nv21"):
+    if family in ("planes-i420", "planes-nv12", "planes-yv12", "planes-nv21", "yuy2", "uyvy", "p010"):
         return t._replace(W=t.W & ~1, H=t.H & ~1)
     return t
 
@@ -169,9 +173,10 @@ def pixels(t, content, channels=3, n=None):
 
 def planes(t, content):
     """Independent noise planes of a member's coded region (read-only): Y [n, ye, xe], Cb and Cr [n, ye / 2, xe / 2]."""
-    key = ("planes", t.W, t.H, t.mode, content)
+    n = FRAMES[t.set]                     # (frame f is the same bytes whatever the number of frames: the generator counts)
+    key = ("planes", t.W, t.H, t.mode, content, n)
     if key not in _cache:
-        sh, n, amp = shape(t.W, t.H, t.mode), FRAMES[t.set], CONTENTS[content][1]
+        sh, amp = shape(t.W, t.H, t.mode), CONTENTS[content][1]
         xe, ye = 16 * sh["n_strips"], 16 * sh["n_mbrows"]
         out = (noise(_seed(t, content, 2), (n, ye, xe), amp), noise(_seed(t, content, 3), (n, ye // 2, xe // 2), amp),
                noise(_seed(t, content, 4), (n, ye // 2, xe // 2), amp))

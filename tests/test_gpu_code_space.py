@@ -2,7 +2,15 @@
 pair a block of samples reaches as its first coded pair, both signs, 20- and 28-bit escapes, and every DC level 0..2042 — the
 content of tests/code_space.py, whose census tests/test_code_space_cpu.py pins — through each kernel family: encodes on the tile
 path, the run kernels, RGBA, a pitched BGRA surface and NV12 / I420 planes, the global-memory fallback of the tile kernels, and
-the size table, the rd table and the frame_sizes probe of the four table kernels.
+the size table, the rd table and the frame_sizes probe of the table kernels.  The families are those of tests/input_families.py:
+
+  rgb, rgb-runs, rgba, surface-4-bgr-gap, planes-nv12, planes-i420   k_*_tiles, the run kernels, k_*_rgba, k_*_surface, k_*_planes
+  rgbplanes-pitched                  k_*_rgb_planes     (encodes, tables)
+  float16-, float32-window           k_*_float_planes   (encodes; float32 the fallback; bfloat16-window the tables): patterns
+                                     whose byte under the rule is the grey picture's, so the census is the pinned one
+  yuy2                               k_*_step2          (encodes, fallback, tables)
+  kt-planes-nv12, kt-surface-4-bgr-gap   kt_*_planes (encodes), kt_*_surface (tables): frames behind a frame table
+  kp-planes-i420, kp-planes-nv12     kp_*_planes        (encodes and fallback; tables): planes behind a plane table
 
 Every comparison is for equality with the CPU oracle (tests/plane_oracle.py for planes, tests/rd_oracle.py for the distortion)
 and every status word is 0.  A set's frames carry one quality each and are encoded with per-frame quality, ten frames to a call;
@@ -14,12 +22,12 @@ import numpy as np
 import pytest
 
 import code_space as cs
+import input_families as fam
 import plane_oracle
 import rd_oracle as rd
-from test_gpu_planes import _buffer, _layout, _plane_encoder, _view, _write_planes
 from test_gpu_rd_table import _rd
 from test_gpu_size_table import _table
-from test_gpu_surface import _encode, _surface, _surface_encoder
+from test_gpu_surface import _encode
 
 pytestmark = pytest.mark.gpu
 
@@ -100,37 +108,20 @@ def _raw(orc, name, plane, f):
 
 class _Case:
     """One encoder (at most BATCH frames a call) on one input family with all frames of one set on the device.
-    family: "rgb" | "rgb-runs" | "rgba" (packed) | "surface-<channels>-<order>-<layout>" | "planes-<layout>"."""
+    family: a family of tests/input_families.py, which builds the encoder and its input; the planes- families, the sample
+    presets and their table twins take the planes of a set, every other family its grey pictures."""
 
     def __init__(self, torch, orc, family, name):
-        from ec504_imageencoder_amd import Mpeg1Encoder
         self.torch, self.orc, self.family, self.name = torch, orc, family, name
         self.Q = cs.TOP["narrow"] if name == "narrow" else cs.TOP["wide"]
-        if family.startswith("planes-"):
-            self.kind = "planes"
+        base = fam.base_family(family)[1]
+        if fam.content_form(family) == "planes":
             fr = _frames(orc, name, "planes")
-            n = len(fr["qualities"])
-            lay, base = _layout(family.split("-")[1], W, H)
-            buf = _buffer(torch, n, lay, base, fill_seed=len(family))
-            _write_planes(torch, buf, lay, base, fr["Y"].copy(), fr["Cb"].copy(), fr["Cr"].copy())     # (the sets are read-only)
-            self.enc = _plane_encoder(W, H, self.Q, "full", BATCH, lay)
-            self.dev = _view(torch, buf, n, lay, base, self.enc)
-            self.keep = buf
-        elif family.startswith("surface-"):
-            _, channels, order, layout = family.split("-")
-            self.kind = "rgb" if channels == "3" else "rgba"
-            self.dev, pitch, stride = _surface(torch, _pixels(orc, name, self.kind), layout, order, fill_seed=len(family))
-            self.enc = _surface_encoder(W, H, self.Q, "full", int(channels), BATCH, pitch, stride, order)
+            content = dict(planes=(fr["Y"].copy(), fr["Cb"].copy(), fr["Cr"].copy()))           # (the sets are read-only)
         else:
-            self.kind = "rgba" if family == "rgba" else "rgb"
-            px = _pixels(orc, name, self.kind)
-            self.dev = torch.from_numpy(px.copy()).cuda()
-            self.enc = Mpeg1Encoder(W, H, self.Q, "full", channels=px.shape[-1], max_frames=BATCH)
-            if family == "rgb-runs":
-                self.enc.debug_set_path("runs")
-                assert self.enc.path == "runs" and self.enc.size_table_fused == 0
-            else:                                 # README: 3 channels on the tile path and 4 channels always take the fused pass
-                assert self.enc.path == ("tiles" if family == "rgb" else "runs") and self.enc.size_table_fused == 1
+            content = dict(pixels=_pixels(orc, name, "rgba" if base == "rgba" or base.startswith("surface-4-") else "rgb"))
+        self.input = fam.build(torch, family, W, H, "full", self.Q, BATCH, float_range=fam.FLOAT_RANGES[SETS.index(name) % 2], **content)
+        self.enc, self.dev, self.kind = self.input.enc, self.input.dev, self.input.kind
         self.frames = _frames(orc, name, self.kind)
         self.qualities = self.frames["qualities"]
         self.n = len(self.qualities)
@@ -175,8 +166,9 @@ class _Case:
 
 
 # ---- 1. encodes -------------------------------------------------------------------------------------------------------------
-ENCODE_FAMILIES = ["rgb", "rgb-runs", "rgba", "surface-4-bgr-gap", "planes-nv12", "planes-i420"]
-FALLBACK_FAMILIES = ["rgb", "surface-4-bgr-gap", "planes-nv12", "planes-i420"]
+ENCODE_FAMILIES = ["rgb", "rgb-runs", "rgba", "surface-4-bgr-gap", "planes-nv12", "planes-i420",
+                   "rgbplanes-pitched", "float16-window", "float32-window", "yuy2", "kt-planes-nv12", "kp-planes-i420"]
+FALLBACK_FAMILIES = ["rgb", "surface-4-bgr-gap", "planes-nv12", "planes-i420", "float32-window", "yuy2", "kp-planes-i420"]
 
 
 @pytest.mark.parametrize("name", SETS)
@@ -208,7 +200,8 @@ def test_global_memory_fallback_matches_the_oracle(torch_cuda, orc, family, name
 
 
 # ---- 2. tables --------------------------------------------------------------------------------------------------------------
-TABLE_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12"]     # one per table kernel
+TABLE_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12",      # one per table kernel
+                  "yuy2", "rgbplanes-pitched", "bfloat16-window", "kt-surface-4-bgr-gap", "kp-planes-nv12"]
 
 
 def _probe(torch, enc, dev, qs):

@@ -11,6 +11,17 @@ tests/test_geometry_space_cpu.py pins — through each kernel family:
   surface-*           encode, size table, rd table (even W): a pitch one byte over, a gap behind BGRA rows, packed BGR
   planes-i420, -nv12  the tight presets (even W and H), planes that are the image of the RGB noise: the oracle's RGB records
   planes-reference, -odd   independent noise planes against tests/plane_oracle.py
+  rgbplanes-pitched, -bgr  k_*_rgb_planes (even W): uint8 NCHW at row pitch W + 13, and tight in plane order B, G, R
+  float16-, bfloat16-, float32-window   k_*_float_planes (even W): a window at an odd x0 and an odd pitch of a 4-plane tensor of
+                      jitter patterns whose byte under the rule is the RGB noise; range unit / byte by the size index
+  yuy2, uyvy, p010    k_*_step2 (even W and H): the tight sample presets, independent noise planes in the addressed bytes
+  kt-<family>         kt_*_surface, _planes, _step2, _rgb_planes: surface-4-bgr-gap, surface-3-rgb-packed, planes-nv12,
+                      planes-i420, yuy2 and rgbplanes-pitched as frames scattered in a pool behind a frame table (planes-odd
+                      too, at the odd widths)
+  kp-planes-i420, -nv12, -reference, kp-rgbplanes-pitched   kp_*_planes, kp_*_rgb_planes: every plane at an address of its own
+                      behind a plane table, its allocation-visible range exactly the read contract's
+Each of the families from rgbplanes- on: encode, size table, rd table.  tests/input_families.py builds every family's input and
+names the kernels it reaches; tests/test_input_families_cpu.py holds those names against the code object.
 
 Every comparison is for equality with the CPU oracle (tests/rd_oracle.py for the distortion) and every status word is 0.  The
 content is noise, so every block differs from its neighbours (tests/test_geometry_space_cpu.py::test_content_is_position_sensitive):
@@ -24,22 +35,21 @@ import pytest
 
 import geometry_space as gs
 import hard_content as hc
+import input_families as fam
 import rd_oracle as rd
-from test_gpu_planes import _addressed, _buffer, _layout, _plane_encoder, _view, _write_planes
 from test_gpu_rd_table import _rd
 from test_gpu_size_table import _table
-from test_gpu_surface import _encode, _surface, _surface_encoder
+from test_gpu_surface import _encode
 
 pytestmark = pytest.mark.gpu
 
 FIRST = gs.FIRST
 TILE_FAMILIES = ["rgb", "rgb-fallback", "rgba", "surface-3-rgb-odd", "surface-4-bgr-gap", "surface-3-bgr-packed",
-                 "planes-i420", "planes-nv12", "planes-reference", "planes-odd"]
-PADDED_FAMILIES = [f for f in TILE_FAMILIES if f.startswith(("surface-", "planes-"))]
-BATCH_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12"]
+                 "planes-i420", "planes-nv12", "planes-reference", "planes-odd"] + fam.NEW_FAMILIES
+PADDED_FAMILIES = [f for f in TILE_FAMILIES if f.startswith(("surface-", "planes-"))] + fam.NEW_FAMILIES
+BATCH_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12", "float32-window", "yuy2", "kt-planes-nv12", "kp-rgbplanes-pitched"]
 RUN_FAMILIES = ["rgba", "rgb-runs"]
-STRICT_FAMILIES = ["rgb", "surface-3-rgb-odd", "planes-reference"]
-
+STRICT_FAMILIES = ["rgb", "surface-3-rgb-odd", "planes-reference", "rgbplanes-pitched", "float16-window", "kt-surface-4-bgr-gap"]
 
 @pytest.fixture(scope="module")
 def torch_cuda():
@@ -76,52 +86,25 @@ def _distortion(orc, t, content, kind, f, q):
 
 class _Case:
     """One encoder on one input family with the first n frames of a member's content on the device.
-    family: "rgb" | "rgb-fallback" | "rgb-runs" | "rgba" (packed) | "surface-<channels>-<order>-<layout>" | "planes-<layout>".
+    family: a family of tests/input_families.py, which builds the encoder and its input.
     offset: bytes between a 256-byte boundary and a packed buffer's first byte."""
 
     def __init__(self, torch, orc, family, t, content, n=None, max_frames=None, fill_seed=None, offset=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
         self.torch, self.orc, self.family, self.content = torch, orc, family, content
         self.t = t = gs.restricted(t, family)
         self.n = n = gs.FRAMES[t.set] if n is None else n
         self.Q = Q = gs.CONTENTS[content][0]
         cap = n if max_frames is None else max_frames
-        fill = len(family) if fill_seed is None else fill_seed
         W, H = t.W, t.H
-        if family.startswith("planes-"):
-            layout = family.split("-")[1]
-            self.kind = "rgb" if layout in ("i420", "nv12") else "planes"
-            lay, base = _layout(layout, W, H)
-            self.keep = buf = _buffer(torch, n, lay, base, fill_seed=fill)
-            if self.kind == "rgb":
-                Y, Cb, Cr = _addressed(orc, gs.pixels(t, content, 3, n), t.mode)
-            else:
-                Y, Cb, Cr = (p[:n].copy() for p in gs.planes(t, content))         # (the content is read-only)
-            _write_planes(torch, buf, lay, base, Y, Cb, Cr)
-            self.enc = _plane_encoder(W, H, Q, t.mode, cap, lay)
-            self.dev = _view(torch, buf, n, lay, base, self.enc)
-        elif family.startswith("surface-"):
-            _, channels, order, layout = family.split("-")
-            self.kind = "rgb" if channels == "3" else "rgba"
-            px = gs.pixels(t, content, int(channels), n).copy()
-            self.dev, pitch, stride = _surface(torch, px, layout, order, fill_seed=fill)
-            self.enc = _surface_encoder(W, H, Q, t.mode, int(channels), cap, pitch, stride, order)
-        else:
-            self.kind = "rgba" if family == "rgba" else "rgb"
-            px = gs.pixels(t, content, 4 if self.kind == "rgba" else 3, n)
-            self.keep = buf = torch.zeros(px.size + 8, dtype=torch.uint8, device="cuda")
-            self.dev = buf[offset:offset + px.size].view(px.shape)
-            self.dev.copy_(torch.from_numpy(px.copy()).cuda())
-            assert self.dev.data_ptr() % 256 == offset
-            self.enc = Mpeg1Encoder(W, H, Q, t.mode, channels=px.shape[-1], max_frames=cap)
-            if family == "rgb-runs":
-                self.enc.debug_set_path("runs")
-                assert self.enc.path == "runs" and self.enc.size_table_fused == 0
-            else:                                 # README: 3 channels on the tile path and 4 channels always take the fused pass
-                assert self.enc.path == ("tiles" if self.kind == "rgb" else "runs") and self.enc.size_table_fused == 1
-            if family == "rgb-fallback":
-                self.enc.debug_set_lds_words(8)
-                self.enc.reserve_scratch(True)
+        base = fam.base_family(family)[1]
+        if fam.content_form(family) == "planes" and base not in ("planes-i420", "planes-nv12"):
+            content_ = dict(planes=tuple(p[:n].copy() for p in gs.planes(t, content)))         # (the content is read-only)
+        else:                                     # the 4:2:0 presets take the planes of the RGB noise: the oracle's RGB records
+            channels = 4 if base == "rgba" else (int(base.split("-")[1]) if base.startswith("surface-") else 3)
+            content_ = dict(pixels=gs.pixels(t, content, channels, n).copy())
+        self.input = fam.build(torch, family, W, H, t.mode, Q, cap, orc=orc, fill_seed=fill_seed, offset=offset,
+                               float_range=fam.FLOAT_RANGES[t.k % 2], **content_)
+        self.enc, self.dev, self.kind = self.input.enc, self.input.dev, self.input.kind
         sh = gs.shape(W, H, t.mode)
         assert (self.enc.strips, self.enc.mb_rows) == (sh["n_strips"], sh["n_mbrows"])
 
@@ -304,7 +287,8 @@ def test_run_set(torch_cuda, orc, family, rows):
 
 
 # ---- 5. odd widths at even heights ------------------------------------------------------------------------------------------
-ODD_WIDTH_FAMILIES = ["rgb", "rgb-fallback", "rgba", "planes-reference", "planes-odd"]     # the families that take an odd width
+# the families that take an odd width (a frame table serves any plane layout, planes-odd's too)
+ODD_WIDTH_FAMILIES = ["rgb", "rgb-fallback", "rgba", "planes-reference", "planes-odd", "kp-planes-reference", "kt-planes-odd"]
 
 
 @pytest.mark.parametrize("family", ODD_WIDTH_FAMILIES)

@@ -1,8 +1,16 @@
-"""GPU tests of the entropy stage on hard content through every kernel family (-m gpu): the fused size tables (k_size_table_tiles,
-_rgba, _surface, _planes; narrow and wide staging), per-frame quality, the frame_sizes probe, the rate calls, and the surface
-and plane encode kernels, on the content of tests/hard_content.py — every run length, levels on both sides of every table row's
-end, 20- and 28-bit escapes, blocks of more than 64 and 128 bits (tests/test_hard_content_cpu.py pins that census).  The
-content of the other GPU test modules is noise, which codes little more than DC sizes.
+"""GPU tests of the entropy stage on hard content through every kernel family (-m gpu): the fused size tables (narrow and wide
+staging), per-frame quality, the frame_sizes probe, the rate calls, and the encode kernels of every layout, on the content of
+tests/hard_content.py — every run length, levels on both sides of every table row's end, 20- and 28-bit escapes, blocks of more
+than 64 and 128 bits (tests/test_hard_content_cpu.py pins that census).  The content of the other GPU test modules is noise,
+which codes little more than DC sizes.  The families are those of tests/input_families.py:
+
+  size tables, row independence, table against probes   rgb (k_size_table_tiles), rgba (_rgba), surface-4-bgr-gap, surface-3-rgb-odd
+                      (_surface), planes-nv12, planes-odd (_planes), yuy2 (_step2), rgbplanes-pitched (_rgb_planes), bfloat16-window
+                      (_float_planes), kt-surface-4-bgr-gap (kt_size_table_surface), kp-planes-nv12 (kp_size_table_planes)
+  encodes, per-frame quality, probe, the fallback        rgb, rgba, eight surfaces, planes-i420, -nv12, -pitched, -odd, rgbplanes-bgr
+                      (k_encode_rgb_planes), float16-window (k_encode_float_planes), uyvy, p010 (k_encode_step2), kt-yuy2
+                      (kt_encode_step2), kp-rgbplanes-pitched (kp_encode_rgb_planes)
+  the rate calls      rgb, surface-4-bgr-gap, planes-nv12, float32-window, kp-planes-nv12
 
 Every comparison is for equality with the CPU oracle (tests/plane_oracle.py for planes); every status word is 0.  Sizes are
 352x288 and, for a partial last tile column, 176x208.  The oracle's records are cached per module."""
@@ -10,10 +18,11 @@ import numpy as np
 import pytest
 
 import hard_content as hc
+import input_families as fam
 import plane_oracle
-from test_gpu_planes import _buffer, _layout, _oracle_on_buffer, _plane_encoder, _view, _write_planes
+from test_gpu_planes import _oracle_on_buffer
 from test_gpu_size_table import _frames, _table
-from test_gpu_surface import _encode, _frame_rule, _surface, _surface_encoder
+from test_gpu_surface import _encode, _frame_rule
 from test_rate_abi import batch_rule, cbr_rule
 
 pytestmark = pytest.mark.gpu
@@ -75,37 +84,21 @@ def _record(orc, kind, W, H, c, q, index):
 
 class _Case:
     """One encoder of quality Q on one input family with a batch of content frames on the device.
-    family: "rgb" | "rgba" (packed, default layout) | "surface-<channels>-<order>-<layout>" | "planes-<layout>"."""
+    family: a family of tests/input_families.py, which builds the encoder and its input; the planes- families, the sample
+    presets and their table twins take hard_planes, every other family hard_frames."""
 
     def __init__(self, torch, orc, family, W, H, ids, forced_runs=False):
-        from ec504_imageencoder_amd import Mpeg1Encoder
         self.torch, self.orc, self.W, self.H, self.ids, self.n = torch, orc, W, H, tuple(ids), len(ids)
         sel = list(ids)
-        n = self.n
-        if family.startswith("planes-"):
-            self.kind = "planes"
-            Y, Cb, Cr = _content(orc, "planes", W, H)
-            self.lay, self.base = _layout(family.split("-")[1], W, H)
-            self.buf = _buffer(torch, n, self.lay, self.base, fill_seed=len(family))
-            _write_planes(torch, self.buf, self.lay, self.base, Y[sel], Cb[sel], Cr[sel])
-            self.enc = _plane_encoder(W, H, Q, "full", n, self.lay)
-            self.dev = _view(torch, self.buf, n, self.lay, self.base, self.enc)
-        elif family.startswith("surface-"):
-            _, channels, order, layout = family.split("-")
-            self.kind = "rgb" if channels == "3" else "rgba"
-            px = _content(orc, self.kind, W, H)[sel]
-            self.dev, pitch, stride = _surface(torch, px, layout, order, fill_seed=len(family))
-            self.enc = _surface_encoder(W, H, Q, "full", int(channels), n, pitch, stride, order)
+        base = fam.base_family(family)[1]
+        if fam.content_form(family) == "planes":
+            content = dict(planes=tuple(p[sel] for p in _content(orc, "planes", W, H)))
         else:
-            self.kind = family
-            px = _content(orc, family, W, H)[sel]
-            self.dev = torch.from_numpy(px).cuda()
-            self.enc = Mpeg1Encoder(W, H, Q, "full", channels=px.shape[-1], max_frames=n)
-            if forced_runs:                       # the K-probe fallback: one run-kernel probe per quality
-                self.enc.debug_set_path("runs")
-                assert self.enc.path == "runs" and self.enc.size_table_fused == 0
-            else:                                 # README: 3 channels on the tile path and 4 channels always take the fused pass
-                assert self.enc.path == ("tiles" if family == "rgb" else "runs") and self.enc.size_table_fused == 1
+            content = dict(pixels=_content(orc, "rgba" if base == "rgba" or base.startswith("surface-4-") else "rgb", W, H)[sel])
+        self.input = fam.build(torch, family, W, H, "full", Q, self.n, forced_runs=forced_runs, float_range=fam.FLOAT_RANGES[W // 176 % 2],
+                               **content)
+        self.enc, self.dev, self.kind = self.input.enc, self.input.dev, self.input.kind
+        self.buf, self.lay, self.base = self.input.buf, self.input.lay, self.input.base
 
     def record(self, f, q):
         return _record(self.orc, self.kind, self.W, self.H, self.ids[f], q, FIRST + f)
@@ -134,8 +127,9 @@ class _Case:
         self.enc.close()
 
 
-TABLE_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "surface-3-rgb-odd", "planes-nv12", "planes-odd"]
-KERNEL_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12"]     # one per size-table kernel
+NEW_TABLE_FAMILIES = ["yuy2", "rgbplanes-pitched", "bfloat16-window", "kt-surface-4-bgr-gap", "kp-planes-nv12"]
+TABLE_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "surface-3-rgb-odd", "planes-nv12", "planes-odd"] + NEW_TABLE_FAMILIES
+KERNEL_FAMILIES = ["rgb", "rgba", "surface-4-bgr-gap", "planes-nv12"] + NEW_TABLE_FAMILIES     # one per size-table kernel
 
 
 # ---- 1. size tables against the oracle --------------------------------------------------------------------------------------
@@ -190,7 +184,8 @@ def test_fused_table_equals_the_probes(torch_cuda, orc, family):
 
 # ---- 4. encode, encode with per-frame quality, frame_sizes ------------------------------------------------------------------
 ENCODE_FAMILIES = (["rgb", "rgba"] + [f"surface-{c}-{o}-{l}" for c in (3, 4) for o in ("rgb", "bgr") for l in ("odd", "window")]
-                   + [f"planes-{l}" for l in ("i420", "nv12", "pitched", "odd")])
+                   + [f"planes-{l}" for l in ("i420", "nv12", "pitched", "odd")]
+                   + ["rgbplanes-bgr", "float16-window", "uyvy", "p010", "kt-yuy2", "kp-rgbplanes-pitched"])
 QS_A = (92, 50, 76, 77)
 QS_B = (77, 92, 50, 76)
 
@@ -227,7 +222,7 @@ def test_encode_per_frame_quality_and_probe(torch_cuda, orc, family, W, H):
 CANDS = (20, 50, 76, 85, 92)
 
 
-@pytest.mark.parametrize("family", ["rgb", "surface-4-bgr-gap", "planes-nv12"])
+@pytest.mark.parametrize("family", ["rgb", "surface-4-bgr-gap", "planes-nv12", "float32-window", "kp-planes-nv12"])
 def test_rate_calls(torch_cuda, orc, family):
     """encode_to_budget, encode_to_batch_budget and a three-call chain of encode_at_bitrate on six frames, hard and flat in
     turn: picks, sizes and bytes are the rules of tests/test_rate_abi.py on the oracle's sizes, with budgets taken from those

@@ -71,16 +71,19 @@ class _Ycc:
     def want(self, orc, pic, W, H, index, Q):
         return sample_oracle.encode_layout(pic, self.oracle_layout(W, H), W, H, index, Q, orc.MODE_FULL)
 
-    def planes(self, W, H):
+    def planes(self, W, H, region=None):
         """Per plane (v, lo, E, A): the virtual frame's index the plane's pointer stands for, the range [lo, E) of the read
-        contract relative to the pointer, and the virtual indices of the samples the definition addresses (W, H multiples of 16)."""
+        contract relative to the pointer, and the virtual indices of the samples the definition addresses.  region: the coded
+        region (xe, ye), by default W & ~15, H & ~15: the header's E_p counts ye rows of xe bytes for Y and ye / 2 rows of
+        (xe / 2 - 1) * c_step + 1 bytes for Cb and Cr."""
+        xe, ye = (W & ~15, H & ~15) if region is None else region
         o, e = self.oracle_layout(W, H), self.encoder_layout(W, H)
-        r, c = np.arange(H)[:, None], np.arange(W)[None, :]
-        out = [(o["y_offset"] - e["y_offset"], 0, e["y_offset"] + (H - 1) * e["y_pitch"] + W,
+        r, c = np.arange(ye)[:, None], np.arange(xe)[None, :]
+        out = [(o["y_offset"] - e["y_offset"], 0, e["y_offset"] + (ye - 1) * e["y_pitch"] + xe,
                 (o["y_offset"] + r * o["y_pitch"] + c).reshape(-1))]
-        r, c = np.arange(H // 2)[:, None], np.arange(W // 2)[None, :]
+        r, c = np.arange(ye // 2)[:, None], np.arange(xe // 2)[None, :]
         for k in ("cb_offset", "cr_offset"):
-            out.append((o[k] - e[k], 0, e[k] + (H // 2 - 1) * e["c_pitch"] + (W // 2 - 1) * e["c_step"] + 1,
+            out.append((o[k] - e[k], 0, e[k] + (ye // 2 - 1) * e["c_pitch"] + (xe // 2 - 1) * e["c_step"] + 1,
                         (o[k] + r * o["c_pitch"] + c * o["c_step"]).reshape(-1)))
         return out
 
@@ -121,7 +124,8 @@ class _Rgb:
     def want(self, orc, pic, W, H, index, Q):
         return orc.encode_frame(pic, W, H, index, Q, orc.MODE_FULL, channels=3)
 
-    def planes(self, W, H):
+    def planes(self, W, H, region=None):
+        """(An RGB plane's range is the layout's own, of the whole picture: width bytes of height rows, whatever the region.)"""
         e = self.encoder_layout(W, H)
         r, c = np.arange(H)[:, None], np.arange(W)[None, :]
         return [(0, e[k], e[k] + (H - 1) * e["row_pitch"] + W, (e[k] + r * e["row_pitch"] + c).reshape(-1))
@@ -139,10 +143,10 @@ FAMILIES = {"i420": _Ycc("i420", SEPARATE),
 
 
 # ---- placement --------------------------------------------------------------------------------------------------------------
-def _blocks(fam, W, H):
+def _blocks(fam, W, H, region=None):
     """Per group (v0, length, [(plane, distance of its pointer from the block's first byte)], virtual indices written): the bytes
     of the virtual frame from v0 on that the block stands for."""
-    planes = fam.planes(W, H)
+    planes = fam.planes(W, H, region)
     out = []
     for group in fam.groups:
         # (the group's pointers are d apart as the family says: [f][2] = [f][1] + 1 stands for virtual indices one apart)
