@@ -61,6 +61,15 @@ class FloatPlaneLayout(_Layout):
     _fields_ = [(name, C.c_uint64) for name in ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")] + \
                [("sample", C.c_int32), ("range", C.c_int32)]
 
+
+class FloatPixelLayout(_Layout):
+    """m1v_float_pixel_layout (include/mpeg1_hip.h): where the float samples of a frame's interleaved pixels lie, in bytes, which
+    of a pixel's samples are R, G and B (ORDER_*), their type (SAMPLE_*) and their value range (RANGE_*)."""
+    _fields_ = [(name, C.c_uint64) for name in ("row_pitch", "frame_stride", "pixel_step")] + \
+               [("order", C.c_int32), ("sample", C.c_int32), ("range", C.c_int32)]
+
+PIXEL_ORDERS = {"rgb": ORDER_RGB, "bgr": ORDER_BGR}
+
 _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
@@ -80,6 +89,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
     "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
     "m1v_float_plane_layout_preset", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force", "m1v_float_planes_to_bytes_device",
+    "m1v_float_pixel_layout_preset", "m1v_set_float_pixel_layout", "m1v_float_pixel_layout_in_force", "m1v_float_pixels_to_bytes_device",
     "m1v_set_frame_table", "m1v_frame_table", "m1v_set_plane_table", "m1v_plane_table",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
@@ -229,6 +239,14 @@ def lib():
     L.m1v_float_plane_layout_in_force.restype = C.c_int
     L.m1v_float_planes_to_bytes_device.argtypes = [vp, vp, C.c_int, vp, vp]
     L.m1v_float_planes_to_bytes_device.restype = C.c_int
+    L.m1v_float_pixel_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FloatPixelLayout)]
+    L.m1v_float_pixel_layout_preset.restype = C.c_int
+    L.m1v_set_float_pixel_layout.argtypes = [vp, C.POINTER(FloatPixelLayout)]
+    L.m1v_set_float_pixel_layout.restype = C.c_int
+    L.m1v_float_pixel_layout_in_force.argtypes = [vp, C.POINTER(FloatPixelLayout)]
+    L.m1v_float_pixel_layout_in_force.restype = C.c_int
+    L.m1v_float_pixels_to_bytes_device.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.m1v_float_pixels_to_bytes_device.restype = C.c_int
     L.m1v_set_frame_table.argtypes = [vp, C.c_int]
     L.m1v_set_frame_table.restype = C.c_int
     L.m1v_frame_table.argtypes = [vp]

@@ -25,6 +25,9 @@
 //   k_encode_float_planes, k_size_table_float_planes, k_rd_table_float_planes   (m1v_float_planes.h, the same bodies) the tile
 //                     kernels on planes of fp16, bf16 or fp32 samples of R, G and B (m1v_set_float_plane_layout: NCHW float
 //                     tensors): each sample becomes a byte by one rule (float_sample_to_byte), then the stage above
+//   k_float_pixels_encode, k_float_pixels_size_table, k_float_pixels_rd_table   (m1v_float_pixels.h, the same bodies) the tile
+//                     kernels on float samples of R, G and B interleaved per pixel (m1v_set_float_pixel_layout: NHWC and
+//                     channels-last float tensors, RGBA16F / RGBA32F targets), by the same rule
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -1268,6 +1271,7 @@ constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 #include "m1v_step2.h"
 #include "m1v_rgb_planes.h"
 #include "m1v_float_planes.h"
+#include "m1v_float_pixels.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1784,7 +1788,7 @@ struct m1v_encoder {
     // The input layout in force, no zeros: its kind, the frame stride every kind but packed has, and one member per kind.  Only the
     // member of the kind in force is set and read (layout_facts: how messages name a kind, its setter and its getter).
     struct Layout {
-        enum class Kind { packed, surface, samples, rgb_planes, float_planes } kind = Kind::packed;
+        enum class Kind { packed, surface, samples, rgb_planes, float_planes, float_pixels } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
         // m1v_set_frame_table / m1v_set_plane_table: d_rgb is a device array of one 64-bit address per frame, or of three (one per
         // plane); frame_stride is kept and unused.  Part of the record, so every setter's fresh record turns tables off and a
@@ -1798,6 +1802,9 @@ struct m1v_encoder {
         // m1v_set_float_plane_layout: planes of fp16, bf16 or fp32 samples of R, G and B, as their kernels take them
         // (m1v_float_planes.h), with the M1V_SAMPLE_* and M1V_RANGE_* values they were set with
         struct FloatPlanes { FloatPlaneFrontArgs front; int sample, range; } float_planes = {};
+        // m1v_set_float_pixel_layout: float samples of R, G and B interleaved per pixel, as their kernels take them
+        // (m1v_float_pixels.h), with the pixel step in bytes and the M1V_SAMPLE_* and M1V_RANGE_* values they were set with
+        struct FloatPixels { FloatPixelFrontArgs front; uint32_t pixel_step; int sample, range; } float_pixels = {};
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
@@ -2034,7 +2041,8 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   aligned buffer (3 channels), 3 = aligned 4-channel pixels, 0 = byte loads.  The strip kernel has modes 0 and 1 and stages
 //   every level wide.
 enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kFloatPlanesF16, kFloatPlanesBf16,
-                   kFloatPlanesF32, kTileVariants };
+                   kFloatPlanesF32, kFloatPixelsF16x3, kFloatPixelsF16x4, kFloatPixelsBf16x3, kFloatPixelsBf16x4, kFloatPixelsF32x3, kFloatPixelsF32x4,
+                   kTileVariants };
 enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
 //   planes[...][...]: their kp_* twins of a plane table (m1v_set_plane_table); kPlanes, kPlanesPaired and kRgbPlanes only
 struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows][kTileVariants][2], *planes[kTileRows][kTileVariants][2], *dense[4][2], *strips[2][2]; };
@@ -2050,6 +2058,10 @@ struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows
 #define M1V_FLOAT_VARIANT(V, T)                                                                                                   \
     (M1V_PAIR(k.tile[kEncode][V], k_encode_float_planes, T), M1V_PAIR(k.tile[kSizeTable][V], k_size_table_float_planes, T),      \
      M1V_PAIR(k.tile[kRdTable][V], k_rd_table_float_planes, T))
+// the float pixel kernels of one sample type and pixel width (m1v_float_pixels.h): no table twins either
+#define M1V_FLOAT_PIXEL_VARIANT(V, T, C)                                                                                          \
+    (M1V_PAIR(k.tile[kEncode][V], k_float_pixels_encode, T, C), M1V_PAIR(k.tile[kSizeTable][V], k_float_pixels_size_table, T, C), \
+     M1V_PAIR(k.tile[kRdTable][V], k_float_pixels_rd_table, T, C))
 // ... and its kp_* kernels of a plane table
 #define M1V_PLANE_TABLE_VARIANT(V, NAME, ...)                                                                                     \
     (M1V_PAIR(k.planes[kEncode][V], kp_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.planes[kSizeTable][V], kp_size_table_##NAME, ##__VA_ARGS__), \
@@ -2081,8 +2093,15 @@ static const Kernels kKernels = [] {
     M1V_FLOAT_VARIANT(kFloatPlanesF16, F16Sample);
     M1V_FLOAT_VARIANT(kFloatPlanesBf16, Bf16Sample);
     M1V_FLOAT_VARIANT(kFloatPlanesF32, F32Sample);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsF16x3, F16Sample, 3);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsF16x4, F16Sample, 4);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsBf16x3, Bf16Sample, 3);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsBf16x4, Bf16Sample, 4);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsF32x3, F32Sample, 3);
+    M1V_FLOAT_PIXEL_VARIANT(kFloatPixelsF32x4, F32Sample, 4);
     return k;
 }();
+#undef M1V_FLOAT_PIXEL_VARIANT
 #undef M1V_FLOAT_VARIANT
 #undef M1V_PLANE_TABLE_VARIANT
 #undef M1V_TILE_VARIANT
@@ -2109,6 +2128,11 @@ static TileVariant tile_variant(const m1v_encoder *e) {
     case LayoutKind::rgb_planes: return kRgbPlanes;
     case LayoutKind::float_planes:
         return l.float_planes.sample == M1V_SAMPLE_F32 ? kFloatPlanesF32 : (l.float_planes.sample == M1V_SAMPLE_BF16 ? kFloatPlanesBf16 : kFloatPlanesF16);
+    case LayoutKind::float_pixels: { // (the variants lie [type][3 | 4 samples per pixel])
+        const int type = l.float_pixels.sample == M1V_SAMPLE_F32 ? 2 : (l.float_pixels.sample == M1V_SAMPLE_BF16 ? 1 : 0);
+        const int wide = l.float_pixels.pixel_step == 4u * (type == 2 ? 4u : 2u) ? 1 : 0;
+        return (TileVariant)(kFloatPixelsF16x3 + 2 * type + wide);
+    }
     case LayoutKind::samples: return l.samples.y_step == 2 ? kStep2 : (l.samples.c_step == 2 ? kPlanesPaired : kPlanes);
     case LayoutKind::surface: return l.surface.order == M1V_ORDER_BGR ? (four ? kSurfaceBgr4 : kSurfaceBgr3) : (four ? kSurfaceRgb4 : kSurfaceRgb3);
     case LayoutKind::packed: return four ? kPacked4 : kPacked3;
@@ -2155,9 +2179,9 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
 
 // What a tile-shaped kernel's base arguments are wrapped in for each layout kind, and their row of Kernels::tile
 template <typename Base> struct TileFamily;
-template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; using FloatPlanes = FloatPlaneArgs; };
-template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; using FloatPlanes = FloatPlaneTableArgs; };
-template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; using FloatPlanes = FloatPlaneRdArgs; };
+template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; using FloatPlanes = FloatPlaneArgs; using FloatPixels = FloatPixelArgs; };
+template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; using FloatPlanes = FloatPlaneTableArgs; using FloatPixels = FloatPixelTableArgs; };
+template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; using FloatPlanes = FloatPlaneRdArgs; using FloatPixels = FloatPixelRdArgs; };
 
 // The tile-shaped kernel of a's family over the grid a carries (fill_tile_grid), with a wrapped for the layout in force
 template <typename Args>
@@ -2187,13 +2211,16 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
         return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, stride});
     case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, stride});
     case LayoutKind::float_planes: return launch(typename Family::FloatPlanes{a, l.float_planes.front, stride});
+    case LayoutKind::float_pixels: return launch(typename Family::FloatPixels{a, l.float_pixels.front, stride});
     case LayoutKind::packed: return launch(a);
     }
 }
 
 // With a frame or plane table on, d_rgb is read as 64-bit words by scalar loads: refused here, in front of every launch, when misaligned.
-// So are float planes whose samples would not be naturally aligned (a float plane layout has no table mode).
+// So are float planes and float pixels whose samples would not be naturally aligned (the float layouts have no table mode).
 static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
+    if (e->layout.kind == LayoutKind::float_pixels && ((uintptr_t)d_rgb & (e->layout.float_pixels.sample == M1V_SAMPLE_F32 ? 3u : 1u)) != 0)
+        return fail(M1V_E_ARG, "a float pixel layout is in force (m1v_set_float_pixel_layout): d_rgb must be a multiple of the sample size%s");
     if (e->layout.kind == LayoutKind::float_planes && ((uintptr_t)d_rgb & (e->layout.float_planes.sample == M1V_SAMPLE_F32 ? 3u : 1u)) != 0)
         return fail(M1V_E_ARG, "a float plane layout is in force (m1v_set_float_plane_layout): d_rgb must be a multiple of the sample size%s");
     if (e->layout.table == TableMode::off || ((uintptr_t)d_rgb & 7) == 0) return M1V_OK;

@@ -318,6 +318,7 @@ static LayoutFacts layout_facts(LayoutKind kind, bool two_apart = false) {
         return {"a plane layout", "m1v_set_plane_layout", "m1v_plane_layout_in_force"};
     case LayoutKind::rgb_planes: return {"an RGB plane layout", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force"};
     case LayoutKind::float_planes: return {"a float plane layout", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force"};
+    case LayoutKind::float_pixels: return {"a float pixel layout", "m1v_set_float_pixel_layout", "m1v_float_pixel_layout_in_force"};
     case LayoutKind::packed: return {"packed input", "m1v_set_input_layout", "m1v_input_layout"}; // (the surface layout's default)
     }
 }
@@ -606,7 +607,8 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     const m1v_encoder::Layout &l = e->layout;
-    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes || l.kind == LayoutKind::float_planes) return ask_its_getter(e);
+    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes || l.kind == LayoutKind::float_planes || l.kind == LayoutKind::float_pixels)
+        return ask_its_getter(e);
     const m1v_encoder::Layout::Surface s = l.kind == LayoutKind::surface ? l.surface : m1v_encoder::Layout::Surface{0, M1V_ORDER_RGB};
     if (row_pitch_bytes) *row_pitch_bytes = s.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)l.frame_stride;
@@ -716,7 +718,8 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes) return ask_its_getter(e);
+    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes || e->layout.kind == LayoutKind::float_pixels)
+        return ask_its_getter(e);
     if (e->layout.kind != LayoutKind::samples) return 0;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (s.y_step == 2) return ask_its_getter(e);
@@ -726,7 +729,8 @@ int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
 
 int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes) return ask_its_getter(e);
+    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes || e->layout.kind == LayoutKind::float_pixels)
+        return ask_its_getter(e);
     if (e->layout.kind != LayoutKind::samples) return 0;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.y_step, s.c_step, (size_t)e->layout.frame_stride};
@@ -860,11 +864,87 @@ int m1v_float_planes_to_bytes_device(m1v_encoder *e, const void *d_frames, int n
     return M1V_OK;
 }
 
+int m1v_float_pixel_layout_preset(int width, int height, int pixel_samples, int order, int sample, int range, m1v_float_pixel_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (pixel_samples != 3 && pixel_samples != 4) return fail(M1V_E_ARG, "a pixel has 3 or 4 samples%s");
+    if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
+    const uint64_t S = float_sample_bytes(sample);
+    if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
+    if (range != M1V_RANGE_UNIT && range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+    const uint64_t step = (uint64_t)pixel_samples * S, pitch = (uint64_t)width * step;
+    *out = {pitch, (uint64_t)height * pitch, step, order, sample, range};
+    return M1V_OK;
+}
+
+int m1v_set_float_pixel_layout(m1v_encoder *e, const m1v_float_pixel_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a float pixel layout needs an encoder created with 3 channels (the pixel's sample count is the layout's)%s");
+        if (g.W & 1) return fail(M1V_E_ARG, "a float pixel layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
+        if (layout->order != M1V_ORDER_RGB && layout->order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
+        const unsigned long long S = float_sample_bytes(layout->sample);
+        if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
+        if (layout->range != M1V_RANGE_UNIT && layout->range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+        const unsigned long long step = layout->pixel_step, pitch = layout->row_pitch;
+        if (step == S)
+            return fail(M1V_E_ARG, "a pixel step of one sample describes a plane, not pixels: m1v_set_float_plane_layout serves planar float frames%s");
+        if (step != 3 * S && step != 4 * S) return fail(M1V_E_ARG, "pixel step must be 3 or 4 samples (%s bytes)", S == 2 ? "6 or 8" : "12 or 16");
+        if ((pitch | layout->frame_stride) % S)
+            return fail(M1V_E_ARG, "row pitch and frame stride must be multiples of the sample size (%s bytes)", S == 2 ? "2" : "4");
+        const unsigned long long row = (unsigned long long)g.W * step;
+        if (pitch < row) return fail(M1V_E_ARG, "row pitch below width * pixel step%s");
+        const unsigned long long limit = 1ull << 32;
+        if (pitch >= limit || (unsigned long long)(g.H - 1) * pitch + row >= limit)
+            return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (layout->frame_stride < (unsigned long long)(g.H - 1) * pitch + row) return fail(M1V_E_ARG, "frame stride below the bytes a frame's rows span%s");
+        want.kind = LayoutKind::float_pixels;
+        want.float_pixels = {{(uint32_t)pitch, layout->range == M1V_RANGE_UNIT ? 255.0f : 1.0f, layout->order == M1V_ORDER_BGR ? 1u : 0u},
+                             (uint32_t)step, layout->sample, layout->range};
+        want.frame_stride = layout->frame_stride;
+    }
+    return apply_layout(e, want);
+}
+
+int m1v_float_pixel_layout_in_force(const m1v_encoder *e, m1v_float_pixel_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::float_pixels) return 0;
+    const m1v_encoder::Layout::FloatPixels &f = e->layout.float_pixels;
+    if (out) *out = {f.front.row_pitch, e->layout.frame_stride, f.pixel_step, (int32_t)(f.front.bgr ? M1V_ORDER_BGR : M1V_ORDER_RGB), f.sample, f.range};
+    return 1;
+}
+
+int m1v_float_pixels_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::float_pixels) return fail(M1V_E_ARG, "m1v_float_pixels_to_bytes_device needs a float pixel layout in force (m1v_set_float_pixel_layout)%s");
+    if (n_frames < 0 || ((!d_frames || !d_bytes) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
+    if (const int rc = check_frame_table(e, static_cast<const uint8_t *>(d_frames))) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const m1v_encoder::Layout::FloatPixels &f = e->layout.float_pixels;
+    const void *kernel = f.sample == M1V_SAMPLE_F32 ? (const void *)&k_float_pixels_to_bytes<F32Sample>
+                         : (f.sample == M1V_SAMPLE_BF16 ? (const void *)&k_float_pixels_to_bytes<Bf16Sample> : (const void *)&k_float_pixels_to_bytes<F16Sample>);
+    const unsigned pixels = (unsigned)e->g.W * (unsigned)e->g.H;
+    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
+        const int n = std::min(n_frames - done, 65535);
+        FloatPixelBytesArgs a = {static_cast<const uint8_t *>(d_frames) + (unsigned long long)done * e->layout.frame_stride,
+                                 d_bytes + (unsigned long long)done * 3ull * pixels, f.front, e->layout.frame_stride,
+                                 (uint32_t)e->g.W, (uint32_t)e->g.H, f.pixel_step};
+        void *args[] = {&a};
+        HIP_TRY(hipLaunchKernel(kernel, dim3((pixels + 255u) / 256u, (unsigned)n), dim3(256u), args, 0, (hipStream_t)stream));
+    }
+    return M1V_OK;
+}
+
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (enable && e->layout.kind == LayoutKind::float_planes)
         return fail(M1V_E_ARG, "a frame table does not serve a float plane layout (m1v_set_float_plane_layout): float frames behind a "
+                               "table are not covered%s");
+    if (enable && e->layout.kind == LayoutKind::float_pixels)
+        return fail(M1V_E_ARG, "a frame table does not serve a float pixel layout (m1v_set_float_pixel_layout): float frames behind a "
                                "table are not covered%s");
     if (enable && !e->layout.tiles_only())
         return fail(M1V_E_ARG, "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
@@ -888,6 +968,9 @@ int m1v_set_plane_table(m1v_encoder *e, int enable) {
         if (l.kind == LayoutKind::float_planes)
             return fail(M1V_E_ARG, "a plane table does not serve a float plane layout (m1v_set_float_plane_layout): float planes behind "
                                    "separate pointers are not covered%s");
+        if (l.kind == LayoutKind::float_pixels)
+            return fail(M1V_E_ARG, "a plane table does not serve a float pixel layout (m1v_set_float_pixel_layout): interleaved pixels "
+                                   "have no planes, and float frames behind a table are not covered%s");
         if (l.kind == LayoutKind::samples && l.samples.y_step == 2)
             return fail(M1V_E_ARG, "a plane table does not serve a (2, 4) sample layout: packed 4:2:2 has no planes, and P010 with separate "
                                    "Y and UV pointers is not covered%s");

@@ -144,6 +144,64 @@ def float_plane_strides(shape, strides, dtype, order="rgb", range="unit"):
     return dict(layout, sample=sample, range=_float_range(range))
 
 
+FLOAT_PIXEL_LAYOUT_FIELDS = ("row_pitch", "frame_stride", "pixel_step", "order", "sample", "range")
+
+
+def _pixel_order(order):
+    if order not in _ffi.PIXEL_ORDERS:
+        raise ValueError(f"unknown pixel order {order!r}: \"rgb\" or \"bgr\" (samples 0, 1, 2 of a pixel)")
+    return _ffi.PIXEL_ORDERS[order]
+
+
+def float_pixel_layout_preset(width, height, pixel_samples, dtype, order="rgb", range="unit"):
+    """The tightly packed float pixel layout of a width x height frame of pixel_samples (3 or 4) float samples per pixel as a dict
+    of FLOAT_PIXEL_LAYOUT_FIELDS (bytes, and the ORDER_* / SAMPLE_* / RANGE_* codes), as Mpeg1Encoder.set_float_pixel_layout takes
+    it (include/mpeg1_hip.h, m1v_float_pixel_layout_preset, whose values these are).  dtype: "float16", "bfloat16", "float32" or the
+    torch dtype; order: "rgb" or "bgr" = samples 0, 1, 2 of a pixel (a 4th is skipped); range: "unit" or "byte".  Pure."""
+    W, H, samples = int(width), int(height), int(pixel_samples)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if samples not in (3, 4):
+        raise ValueError("a pixel has 3 or 4 samples")
+    sample = _float_sample(dtype)
+    step = samples * _ffi.FLOAT_SAMPLE_BYTES[sample]
+    return dict(row_pitch=W * step, frame_stride=H * W * step, pixel_step=step, order=_pixel_order(order), sample=sample,
+                range=_float_range(range))
+
+
+def float_pixel_strides(shape, strides, dtype, dims="nhwc", order="rgb", range="unit"):
+    """The float pixel layout (a dict of FLOAT_PIXEL_LAYOUT_FIELDS, as Mpeg1Encoder.set_float_pixel_layout takes it) of a 4-D float
+    array with the given strides in elements, as torch gives them.  dims="nhwc": an [n, H, W, C] array — a packed tensor of 3 or 4
+    samples per pixel, a window x[:, y0:y0+H, x0:x0+W, :3] of a larger one; dims="nchw": an [n, C, H, W] array with channels-last
+    strides (torch.channels_last).  dtype, order and range as in float_pixel_layout_preset.  Raises ValueError for what the layout
+    does not describe: fewer than 3 channels, a channel stride other than 1, a pixel stride other than 3 or 4 elements or below
+    C, a row pitch below W pixels, negative strides.  Pure: no torch."""
+    if len(shape) != 4 or len(strides) != 4:
+        raise ValueError("frames must be 4-D: [n, H, W, C], or [n, C, H, W] with channels-last strides")
+    if dims == "nhwc":
+        (n, H, W, C), (frame, row, pixel, channel) = (int(x) for x in shape), (int(x) for x in strides)
+    elif dims == "nchw":
+        (n, C, H, W), (frame, channel, row, pixel) = (int(x) for x in shape), (int(x) for x in strides)
+    else:
+        raise ValueError(f"unknown dims {dims!r}: \"nhwc\" or \"nchw\"")
+    sample = _float_sample(dtype)
+    S = _ffi.FLOAT_SAMPLE_BYTES[sample]
+    if C < 3:
+        raise ValueError(f"a pixel needs 3 colour samples, not {C}")
+    if channel != 1:
+        raise ValueError(f"the samples of a pixel must be adjacent (channel stride {channel}): planar frames go through float_plane_strides")
+    if pixel not in (3, 4) or pixel < C:
+        raise ValueError(f"pixels must lie 3 or 4 samples apart and hold their {C} channels (pixel stride {pixel})")
+    if row < W * pixel:
+        raise ValueError(f"row pitch {row} below W * pixel stride = {W * pixel}")
+    if frame < 0:
+        raise ValueError("negative strides")
+    if n <= 1:  # (a single frame's stride is arbitrary)
+        frame = (H - 1) * row + W * pixel
+    return dict(row_pitch=row * S, frame_stride=frame * S, pixel_step=pixel * S, order=_pixel_order(order), sample=sample,
+                range=_float_range(range))
+
+
 def distortion_to_psnr(d, blocks):
     """The distortion d of a frame of `blocks` blocks (Mpeg1Encoder.blocks_per_frame = strips * mb_rows * 6) as a PSNR in dB:
     10 * log10(255^2 * 64 * blocks / d), the coefficient-domain squared error read as a pixel-domain one (the FDCT is scaled like
@@ -240,7 +298,8 @@ class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
     Input: packed uint8 frames by default; the set_*_layout methods put surfaces, YCbCr planes, planes of R, G and B bytes, or
-    planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32) in their place.
+    planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32), or float R, G, B pixels
+    (set_float_pixel_layout: channels-last tensors) in their place.
 
     mode: "strict" = the 96x144 region the unmodified reference encodes (encoder.h:238,248),
           "full"   = every macroblock (the reference with its loop bounds restored).
@@ -279,7 +338,8 @@ class Mpeg1Encoder:
         """rgb: uint8 CUDA tensor [n, H, W, C], contiguous — or, after set_input_layout, a view with that layout's strides, such
         as surface[:, y0:y0+H, x0:x0+W, :]; or, after set_plane_layout, [n, L] YCbCr planes; or, after set_rgb_plane_layout,
         [n, C, H, W] planes of R, G and B; or, after set_float_plane_layout, a float16, bfloat16 or float32 tensor [n, C, H, W] of
-        the layout's dtype (a uint8 tensor is then refused, as a float tensor is under every other layout); or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
+        the layout's dtype (a uint8 tensor is then refused, as a float tensor is under every other layout); or, after set_float_pixel_layout, a float tensor [n, H, W, C] or a
+        channels-last [n, C, H, W] of the layout's dtype; or, after set_frame_table, what frames() returns or an int64 CUDA tensor [n] of frame
         addresses; or, after set_plane_table, what plane_frames() returns or an int64 CUDA tensor [n, 3] of plane addresses
         (this holds for every method that takes rgb).  Asynchronous on torch's current stream.
         quality: None (the encoder's quality factor) or one quality per frame, 1 <= q <= quality_factor (a sequence or a
@@ -307,7 +367,7 @@ class Mpeg1Encoder:
         """What _check_input holds tensors against: (the property that describes the input layout in force, its value), asked of
         the library in the order in which its getters cannot fail.  sample_layout also holds a plane layout (y_step 1);
         input_layout is never None: all zeros = packed frames."""
-        kinds = ("float_plane_layout", "rgb_plane_layout", "sample_layout", "input_layout")
+        kinds = ("float_pixel_layout", "float_plane_layout", "rgb_plane_layout", "sample_layout", "input_layout")
         self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
         self._table_on = self.frame_table   # (every successful layout setter turns the tables off)
         self._planes_on = self.plane_table
@@ -327,6 +387,32 @@ class Mpeg1Encoder:
             return
         assert not isinstance(rgb, FrameTable), "a FrameTable needs set_frame_table()"
         kind, want = self._input
+        if kind == "float_pixel_layout":  # [n, H, W, C], or [n, C, H, W] with channels-last strides, of the layout's dtype
+            dtype = {_ffi.SAMPLE_F16: torch.float16, _ffi.SAMPLE_BF16: torch.bfloat16, _ffi.SAMPLE_F32: torch.float32}[want["sample"]]
+            S = _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
+            assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
+                f"the float pixel layout in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+            assert rgb.is_cuda and rgb.dim() == 4, "float pixel frames must be a CUDA tensor [n, H, W, C] or a channels-last [n, C, H, W]"
+            size = (self.height, self.width)
+            if tuple(rgb.shape[1:3]) == size and rgb.shape[3] in (3, 4):
+                frame, row, pixel, channel = rgb.stride()
+                C_ = rgb.shape[3]
+            else:
+                assert tuple(rgb.shape[2:]) == size and rgb.shape[1] in (3, 4), \
+                    "frames must be [n, H, W, C] or a channels-last [n, C, H, W] with C = 3 or 4"
+                frame, channel, row, pixel = rgb.stride()
+                C_ = rgb.shape[1]
+            assert channel == 1, \
+                f"strides {tuple(rgb.stride())}: the samples of a pixel must be adjacent (planar NCHW frames: set_float_plane_layout)"
+            assert pixel * S == want["pixel_step"] and pixel >= C_ and row * S == want["row_pitch"], \
+                f"strides {tuple(rgb.stride())} are not the float pixel layout in force (pixel step {want['pixel_step']}, row pitch {want['row_pitch']} bytes)"
+            assert rgb.shape[0] <= 1 or frame * S == want["frame_stride"], \
+                f"frames must lie {want['frame_stride']} bytes apart (stride {frame} elements)"
+            # every whole pixel of the read contract lies in the storage (a window's last pixel may lack its 4th sample)
+            last = rgb.storage_offset() + max(rgb.shape[0] - 1, 0) * frame + (self.height - 1) * row + self.width * pixel
+            assert rgb.shape[0] == 0 or last * S <= rgb.untyped_storage().nbytes(), \
+                "the tensor's storage ends inside the last pixel the encoder reads (a 4th sample beyond the view)"
+            return
         if kind == "float_plane_layout":  # [n, C, H, W] of the layout's dtype: strides in elements, times S = the layout's bytes
             dtype = {_ffi.SAMPLE_F16: torch.float16, _ffi.SAMPLE_BF16: torch.bfloat16, _ffi.SAMPLE_F32: torch.float32}[want["sample"]]
             S = _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
@@ -343,7 +429,7 @@ class Mpeg1Encoder:
                 f"the plane offsets in force are not channels of this tensor (plane stride {plane} bytes)"
             return
         assert not (isinstance(rgb, torch.Tensor) and rgb.dtype.is_floating_point), \
-            f"the layout in force takes torch.uint8 tensors, not {rgb.dtype} (float planes: set_float_plane_layout)"
+            f"the layout in force takes torch.uint8 tensors, not {rgb.dtype} (float planes: set_float_plane_layout; float pixels: set_float_pixel_layout)"
         if kind == "rgb_plane_layout":  # [n, C, H, W]: channel k of the tensor = the plane at offset k * stride(1)
             assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4, "RGB plane frames must be a CUDA uint8 tensor [n, C, H, W]"
             assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
@@ -456,6 +542,37 @@ class Mpeg1Encoder:
         _call("m1v_float_planes_to_bytes_device", self._h, _ptr(x), n, _ptr(out), _stream())
         return out
 
+    def set_float_pixel_layout(self, layout):
+        """Frames as float R, G and B samples interleaved per pixel on the device — [n, H, W, 3] or [n, H, W, 4] tensors of float16,
+        bfloat16 or float32, torch.channels_last model outputs, RGBA16F / RGBA32F targets — encoded where they lie, without a
+        conversion to uint8 or a permute and copy to planes in front (include/mpeg1_hip.h, m1v_set_float_pixel_layout; the byte of
+        a sample is the float plane layout's; 3-channel encoders, even widths).  layout: a dict of FLOAT_PIXEL_LAYOUT_FIELDS
+        (float_pixel_layout_preset, or float_pixel_strides from a tensor's shape and strides), or None = back to the default
+        layout and its kernels.  Every call then takes CUDA tensors of exactly that dtype with those strides, as [n, H, W, C] or as
+        a channels-last-strided [n, C, H, W]; a window x[:, y0:y0+H, x0:x0+W, :3] goes in as it is; uint8 and NCHW-contiguous
+        tensors are refused.  Frame and plane tables do not serve it.  A reconfiguration: call it between batches."""
+        c = None
+        if layout is not None:
+            if set(layout) != set(FLOAT_PIXEL_LAYOUT_FIELDS):
+                raise ValueError(f"a float pixel layout has the fields {FLOAT_PIXEL_LAYOUT_FIELDS}")
+            c = C.byref(_ffi.FloatPixelLayout(**{k: int(v) for k, v in layout.items()}))
+        _call("m1v_set_float_pixel_layout", self._h, c)
+        self._refresh_input()
+
+    def float_pixels_to_bytes(self, x, out=None):
+        """The bytes the encoder codes for the float tensor x under the float pixel layout in force (include/mpeg1_hip.h,
+        m1v_float_pixels_to_bytes_device: the kernels' own conversion function): a uint8 CUDA tensor [n, H, W, 3] in R, G, B
+        order, what the default packed layout takes.  Asynchronous on torch's current stream."""
+        import torch
+        assert self._input[0] == "float_pixel_layout", "float_pixels_to_bytes() needs a float pixel layout in force (set_float_pixel_layout)"
+        self._check_input(x)
+        n = x.shape[0]
+        if out is None:
+            out = torch.empty((n, self.height, self.width, 3), dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, self.height, self.width, 3)
+        _call("m1v_float_pixels_to_bytes_device", self._h, _ptr(x), n, _ptr(out), _stream())
+        return out
+
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
         method takes, in the place of `rgb`, what frames() returns or a contiguous CUDA int64 tensor [n] of the frames' base
@@ -492,6 +609,7 @@ class Mpeg1Encoder:
         planes = [tuple(f) for f in planes]
         assert planes and all(len(f) == 3 for f in planes), "plane_frames() needs at least one frame of three planes"
         kind, want = self._input
+        assert kind != "float_pixel_layout", "a plane table does not serve a float pixel layout (set_float_pixel_layout)"
         assert kind in ("rgb_plane_layout", "sample_layout") and want.get("y_step", 1) == 1, \
             "a plane table needs a plane layout or an RGB plane layout in force"
         xe, ye = self.strips * 16, self.mb_rows * 16
@@ -530,6 +648,7 @@ class Mpeg1Encoder:
         import torch
         tensors = list(tensors)
         assert tensors, "frames() needs at least one frame"
+        assert self._input[0] != "float_pixel_layout", "a frame table does not serve a float pixel layout (set_float_pixel_layout)"
         assert self._input != ("input_layout", (0, 0, "rgb")), "a frame table needs a layout: set_input_layout(width * channels) for packed frames"
         on, self._table_on = self._table_on, False
         try:
@@ -548,6 +667,11 @@ class Mpeg1Encoder:
         if rc < 0:
             raise EncoderError(rc, name)
         return c.as_dict() if rc == 1 else None
+
+    @property
+    def float_pixel_layout(self):
+        """The float pixel layout in force as a dict of FLOAT_PIXEL_LAYOUT_FIELDS (bytes; order, sample and range codes), or None."""
+        return self._in_force("m1v_float_pixel_layout_in_force", _ffi.FloatPixelLayout)
 
     @property
     def float_plane_layout(self):

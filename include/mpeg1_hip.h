@@ -603,8 +603,8 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *enc, m1v_rgb_plane_layout *
  * Read contract: of frame f only bytes of the three ranges [F + c_offset, F + c_offset + (height - 1) * row_pitch + width * S) are
  * read, and of those only addressed samples: every load of the kernels is 8 addressed samples of one row.  Row padding, a fourth
  * plane, gaps between frames and whatever lies in front of and behind the batch are never read.
- * Not covered: float frames behind a frame table and float planes behind a plane table; channels-last float tensors; float
- * YCbCr; value ranges other than the two named; the host-buffer entry points. */
+ * Not covered: float frames behind a frame table and float planes behind a plane table; float
+ * YCbCr (channels-last float tensors: the float pixel layout below); value ranges other than the two named; the host-buffer entry points. */
 typedef struct m1v_float_plane_layout {
     uint64_t r_offset, g_offset, b_offset; /* bytes from the frame's base to pixel (0,0) of each plane; multiples of S       */
     uint64_t row_pitch;                    /* bytes between picture rows, the same in the three planes; >= width * S         */
@@ -618,6 +618,68 @@ int m1v_float_plane_layout_preset(int width, int height, int order, int sample, 
 int m1v_set_float_plane_layout(m1v_encoder *enc, const m1v_float_plane_layout *layout);
 int m1v_float_plane_layout_in_force(const m1v_encoder *enc, m1v_float_plane_layout *out);
 int m1v_float_planes_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
+
+/* Float pixel layout: frames whose R, G and B samples are floating-point numbers interleaved per pixel on the device — a PyTorch
+ * tensor [n, H, W, 3] or [n, H, W, 4] of float16, bfloat16 or float32, a torch.channels_last model output (NCHW-shaped with NHWC
+ * strides), a renderer's RGBA16F or RGBA32F target, a window of one — encoded where they lie: no conversion to uint8 and no
+ * permute-and-copy to planes in front of the encoder.  For encoders created with channels = 3: the pixel's sample count (3 or 4)
+ * is the layout's, not the encoder's.
+ *
+ * Definition.  Samples are of one type, S bytes each (S = 2 for fp16 and bf16, S = 4 for fp32).  d_rgb points at sample 0 of
+ * pixel (0, 0) of frame 0, as for a surface.  Frame f starts at F = d_rgb + f * frame_stride, and sample i (0, 1 or 2) of pixel
+ * (x, y) is the S bytes at
+ *     F + y * row_pitch + x * pixel_step + i * S
+ * (all quantities in bytes).  order says whether samples 0, 1, 2 are R, G, B (M1V_ORDER_RGB) or B, G, R (M1V_ORDER_BGR); with
+ * pixel_step = 4 * S a 4th sample follows them and is skipped.  The byte of a sample is that of the float plane layout above
+ * ("Float plane layout", Definition: f, t, r, byte), unchanged and computed by the same device function.  The record of a frame is
+ * the packed calls' record for the interleaved picture [y][x] = (R, G, B) of those bytes: the same colour arithmetic, chroma quirk,
+ * headers, first_frame_index, per-frame quality, sizes and status bits.
+ *
+ *   m1v_float_pixel_layout_preset(width, height, pixel_samples, order, sample, range, &layout)   pure host arithmetic: tightly
+ *     packed pixels of pixel_samples (3 or 4) samples, pixel_step = pixel_samples * S, row_pitch = width * pixel_step,
+ *     frame_stride = height * row_pitch.  M1V_E_ARG (out untouched): a null out, width or height <= 0, pixel_samples other than
+ *     3 or 4, an unknown order, sample or range.
+ *   m1v_set_float_pixel_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like the other layout setters:
+ *     it replaces whichever layout is in force, turns tables off, allocates first and swaps on success, and a failed call leaves
+ *     the layout and the table mode as they were.  The encoder takes the tile plan behind k_float_pixels_encode,
+ *     k_float_pixels_size_table and k_float_pixels_rd_table.  While it is in force m1v_input_layout, m1v_plane_layout_in_force and
+ *     m1v_sample_layout_in_force return M1V_E_ARG ("ask m1v_float_pixel_layout_in_force"); m1v_rgb_plane_layout_in_force and
+ *     m1v_float_plane_layout_in_force return 0.
+ *     M1V_E_ARG with a message that names the reason, before anything is launched or reallocated: a null encoder; channels != 3;
+ *     an odd width; an unknown order, sample or range; a pixel_step other than 3 * S or 4 * S (pixel_step == S: the message names
+ *     m1v_set_float_plane_layout); a row_pitch or frame_stride that is not a multiple of S; row_pitch < width * pixel_step;
+ *     (height - 1) * row_pitch + width * pixel_step >= 2^32 (offsets inside a frame are 32-bit); frame_stride below
+ *     (height - 1) * row_pitch + width * pixel_step; an encoder that a hook has forced to the run kernels (those hooks return
+ *     M1V_E_ARG on an encoder with this layout).
+ *     Served: every call that serves the float plane layout — m1v_encode_device, m1v_encode_quality_device,
+ *     m1v_frame_sizes_device, m1v_frame_size_table_device, m1v_frame_rd_table_device, the budget, rd, batch-budget and bitrate
+ *     encodes by size and by distortion, pipelined mode, m1v_delivery_step with its scratch retry, the m1v_profile_* counters and
+ *     m1v_debug_set_lds_words.  Each returns M1V_E_ARG in front of every launch when d_rgb is not a multiple of S.  The packed-only
+ *     calls refuse it as they refuse every other layout.  m1v_set_frame_table and m1v_set_plane_table return M1V_E_ARG while it is
+ *     in force.
+ *   m1v_float_pixel_layout_in_force(enc, &layout)   1 = a float pixel layout is in force (layout filled; may be NULL), 0 = another
+ *     layout or none, < 0 = error.
+ *   m1v_float_pixels_to_bytes_device(enc, d_frames, n_frames, d_bytes, stream)   the bytes the encoder codes for these samples, by
+ *     the same device function: d_bytes is uint8 [n_frames][height][width][3] in R, G, B order, tightly packed — exactly what the
+ *     default packed layout encodes.  Needs this layout in force (M1V_E_ARG otherwise, and for null pointers, n_frames < 0 and a
+ *     misaligned d_frames); asynchronous on `stream`.
+ * Read contract: of frame f only bytes of the rows [F + y * row_pitch, F + y * row_pitch + width * pixel_step), y in 0 ...
+ * height - 1, are read.  A 4th sample inside a pixel may be read and never influences the output.  Row padding, gaps between
+ * frames and whatever lies in front of and behind the batch are never read (the proof, per wave, heads csrc/m1v_float_pixels.h).
+ * Not covered: float pixels behind a frame table or a plane table; pixels whose colour samples do not start at sample 0 (ARGB,
+ * ABGR); float YCbCr; value ranges other than the two named; the host-buffer entry points. */
+typedef struct m1v_float_pixel_layout {
+    uint64_t row_pitch;     /* bytes between picture rows; multiple of S; >= width * pixel_step */
+    uint64_t frame_stride;  /* bytes between frames; multiple of S; >= (height - 1) * row_pitch + width * pixel_step */
+    uint64_t pixel_step;    /* bytes between neighbouring pixels of a row: 3 * S or 4 * S */
+    int32_t order;          /* M1V_ORDER_RGB or M1V_ORDER_BGR: samples 0, 1, 2 of a pixel; a 4th sample is skipped */
+    int32_t sample;         /* M1V_SAMPLE_F16 / _BF16 / _F32 (S = 2, 2, 4) */
+    int32_t range;          /* M1V_RANGE_UNIT / _BYTE */
+} m1v_float_pixel_layout;
+int m1v_float_pixel_layout_preset(int width, int height, int pixel_samples /* 3 or 4 */, int order, int sample, int range, m1v_float_pixel_layout *out);
+int m1v_set_float_pixel_layout(m1v_encoder *enc, const m1v_float_pixel_layout *layout);   /* NULL = the default layout */
+int m1v_float_pixel_layout_in_force(const m1v_encoder *enc, m1v_float_pixel_layout *out); /* 1 / 0 / < 0 */
+int m1v_float_pixels_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
 
 /* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
  * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
