@@ -8,4 +8,4 @@ from .encoder import (EncoderError, FrameTable, Mpeg1Encoder, distortion_to_psnr
                       float_plane_layout_preset,
                       float_plane_strides, mpeg_encode_procedure,
                       plane_layout_preset, psnr_to_distortion, rgb_plane_layout_preset, rgb_plane_strides, sample_layout_preset,
-                      set_image_loader, surface_strides)
+                      set_image_loader, surface_strides, StreamSpans, stream_spans)

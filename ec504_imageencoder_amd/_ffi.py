@@ -70,6 +70,21 @@ class FloatPixelLayout(_Layout):
 
 PIXEL_ORDERS = {"rgb": ORDER_RGB, "bgr": ORDER_BGR}
 
+STATUS_STREAMS = 64
+MAX_STREAMS = 4096
+STREAMS_LARGEST_THAT_FITS, STREAMS_LEAST_DISTORTION = 0, 1
+STREAMS_RULES = {"size": STREAMS_LARGEST_THAT_FITS, "distortion": STREAMS_LEAST_DISTORTION}
+
+
+class StreamSpan(C.Structure):
+    """m1v_stream_span (include/mpeg1_hip.h): the frames of one stream in a batch.  The array the calls take lives on the device."""
+    _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("first_frame_index", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class StreamRate(C.Structure):
+    """m1v_stream_rate (include/mpeg1_hip.h): the refill per frame and the buffer of one stream's leaky bucket, in bytes."""
+    _fields_ = [("bytes_per_frame", C.c_uint64), ("buffer_bytes", C.c_uint64)]
+
 _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
@@ -80,6 +95,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_frame_size_table_device", "m1v_encode_batch_budget_device", "m1v_encode_cbr_device",
     "m1v_frame_rd_table_device", "m1v_encode_rd_device",
     "m1v_encode_rd_batch_device", "m1v_encode_rd_cbr_device", "m1v_rd_batch_pick_device", "m1v_rd_cbr_pick_device",
+    "m1v_encode_streams_device", "m1v_encode_streams_cbr_device", "m1v_streams_cbr_pick_device",
     "m1v_set_pipelined", "m1v_flush", "m1v_alloc_host", "m1v_free_host", "m1v_alloc_device", "m1v_free_device",
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
@@ -163,6 +179,14 @@ def lib():
     L.m1v_rd_batch_pick_device.restype = C.c_int
     L.m1v_rd_cbr_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp]
     L.m1v_rd_cbr_pick_device.restype = C.c_int
+    L.m1v_encode_streams_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.m1v_encode_streams_device.restype = C.c_int
+    L.m1v_encode_streams_cbr_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, _u8p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp,
+                                                vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.m1v_encode_streams_cbr_device.restype = C.c_int
+    L.m1v_streams_cbr_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp,
+                                              vp, vp, vp, vp, vp, vp]
+    L.m1v_streams_cbr_pick_device.restype = C.c_int
     L.m1v_set_pipelined.argtypes = [vp, C.c_int]
     L.m1v_set_pipelined.restype = C.c_int
     L.m1v_flush.argtypes = [vp, vp]

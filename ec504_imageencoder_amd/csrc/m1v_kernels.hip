@@ -1544,6 +1544,7 @@ __global__ __launch_bounds__(kPickThreads) void k_rate_pick(PickArgs a) {
 }
 
 #include "m1v_rd_rate.h"
+#include "m1v_streams.h"
 
 // The probe's place of k_assemble (one workgroup per frame): each record's size (its strips' bytes + 48 bytes of headers and
 // trailer, what k_assemble derives) and the status word, and the same counter hand-over — the set the next call adds into is
@@ -1842,6 +1843,7 @@ struct m1v_encoder {
         unsigned long long *frame_bytes = nullptr; // [frame] bytes of the frame's strips
         uint32_t *words = nullptr;                 // [0] status bits of the encode kernel, [1] sink for callers without a status word, [2] arena counter
         int dirty_frames = 0;                      // frames of the set's last batch that nobody has cleared yet
+        int32_t *frame_index = nullptr;            // [max_frames] a streams batch: each frame's index in its stream (k_streams_map)
     };
     // Everything one batch owns between its encode kernel and the end of its assembly.  Two sets, so that in
     // pipelined mode batch k+1 can encode while batch k is still being assembled.
@@ -2255,10 +2257,15 @@ static int hand_over(Args &a, m1v_encoder::Counters &cur, m1v_encoder::Counters 
 
 // What writes the per-frame selection (e->d_qsel) of a batch that is not encoded at the encoder's own quality: launch() queues,
 // on st, whatever does (k_frame_quality; k_rd_pick; k_rd_batch_pick, then k_frame_quality: m1v_runtime.h) with `args`, the
-// batch's status word and n_frames.  One step per batch: a batch cannot be given two.
+// batch's counter set (its words[0] is the batch's status word) and n_frames.  One step per batch: a batch cannot be given two.
+// own_quality: the step leaves the selection alone and the batch is encoded at the encoder's own quality.  finish (may be null)
+// queues what the step needs behind k_assemble, on the stream k_assemble runs on (a streams batch: k_streams_finish).
+struct EncodeOut;
 struct Selection {
-    int (*launch)(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st);
+    int (*launch)(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st);
     void *args;
+    bool own_quality = false;
+    int (*finish)(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, const EncodeOut &o, int n_frames, hipStream_t gs) = nullptr;
 };
 
 // Where a batch's results go (the last five arguments of m1v_encode_device).  A probe writes frame_sizes and status only.
@@ -2310,8 +2317,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     PoisonOnReturn poison{&bt.poisoned};
     if (fail_encode_at(1) != M1V_OK) return M1V_E_HIP;
     if (sel)
-        if (const int rc = sel->launch(e, sel->args, cur.words, n_frames, st)) return rc;
-    const uint32_t *qsel = sel ? e->d_qsel : e->d_qsel_own;
+        if (const int rc = sel->launch(e, sel->args, cur, n_frames, st)) return rc;
+    const uint32_t *qsel = sel && !sel->own_quality ? e->d_qsel : e->d_qsel_own;
     // the plan's producer kernel over n_frames
     const size_t grid = (size_t)n_frames * p.units;
     int rc;
@@ -2434,6 +2441,8 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
         else
             hipLaunchKernelGGL(k_assemble<false>, grid, dim3(kAsmThreads), lds, gs, ga);
         HIP_TRY(hipGetLastError());
+        if (sel && sel->finish)
+            if (const int rc = sel->finish(e, sel->args, cur, o, n_frames, gs)) return rc;
     }
     if (fail_encode_at(3) != M1V_OK) return M1V_E_HIP;
     if (e->pipelined) {

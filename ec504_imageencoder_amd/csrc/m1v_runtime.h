@@ -3,7 +3,8 @@
 // quality, size-table and rate entry points, delivery, the host path, profiling and the debug hooks.  The calls that take
 // candidates share one argument check (check_candidate_call, the pick-only calls included), one table step (own_table, into the
 // encoder's own buffers), one description of the table a pick reads (PickTable, the encoder's own or the caller's) and one launch
-// site per pick kernel; what writes a batch's per-frame selection reaches encode_batch as a Selection (the select_by_* steps).
+// site per pick kernel; what writes a batch's per-frame selection reaches encode_batch as a Selection (the select_by_* steps; a
+// batch of many streams, m1v_streams.h, is one too: select_streams in front of the encode kernel, finish_streams behind k_assemble).
 // Geometry (CodedRegion, TileGrid, wave_region), the kernel registry (kKernels) and the hook predicates of m1v_encoder come from
 // m1v_kernels.hip.  Not standalone: included once, at the end of m1v_kernels.hip.
 
@@ -130,17 +131,20 @@ static hipError_t counters_clear(const m1v_encoder *e, m1v_encoder::Counters &c,
     hipError_t err = hipMemsetAsync(c.strip_ctr, 0, (size_t)e->max_frames * e->g.n_strips * 8, st);
     if (err == hipSuccess) err = hipMemsetAsync(c.frame_bytes, 0, (size_t)e->max_frames * 8, st);
     if (err == hipSuccess) err = hipMemsetAsync(c.words, 0, 4 * sizeof(uint32_t), st);
-    return err;
+    return err; // (frame_index holds no count: every streams batch writes what it reads)
 }
 static bool counters_alloc(const m1v_encoder *e, m1v_encoder::Counters &c) {
     return plan_malloc(&c.strip_ctr, (size_t)e->max_frames * e->g.n_strips * 8) == hipSuccess &&
            plan_malloc(&c.frame_bytes, (size_t)e->max_frames * 8) == hipSuccess && plan_malloc(&c.words, 4 * sizeof(uint32_t)) == hipSuccess &&
+           plan_malloc(&c.frame_index, (size_t)e->max_frames * sizeof(int32_t)) == hipSuccess &&
+           hipMemsetAsync(c.frame_index, 0, (size_t)e->max_frames * sizeof(int32_t), nullptr) == hipSuccess &&
            counters_clear(e, c, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
 }
 static void counters_free(m1v_encoder::Counters &c) {
     (void)hipFree(c.strip_ctr);
     (void)hipFree(c.frame_bytes);
     (void)hipFree(c.words);
+    (void)hipFree(c.frame_index);
 }
 
 // The size table's counters: the same three and the rd table's distortion sums (allocated by m1v_create, so not through plan_malloc)
@@ -1033,7 +1037,8 @@ int m1v_profile_read_times(m1v_encoder *e, float *ms, int cap, int *launches) {
 }
 
 // ---- what writes a batch's per-frame selection (the steps a Selection of encode_batch names) ------------------------------------
-static int select_by_quality(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+static int select_by_quality(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
+    uint32_t *const batch_status = cur.words;
     QualityArgs &qa = *static_cast<QualityArgs *>(args);
     qa.max_q = encoder_quality(e);
     qa.n_frames = n_frames;
@@ -1044,7 +1049,8 @@ static int select_by_quality(m1v_encoder *e, void *args, uint32_t *batch_status,
     return M1V_OK;
 }
 
-static int select_by_rd(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+static int select_by_rd(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
+    uint32_t *const batch_status = cur.words;
     RdPickArgs &ra = *static_cast<RdPickArgs *>(args);
     ra.n_frames = n_frames;
     ra.qsel = e->d_qsel;
@@ -1064,13 +1070,13 @@ static int launch_rd_batch_pick(RdBatchArgs &ba, uint32_t *batch_status, hipStre
 }
 
 // The batch pick (here, where the batch's status word is known), then k_frame_quality on the qualities and status word it wrote
-static int select_by_rd_batch(m1v_encoder *e, void *args, uint32_t *batch_status, int n_frames, hipStream_t st) {
+static int select_by_rd_batch(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
     RdBatchArgs &ba = *static_cast<RdBatchArgs *>(args);
-    if (const int rc = launch_rd_batch_pick(ba, batch_status, st)) return rc;
+    if (const int rc = launch_rd_batch_pick(ba, cur.words, st)) return rc;
     QualityArgs qa = {};
     qa.quality = ba.chosen;
     qa.pick_status = ba.status;
-    return select_by_quality(e, &qa, batch_status, n_frames, st);
+    return select_by_quality(e, &qa, cur, n_frames, st);
 }
 
 // A batch at one quality per frame (null: the encoder's own), which a pick may have written with its status word (pick_status,
@@ -1384,6 +1390,170 @@ int m1v_rd_cbr_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64
     out.pick_dist = (unsigned long long *)d_pick_distortion;
     out.status = d_status;
     return launch_rd_cbr_pick(t, n_frames, bytes_per_frame, buffer_bytes, d_level_in, d_level_out, out, (hipStream_t)stream);
+}
+
+// ---- batches of many streams (m1v_streams.h) ----------------------------------------------------------------------------------
+} // extern "C"
+
+static int check_spans(const m1v_stream_span *d_spans, int n_streams) {
+    if (!d_spans) return fail(M1V_E_ARG, "null spans%s");
+    if (n_streams < 1 || n_streams > M1V_MAX_STREAMS) return fail(M1V_E_ARG, "n_streams must be 1 .. M1V_MAX_STREAMS%s");
+    if ((uintptr_t)d_spans & 3) return fail(M1V_E_ARG, "the spans must be 4-byte aligned%s");
+    return M1V_OK;
+}
+
+static int check_streams_rule(int rule) {
+    return rule == M1V_STREAMS_LARGEST_THAT_FITS || rule == M1V_STREAMS_LEAST_DISTORTION ? M1V_OK : fail(M1V_E_ARG, "unknown streams rule%s");
+}
+
+// k_streams_bitrate over a table (an empty batch too: it writes the levels).  ra comes with its outputs, spans and rates set; its
+// status word is cleared here, in front of the launch.
+static int launch_streams_bitrate(const PickTable &t, int n_frames, int rule, StreamsRateArgs ra, hipStream_t st) {
+    ra.sizes = t.sizes; ra.dist = t.dist; ra.stride = t.stride; ra.n_cand = t.n_cand; ra.cand = t.cand; ra.table_status = t.status; // the table
+    ra.n_frames = n_frames;
+    HIP_TRY(hipMemsetAsync(ra.status, 0, 4, st));
+    const dim3 grid((unsigned)((ra.n_streams + kStreamsWaves - 1) / kStreamsWaves)), block(kStreamsWaves * kWave);
+    if (rule == M1V_STREAMS_LEAST_DISTORTION)
+        hipLaunchKernelGGL(k_streams_bitrate<M1V_STREAMS_LEAST_DISTORTION>, grid, block, 0, st, ra);
+    else
+        hipLaunchKernelGGL(k_streams_bitrate<M1V_STREAMS_LARGEST_THAT_FITS>, grid, block, 0, st, ra);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+// What a streams batch hands its Selection: the spans; the per-frame qualities, if any, and what wrote them (`bitrate` with `table`
+// and `rule`: k_streams_bitrate, launched by the step, where the batch's status word is known); where the spans' bytes go.
+struct StreamsStep {
+    const m1v_stream_span *spans;
+    int n_streams;
+    QualityArgs qa;          // qa.quality null: the encoder's own quality
+    bool bitrate;
+    PickTable table;
+    int rule;
+    StreamsRateArgs ra;
+    unsigned long long *stream_bytes;
+};
+
+static int select_streams(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
+    StreamsStep &s = *static_cast<StreamsStep *>(args);
+    const StreamsMapArgs ma = {s.spans, s.n_streams, n_frames, cur.frame_index, cur.words};
+    hipLaunchKernelGGL(k_streams_map, dim3((unsigned)((s.n_streams + 255) / 256)), dim3(256), 0, st, ma);
+    HIP_TRY(hipGetLastError());
+    if (s.bitrate) {
+        s.ra.batch_status = cur.words;
+        if (const int rc = launch_streams_bitrate(s.table, n_frames, s.rule, s.ra, st)) return rc;
+    }
+    return s.qa.quality ? select_by_quality(e, &s.qa, cur, n_frames, st) : M1V_OK;
+}
+
+static int finish_streams(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, const EncodeOut &o, int n_frames, hipStream_t gs) {
+    const StreamsStep &s = *static_cast<StreamsStep *>(args);
+    const int header_blocks = (n_frames + kStreamsFinishThreads - 1) / kStreamsFinishThreads;
+    const int span_blocks = s.stream_bytes ? (s.n_streams + kStreamsFinishThreads / kWave - 1) / (kStreamsFinishThreads / kWave) : 0;
+    const StreamsFinishArgs fa = {s.spans, s.n_streams, n_frames, cur.frame_bytes, cur.frame_index, e->d_tab, o.out,
+                                  (unsigned long long)o.cap, s.stream_bytes, header_blocks};
+    hipLaunchKernelGGL(k_streams_finish, dim3((unsigned)(header_blocks + span_blocks)), dim3(kStreamsFinishThreads), 0, gs, fa);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
+// The encode of a streams batch: the step above around encode_batch (index 0 for k_assemble; k_streams_finish sets the headers)
+static int encode_streams(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, StreamsStep &s, const EncodeOut &o, void *stream) {
+    if (n_frames == 0 && s.stream_bytes) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMemsetAsync(s.stream_bytes, 0, (size_t)s.n_streams * 8, (hipStream_t)stream));
+    }
+    Selection sel = {select_streams, &s};
+    sel.own_quality = !s.qa.quality;
+    sel.finish = finish_streams;
+    return encode_batch(e, d_rgb, n_frames, 0, &sel, false, o, stream);
+}
+
+extern "C" {
+
+int m1v_encode_streams_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                              uint64_t *d_stream_bytes, uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (const int rc = check_spans(d_spans, n_streams)) return rc;
+    if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    StreamsStep s = {};
+    s.spans = d_spans;
+    s.n_streams = n_streams;
+    s.qa.quality = d_quality;
+    s.stream_bytes = (unsigned long long *)d_stream_bytes;
+    return encode_streams(e, d_rgb, n_frames, s, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
+}
+
+int m1v_encode_streams_cbr_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                                  const uint8_t *candidates, int n_candidates, int rule, uint64_t bytes_per_frame,
+                                  uint64_t buffer_bytes, const m1v_stream_rate *d_stream_rates, const int64_t *d_level_in,
+                                  int64_t *d_level_out, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                                  uint64_t *d_frame_distortion, uint64_t *d_stream_bytes, uint64_t *d_total, uint32_t *d_status,
+                                  void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (const int rc = check_spans(d_spans, n_streams)) return rc;
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out && d_level_in && d_level_out))
+        return rc;
+    if (const int rc = check_streams_rule(rule)) return rc;
+    if (((uintptr_t)d_stream_rates & 7) != 0) return fail(M1V_E_ARG, "the stream rates must be 8-byte aligned%s");
+    if (!d_stream_rates)
+        if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
+    const bool by_dist = rule == M1V_STREAMS_LEAST_DISTORTION;
+    StreamsStep s = {};
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, by_dist, stream, s.table)) return rc;
+    s.spans = d_spans;
+    s.n_streams = n_streams;
+    s.bitrate = true;
+    s.rule = rule;
+    s.ra.spans = d_spans;
+    s.ra.n_streams = n_streams;
+    s.ra.rates = d_stream_rates;
+    s.ra.rate = (long long)bytes_per_frame;
+    s.ra.capacity = (long long)buffer_bytes;
+    s.ra.level_in = (const long long *)d_level_in;
+    s.ra.level_out = (long long *)d_level_out;
+    s.ra.chosen = d_chosen ? d_chosen : e->d_chosen;
+    s.ra.pick_dist = (unsigned long long *)d_frame_distortion;
+    s.ra.status = e->d_pick_status;
+    s.qa.quality = s.ra.chosen;
+    s.qa.pick_status = s.ra.status;
+    s.stream_bytes = (unsigned long long *)d_stream_bytes;
+    if (n_frames == 0) // (an empty batch has no Selection step: the pick alone moves the levels)
+        if (const int rc = launch_streams_bitrate(s.table, 0, rule, s.ra, (hipStream_t)stream)) return rc;
+    return encode_streams(e, d_rgb, n_frames, s, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
+}
+
+int m1v_streams_cbr_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                                int n_frames, int n_candidates, const m1v_stream_span *d_spans, int n_streams, int rule,
+                                uint64_t bytes_per_frame, uint64_t buffer_bytes, const m1v_stream_rate *d_stream_rates,
+                                const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                                uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (const int rc = check_spans(d_spans, n_streams)) return rc;
+    if (const int rc = check_streams_rule(rule)) return rc;
+    const bool by_dist = rule == M1V_STREAMS_LEAST_DISTORTION;
+    if (const int rc = check_candidate_call(e, d_sizes && (d_distortion || !by_dist) && d_picks && d_status, nullptr, n_candidates, n_frames,
+                                            d_level_in && d_level_out, true))
+        return rc;
+    if (((uintptr_t)d_stream_rates & 7) != 0) return fail(M1V_E_ARG, "the stream rates must be 8-byte aligned%s");
+    if (!d_stream_rates)
+        if (const int rc = check_cbr_rate(bytes_per_frame, buffer_bytes)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const PickTable t = {(const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames, n_candidates, 0, d_table_status};
+    StreamsRateArgs ra = {};
+    ra.spans = d_spans;
+    ra.n_streams = n_streams;
+    ra.rates = d_stream_rates;
+    ra.rate = (long long)bytes_per_frame;
+    ra.capacity = (long long)buffer_bytes;
+    ra.level_in = (const long long *)d_level_in;
+    ra.level_out = (long long *)d_level_out;
+    ra.picks = d_picks;
+    ra.pick_dist = (unsigned long long *)d_pick_distortion;
+    ra.status = d_status;
+    return launch_streams_bitrate(t, n_frames, rule, ra, (hipStream_t)stream);
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

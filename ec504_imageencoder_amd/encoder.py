@@ -294,6 +294,47 @@ class FrameTable:
         return self.shape[0]
 
 
+class StreamSpans:
+    """The spans of a batch of many streams (stream_spans, Mpeg1Encoder.encode_streams): `table` is the int32 CUDA tensor [n_streams, 4]
+    of m1v_stream_span records (first_frame, n_frames, first_frame_index, 0), which the kernels read on the stream; `spans` the
+    (n_frames, first_frame_index) pairs it was made from."""
+
+    def __init__(self, table, spans):
+        self.table, self.spans = table, tuple((int(n), int(i)) for n, i in spans)
+        self.n_streams, self.n_frames = len(self.spans), sum(n for n, _ in self.spans)
+        self.device = table.device
+
+    def data_ptr(self):
+        return self.table.data_ptr()
+
+    def __len__(self):
+        return self.n_streams
+
+    def ranges(self):
+        """[(first_frame, n_frames, first_frame_index)] of every span, in batch order."""
+        out, at = [], 0
+        for n, i in self.spans:
+            out.append((at, n, i))
+            at += n
+        return out
+
+
+def stream_spans(spans, device="cuda"):
+    """The device array of spans for a batch that is the concatenation of `spans`: [(n_frames, first_frame_index), ...], one pair
+    per stream in batch order (n_frames may be 0).  Returns a StreamSpans holder with .data_ptr()."""
+    import torch
+    pairs = [(int(n), int(i)) for n, i in spans]
+    if not 1 <= len(pairs) <= _ffi.MAX_STREAMS:
+        raise EncoderError(_ffi.E_ARG, f"stream_spans: 1 to {_ffi.MAX_STREAMS} streams")
+    if any(n < 0 or not -2 ** 31 <= i < 2 ** 31 for n, i in pairs) or sum(n for n, _ in pairs) >= 2 ** 31:
+        raise EncoderError(_ffi.E_ARG, "stream_spans: n_frames >= 0 and a first_frame_index that fits int32")
+    rows, at = [], 0
+    for n, i in pairs:
+        rows.append((at, n, i, 0))
+        at += n
+    return StreamSpans(torch.tensor(rows, dtype=torch.int32).to(device), pairs)
+
+
 class Mpeg1Encoder:
     """One picture geometry + quality factor on one GPU.
 
@@ -787,6 +828,8 @@ class Mpeg1Encoder:
                 raise EncoderError(_ffi.E_UNENCODABLE, "encode: |level| >= 256 (the reference crashes on this input)")
             if status & _ffi.STATUS_QUALITY:
                 raise EncoderError(_ffi.E_ARG, f"{name}: a quality outside 1 .. quality_factor")
+            if status & _ffi.STATUS_STREAMS:
+                raise EncoderError(_ffi.E_ARG, f"{name}: spans that do not tile the batch, or a stream's rate outside 1 <= r <= C < 2^62")
             if not status & (_ffi.STATUS_NOSPACE | _ffi.STATUS_SCRATCH):
                 break
             if status & _ffi.STATUS_SCRATCH:        # more runs overflowed their compact slot than the arena holds
@@ -1007,6 +1050,147 @@ class Mpeg1Encoder:
         level.copy_(level_out.view_as(level))
         rows = sizes.cpu()
         return picks_l, self._over_level([int(rows[k, f]) for f, k in enumerate(picks_l)], start, rate, cap)
+
+    # ---- batches of many streams (include/mpeg1_hip.h, "Streams") ----------------------------------------------------------
+    @staticmethod
+    def _spans(spans, n, device):
+        """`spans` as a StreamSpans on the device: what stream_spans() made, or the pairs it takes.  They must add up to n."""
+        if not isinstance(spans, StreamSpans):
+            spans = stream_spans(spans, device)
+        assert spans.n_frames == n, f"the spans hold {spans.n_frames} frames, the batch {n}"
+        return spans
+
+    def encode_streams_device(self, rgb, spans, out=None, sizes=None, meta=None, stream_bytes=None, quality=None):
+        """encode() for a batch that is the concatenation of `spans` (what stream_spans() returns: the spans are not checked on
+        the host, the device reports STATUS_STREAMS in meta[1]).  Asynchronous on torch's current stream.  Returns
+        (out, sizes, meta, stream_bytes): encode()'s three and int64[n_streams], the bytes of each stream's records, which lie in
+        `out` back to back in batch order."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        if out is None:
+            out = torch.empty(self.default_out_capacity(n), dtype=torch.uint8, device=rgb.device)
+        if sizes is None:
+            sizes = torch.empty(max(n, 1), dtype=torch.int64, device=rgb.device)
+        if meta is None:
+            meta = torch.zeros(2, dtype=torch.int64, device=rgb.device)
+        if stream_bytes is None:
+            stream_bytes = torch.empty(len(spans), dtype=torch.int64, device=rgb.device)
+        q = self._quality_tensor(quality, n, rgb.device) if quality is not None else None
+        _call("m1v_encode_streams_device", self._h, _ptr(rgb), n, _ptr(spans), len(spans), _ptr(q), _ptr(out), out.numel(),
+              _ptr(sizes), _ptr(stream_bytes), *_meta_ptrs(meta), _stream())
+        return out, sizes, meta, stream_bytes
+
+    def encode_streams(self, rgb, spans, quality=None):
+        """Synchronous: one batch of many streams.  spans: stream_spans([(n_frames, first_frame_index), ...]) or those pairs, one
+        per stream in batch order; frame j of a span is frame first_frame_index + j of its stream, and its record is what
+        encode(..., first_frame_index=...) gives for it.  quality: as in encode().  Returns (bytes, sizes, stream_bytes): the
+        records in batch order, each record's size, and the bytes of each stream's contiguous range."""
+        import torch
+        n = rgb.shape[0]
+        spans = self._spans(spans, n, rgb.device)
+        if quality is not None:
+            quality = self._quality_tensor(quality, n, rgb.device)
+        stream_bytes = torch.zeros(len(spans), dtype=torch.int64, device=rgb.device)
+        data, sizes_l, _ = self._encode_retrying(
+            rgb, "encode_streams",
+            lambda out, sizes, meta: self.encode_streams_device(rgb, spans, out, sizes, meta, stream_bytes, quality))
+        return data, sizes_l, [int(b) for b in stream_bytes.cpu()]
+
+    @staticmethod
+    def _stream_rates(name, bytes_per_frame, buffer_bytes, n_streams, device):
+        """One rate for every stream (scalars, checked here) or one per stream (sequences, or bytes_per_frame a CUDA int64 tensor
+        [n_streams, 2] of (bytes_per_frame, buffer_bytes); checked on the device): (rate, cap, tensor or None)."""
+        import torch
+        if isinstance(bytes_per_frame, torch.Tensor):
+            assert bytes_per_frame.is_cuda and bytes_per_frame.dtype == torch.int64 and tuple(bytes_per_frame.shape) == (n_streams, 2), \
+                "rates: CUDA int64 [n_streams, 2]"
+            return 0, 0, bytes_per_frame.contiguous()
+        if isinstance(bytes_per_frame, numbers.Integral) and isinstance(buffer_bytes, numbers.Integral):
+            rate, cap = int(bytes_per_frame), int(buffer_bytes)
+            if not 1 <= rate <= cap < 2 ** 62:
+                raise EncoderError(_ffi.E_ARG, f"{name}: need 1 <= bytes_per_frame <= buffer_bytes < 2^62")
+            return rate, cap, None
+        per_stream = [[x] * n_streams if isinstance(x, numbers.Integral) else list(x) for x in (bytes_per_frame, buffer_bytes)]
+        assert all(len(x) == n_streams for x in per_stream), "rates: one per stream"
+        rates = [[int(r), int(c)] for r, c in zip(*per_stream)]
+        if any(not 0 <= x < 2 ** 63 for row in rates for x in row):
+            raise EncoderError(_ffi.E_ARG, f"{name}: rates must fit int64")
+        return 0, 0, torch.tensor(rates, dtype=torch.int64).to(device)
+
+    @staticmethod
+    def _levels(levels, n_streams):
+        import torch
+        assert isinstance(levels, torch.Tensor) and levels.is_cuda and levels.dtype == torch.int64 and levels.numel() == n_streams, \
+            "levels: CUDA int64 tensor, one element per stream"
+
+    def encode_streams_at_bitrate(self, rgb, spans, candidates, bytes_per_frame, buffer_bytes, levels, by="size"):
+        """Synchronous constant bitrate with one leaky bucket per stream (include/mpeg1_hip.h, m1v_encode_streams_cbr_device): one
+        table pass, one pick and one encode for the whole batch.  spans: as in encode_streams.  bytes_per_frame, buffer_bytes: one
+        rate for every stream, or one per stream (sequences).  levels: CUDA int64 tensor [n_streams], the bytes available to each
+        stream's next frame, advanced in place, only when the call succeeds.  by: "size" (each frame at the largest candidate
+        whose record fits its stream's level, encode_at_bitrate's pick) or "distortion" (the least distortion that fits,
+        encode_best_at_bitrate's).  Returns (bytes, sizes, chosen, stream_bytes, over_budget, distortion or None)."""
+        import torch
+        n = rgb.shape[0]
+        name = "encode_streams_at_bitrate"
+        self._check_input(rgb)
+        spans = self._spans(spans, n, rgb.device)
+        rule = _ffi.STREAMS_RULES[by]
+        rate, cap, d_rates = self._stream_rates(name, bytes_per_frame, buffer_bytes, len(spans), rgb.device)
+        self._levels(levels, len(spans))
+        level_in = levels.contiguous()
+        level_out = torch.empty_like(level_in)                               # a retry starts from the same levels
+        cand_buf = self._candidates(candidates, name)
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        with_dist = rule == _ffi.STREAMS_LEAST_DISTORTION
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device) if with_dist else None
+        stream_bytes = torch.zeros(len(spans), dtype=torch.int64, device=rgb.device)
+        data, sizes_l, status = self._encode_retrying(
+            rgb, name,
+            lambda out, sizes, meta: _call(
+                "m1v_encode_streams_cbr_device", self._h, _ptr(rgb), n, _ptr(spans), len(spans), cand_buf, len(cand_buf), rule,
+                rate, cap, _ptr(d_rates), _ptr(level_in), _ptr(level_out), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes),
+                _ptr(dist), _ptr(stream_bytes), *_meta_ptrs(meta), _stream()))
+        levels.copy_(level_out.view_as(levels))
+        return (data, sizes_l, [int(c) for c in chosen[:n].cpu()], [int(b) for b in stream_bytes.cpu()],
+                bool(status & _ffi.STATUS_OVER_BUDGET), [int(d) for d in dist[:n].cpu()] if with_dist else None)
+
+    def streams_bitrate_pick(self, sizes, dist, spans, bytes_per_frame, buffer_bytes, levels, by="size", status=None, levels_out=None):
+        """The pick of encode_streams_at_bitrate alone, on a table the caller holds (frame_size_table's or frame_rd_table's CUDA
+        int64 tensors [K, n]; dist may be None when by="size"; status: the table's CUDA int32 status words, or None).  The
+        spans and per-stream rates are checked on the device.  levels: CUDA int64 [n_streams], advanced in place, or, with
+        levels_out (CUDA int64 [n_streams], which may be `levels` itself), left alone while levels_out receives the new
+        levels.  Synchronous.  Returns (picks, distortion, status bits): the candidate INDEX of every frame, the picks'
+        distortion (None without dist) and the pick's status word (STATUS_OVER_BUDGET, STATUS_STREAMS, ...)."""
+        import torch
+        assert sizes.is_cuda and sizes.dtype == torch.int64 and sizes.dim() == 2, "sizes: CUDA int64 [K, n]"
+        K, n = sizes.shape
+        sizes = sizes.contiguous()
+        if dist is not None:
+            assert dist.is_cuda and dist.dtype == torch.int64 and dist.shape == sizes.shape, "dist: CUDA int64 [K, n]"
+            dist = dist.contiguous()
+        if status is not None:
+            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= K, "status: CUDA int32, one per candidate"
+        if not isinstance(spans, StreamSpans):
+            spans = stream_spans(spans, sizes.device)
+        rate, cap, d_rates = self._stream_rates("streams_bitrate_pick", bytes_per_frame, buffer_bytes, len(spans), sizes.device)
+        self._levels(levels, len(spans))
+        level_in = levels.contiguous()
+        if levels_out is not None:
+            self._levels(levels_out, len(spans))
+            assert levels_out.is_contiguous()
+        level_out = levels_out if levels_out is not None else torch.empty_like(level_in)
+        picks = torch.zeros(max(n, 1), dtype=torch.uint8, device=sizes.device)
+        pick_dist = torch.zeros(max(n, 1), dtype=torch.int64, device=sizes.device) if dist is not None else None
+        word = torch.zeros(1, dtype=torch.int32, device=sizes.device)
+        _call("m1v_streams_cbr_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, _ptr(spans), len(spans),
+              _ffi.STREAMS_RULES[by], rate, cap, _ptr(d_rates), _ptr(level_in), _ptr(level_out), _ptr(picks), _ptr(pick_dist),
+              _ptr(word), _stream())
+        bits = int(word.item()) & 0xFFFFFFFF
+        if levels_out is None:
+            levels.copy_(level_out.view_as(levels))
+        return ([int(k) for k in picks[:n].cpu()], [int(d) for d in pick_dist[:n].cpu()] if pick_dist is not None else None, bits)
 
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.

@@ -351,6 +351,93 @@ int m1v_rd_cbr_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint
                            const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
                            uint32_t *d_status, void *stream);
 
+/* Streams: many in one batch.  Every call above takes one first_frame_index (frame f of the batch is frame first_frame_index + f
+ * of ONE stream), and the bitrate calls keep one leaky bucket.  No single stream feeds this encoder; a deployment mixes tens or
+ * hundreds, a few frames each per step.  These calls take a batch that is the concatenation of n_streams spans,
+ * 1 <= n_streams <= M1V_MAX_STREAMS:
+ *
+ *   d_rgb          exactly what it is for m1v_encode_device under the layout and table mode in force.  Span s covers batch
+ *                  positions [first_frame, first_frame + n_frames); with a frame table or plane table the caller orders the
+ *                  entries stream by stream at no cost.
+ *   the index      frame first_frame + j of span s is frame first_frame_index + j of its stream.
+ *   the record     byte for byte what m1v_encode_quality_device gives for that frame alone, at that index and quality.
+ *   the output     records lie in d_out in batch order, so each stream's records are one contiguous range;
+ *                  d_stream_bytes[s] (uint64[n_streams] on the device, may be NULL) is the length of that range.  A span of 0
+ *                  frames writes 0.
+ *
+ * The spans (d_spans, m1v_stream_span[n_streams]) live on the DEVICE and are read only by kernels, on `stream`, as a frame table
+ * is: a caller may build them with work queued in front of the call.  The host cannot validate them, so the device does.  The
+ * spans must tile the batch in order: first_frame of span 0 is 0; first_frame of span s + 1 is first_frame + n_frames of span s;
+ * the last span ends at the call's n_frames.  Anything else sets M1V_STATUS_STREAMS in d_status, and the batch's output is then
+ * undefined, as it is for M1V_STATUS_QUALITY.  Every index derived from a span is clamped into [0, n_frames] before it addresses
+ * anything: bad spans give unspecified records and never an access outside the arrays.  M1V_E_ARG before anything is launched:
+ * null spans, n_streams outside 1 .. M1V_MAX_STREAMS, a spans pointer that is not 4-byte aligned, and everything the plain calls
+ * check.
+ *
+ * m1v_encode_streams_device   m1v_encode_quality_device (d_quality may be NULL: the encoder's quality) with the indices taken from
+ *                             the spans.  n_frames == 0 writes *d_total = 0, *d_status = 0 and zeros into d_stream_bytes.
+ *                             Kernels: k_streams_map (a lane per span) in front of the encode kernel checks the tiling and
+ *                             expands the spans into a per-frame index array of the encoder (one per counter set: in pipelined
+ *                             mode both batches in flight keep theirs); k_assemble runs as in every other call, with index 0;
+ *                             k_streams_finish behind it, on the stream k_assemble runs on, rewrites the 44 header bytes of every
+ *                             record that fitted d_out (all but the packet length) from the frame's own index and sums each
+ *                             span's records.  Cost beside m1v_encode_device with one span: 1.03 x at 300 x 1080p, 1.01 x at
+ *                             100 x 4K (16 and 9 us; the A/A spread is 0.98 .. 1.12; profiles/r26_streams_timing.txt).
+ * m1v_encode_streams_cbr_device   a constant bitrate with one leaky bucket per stream: the arguments of m1v_encode_cbr_device
+ *                             with the spans in place of first_frame_index.  The bucket of stream s is the existing one,
+ *                             unchanged: it starts at min(d_level_in[s], C_s) and walks the span's frames in order with
+ *                             L = min(C_s, L - record + r_s); the final L goes to d_level_out[s] (int64[n_streams] each; they
+ *                             may alias elementwise).  Streams do not interact.  `rule` selects the pick:
+ *     M1V_STREAMS_LARGEST_THAT_FITS   m1v_encode_cbr_device's pick, on one size table.
+ *     M1V_STREAMS_LEAST_DISTORTION    m1v_encode_rd_cbr_device's pick, on one rd table (unencodable candidates are out of the
+ *                                     running, as they are there).
+ *                             d_stream_rates (m1v_stream_rate[n_streams] on the device) holds r_s and C_s; NULL means
+ *                             bytes_per_frame and buffer_bytes apply to every stream, host-checked as in m1v_encode_cbr_device.
+ *                             A device entry outside 1 <= r <= C < 2^62 sets M1V_STATUS_STREAMS; its stream's frames go to
+ *                             candidate 0 and its level passes through unchanged.  M1V_STATUS_OVER_BUDGET is set if any stream
+ *                             found a frame that nothing fits.  An empty span writes d_level_out[s] = min(d_level_in[s], C_s).
+ *                             d_chosen, d_frame_distortion (written under the distortion rule) and d_stream_bytes may be NULL.
+ *                             One table pass, one pick launch (k_streams_bitrate, one wave per stream over a grid of
+ *                             workgroups) and one encode for the whole batch, with no host wait, in pipelined mode too.  An
+ *                             encoder whose tables are not fused behaves as in the two existing bitrate calls (the distortion
+ *                             rule returns M1V_E_ARG).  Cost at K = 8 (tools/streams_timing.py, profiles/r26_streams_timing.txt):
+ *                             30 streams x 10 frames of 1080p take 0.59 of the time of one existing bitrate call per stream
+ *                             (either rule; 20 x 5 frames of 4K: 0.74 and 0.73), and 1.02 / 1.00 of ONE existing call over
+ *                             the 300 frames behind one bucket (byte rule / distortion rule).
+ * m1v_streams_cbr_pick_device the pick alone on a table the caller holds: the streams form of m1v_rd_cbr_pick_device, with the same
+ *                             table layout, preconditions and WRITTEN, not OR'ed, status.  d_distortion may be NULL under the
+ *                             byte rule (d_pick_distortion is then not written).  Bad spans set M1V_STATUS_STREAMS here too.
+ *
+ * Not covered: m1v_delivery_step (and the CLI) with spans; per-stream batch budgets and distortion ceilings; the host-buffer
+ * entry points. */
+typedef struct m1v_stream_span {
+    uint32_t first_frame;        /* position in the batch of the span's first frame          */
+    uint32_t n_frames;           /* frames of this stream in the batch; 0 is allowed         */
+    int32_t  first_frame_index;  /* global index, in ITS stream, of the span's first frame   */
+    uint32_t reserved;           /* 0                                                        */
+} m1v_stream_span;               /* 16 bytes; the array lives on the DEVICE                  */
+typedef struct m1v_stream_rate {
+    uint64_t bytes_per_frame;    /* r_s: 1 <= r_s <= C_s                                     */
+    uint64_t buffer_bytes;       /* C_s < 2^62                                               */
+} m1v_stream_rate;               /* 16 bytes; the array lives on the DEVICE                  */
+enum { M1V_STATUS_STREAMS = 64u };
+enum { M1V_MAX_STREAMS = 4096 };
+enum { M1V_STREAMS_LARGEST_THAT_FITS = 0, M1V_STREAMS_LEAST_DISTORTION = 1 };
+int m1v_encode_streams_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                              const uint8_t *d_quality, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                              uint64_t *d_stream_bytes, uint64_t *d_total, uint32_t *d_status, void *stream);
+int m1v_encode_streams_cbr_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                                  const uint8_t *candidates, int n_candidates, int rule, uint64_t bytes_per_frame,
+                                  uint64_t buffer_bytes, const m1v_stream_rate *d_stream_rates, const int64_t *d_level_in,
+                                  int64_t *d_level_out, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap, uint64_t *d_frame_sizes,
+                                  uint64_t *d_frame_distortion, uint64_t *d_stream_bytes, uint64_t *d_total, uint32_t *d_status,
+                                  void *stream);
+int m1v_streams_cbr_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                                int n_frames, int n_candidates, const m1v_stream_span *d_spans, int n_streams, int rule,
+                                uint64_t bytes_per_frame, uint64_t buffer_bytes, const m1v_stream_rate *d_stream_rates,
+                                const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                                uint32_t *d_status, void *stream);
+
 /* Input layout: frames that already live on the device as windows of pitched surfaces, in R,G,B(,A) or B,G,R(,A) byte order,
  * encoded where they lie (no compaction or swizzle copy in front of the encoder).
  *

@@ -1,0 +1,146 @@
+"""CPU-side checks of batches of many streams (include/mpeg1_hip.h "Streams": m1v_encode_streams_device,
+m1v_encode_streams_cbr_device, m1v_streams_cbr_pick_device): the struct, the constants and the prototypes are in the header,
+exported and bound; a null encoder or null spans is an argument error without a device; and exactly the k_streams_* kernels of
+csrc/m1v_streams.h are in the gfx950 code object, without scratch and under names no other test counts."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from test_abi import _gfx950_disassembly
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {
+    "m1v_encode_streams_device": ["enc", "d_rgb", "n_frames", "d_spans", "n_streams", "d_quality", "d_out", "out_cap", "d_frame_sizes",
+                                  "d_stream_bytes", "d_total", "d_status", "stream"],
+    "m1v_encode_streams_cbr_device": ["enc", "d_rgb", "n_frames", "d_spans", "n_streams", "candidates", "n_candidates", "rule",
+                                      "bytes_per_frame", "buffer_bytes", "d_stream_rates", "d_level_in", "d_level_out", "d_chosen",
+                                      "d_out", "out_cap", "d_frame_sizes", "d_frame_distortion", "d_stream_bytes", "d_total",
+                                      "d_status", "stream"],
+    "m1v_streams_cbr_pick_device": ["enc", "d_sizes", "d_distortion", "d_table_status", "n_frames", "n_candidates", "d_spans",
+                                    "n_streams", "rule", "bytes_per_frame", "buffer_bytes", "d_stream_rates", "d_level_in",
+                                    "d_level_out", "d_picks", "d_pick_distortion", "d_status", "stream"],
+}
+# the substrings and the pattern by which other tests count kernels of the code object
+COUNTED = ("k_assemble", "k_rate_pick", "float_planes", "k_float_pixels_")
+TILE_SHAPED = r"k[tp]?_(?:encode|size_table|rd_table)_"
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "mpeg1_hip.h")).read()
+
+
+@pytest.mark.parametrize("name", sorted(NAMES))
+def test_declared_exported_and_bound(name):
+    from ec504_imageencoder_amd import _ffi
+    m = re.search(r"\bint\s+%s\s*\(([^;]*)\);" % name, _header())
+    assert m, name
+    assert [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == NAMES[name]
+    L = _ffi.lib()
+    assert name in _ffi.MPEG1_HIP_SYMBOLS and hasattr(L, name)
+    fn = getattr(L, name)
+    assert fn.restype is C.c_int and len(fn.argtypes) == len(NAMES[name])
+
+
+def test_signatures_match_the_header():
+    from ec504_imageencoder_amd import _ffi
+    L = _ffi.lib()
+    vp, u8p, i, u64, sz = C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_uint64, C.c_size_t
+    assert L.m1v_encode_streams_device.argtypes == [vp, vp, i, vp, i, vp, vp, sz, vp, vp, vp, vp, vp]
+    assert L.m1v_encode_streams_cbr_device.argtypes == [vp, vp, i, vp, i, u8p, i, i, u64, u64, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp,
+                                                        vp, vp]
+    assert L.m1v_streams_cbr_pick_device.argtypes == [vp, vp, vp, vp, i, i, vp, i, i, u64, u64, vp, vp, vp, vp, vp, vp, vp]
+
+
+def test_the_struct_and_the_constants():
+    from ec504_imageencoder_amd import _ffi
+    text = _header()
+    assert "Streams" in text
+    m = re.search(r"typedef struct m1v_stream_span \{(.*?)\} m1v_stream_span;", text, re.S)
+    assert m
+    fields = re.findall(r"^\s*(u?int32_t)\s+(\w+);", m.group(1), re.M)
+    assert fields == [("uint32_t", "first_frame"), ("uint32_t", "n_frames"), ("int32_t", "first_frame_index"), ("uint32_t", "reserved")]
+    assert [(n, t) for n, t in _ffi.StreamSpan._fields_] == [("first_frame", C.c_uint32), ("n_frames", C.c_uint32),
+                                                              ("first_frame_index", C.c_int32), ("reserved", C.c_uint32)]
+    assert C.sizeof(_ffi.StreamSpan) == 16 and C.sizeof(_ffi.StreamRate) == 16
+    assert re.search(r"M1V_STATUS_STREAMS\s*=\s*64u", text) and re.search(r"M1V_MAX_STREAMS\s*=\s*4096", text)
+    assert re.search(r"M1V_STREAMS_LARGEST_THAT_FITS\s*=\s*0\s*,\s*M1V_STREAMS_LEAST_DISTORTION\s*=\s*1", text)
+    assert (_ffi.STATUS_STREAMS, _ffi.MAX_STREAMS) == (64, 4096)
+    assert (_ffi.STREAMS_LARGEST_THAT_FITS, _ffi.STREAMS_LEAST_DISTORTION) == (0, 1)
+    assert _ffi.STREAMS_RULES == {"size": 0, "distortion": 1}
+    import streams_model as sm
+    assert (sm.STATUS_STREAMS, sm.MAX_STREAMS, sm.LARGEST_THAT_FITS, sm.LEAST_DISTORTION) == (64, 4096, 0, 1)
+    assert (sm.STATUS_SCRATCH, sm.STATUS_OVER_BUDGET) == (_ffi.STATUS_SCRATCH, _ffi.STATUS_OVER_BUDGET)
+    # no status bit is used twice
+    bits = [_ffi.STATUS_UNENCODABLE, _ffi.STATUS_NOSPACE, _ffi.STATUS_SCRATCH, _ffi.STATUS_QUALITY, _ffi.STATUS_OVER_BUDGET,
+            _ffi.STATUS_OVER_DISTORTION, _ffi.STATUS_STREAMS]
+    assert sorted(bits) == [1, 2, 4, 8, 16, 32, 64]
+
+
+def test_sizeof_the_span_in_c():
+    """sizeof(m1v_stream_span) == 16, and the rate's, as a C compiler lays the header's structs out."""
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if not cc:
+        pytest.skip("no C compiler")
+    src = ('#include "mpeg1_hip.h"\n'
+           '_Static_assert(sizeof(m1v_stream_span) == 16, "span");\n'
+           '_Static_assert(sizeof(m1v_stream_rate) == 16, "rate");\n'
+           '_Static_assert(M1V_STATUS_STREAMS == 64 && M1V_MAX_STREAMS == 4096, "constants");\n')
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "span.c")
+        open(path, "w").write(src)
+        r = subprocess.run([cc, "-std=c11", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_null_encoder_or_null_spans_is_an_argument_error():
+    from ec504_imageencoder_amd import _ffi
+    L = _ffi.lib()
+    q = (C.c_uint8 * 2)(4, 8)
+    spans = (_ffi.StreamSpan * 1)(_ffi.StreamSpan(0, 0, 0, 0))
+    enc = C.c_void_p(8)   # never dereferenced: the spans are checked behind the encoder and in front of everything else
+    for e, sp in ((None, C.cast(spans, C.c_void_p)), (enc, None)):
+        calls = (
+            lambda: L.m1v_encode_streams_device(e, None, 0, sp, 1, None, None, 0, None, None, None, None, None),
+            lambda: L.m1v_encode_streams_cbr_device(e, None, 0, sp, 1, q, 2, 0, 100, 1000, None, None, None, None, None, 0, None, None,
+                                                    None, None, None, None),
+            lambda: L.m1v_streams_cbr_pick_device(e, None, None, None, 0, 2, sp, 1, 0, 100, 1000, None, None, None, None, None, None,
+                                                  None),
+        )
+        for call in calls:
+            assert call() == _ffi.E_ARG
+            assert "null" in _ffi.last_error()
+    # n_streams out of range and a spans pointer that is not 4-byte aligned, in front of any launch
+    sp = C.cast(spans, C.c_void_p)
+    for n_streams in (0, -1, _ffi.MAX_STREAMS + 1):
+        assert L.m1v_encode_streams_device(enc, None, 0, sp, n_streams, None, None, 0, None, None, None, None, None) == _ffi.E_ARG
+        assert "n_streams" in _ffi.last_error()
+    assert L.m1v_encode_streams_device(enc, None, 0, C.c_void_p(sp.value + 2), 1, None, None, 0, None, None, None, None, None) == _ffi.E_ARG
+    assert "aligned" in _ffi.last_error()
+
+
+def test_python_surface_exists():
+    import ec504_imageencoder_amd as pkg
+    for name in ("encode_streams", "encode_streams_device", "encode_streams_at_bitrate", "streams_bitrate_pick"):
+        assert callable(getattr(pkg.Mpeg1Encoder, name)), name
+    assert callable(pkg.stream_spans) and hasattr(pkg.StreamSpans, "data_ptr")
+    with pytest.raises(pkg.EncoderError):
+        pkg.stream_spans([])
+
+
+def test_exactly_the_streams_kernels_exist_without_scratch():
+    """k_streams_map, k_streams_bitrate (one instantiation per rule) and k_streams_finish: 0 bytes of private segment, no spills;
+    and none of their names holds a substring by which another test counts kernels."""
+    _, notes = _gfx950_disassembly()
+    recs = re.findall(r"\.name:\s*(\S*k_streams_\S*).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_spill_count:\s*(\d+)", notes, re.S)
+    kinds = sorted(re.search(r"k_streams_([a-z]+)", name).group(1) for name, _, _ in recs)
+    assert kinds == ["bitrate", "bitrate", "finish", "map"], recs
+    assert len({name for name, _, _ in recs}) == 4
+    for name, scratch, spills in recs:
+        assert int(scratch) == 0 and int(spills) == 0, (name, scratch, spills)
+        assert not any(c in name for c in COUNTED), name
+        assert not re.search(TILE_SHAPED, name), name
