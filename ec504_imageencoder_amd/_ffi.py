@@ -51,6 +51,7 @@ class RgbPlaneLayout(_Layout):
 SAMPLE_F16, SAMPLE_BF16, SAMPLE_F32 = 0, 1, 2
 FLOAT_SAMPLES = {"float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16, "float32": SAMPLE_F32}
 FLOAT_SAMPLE_BYTES = {SAMPLE_F16: 2, SAMPLE_BF16: 2, SAMPLE_F32: 4}
+FLOAT_SAMPLE_DTYPES = {code: name for name, code in FLOAT_SAMPLES.items()}   # the torch dtype's name: getattr(torch, ...)
 RANGE_UNIT, RANGE_BYTE = 0, 1
 FLOAT_RANGES = {"unit": RANGE_UNIT, "byte": RANGE_BYTE}
 
@@ -237,40 +238,17 @@ def lib():
     L.m1v_set_input_layout.restype = C.c_int
     L.m1v_input_layout.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.m1v_input_layout.restype = C.c_int
-    L.m1v_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(PlaneLayout)]
-    L.m1v_plane_layout_preset.restype = C.c_int
-    L.m1v_set_plane_layout.argtypes = [vp, C.POINTER(PlaneLayout)]
-    L.m1v_set_plane_layout.restype = C.c_int
-    L.m1v_plane_layout_in_force.argtypes = [vp, C.POINTER(PlaneLayout)]
-    L.m1v_plane_layout_in_force.restype = C.c_int
-    L.m1v_sample_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SampleLayout)]
-    L.m1v_sample_layout_preset.restype = C.c_int
-    L.m1v_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
-    L.m1v_set_sample_layout.restype = C.c_int
-    L.m1v_sample_layout_in_force.argtypes = [vp, C.POINTER(SampleLayout)]
-    L.m1v_sample_layout_in_force.restype = C.c_int
-    L.m1v_rgb_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(RgbPlaneLayout)]
-    L.m1v_rgb_plane_layout_preset.restype = C.c_int
-    L.m1v_set_rgb_plane_layout.argtypes = [vp, C.POINTER(RgbPlaneLayout)]
-    L.m1v_set_rgb_plane_layout.restype = C.c_int
-    L.m1v_rgb_plane_layout_in_force.argtypes = [vp, C.POINTER(RgbPlaneLayout)]
-    L.m1v_rgb_plane_layout_in_force.restype = C.c_int
-    L.m1v_float_plane_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FloatPlaneLayout)]
-    L.m1v_float_plane_layout_preset.restype = C.c_int
-    L.m1v_set_float_plane_layout.argtypes = [vp, C.POINTER(FloatPlaneLayout)]
-    L.m1v_set_float_plane_layout.restype = C.c_int
-    L.m1v_float_plane_layout_in_force.argtypes = [vp, C.POINTER(FloatPlaneLayout)]
-    L.m1v_float_plane_layout_in_force.restype = C.c_int
-    L.m1v_float_planes_to_bytes_device.argtypes = [vp, vp, C.c_int, vp, vp]
-    L.m1v_float_planes_to_bytes_device.restype = C.c_int
-    L.m1v_float_pixel_layout_preset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FloatPixelLayout)]
-    L.m1v_float_pixel_layout_preset.restype = C.c_int
-    L.m1v_set_float_pixel_layout.argtypes = [vp, C.POINTER(FloatPixelLayout)]
-    L.m1v_set_float_pixel_layout.restype = C.c_int
-    L.m1v_float_pixel_layout_in_force.argtypes = [vp, C.POINTER(FloatPixelLayout)]
-    L.m1v_float_pixel_layout_in_force.restype = C.c_int
-    L.m1v_float_pixels_to_bytes_device.argtypes = [vp, vp, C.c_int, vp, vp]
-    L.m1v_float_pixels_to_bytes_device.restype = C.c_int
+    # per layout struct: its preset (the number of ints it takes in front of the struct), its setter and its getter
+    for kind, struct, preset_ints in (("plane", PlaneLayout, 3), ("sample", SampleLayout, 3), ("rgb_plane", RgbPlaneLayout, 3),
+                                      ("float_plane", FloatPlaneLayout, 5), ("float_pixel", FloatPixelLayout, 6)):
+        getattr(L, f"m1v_{kind}_layout_preset").argtypes = [C.c_int] * preset_ints + [C.POINTER(struct)]
+        getattr(L, f"m1v_set_{kind}_layout").argtypes = [vp, C.POINTER(struct)]
+        getattr(L, f"m1v_{kind}_layout_in_force").argtypes = [vp, C.POINTER(struct)]
+        for name in (f"m1v_{kind}_layout_preset", f"m1v_set_{kind}_layout", f"m1v_{kind}_layout_in_force"):
+            getattr(L, name).restype = C.c_int
+    for name in ("m1v_float_planes_to_bytes_device", "m1v_float_pixels_to_bytes_device"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int, vp, vp]
+        getattr(L, name).restype = C.c_int
     L.m1v_set_frame_table.argtypes = [vp, C.c_int]
     L.m1v_set_frame_table.restype = C.c_int
     L.m1v_frame_table.argtypes = [vp]

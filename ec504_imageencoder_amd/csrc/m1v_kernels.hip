@@ -1786,8 +1786,11 @@ struct m1v_encoder {
     bool run_hook_set() const { return runs_by_path_or_mode() || forced_T > 0; }
     // plan_for's 4-channel fused table: every hook keeps one probe per quality, the A/B reference inside one process
     bool any_hook_set() const { return forced_path >= 0 || forced_mode >= 0 || forced_T != 0; }
+    // The sample format of a float layout, as float_format checks and fills it: the M1V_SAMPLE_* and M1V_RANGE_* values it was set
+    // with, a sample's bytes, and the factor that takes a sample to a byte's range
+    struct FloatFormat { int sample, range; uint32_t bytes; float scale; };
     // The input layout in force, no zeros: its kind, the frame stride every kind but packed has, and one member per kind.  Only the
-    // member of the kind in force is set and read (layout_facts: how messages name a kind, its setter and its getter).
+    // member of the kind in force is set and read (kind_facts: what the host knows of each kind).
     struct Layout {
         enum class Kind { packed, surface, samples, rgb_planes, float_planes, float_pixels } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
@@ -1800,12 +1803,12 @@ struct m1v_encoder {
         // extent: bytes of a frame the kernels may read (the read contract of mpeg1_hip.h)
         struct Samples { uint32_t y_off, cb_off, cr_off, y_pitch, c_pitch, y_step, c_step; unsigned long long extent; } samples = {};
         RgbPlaneFrontArgs rgb_planes = {}; // m1v_set_rgb_plane_layout: planes of R, G and B bytes, as their kernels take them (m1v_rgb_planes.h)
-        // m1v_set_float_plane_layout: planes of fp16, bf16 or fp32 samples of R, G and B, as their kernels take them
-        // (m1v_float_planes.h), with the M1V_SAMPLE_* and M1V_RANGE_* values they were set with
-        struct FloatPlanes { FloatPlaneFrontArgs front; int sample, range; } float_planes = {};
+        FloatFormat fmt = {};                // the samples of a float plane or float pixel layout
+        // m1v_set_float_plane_layout: planes of fp16, bf16 or fp32 samples of R, G and B, as their kernels take them (m1v_float_planes.h)
+        FloatPlaneFrontArgs float_planes = {};
         // m1v_set_float_pixel_layout: float samples of R, G and B interleaved per pixel, as their kernels take them
-        // (m1v_float_pixels.h), with the pixel step in bytes and the M1V_SAMPLE_* and M1V_RANGE_* values they were set with
-        struct FloatPixels { FloatPixelFrontArgs front; uint32_t pixel_step; int sample, range; } float_pixels = {};
+        // (m1v_float_pixels.h), with the pixel step in bytes
+        struct FloatPixels { FloatPixelFrontArgs front; uint32_t pixel_step; } float_pixels = {};
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
@@ -1875,6 +1878,74 @@ struct m1v_encoder {
 
 using LayoutKind = m1v_encoder::Layout::Kind;
 using TableMode = m1v_encoder::Layout::Table;
+using FloatFormat = m1v_encoder::FloatFormat;
+
+// What the host knows of a layout kind, apart from its kernels' arguments (launch_tiles) and its registry entries (tile_variant).
+// The entry points that ask what kind is in force read a row; none keeps a list of kinds.
+struct KindFacts {
+    const char *name, *setter, *getter; // how messages call the kind, its setter, and the getter that can describe it
+    int plane_getters;                  // what m1v_plane_layout_in_force and m1v_sample_layout_in_force answer: 1 theirs to describe, 0 none
+                                        // in force (m1v_input_layout describes it), M1V_E_ARG naming `getter`, as m1v_input_layout then does
+    const char *no_frame_table;         // why m1v_set_frame_table refuses the kind; null: a frame table serves it
+    const char *no_plane_table;         // why m1v_set_plane_table refuses the kind; null: a plane table serves it
+    const char *misaligned;             // the refusal of frames that are no multiple of the float format's sample size; null: bytes, at any address
+};
+#pragma clang diagnostic push
+#pragma clang diagnostic error "-Wswitch" // a kind without a row does not compile
+static KindFacts kind_facts(LayoutKind kind) {
+    switch (kind) {
+    case LayoutKind::packed: // (the surface layout's default)
+        return {"packed input", "m1v_set_input_layout", "m1v_input_layout", 0,
+                "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
+                "m1v_set_input_layout(enc, width * channels, 0, order)",
+                "a plane table needs a plane layout (m1v_set_plane_layout) or an RGB plane layout (m1v_set_rgb_plane_layout): "
+                "packed pixels have no planes",
+                nullptr};
+    case LayoutKind::surface:
+        return {"a surface layout", "m1v_set_input_layout", "m1v_input_layout", 0, nullptr,
+                "a surface layout has one plane: m1v_set_frame_table serves it", nullptr};
+    case LayoutKind::samples: return {"a plane layout", "m1v_set_plane_layout", "m1v_plane_layout_in_force", 1, nullptr, nullptr, nullptr};
+    case LayoutKind::rgb_planes:
+        return {"an RGB plane layout", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force", M1V_E_ARG, nullptr, nullptr, nullptr};
+    case LayoutKind::float_planes:
+        return {"a float plane layout", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force", M1V_E_ARG,
+                "a frame table does not serve a float plane layout (m1v_set_float_plane_layout): float frames behind a table are not covered",
+                "a plane table does not serve a float plane layout (m1v_set_float_plane_layout): float planes behind separate pointers are "
+                "not covered",
+                "a float plane layout is in force (m1v_set_float_plane_layout): d_rgb must be a multiple of the sample size"};
+    case LayoutKind::float_pixels:
+        return {"a float pixel layout", "m1v_set_float_pixel_layout", "m1v_float_pixel_layout_in_force", M1V_E_ARG,
+                "a frame table does not serve a float pixel layout (m1v_set_float_pixel_layout): float frames behind a table are not covered",
+                "a plane table does not serve a float pixel layout (m1v_set_float_pixel_layout): interleaved pixels have no planes, and "
+                "float frames behind a table are not covered",
+                "a float pixel layout is in force (m1v_set_float_pixel_layout): d_rgb must be a multiple of the sample size"};
+    }
+}
+#pragma clang diagnostic pop
+// ... of the layout in force as its getters and the plane table see it: to them a sample layout with y_step 2 is a kind of its
+// own, which m1v_plane_layout cannot hold and whose planes no table can name
+static KindFacts kind_facts(const m1v_encoder::Layout &l) {
+    if (l.kind == LayoutKind::samples && l.samples.y_step == 2)
+        return {"a layout with samples two bytes apart", "m1v_set_sample_layout", "m1v_sample_layout_in_force", 1, nullptr,
+                "a plane table does not serve a (2, 4) sample layout: packed 4:2:2 has no planes, and P010 with separate Y and UV "
+                "pointers is not covered",
+                nullptr};
+    return kind_facts(l.kind);
+}
+
+// The one check of a float layout's sample type and range, for the presets and the setters; fills what the rest of the host reads
+static int float_format(int sample, int range, FloatFormat &out) {
+    const uint32_t bytes = sample == M1V_SAMPLE_F16 || sample == M1V_SAMPLE_BF16 ? 2 : (sample == M1V_SAMPLE_F32 ? 4 : 0);
+    if (!bytes) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
+    if (range != M1V_RANGE_UNIT && range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+    out = {sample, range, bytes, range == M1V_RANGE_UNIT ? 255.0f : 1.0f};
+    return M1V_OK;
+}
+// ... and of what a float layout gives in bytes (`fields`: all of them ORed; `what`: their names, as the refusal lists them)
+static int whole_samples(const FloatFormat &f, unsigned long long fields, const char *what) {
+    if (fields % f.bytes == 0) return M1V_OK;
+    return fail(M1V_E_ARG, "%s must be multiples of the sample size (%s bytes)", what, f.bytes == 2 ? "2" : "4");
+}
 
 // The order in which a frame's tile rows are processed.  Tile row R (macroblock rows 4R..4R+3) reads its luma from picture
 // rows [64R, 64R+64) and — the chroma quirk, encoder.h:347-348 — its chroma from rows [16R, 16R+16), i.e. from one quarter of
@@ -2124,17 +2195,15 @@ static int encoder_quality(const m1v_encoder *e) { return std::min(std::max(e->q
 // The tile-shaped kernels' variant for the layout in force (Kernels::tile): the one place that maps channels, byte order and
 // sample steps to an instantiation
 static TileVariant tile_variant(const m1v_encoder *e) {
+    static_assert(M1V_SAMPLE_F16 == 0 && M1V_SAMPLE_BF16 == 1 && M1V_SAMPLE_F32 == 2 && kFloatPlanesF32 == kFloatPlanesF16 + 2 &&
+                  kFloatPixelsBf16x3 == kFloatPixelsF16x3 + 2 && kFloatPixelsF32x4 == kFloatPixelsF16x3 + 5, "the float variants' order");
     const m1v_encoder::Layout &l = e->layout;
     const bool four = e->g.C == 4;
     switch (l.kind) {
     case LayoutKind::rgb_planes: return kRgbPlanes;
-    case LayoutKind::float_planes:
-        return l.float_planes.sample == M1V_SAMPLE_F32 ? kFloatPlanesF32 : (l.float_planes.sample == M1V_SAMPLE_BF16 ? kFloatPlanesBf16 : kFloatPlanesF16);
-    case LayoutKind::float_pixels: { // (the variants lie [type][3 | 4 samples per pixel])
-        const int type = l.float_pixels.sample == M1V_SAMPLE_F32 ? 2 : (l.float_pixels.sample == M1V_SAMPLE_BF16 ? 1 : 0);
-        const int wide = l.float_pixels.pixel_step == 4u * (type == 2 ? 4u : 2u) ? 1 : 0;
-        return (TileVariant)(kFloatPixelsF16x3 + 2 * type + wide);
-    }
+    // (the float variants lie in the order of the M1V_SAMPLE_* values; those of pixels [type][3 | 4 samples per pixel])
+    case LayoutKind::float_planes: return (TileVariant)(kFloatPlanesF16 + l.fmt.sample);
+    case LayoutKind::float_pixels: return (TileVariant)(kFloatPixelsF16x3 + 2 * l.fmt.sample + (l.float_pixels.pixel_step == 4u * l.fmt.bytes ? 1 : 0));
     case LayoutKind::samples: return l.samples.y_step == 2 ? kStep2 : (l.samples.c_step == 2 ? kPlanesPaired : kPlanes);
     case LayoutKind::surface: return l.surface.order == M1V_ORDER_BGR ? (four ? kSurfaceBgr4 : kSurfaceBgr3) : (four ? kSurfaceRgb4 : kSurfaceRgb3);
     case LayoutKind::packed: return four ? kPacked4 : kPacked3;
@@ -2212,19 +2281,17 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
     case LayoutKind::samples: // (the 16-byte unit that ends with the frame's extent, rounded up to whole dwords, is the last one a plane kernel may load)
         return launch(typename Family::Samples{a, {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, (uint32_t)(((s.extent + 3ull) & ~3ull) - 16ull)}, stride});
     case LayoutKind::rgb_planes: return launch(typename Family::RgbPlanes{a, l.rgb_planes, stride});
-    case LayoutKind::float_planes: return launch(typename Family::FloatPlanes{a, l.float_planes.front, stride});
+    case LayoutKind::float_planes: return launch(typename Family::FloatPlanes{a, l.float_planes, stride});
     case LayoutKind::float_pixels: return launch(typename Family::FloatPixels{a, l.float_pixels.front, stride});
     case LayoutKind::packed: return launch(a);
     }
 }
 
 // With a frame or plane table on, d_rgb is read as 64-bit words by scalar loads: refused here, in front of every launch, when misaligned.
-// So are float planes and float pixels whose samples would not be naturally aligned (the float layouts have no table mode).
+// So are float frames whose samples would not be naturally aligned (KindFacts::misaligned; the float layouts have no table mode).
 static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
-    if (e->layout.kind == LayoutKind::float_pixels && ((uintptr_t)d_rgb & (e->layout.float_pixels.sample == M1V_SAMPLE_F32 ? 3u : 1u)) != 0)
-        return fail(M1V_E_ARG, "a float pixel layout is in force (m1v_set_float_pixel_layout): d_rgb must be a multiple of the sample size%s");
-    if (e->layout.kind == LayoutKind::float_planes && ((uintptr_t)d_rgb & (e->layout.float_planes.sample == M1V_SAMPLE_F32 ? 3u : 1u)) != 0)
-        return fail(M1V_E_ARG, "a float plane layout is in force (m1v_set_float_plane_layout): d_rgb must be a multiple of the sample size%s");
+    const char *misaligned = kind_facts(e->layout.kind).misaligned;
+    if (misaligned && ((uintptr_t)d_rgb & (e->layout.fmt.bytes - 1u)) != 0) return fail(M1V_E_ARG, "%s", misaligned);
     if (e->layout.table == TableMode::off || ((uintptr_t)d_rgb & 7) == 0) return M1V_OK;
     if (e->layout.table == TableMode::planes)
         return fail(M1V_E_ARG, "a plane table is on (m1v_set_plane_table): d_rgb is an array of three 64-bit plane addresses per frame and must be 8-byte aligned%s");
@@ -2453,9 +2520,9 @@ static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int 
     return M1V_OK;
 }
 
-// The fused size table (Plan::table_units): k_size_table_tiles (3 channels) or k_size_table_rgba (4), or k_size_table_surface on
-// a surface layout, or k_size_table_planes on a plane layout, then k_size_table_sizes,
-// both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
+// The fused size table (Plan::table_units): the size-table kernel of the layout in force (launch_tiles on the kSizeTable row of the
+// registry: k_size_table_tiles for packed 3-channel input, k_size_table_rgba for 4 channels, one kernel family per layout kind
+// beside them), then k_size_table_sizes, both on the caller's stream (no Batch, no scratch: in pipelined mode too).  qualities: 1..8, strictly increasing, each <= the encoder's quality (checked by the caller).
 // sizes[k * stride + frame], status[k] (may be null).  Fail hooks: 1 before the probe kernel, 2 before the sizes kernel, 3 after.
 // dist != null: the rd table (the k_rd_table_* kernels and k_rd_table_sizes in their places), dist[k * stride + frame] beside the sizes.
 static int size_table_fused(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const uint8_t *qualities, int n_q,

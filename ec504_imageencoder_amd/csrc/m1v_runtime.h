@@ -5,8 +5,10 @@
 // encoder's own buffers), one description of the table a pick reads (PickTable, the encoder's own or the caller's) and one launch
 // site per pick kernel; what writes a batch's per-frame selection reaches encode_batch as a Selection (the select_by_* steps; a
 // batch of many streams, m1v_streams.h, is one too: select_streams in front of the encode kernel, finish_streams behind k_assemble).
-// Geometry (CodedRegion, TileGrid, wave_region), the kernel registry (kKernels) and the hook predicates of m1v_encoder come from
-// m1v_kernels.hip.  Not standalone: included once, at the end of m1v_kernels.hip.
+// The input layouts (packed, surface, plane / sample, RGB plane, float plane, float pixel): a setter, a getter and a preset each, the
+// two table modes and the two to-bytes calls; what differs per kind beyond a setter's own checks is a row of kind_facts.
+// Geometry (CodedRegion, TileGrid, wave_region), the kernel registry (kKernels), the layout record with kind_facts and float_format,
+// and the hook predicates of m1v_encoder come from m1v_kernels.hip.  Not standalone: included once, at the end of m1v_kernels.hip.
 
 namespace {
 
@@ -311,34 +313,56 @@ static int reconfigure(m1v_encoder *e, T m1v_encoder::*field, T value) {
     return rc;
 }
 
-// How messages name a layout kind, its setter and its getter.  two_apart: a sample layout with y_step 2, which the getters name
-// for what it is (m1v_plane_layout cannot hold it)
-struct LayoutFacts { const char *name, *setter, *getter; };
-static LayoutFacts layout_facts(LayoutKind kind, bool two_apart = false) {
-    switch (kind) {
-    case LayoutKind::surface: return {"a surface layout", "m1v_set_input_layout", "m1v_input_layout"};
-    case LayoutKind::samples:
-        if (two_apart) return {"a layout with samples two bytes apart", "m1v_set_sample_layout", "m1v_sample_layout_in_force"};
-        return {"a plane layout", "m1v_set_plane_layout", "m1v_plane_layout_in_force"};
-    case LayoutKind::rgb_planes: return {"an RGB plane layout", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force"};
-    case LayoutKind::float_planes: return {"a float plane layout", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force"};
-    case LayoutKind::float_pixels: return {"a float pixel layout", "m1v_set_float_pixel_layout", "m1v_float_pixel_layout_in_force"};
-    case LayoutKind::packed: return {"packed input", "m1v_set_input_layout", "m1v_input_layout"}; // (the surface layout's default)
-    }
-}
-
 // What takes packed input only: the entry points that do not go through the producer / table kernels, and the hooks that force
 // the run kernels
 static int packed_only(const m1v_encoder *e) {
     if (!e->layout.tiles_only()) return M1V_OK;
-    const LayoutFacts f = layout_facts(e->layout.kind);
+    const KindFacts f = kind_facts(e->layout.kind);
     return fail(M1V_E_ARG, "packed input only: %s is set (%s)", f.name, f.setter);
 }
 
 // A getter that cannot describe the layout in force names the one that can
 static int ask_its_getter(const m1v_encoder *e) {
-    const LayoutFacts f = layout_facts(e->layout.kind, e->layout.kind == LayoutKind::samples && e->layout.samples.y_step == 2);
+    const KindFacts f = kind_facts(e->layout);
     return fail(M1V_E_ARG, "%s is in force: ask %s", f.name, f.getter);
+}
+
+// The preamble of the getters of Y, Cb, Cr layouts: 1 = a plane or sample layout is in force, 0 = none is (packed or surface input),
+// else the refusal that names the getter to ask
+static int samples_in_force(const m1v_encoder *e) {
+    const int answer = kind_facts(e->layout).plane_getters;
+    return answer < 0 ? ask_its_getter(e) : answer;
+}
+
+// What rows of `row` bytes that lie `pitch` apart must satisfy in the surface and float pixel setters: a pitch not below the row,
+// the rows of a frame (`what` the refusal calls them) below 4 GiB, a frame stride not below them
+static int rows_fit(unsigned long long pitch, unsigned long long row, unsigned long long H, unsigned long long frame_stride,
+                    const char *pitch_below_row, const char *what, const char *stride_below_rows) {
+    if (pitch < row) return fail(M1V_E_ARG, "%s", pitch_below_row);
+    const unsigned long long limit = 1ull << 32, extent = (H - 1) * pitch + row;
+    if (pitch >= limit || extent >= limit) return fail(M1V_E_ARG, "a %s of 4 GiB or more (byte offsets inside a frame are 32-bit)", what);
+    if (frame_stride < extent) return fail(M1V_E_ARG, "%s", stride_below_rows);
+    return M1V_OK;
+}
+
+// The launches behind the two to-bytes calls, 65535 frames (a grid's y extent) each: `kind` must be in force (`needs`: the refusal
+// where it is not); kernels: the call's kernel per M1V_SAMPLE_* value; args(frames, bytes): its argument struct for the frames from
+// `frames` on, written from `bytes` on; grid: the launch over n frames
+template <typename MakeArgs, typename Grid>
+static int float_to_bytes(m1v_encoder *e, LayoutKind kind, const char *needs, const void *const (&kernels)[3], const void *d_frames,
+                          int n_frames, uint8_t *d_bytes, void *stream, MakeArgs args, Grid grid) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != kind) return fail(M1V_E_ARG, "%s", needs);
+    if (n_frames < 0 || ((!d_frames || !d_bytes) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
+    if (const int rc = check_frame_table(e, static_cast<const uint8_t *>(d_frames))) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const unsigned long long frame_out = 3ull * (unsigned)e->g.W * (unsigned)e->g.H;
+    for (int done = 0; done < n_frames; done += 65535) {
+        auto a = args(static_cast<const uint8_t *>(d_frames) + (unsigned long long)done * e->layout.frame_stride, d_bytes + (unsigned long long)done * frame_out);
+        void *argv[] = {&a};
+        HIP_TRY(hipLaunchKernel(kernels[e->layout.fmt.sample], grid((unsigned)std::min(n_frames - done, 65535)), dim3(256u), argv, 0, (hipStream_t)stream));
+    }
+    return M1V_OK;
 }
 
 // The shared tail of the layout setters, behind their argument checks: a layout of the tile kernels and a hook that forces the run
@@ -594,16 +618,13 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
     m1v_encoder::Layout want;
     if (row_pitch_bytes != 0 || frame_stride_bytes != 0 || order != M1V_ORDER_RGB) {
         want.kind = LayoutKind::surface;
-        const unsigned long long row = (unsigned long long)g.W * g.C;
         if (g.W & 1) return fail(M1V_E_ARG, "a surface layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
-        if (row_pitch_bytes != 0 && row_pitch_bytes < row) return fail(M1V_E_ARG, "row pitch below width * channels%s");
-        const unsigned long long pitch = row_pitch_bytes ? row_pitch_bytes : row;
-        if (pitch >= (1ull << 32) || (unsigned long long)(g.H - 1) * pitch + row >= (1ull << 32))
-            return fail(M1V_E_ARG, "a window of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
-        const unsigned long long extent = (unsigned long long)(g.H - 1) * pitch + row;
-        if (frame_stride_bytes != 0 && frame_stride_bytes < extent) return fail(M1V_E_ARG, "frame stride below the bytes a frame's window spans%s");
+        const unsigned long long row = (unsigned long long)g.W * g.C, pitch = row_pitch_bytes ? row_pitch_bytes : row;
+        want.frame_stride = frame_stride_bytes ? frame_stride_bytes : (unsigned long long)g.H * pitch; // (0: the rows, no gap)
+        if (const int rc = rows_fit(pitch, row, (unsigned long long)g.H, want.frame_stride, "row pitch below width * channels", "window",
+                                    "frame stride below the bytes a frame's window spans"))
+            return rc;
         want.surface = {(uint32_t)pitch, order};
-        want.frame_stride = frame_stride_bytes ? frame_stride_bytes : (unsigned long long)g.H * pitch;
     }
     return apply_layout(e, want);
 }
@@ -611,12 +632,11 @@ int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_st
 int m1v_input_layout(const m1v_encoder *e, size_t *row_pitch_bytes, size_t *frame_stride_bytes, int *order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     const m1v_encoder::Layout &l = e->layout;
-    if (l.kind == LayoutKind::samples || l.kind == LayoutKind::rgb_planes || l.kind == LayoutKind::float_planes || l.kind == LayoutKind::float_pixels)
-        return ask_its_getter(e);
-    const m1v_encoder::Layout::Surface s = l.kind == LayoutKind::surface ? l.surface : m1v_encoder::Layout::Surface{0, M1V_ORDER_RGB};
-    if (row_pitch_bytes) *row_pitch_bytes = s.row_pitch;
+    if (kind_facts(l).plane_getters != 0) return ask_its_getter(e);
+    static_assert(M1V_ORDER_RGB == 0, "packed input leaves the record's zeros: (0, 0, M1V_ORDER_RGB)");
+    if (row_pitch_bytes) *row_pitch_bytes = l.surface.row_pitch;
     if (frame_stride_bytes) *frame_stride_bytes = (size_t)l.frame_stride;
-    if (order) *order = s.order;
+    if (order) *order = l.surface.order;
     return M1V_OK;
 }
 
@@ -676,7 +696,8 @@ int m1v_sample_layout_preset(int width, int height, int preset, m1v_sample_layou
     return M1V_OK;
 }
 
-// (m1v_set_plane_layout too: the checks of include/mpeg1_hip.h with the steps put in, then the reconfiguration)
+// (m1v_set_plane_layout ends here too, with y_step 1: the checks of include/mpeg1_hip.h on the two steps, then on offsets,
+// pitches and the frame's extent with the steps put in, then the reconfiguration)
 int m1v_set_sample_layout(m1v_encoder *e, const m1v_sample_layout *layout) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     m1v_encoder::Layout want;
@@ -722,9 +743,7 @@ int m1v_set_plane_layout(m1v_encoder *e, const m1v_plane_layout *layout) {
 
 int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes || e->layout.kind == LayoutKind::float_pixels)
-        return ask_its_getter(e);
-    if (e->layout.kind != LayoutKind::samples) return 0;
+    if (const int rc = samples_in_force(e); rc != 1) return rc;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (s.y_step == 2) return ask_its_getter(e);
     if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.c_step, (size_t)e->layout.frame_stride};
@@ -733,9 +752,7 @@ int m1v_plane_layout_in_force(const m1v_encoder *e, m1v_plane_layout *out) {
 
 int m1v_sample_layout_in_force(const m1v_encoder *e, m1v_sample_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind == LayoutKind::rgb_planes || e->layout.kind == LayoutKind::float_planes || e->layout.kind == LayoutKind::float_pixels)
-        return ask_its_getter(e);
-    if (e->layout.kind != LayoutKind::samples) return 0;
+    if (const int rc = samples_in_force(e); rc != 1) return rc;
     const m1v_encoder::Layout::Samples &s = e->layout.samples;
     if (out) *out = {s.y_off, s.cb_off, s.cr_off, s.y_pitch, s.c_pitch, s.y_step, s.c_step, (size_t)e->layout.frame_stride};
     return 1;
@@ -799,16 +816,11 @@ int m1v_rgb_plane_layout_in_force(const m1v_encoder *e, m1v_rgb_plane_layout *ou
     return 1;
 }
 
-// bytes of a sample of M1V_SAMPLE_*; 0 = unknown
-static unsigned long long float_sample_bytes(int sample) {
-    return sample == M1V_SAMPLE_F16 || sample == M1V_SAMPLE_BF16 ? 2 : (sample == M1V_SAMPLE_F32 ? 4 : 0);
-}
-
 int m1v_float_plane_layout_preset(int width, int height, int order, int sample, int range, m1v_float_plane_layout *out) {
     if (!out) return fail(M1V_E_ARG, "null out%s");
-    const uint64_t S = float_sample_bytes(sample);
-    if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
-    if (range != M1V_RANGE_UNIT && range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
+    FloatFormat fmt;
+    if (const int rc = float_format(sample, range, fmt)) return rc;
+    const uint64_t S = fmt.bytes;
     m1v_rgb_plane_layout bytes;
     if (const int rc = m1v_rgb_plane_layout_preset(width, height, order, &bytes)) return rc;
     *out = {bytes.r_offset * S, bytes.g_offset * S, bytes.b_offset * S, bytes.row_pitch * S, bytes.frame_stride * S, sample, range};
@@ -822,18 +834,14 @@ int m1v_set_float_plane_layout(m1v_encoder *e, const m1v_float_plane_layout *lay
         const Geometry &g = e->g;
         if (g.C != 3) return fail(M1V_E_ARG, "a float plane layout needs an encoder created with 3 channels%s");
         if (g.W & 1) return fail(M1V_E_ARG, "a float plane layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
-        const unsigned long long S = float_sample_bytes(layout->sample);
-        if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
-        if (layout->range != M1V_RANGE_UNIT && layout->range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
-        const unsigned long long row = (unsigned long long)g.W * S, pitch = layout->row_pitch;
+        if (const int rc = float_format(layout->sample, layout->range, want.fmt)) return rc;
+        const unsigned long long row = (unsigned long long)g.W * want.fmt.bytes, pitch = layout->row_pitch;
         const unsigned long long off[3] = {layout->r_offset, layout->g_offset, layout->b_offset};
-        if ((off[0] | off[1] | off[2] | pitch | layout->frame_stride) % S)
-            return fail(M1V_E_ARG, "offsets, row pitch and frame stride must be multiples of the sample size (%s bytes)", S == 2 ? "2" : "4");
+        if (const int rc = whole_samples(want.fmt, off[0] | off[1] | off[2] | pitch | layout->frame_stride, "offsets, row pitch and frame stride")) return rc;
         if (pitch < row) return fail(M1V_E_ARG, "row pitch below width * sample size%s");
         if (const int rc = three_planes_fit(off, pitch, row, (unsigned long long)g.H, layout->frame_stride)) return rc;
         want.kind = LayoutKind::float_planes;
-        want.float_planes = {{(uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2], (uint32_t)pitch, layout->range == M1V_RANGE_UNIT ? 255.0f : 1.0f},
-                             layout->sample, layout->range};
+        want.float_planes = {(uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2], (uint32_t)pitch, want.fmt.scale};
         want.frame_stride = layout->frame_stride;
     }
     return apply_layout(e, want);
@@ -842,30 +850,21 @@ int m1v_set_float_plane_layout(m1v_encoder *e, const m1v_float_plane_layout *lay
 int m1v_float_plane_layout_in_force(const m1v_encoder *e, m1v_float_plane_layout *out) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (e->layout.kind != LayoutKind::float_planes) return 0;
-    const m1v_encoder::Layout::FloatPlanes &f = e->layout.float_planes;
-    if (out) *out = {f.front.r_off, f.front.g_off, f.front.b_off, f.front.row_pitch, e->layout.frame_stride, f.sample, f.range};
+    const FloatPlaneFrontArgs &f = e->layout.float_planes;
+    if (out) *out = {f.r_off, f.g_off, f.b_off, f.row_pitch, e->layout.frame_stride, e->layout.fmt.sample, e->layout.fmt.range};
     return 1;
 }
 
 int m1v_float_planes_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind != LayoutKind::float_planes) return fail(M1V_E_ARG, "m1v_float_planes_to_bytes_device needs a float plane layout in force (m1v_set_float_plane_layout)%s");
-    if (n_frames < 0 || ((!d_frames || !d_bytes) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
-    if (const int rc = check_frame_table(e, static_cast<const uint8_t *>(d_frames))) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    const m1v_encoder::Layout::FloatPlanes &f = e->layout.float_planes;
-    const void *kernel = f.sample == M1V_SAMPLE_F32 ? (const void *)&k_float_planes_to_bytes<F32Sample>
-                         : (f.sample == M1V_SAMPLE_BF16 ? (const void *)&k_float_planes_to_bytes<Bf16Sample> : (const void *)&k_float_planes_to_bytes<F16Sample>);
-    const unsigned pairs = (unsigned)e->g.W / 2u * (unsigned)e->g.H;
-    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
-        const int n = std::min(n_frames - done, 65535);
-        FloatBytesArgs a = {static_cast<const uint8_t *>(d_frames) + (unsigned long long)done * e->layout.frame_stride,
-                            d_bytes + (unsigned long long)done * 3ull * (unsigned)e->g.W * (unsigned)e->g.H, f.front, e->layout.frame_stride,
-                            (uint32_t)e->g.W, (uint32_t)e->g.H};
-        void *args[] = {&a};
-        HIP_TRY(hipLaunchKernel(kernel, dim3((pairs + 255u) / 256u, (unsigned)n, 3u), dim3(256u), args, 0, (hipStream_t)stream));
-    }
-    return M1V_OK;
+    static const void *const kernels[3] = {(const void *)&k_float_planes_to_bytes<F16Sample>, (const void *)&k_float_planes_to_bytes<Bf16Sample>,
+                                           (const void *)&k_float_planes_to_bytes<F32Sample>};
+    return float_to_bytes(
+        e, LayoutKind::float_planes, "m1v_float_planes_to_bytes_device needs a float plane layout in force (m1v_set_float_plane_layout)", kernels,
+        d_frames, n_frames, d_bytes, stream,
+        [e](const uint8_t *frames, uint8_t *bytes) {
+            return FloatBytesArgs{frames, bytes, e->layout.float_planes, e->layout.frame_stride, (uint32_t)e->g.W, (uint32_t)e->g.H};
+        },
+        [e](unsigned n) { return dim3(((unsigned)e->g.W / 2u * (unsigned)e->g.H + 255u) / 256u, n, 3u); }); // (pairs of samples, per plane)
 }
 
 int m1v_float_pixel_layout_preset(int width, int height, int pixel_samples, int order, int sample, int range, m1v_float_pixel_layout *out) {
@@ -873,10 +872,9 @@ int m1v_float_pixel_layout_preset(int width, int height, int pixel_samples, int 
     if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
     if (pixel_samples != 3 && pixel_samples != 4) return fail(M1V_E_ARG, "a pixel has 3 or 4 samples%s");
     if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
-    const uint64_t S = float_sample_bytes(sample);
-    if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
-    if (range != M1V_RANGE_UNIT && range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
-    const uint64_t step = (uint64_t)pixel_samples * S, pitch = (uint64_t)width * step;
+    FloatFormat fmt;
+    if (const int rc = float_format(sample, range, fmt)) return rc;
+    const uint64_t step = (uint64_t)pixel_samples * fmt.bytes, pitch = (uint64_t)width * step;
     *out = {pitch, (uint64_t)height * pitch, step, order, sample, range};
     return M1V_OK;
 }
@@ -889,24 +887,17 @@ int m1v_set_float_pixel_layout(m1v_encoder *e, const m1v_float_pixel_layout *lay
         if (g.C != 3) return fail(M1V_E_ARG, "a float pixel layout needs an encoder created with 3 channels (the pixel's sample count is the layout's)%s");
         if (g.W & 1) return fail(M1V_E_ARG, "a float pixel layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
         if (layout->order != M1V_ORDER_RGB && layout->order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
-        const unsigned long long S = float_sample_bytes(layout->sample);
-        if (!S) return fail(M1V_E_ARG, "unknown sample type (M1V_SAMPLE_F16, M1V_SAMPLE_BF16, M1V_SAMPLE_F32)%s");
-        if (layout->range != M1V_RANGE_UNIT && layout->range != M1V_RANGE_BYTE) return fail(M1V_E_ARG, "unknown range (M1V_RANGE_UNIT, M1V_RANGE_BYTE)%s");
-        const unsigned long long step = layout->pixel_step, pitch = layout->row_pitch;
+        if (const int rc = float_format(layout->sample, layout->range, want.fmt)) return rc;
+        const unsigned long long S = want.fmt.bytes, step = layout->pixel_step, pitch = layout->row_pitch;
         if (step == S)
             return fail(M1V_E_ARG, "a pixel step of one sample describes a plane, not pixels: m1v_set_float_plane_layout serves planar float frames%s");
         if (step != 3 * S && step != 4 * S) return fail(M1V_E_ARG, "pixel step must be 3 or 4 samples (%s bytes)", S == 2 ? "6 or 8" : "12 or 16");
-        if ((pitch | layout->frame_stride) % S)
-            return fail(M1V_E_ARG, "row pitch and frame stride must be multiples of the sample size (%s bytes)", S == 2 ? "2" : "4");
-        const unsigned long long row = (unsigned long long)g.W * step;
-        if (pitch < row) return fail(M1V_E_ARG, "row pitch below width * pixel step%s");
-        const unsigned long long limit = 1ull << 32;
-        if (pitch >= limit || (unsigned long long)(g.H - 1) * pitch + row >= limit)
-            return fail(M1V_E_ARG, "a frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
-        if (layout->frame_stride < (unsigned long long)(g.H - 1) * pitch + row) return fail(M1V_E_ARG, "frame stride below the bytes a frame's rows span%s");
+        if (const int rc = whole_samples(want.fmt, pitch | layout->frame_stride, "row pitch and frame stride")) return rc;
+        if (const int rc = rows_fit(pitch, (unsigned long long)g.W * step, (unsigned long long)g.H, layout->frame_stride,
+                                    "row pitch below width * pixel step", "frame", "frame stride below the bytes a frame's rows span"))
+            return rc;
         want.kind = LayoutKind::float_pixels;
-        want.float_pixels = {{(uint32_t)pitch, layout->range == M1V_RANGE_UNIT ? 255.0f : 1.0f, layout->order == M1V_ORDER_BGR ? 1u : 0u},
-                             (uint32_t)step, layout->sample, layout->range};
+        want.float_pixels = {{(uint32_t)pitch, want.fmt.scale, layout->order == M1V_ORDER_BGR ? 1u : 0u}, (uint32_t)step};
         want.frame_stride = layout->frame_stride;
     }
     return apply_layout(e, want);
@@ -916,43 +907,28 @@ int m1v_float_pixel_layout_in_force(const m1v_encoder *e, m1v_float_pixel_layout
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (e->layout.kind != LayoutKind::float_pixels) return 0;
     const m1v_encoder::Layout::FloatPixels &f = e->layout.float_pixels;
-    if (out) *out = {f.front.row_pitch, e->layout.frame_stride, f.pixel_step, (int32_t)(f.front.bgr ? M1V_ORDER_BGR : M1V_ORDER_RGB), f.sample, f.range};
+    if (out) *out = {f.front.row_pitch, e->layout.frame_stride, f.pixel_step, (int32_t)(f.front.bgr ? M1V_ORDER_BGR : M1V_ORDER_RGB), e->layout.fmt.sample, e->layout.fmt.range};
     return 1;
 }
 
 int m1v_float_pixels_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream) {
-    if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (e->layout.kind != LayoutKind::float_pixels) return fail(M1V_E_ARG, "m1v_float_pixels_to_bytes_device needs a float pixel layout in force (m1v_set_float_pixel_layout)%s");
-    if (n_frames < 0 || ((!d_frames || !d_bytes) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
-    if (const int rc = check_frame_table(e, static_cast<const uint8_t *>(d_frames))) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    const m1v_encoder::Layout::FloatPixels &f = e->layout.float_pixels;
-    const void *kernel = f.sample == M1V_SAMPLE_F32 ? (const void *)&k_float_pixels_to_bytes<F32Sample>
-                         : (f.sample == M1V_SAMPLE_BF16 ? (const void *)&k_float_pixels_to_bytes<Bf16Sample> : (const void *)&k_float_pixels_to_bytes<F16Sample>);
-    const unsigned pixels = (unsigned)e->g.W * (unsigned)e->g.H;
-    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
-        const int n = std::min(n_frames - done, 65535);
-        FloatPixelBytesArgs a = {static_cast<const uint8_t *>(d_frames) + (unsigned long long)done * e->layout.frame_stride,
-                                 d_bytes + (unsigned long long)done * 3ull * pixels, f.front, e->layout.frame_stride,
-                                 (uint32_t)e->g.W, (uint32_t)e->g.H, f.pixel_step};
-        void *args[] = {&a};
-        HIP_TRY(hipLaunchKernel(kernel, dim3((pixels + 255u) / 256u, (unsigned)n), dim3(256u), args, 0, (hipStream_t)stream));
-    }
-    return M1V_OK;
+    static const void *const kernels[3] = {(const void *)&k_float_pixels_to_bytes<F16Sample>, (const void *)&k_float_pixels_to_bytes<Bf16Sample>,
+                                           (const void *)&k_float_pixels_to_bytes<F32Sample>};
+    return float_to_bytes(
+        e, LayoutKind::float_pixels, "m1v_float_pixels_to_bytes_device needs a float pixel layout in force (m1v_set_float_pixel_layout)", kernels,
+        d_frames, n_frames, d_bytes, stream,
+        [e](const uint8_t *frames, uint8_t *bytes) {
+            const m1v_encoder::Layout::FloatPixels &f = e->layout.float_pixels;
+            return FloatPixelBytesArgs{frames, bytes, f.front, e->layout.frame_stride, (uint32_t)e->g.W, (uint32_t)e->g.H, f.pixel_step};
+        },
+        [e](unsigned n) { return dim3(((unsigned)e->g.W * (unsigned)e->g.H + 255u) / 256u, n); }); // (pixels)
 }
 
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (enable && e->layout.kind == LayoutKind::float_planes)
-        return fail(M1V_E_ARG, "a frame table does not serve a float plane layout (m1v_set_float_plane_layout): float frames behind a "
-                               "table are not covered%s");
-    if (enable && e->layout.kind == LayoutKind::float_pixels)
-        return fail(M1V_E_ARG, "a frame table does not serve a float pixel layout (m1v_set_float_pixel_layout): float frames behind a "
-                               "table are not covered%s");
-    if (enable && !e->layout.tiles_only())
-        return fail(M1V_E_ARG, "a frame table needs a surface, plane, sample or RGB plane layout: packed frames go through a table after "
-                               "m1v_set_input_layout(enc, width * channels, 0, order)%s");
+    const char *refusal = kind_facts(e->layout).no_frame_table;
+    if (enable && refusal) return fail(M1V_E_ARG, "%s", refusal);
     e->layout.table = enable ? TableMode::frames : TableMode::off;
     return M1V_OK;
 }
@@ -962,23 +938,8 @@ int m1v_frame_table(const m1v_encoder *e) { return e ? (e->layout.table == Table
 // The plane table is another value of the same field: each setter selects its own mode, either turns tables off
 int m1v_set_plane_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
-    if (enable) {
-        const m1v_encoder::Layout &l = e->layout;
-        if (l.kind == LayoutKind::packed)
-            return fail(M1V_E_ARG, "a plane table needs a plane layout (m1v_set_plane_layout) or an RGB plane layout (m1v_set_rgb_plane_layout): "
-                                   "packed pixels have no planes%s");
-        if (l.kind == LayoutKind::surface)
-            return fail(M1V_E_ARG, "a surface layout has one plane: m1v_set_frame_table serves it%s");
-        if (l.kind == LayoutKind::float_planes)
-            return fail(M1V_E_ARG, "a plane table does not serve a float plane layout (m1v_set_float_plane_layout): float planes behind "
-                                   "separate pointers are not covered%s");
-        if (l.kind == LayoutKind::float_pixels)
-            return fail(M1V_E_ARG, "a plane table does not serve a float pixel layout (m1v_set_float_pixel_layout): interleaved pixels "
-                                   "have no planes, and float frames behind a table are not covered%s");
-        if (l.kind == LayoutKind::samples && l.samples.y_step == 2)
-            return fail(M1V_E_ARG, "a plane table does not serve a (2, 4) sample layout: packed 4:2:2 has no planes, and P010 with separate "
-                                   "Y and UV pointers is not covered%s");
-    }
+    const char *refusal = kind_facts(e->layout).no_plane_table;
+    if (enable && refusal) return fail(M1V_E_ARG, "%s", refusal);
     e->layout.table = enable ? TableMode::planes : TableMode::off;
     return M1V_OK;
 }

@@ -8,6 +8,7 @@ arithmetic happens in libencoder.so's HIP kernels.
 """
 import ctypes as C
 import numbers
+from collections import namedtuple
 
 from . import _ffi
 
@@ -277,6 +278,32 @@ def plane_layout_extent(layout, strips, mb_rows):
     return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
 
 
+# The layout kinds: the property that describes one, its name in the C API (m1v_set_<c>_layout, m1v_<c>_layout_in_force), its
+# ctypes struct, fields, name in messages and preset function, whether a dict must hold every field, why frames() and
+# plane_frames() refuse it (None: they serve it).  In the order in which the C getters cannot fail (_refresh_input):
+# sample_layout holds a plane layout too (y_step 1); input_layout is never None (all zeros = packed frames).
+_Kind = namedtuple("_Kind", "prop c struct fields name preset exact no_frames no_plane_frames")
+_NO_PLANES = "a plane table needs a plane layout or an RGB plane layout in force"
+_KINDS = (
+    _Kind("float_pixel_layout", "float_pixel", _ffi.FloatPixelLayout, FLOAT_PIXEL_LAYOUT_FIELDS, "a float pixel layout", None, True,
+          "a frame table does not serve a float pixel layout (set_float_pixel_layout)",
+          "a plane table does not serve a float pixel layout (set_float_pixel_layout)"),
+    # (frames() checks and uploads float planes although m1v_set_frame_table refuses them)
+    _Kind("float_plane_layout", "float_plane", _ffi.FloatPlaneLayout, FLOAT_PLANE_LAYOUT_FIELDS, "a float plane layout", None, True, None, _NO_PLANES),
+    _Kind("rgb_plane_layout", "rgb_plane", _ffi.RgbPlaneLayout, RGB_PLANE_LAYOUT_FIELDS, "an RGB plane layout", rgb_plane_layout_preset, True, None, None),
+    _Kind("sample_layout", "sample", _ffi.SampleLayout, SAMPLE_LAYOUT_FIELDS, "a sample layout", sample_layout_preset, False, None, None),
+    _Kind("plane_layout", "plane", _ffi.PlaneLayout, PLANE_LAYOUT_FIELDS, "a plane layout", plane_layout_preset, False, None, None),
+    _Kind("input_layout", "input", None, ("row_pitch", "frame_stride", "order"), "a surface layout", None, False, None, _NO_PLANES),
+)
+_KIND = {k.prop: k for k in _KINDS}
+
+
+def _frames_apart(rgb, frame_stride, S=None):
+    """S: the bytes of an element where strides count elements"""
+    assert rgb.shape[0] <= 1 or rgb.stride(0) * (S or 1) == frame_stride, \
+        f"frames must lie {frame_stride} bytes apart (stride {rgb.stride(0)}{' elements' if S else ''})"
+
+
 class FrameTable:
     """A batch whose frames lie at separate device addresses (Mpeg1Encoder.frames, Mpeg1Encoder.set_frame_table): `table` is the
     int64 CUDA tensor [n] of the frames' base addresses, which the kernels read on the stream; `frames` keeps the tensors it
@@ -406,10 +433,8 @@ class Mpeg1Encoder:
 
     def _refresh_input(self):
         """What _check_input holds tensors against: (the property that describes the input layout in force, its value), asked of
-        the library in the order in which its getters cannot fail.  sample_layout also holds a plane layout (y_step 1);
-        input_layout is never None: all zeros = packed frames."""
-        kinds = ("float_pixel_layout", "float_plane_layout", "rgb_plane_layout", "sample_layout", "input_layout")
-        self._input = next((k, v) for k, v in ((k, getattr(self, k)) for k in kinds) if v is not None)
+        the library in the order of _KINDS."""
+        self._input = next((k.prop, v) for k, v in ((k, getattr(self, k.prop)) for k in _KINDS) if v is not None)
         self._table_on = self.frame_table   # (every successful layout setter turns the tables off)
         self._planes_on = self.plane_table
 
@@ -428,11 +453,11 @@ class Mpeg1Encoder:
             return
         assert not isinstance(rgb, FrameTable), "a FrameTable needs set_frame_table()"
         kind, want = self._input
-        if kind == "float_pixel_layout":  # [n, H, W, C], or [n, C, H, W] with channels-last strides, of the layout's dtype
-            dtype = {_ffi.SAMPLE_F16: torch.float16, _ffi.SAMPLE_BF16: torch.bfloat16, _ffi.SAMPLE_F32: torch.float32}[want["sample"]]
-            S = _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
+        if "sample" in _KIND[kind].fields:  # a float layout: tensors of its dtype, whose strides count elements of S bytes
+            dtype, S = getattr(torch, _ffi.FLOAT_SAMPLE_DTYPES[want["sample"]]), _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
-                f"the float pixel layout in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+                f"the {_KIND[kind].name[2:]} in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+        if kind == "float_pixel_layout":  # [n, H, W, C], or [n, C, H, W] with channels-last strides
             assert rgb.is_cuda and rgb.dim() == 4, "float pixel frames must be a CUDA tensor [n, H, W, C] or a channels-last [n, C, H, W]"
             size = (self.height, self.width)
             if tuple(rgb.shape[1:3]) == size and rgb.shape[3] in (3, 4):
@@ -447,24 +472,18 @@ class Mpeg1Encoder:
                 f"strides {tuple(rgb.stride())}: the samples of a pixel must be adjacent (planar NCHW frames: set_float_plane_layout)"
             assert pixel * S == want["pixel_step"] and pixel >= C_ and row * S == want["row_pitch"], \
                 f"strides {tuple(rgb.stride())} are not the float pixel layout in force (pixel step {want['pixel_step']}, row pitch {want['row_pitch']} bytes)"
-            assert rgb.shape[0] <= 1 or frame * S == want["frame_stride"], \
-                f"frames must lie {want['frame_stride']} bytes apart (stride {frame} elements)"
+            _frames_apart(rgb, want["frame_stride"], S)
             # every whole pixel of the read contract lies in the storage (a window's last pixel may lack its 4th sample)
             last = rgb.storage_offset() + max(rgb.shape[0] - 1, 0) * frame + (self.height - 1) * row + self.width * pixel
             assert rgb.shape[0] == 0 or last * S <= rgb.untyped_storage().nbytes(), \
                 "the tensor's storage ends inside the last pixel the encoder reads (a 4th sample beyond the view)"
             return
-        if kind == "float_plane_layout":  # [n, C, H, W] of the layout's dtype: strides in elements, times S = the layout's bytes
-            dtype = {_ffi.SAMPLE_F16: torch.float16, _ffi.SAMPLE_BF16: torch.bfloat16, _ffi.SAMPLE_F32: torch.float32}[want["sample"]]
-            S = _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
-            assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
-                f"the float plane layout in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+        if kind == "float_plane_layout":  # [n, C, H, W]: strides times S = the layout's bytes
             assert rgb.is_cuda and rgb.dim() == 4, "float plane frames must be a CUDA tensor [n, C, H, W]"
             assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
             assert rgb.stride(3) == 1 and rgb.stride(2) * S == want["row_pitch"], \
                 f"strides {tuple(rgb.stride())} are not the float plane layout in force (row pitch {want['row_pitch']} bytes)"
-            assert rgb.shape[0] <= 1 or rgb.stride(0) * S == want["frame_stride"], \
-                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)} elements)"
+            _frames_apart(rgb, want["frame_stride"], S)
             plane = rgb.stride(1) * S
             assert all(plane > 0 and want[k] % plane == 0 and want[k] // plane < rgb.shape[1] for k in ("r_offset", "g_offset", "b_offset")), \
                 f"the plane offsets in force are not channels of this tensor (plane stride {plane} bytes)"
@@ -476,8 +495,7 @@ class Mpeg1Encoder:
             assert rgb.shape[1] >= 3 and tuple(rgb.shape[2:]) == (self.height, self.width), "frames must be [n, C >= 3, H, W]"
             assert rgb.stride(3) == 1 and rgb.stride(2) == want["row_pitch"], \
                 f"strides {tuple(rgb.stride())} are not the RGB plane layout in force (row pitch {want['row_pitch']})"
-            assert rgb.shape[0] <= 1 or rgb.stride(0) == want["frame_stride"], \
-                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)})"
+            _frames_apart(rgb, want["frame_stride"])
             plane = rgb.stride(1)
             assert all(plane > 0 and want[k] % plane == 0 and want[k] // plane < rgb.shape[1] for k in ("r_offset", "g_offset", "b_offset")), \
                 f"the plane offsets in force are not channels of this tensor (plane stride {plane})"
@@ -487,8 +505,7 @@ class Mpeg1Encoder:
             extent = plane_layout_extent(want, self.strips, self.mb_rows)
             assert rgb.shape[0] == 0 or (rgb.stride(1) == 1 and rgb.shape[1] >= extent), \
                 f"a frame's row must be contiguous and hold the {extent} bytes its planes span"
-            assert rgb.shape[0] <= 1 or rgb.stride(0) == want["frame_stride"], \
-                f"frames must lie {want['frame_stride']} bytes apart (stride {rgb.stride(0)})"
+            _frames_apart(rgb, want["frame_stride"])
             return
         row_pitch, frame_stride, _ = want
         if row_pitch == 0:      # the default layout: packed frames
@@ -510,18 +527,18 @@ class Mpeg1Encoder:
         _call("m1v_set_input_layout", self._h, int(row_pitch), int(frame_stride), int(code))
         self._refresh_input()   # one input layout is in force at a time
 
-    def _set_layout(self, what, layout, preset, struct, fields, exact=False):
-        """m1v_set_<what>_layout with `layout`: a preset name, a dict of `fields` (exact: of all of them), or None."""
-        c = None
+    def _set_layout(self, prop, layout):
+        """The C setter of the kind of `prop` (_KINDS) with `layout`: a preset name, a dict of its fields, or None."""
+        k, c = _KIND[prop], None
         if layout is not None:
-            if isinstance(layout, str):
-                layout = preset(self.width, self.height, layout)
-            if exact and set(layout) != set(fields):
-                raise ValueError(f"an RGB plane layout has the fields {fields}")
-            if set(layout) - set(fields):
-                raise ValueError(f"unknown {what} layout fields {sorted(set(layout) - set(fields))}")
-            c = C.byref(struct(**{k: int(v) for k, v in layout.items()}))
-        _call(f"m1v_set_{what}_layout", self._h, c)
+            if isinstance(layout, str) and k.preset:
+                layout = k.preset(self.width, self.height, layout)
+            if k.exact and set(layout) != set(k.fields):
+                raise ValueError(f"{k.name} has the fields {k.fields}")
+            if set(layout) - set(k.fields):
+                raise ValueError(f"unknown {k.c} layout fields {sorted(set(layout) - set(k.fields))}")
+            c = C.byref(k.struct(**{f: int(v) for f, v in layout.items()}))
+        _call(f"m1v_set_{k.c}_layout", self._h, c)
         self._refresh_input()
 
     def set_plane_layout(self, layout):
@@ -531,7 +548,7 @@ class Mpeg1Encoder:
         header), or None = back to the default layout and its kernels.  Every call then takes uint8 CUDA tensors [n, L] whose
         rows are the frames: L >= the bytes a frame's planes span, rows frame_stride apart — convert(rgb).view(n, -1) and
         torch.as_strided views go in as they are.  A reconfiguration: call it between batches."""
-        self._set_layout("plane", layout, plane_layout_preset, _ffi.PlaneLayout, PLANE_LAYOUT_FIELDS)
+        self._set_layout("plane_layout", layout)
 
     def set_sample_layout(self, layout):
         """Frames whose samples lie one or two bytes apart, encoded where they lie (include/mpeg1_hip.h, m1v_set_sample_layout;
@@ -541,7 +558,7 @@ class Mpeg1Encoder:
         then takes uint8 CUDA tensors [n, L] as after set_plane_layout.  A uint16 P010 tensor goes in as
         frames.view(torch.uint8) (reshaped to [n, L]): the coded sample is each word's high byte, truncation, not rounding.
         A reconfiguration: call it between batches."""
-        self._set_layout("sample", layout, sample_layout_preset, _ffi.SampleLayout, SAMPLE_LAYOUT_FIELDS)
+        self._set_layout("sample_layout", layout)
 
     def set_rgb_plane_layout(self, layout):
         """Frames as planes of R, G and B bytes on the device — NCHW uint8 tensors — encoded where they lie, without a permute and
@@ -550,7 +567,7 @@ class Mpeg1Encoder:
         (rgb_plane_strides derives one from a tensor's shape and strides), or None = back to the default layout and its kernels.
         Every call then takes uint8 CUDA tensors [n, C >= 3, H, W] with those strides: a view x[:, :, y0:y0+H, x0:x0+W] of a larger
         tensor goes in as it is.  A reconfiguration: call it between batches."""
-        self._set_layout("rgb_plane", layout, rgb_plane_layout_preset, _ffi.RgbPlaneLayout, RGB_PLANE_LAYOUT_FIELDS, exact=True)
+        self._set_layout("rgb_plane_layout", layout)
 
     def set_float_plane_layout(self, layout):
         """Frames as planes of float R, G and B samples on the device — NCHW float16, bfloat16 or float32 tensors, a model's output
@@ -561,26 +578,25 @@ class Mpeg1Encoder:
         layout and its kernels.  Every call then takes CUDA tensors [n, C >= 3, H, W] of exactly that dtype with those strides: a
         view x[:, :, y0:y0+H, x0:x0+W] and three planes of a 4-plane tensor go in as they are; a uint8 tensor is refused.  Frame
         and plane tables do not serve it.  A reconfiguration: call it between batches."""
-        c = None
-        if layout is not None:
-            if set(layout) != set(FLOAT_PLANE_LAYOUT_FIELDS):
-                raise ValueError(f"a float plane layout has the fields {FLOAT_PLANE_LAYOUT_FIELDS}")
-            c = C.byref(_ffi.FloatPlaneLayout(**{k: int(v) for k, v in layout.items()}))
-        _call("m1v_set_float_plane_layout", self._h, c)
-        self._refresh_input()
+        self._set_layout("float_plane_layout", layout)
 
     def float_planes_to_bytes(self, x, out=None):
         """The bytes the encoder codes for the float tensor x under the float plane layout in force (include/mpeg1_hip.h,
         m1v_float_planes_to_bytes_device: the kernels' own conversion function): a uint8 CUDA tensor [n, 3, H, W] in R, G, B
         order, what set_rgb_plane_layout("rgb") takes.  Asynchronous on torch's current stream."""
+        return self._to_bytes("float_plane_layout", x, out, lambda n: (n, 3, self.height, self.width))
+
+    def _to_bytes(self, prop, x, out, shape):
+        """m1v_<c>s_to_bytes_device under the float layout that `prop` describes: the bytes of x as a uint8 tensor of shape(n)."""
         import torch
-        assert self._input[0] == "float_plane_layout", "float_planes_to_bytes() needs a float plane layout in force (set_float_plane_layout)"
+        k = _KIND[prop]
+        assert self._input[0] == prop, f"{k.c}s_to_bytes() needs {k.name} in force (set_{k.c}_layout)"
         self._check_input(x)
-        n = x.shape[0]
+        shape = shape(x.shape[0])
         if out is None:
-            out = torch.empty((n, 3, self.height, self.width), dtype=torch.uint8, device=x.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, 3, self.height, self.width)
-        _call("m1v_float_planes_to_bytes_device", self._h, _ptr(x), n, _ptr(out), _stream())
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape
+        _call(f"m1v_{k.c}s_to_bytes_device", self._h, _ptr(x), shape[0], _ptr(out), _stream())
         return out
 
     def set_float_pixel_layout(self, layout):
@@ -592,27 +608,13 @@ class Mpeg1Encoder:
         layout and its kernels.  Every call then takes CUDA tensors of exactly that dtype with those strides, as [n, H, W, C] or as
         a channels-last-strided [n, C, H, W]; a window x[:, y0:y0+H, x0:x0+W, :3] goes in as it is; uint8 and NCHW-contiguous
         tensors are refused.  Frame and plane tables do not serve it.  A reconfiguration: call it between batches."""
-        c = None
-        if layout is not None:
-            if set(layout) != set(FLOAT_PIXEL_LAYOUT_FIELDS):
-                raise ValueError(f"a float pixel layout has the fields {FLOAT_PIXEL_LAYOUT_FIELDS}")
-            c = C.byref(_ffi.FloatPixelLayout(**{k: int(v) for k, v in layout.items()}))
-        _call("m1v_set_float_pixel_layout", self._h, c)
-        self._refresh_input()
+        self._set_layout("float_pixel_layout", layout)
 
     def float_pixels_to_bytes(self, x, out=None):
         """The bytes the encoder codes for the float tensor x under the float pixel layout in force (include/mpeg1_hip.h,
         m1v_float_pixels_to_bytes_device: the kernels' own conversion function): a uint8 CUDA tensor [n, H, W, 3] in R, G, B
         order, what the default packed layout takes.  Asynchronous on torch's current stream."""
-        import torch
-        assert self._input[0] == "float_pixel_layout", "float_pixels_to_bytes() needs a float pixel layout in force (set_float_pixel_layout)"
-        self._check_input(x)
-        n = x.shape[0]
-        if out is None:
-            out = torch.empty((n, self.height, self.width, 3), dtype=torch.uint8, device=x.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, self.height, self.width, 3)
-        _call("m1v_float_pixels_to_bytes_device", self._h, _ptr(x), n, _ptr(out), _stream())
-        return out
+        return self._to_bytes("float_pixel_layout", x, out, lambda n: (n, self.height, self.width, 3))
 
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
@@ -650,9 +652,8 @@ class Mpeg1Encoder:
         planes = [tuple(f) for f in planes]
         assert planes and all(len(f) == 3 for f in planes), "plane_frames() needs at least one frame of three planes"
         kind, want = self._input
-        assert kind != "float_pixel_layout", "a plane table does not serve a float pixel layout (set_float_pixel_layout)"
-        assert kind in ("rgb_plane_layout", "sample_layout") and want.get("y_step", 1) == 1, \
-            "a plane table needs a plane layout or an RGB plane layout in force"
+        refusal = _KIND[kind].no_plane_frames
+        assert refusal is None and want.get("y_step", 1) == 1, refusal or _NO_PLANES
         xe, ye = self.strips * 16, self.mb_rows * 16
         back = [0, 0, 0]    # how far in front of the tensor's first byte the plane's pointer stands
         if kind == "rgb_plane_layout":  # a plane's range starts at its offset: the tensor is the plane, its pointer lies c_offset in front
@@ -689,7 +690,8 @@ class Mpeg1Encoder:
         import torch
         tensors = list(tensors)
         assert tensors, "frames() needs at least one frame"
-        assert self._input[0] != "float_pixel_layout", "a frame table does not serve a float pixel layout (set_float_pixel_layout)"
+        refusal = _KIND[self._input[0]].no_frames
+        assert refusal is None, refusal
         assert self._input != ("input_layout", (0, 0, "rgb")), "a frame table needs a layout: set_input_layout(width * channels) for packed frames"
         on, self._table_on = self._table_on, False
         try:
@@ -701,9 +703,9 @@ class Mpeg1Encoder:
         table = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(tensors[0].device)
         return FrameTable(table, tensors)
 
-    def _in_force(self, name, struct):
-        """The C getter `name` of a layout `struct`: the layout in force as a dict, or None where another kind is."""
-        c = struct()
+    def _in_force(self, prop):
+        """The C getter of the kind of `prop` (_KINDS): the layout in force as a dict, or None where another kind is."""
+        c, name = _KIND[prop].struct(), f"m1v_{_KIND[prop].c}_layout_in_force"
         rc = getattr(_ffi.lib(), name)(self._h, C.byref(c))
         if rc < 0:
             raise EncoderError(rc, name)
@@ -712,28 +714,28 @@ class Mpeg1Encoder:
     @property
     def float_pixel_layout(self):
         """The float pixel layout in force as a dict of FLOAT_PIXEL_LAYOUT_FIELDS (bytes; order, sample and range codes), or None."""
-        return self._in_force("m1v_float_pixel_layout_in_force", _ffi.FloatPixelLayout)
+        return self._in_force("float_pixel_layout")
 
     @property
     def float_plane_layout(self):
         """The float plane layout in force as a dict of FLOAT_PLANE_LAYOUT_FIELDS (bytes; sample and range codes), or None."""
-        return self._in_force("m1v_float_plane_layout_in_force", _ffi.FloatPlaneLayout)
+        return self._in_force("float_plane_layout")
 
     @property
     def rgb_plane_layout(self):
         """The RGB plane layout in force as a dict of RGB_PLANE_LAYOUT_FIELDS in bytes, or None."""
-        return self._in_force("m1v_rgb_plane_layout_in_force", _ffi.RgbPlaneLayout)
+        return self._in_force("rgb_plane_layout")
 
     @property
     def sample_layout(self):
         """The plane or sample layout in force as a dict of SAMPLE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros;
         y_step = 1 for a layout set through set_plane_layout), or None."""
-        return self._in_force("m1v_sample_layout_in_force", _ffi.SampleLayout)
+        return self._in_force("sample_layout")
 
     @property
     def plane_layout(self):
         """The plane layout in force as a dict of PLANE_LAYOUT_FIELDS in bytes, as the kernels use it (no zeros), or None."""
-        return self._in_force("m1v_plane_layout_in_force", _ffi.PlaneLayout)
+        return self._in_force("plane_layout")
 
     @property
     def input_layout(self):
