@@ -93,7 +93,7 @@
     const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
 
     // ---- entropy pass 1 (private: own staged levels, shared read-only VLC table) ----
-    auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
+    auto fetch = [&](int p) -> int { return tile_fetch_level<STAGE8>(blkp, (uint32_t)p); };
     uint32_t hdr = 0, bad = 0;
     int hlen = 0;
     BlockBits bb = {0, 0};
@@ -101,7 +101,7 @@
     const unsigned long long emit = emit_set(nz);
     // one coefficient per trip: two per trip (half the dependent LDS round trips) measured no faster in bursts and 1 % slower in
     // a sustained run — the lanes with a single coefficient left do the second one's work for nothing (r03_ab_history.txt)
-    block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit, vlc, fetch, bb.acc, bb.tot, bad);
+    tile_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit, vlc, fetch, bb.acc, bb.tot, bad);
     if (!valid) {
         bb.tot = 0;
         bad = 0;
@@ -141,7 +141,7 @@
     const uint32_t off = my_base * 32u + slice_bits + (G[e] - my_gs);
     TSTAMP(6);
 
-    auto walk = [&](auto &sink) { walk_codes<STAGE8>(hdr, hlen, dc != 0, emit, vlc, fetch, sink); };
+    auto walk = [&](auto &sink) { tile_walk_codes<STAGE8>(hdr, hlen, dc != 0, emit, vlc, fetch, sink); };
     // The strip's bit total (wave 0, lanes < strips_here): one returning atomic per segment; the tile whose add finds every other
     // tile row of the strip already counted knows the strip's bits and adds its bytes (zero bits pad a strip to a byte,
     // encoder.h:442-443) to the frame's total.  Only the values the atomics return travel between tiles: no fence.

@@ -87,7 +87,7 @@
     const int e = j * kTileSegBlocks + m * 6 + blk; // position in the tile's emission order (strip, macroblock, block)
     // every row-step has landed and has been read: the ring's bytes now hold the staged levels of the wave's blocks
     const uint32_t *blkp = lds + region_off / 4u + lane * kStride;
-    auto fetch = [&](int p) -> int { return fetch_level<STAGE8>(blkp, p); };
+    auto fetch = [&](int p) -> int { return tile_fetch_level<STAGE8>(blkp, (uint32_t)p); };
 
     // ---- per quality: quantise, stage, mask, count (pass 1) ----
     uint32_t bad_q = 0; // bit k: an unencodable level at quality k
@@ -108,7 +108,7 @@
         int hlen = 0;
         BlockBits bb = {0, 0};
         dc_header(dc, blk < 4, blk, vlc, hdr, hlen);
-        block_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
+        tile_bits_pass1<STAGE8>(hdr, hlen, dc != 0, emit_set(nz), vlc, fetch, bb.acc, bb.tot, bad);
         cnt[k * kTileThreads + e] = valid ? (uint32_t)bb.tot : 0u;
         bad_q |= (valid && bad) ? 1u << k : 0u;
         if constexpr (RD) {

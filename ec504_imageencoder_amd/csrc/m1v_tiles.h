@@ -225,19 +225,30 @@ struct StagePack {
         }
     }
     // stage_nonzero_mask on the registers (bit 0, the DC level's, is clear: the caller sets it), then the stores are waited
-    // for: the lane's LDS reads of its staged levels (fetch_level) come behind this statement, and so does every use of the
+    // for: the lane's LDS reads of its staged levels (tile_fetch_level) come behind this statement, and so does every use of the
     // mask, so the wait sits behind the mask arithmetic.
     __device__ __forceinline__ unsigned long long mask_and_fence(uint32_t &lds_addr) const {
         uint32_t half[2] = {0u, 0u};
+        if constexpr (STAGE8) {
+            // Byte staging: v_lerp_u8(w, ~0, 0) = (byte + 255) >> 1 per byte sets bit 7 of a byte exactly when the byte is
+            // non-zero: one instruction for a word's flags instead of three ((w & 0x7f..) + 0x7f.. | w).  Word j's flags belong
+            // at bit j of each byte: the words are taken in order, the collected flags move down one bit per word and
+            // v_bfi_b32 takes bit 7 of every byte from the new word: three instructions per word, five to six before.  What
+            // else word 0's lerp leaves in bits 0..6 has been shifted through a bit 7, and so replaced, by the time word 7 is
+            // in.  (asm: written in C++ the compiler reassociates the chain into shifts, ANDs and ORs of its own, a third more.)
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if (STAGE8) {
+            for (int h = 0; h < 2; h++) {
+                uint32_t acc = __builtin_amdgcn_lerp(w[h * 8], ~0u, 0u);
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const uint32_t f = ((w[h * 8 + j] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w[h * 8 + j];
-                    half[h] |= (f >> (7 - j)) & (0x01010101u << j);
+                for (int j = 1; j < 8; j++) {
+                    const uint32_t f = __builtin_amdgcn_lerp(w[h * 8 + j], ~0u, 0u), down = acc >> 1;
+                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(acc) : "s"(0x80808080u), "v"(f), "v"(down));
                 }
-            } else {
+                half[h] = acc;
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
 #pragma unroll
                 for (int j = 0; j < 16; j++) {
                     const uint32_t f = ((w[h * 16 + j] & 0x7fff7fffu) + 0x7fff7fffu) | w[h * 16 + j];
@@ -251,6 +262,82 @@ struct StagePack {
 };
 // (tests/test_stage_packing.py replays the whole plan; here only its first pair: the narrow form finishes no word before column 4)
 static_assert(StagePack<true>::pair(3, 0, 0) == -1 && StagePack<true>::pair(4, 0, 0) == 0 && StagePack<true>::pair(4, 0, 1) == 1, "narrow staging plan");
+
+// ---- the code walk of the tile kernels ----------------------------------------------------------------------------------
+// The same walk as the run kernels' (block_bits_pass1, walk_codes in m1v_kernels.hip: one coded level per trip, branch-free,
+// ac_code for the code word) with a cheaper trip; the run kernels keep theirs instruction for instruction.
+//
+// The staged level at zigzag position p, by ONE sign-extending LDS read at the level's own byte (halfword): no word read, no
+// computed shift amount, no shift pair.  The address is stage_byte8(p) / stage_byte16(p), written as bit moves:
+//   narrow  ((p & 7) + 8 (p >> 5)) * 4 + ((p >> 3) & 3)  =  (p & 32) | rotl5(p & 31, 2)       (bits 4..0 rotated left by two)
+//   wide    ((p & 15) + 16 (p >> 5)) * 4 + 2 ((p >> 4) & 1)  =  (p & 15) << 2 | (p & 32) << 1 | (p & 16) >> 3
+// (tests/test_bits_trip_cpu.py checks both forms against the layout for every p).
+typedef int16_t __attribute__((may_alias)) staged_i16;
+__host__ __device__ constexpr uint32_t tile_stage_byte8(uint32_t p) { return (p & 32u) | (((((p & 31u) << 5) | (p & 31u)) >> 3) & 31u); }
+__host__ __device__ constexpr uint32_t tile_stage_byte16(uint32_t p) { return ((p & 15u) << 2) | ((p & 32u) << 1) | ((p & 16u) >> 3); }
+template <bool STAGE8>
+__device__ __forceinline__ int tile_fetch_level(const uint32_t *blk, uint32_t p) {
+    int level;
+    if constexpr (STAGE8)
+        level = reinterpret_cast<const int8_t *>(blk)[tile_stage_byte8(p)];
+    else
+        level = *reinterpret_cast<const staged_i16 *>(reinterpret_cast<const char *>(blk) + tile_stage_byte16(p));
+    // (opaque: ac_code also takes the level's low byte, and seeing that use the compiler loads the byte unsigned and extends
+    //  the sign with an instruction of its own)
+    asm("" : "+v"(level));
+    return level;
+}
+static_assert(tile_stage_byte8(0) == stage_byte8(0) && tile_stage_byte8(27) == stage_byte8(27) && tile_stage_byte8(63) == stage_byte8(63), "narrow staging address");
+static_assert(tile_stage_byte16(0) == stage_byte16(0) && tile_stage_byte16(27) == stage_byte16(27) && tile_stage_byte16(63) == stage_byte16(63), "wide staging address");
+
+// The coded positions of `emit` in ascending order, each with its run - 1 (ac_code's r), by shifting the set out: `rest` holds
+// the positions behind the one coded last (`pos`), its lowest set bit z zeros further on.  One 64-bit shift per trip instead
+// of emit &= emit - 1 (a 64-bit subtract and two ANDs), and the run comes from z, not from a difference of positions.
+// emit's bit 0 (the DC level's) is clear, so the set starts shifted by one: z <= 62 and the shift count z + 1 stays below 64.
+// A zero DC level is one more zero in front of the FIRST coded level only (image_processing.c:716-722): `lead` is -1 from the
+// second trip on, and the compiler peels the first trip off the loop, so the loop itself adds a constant.
+template <typename Each>
+__device__ __forceinline__ void tile_walk_emit(bool dc_nonzero, unsigned long long emit, Each each) {
+    unsigned long long rest = emit >> 1;
+    int pos = 0;
+    int lead = dc_nonzero ? -1 : 0;
+    while (rest) {
+        const int z = __builtin_ctzll(rest);
+        rest >>= z + 1;
+        pos += z + 1;
+        const int r = z + lead;
+        __builtin_assume(r >= 0 && r < 63); // (no two neighbours in emit_set, and not position 1 behind a non-zero DC level)
+        each(pos, r);
+        lead = -1;
+    }
+}
+// block_bits_pass1 and walk_codes on that walk
+template <bool NARROW, typename Fetch>
+__device__ __forceinline__ void tile_bits_pass1(uint32_t hdr, int hlen, bool dc_nonzero, unsigned long long emit, const uint32_t *vlc,
+                                                Fetch fetch, unsigned long long &acc, int &tot, uint32_t &bad) {
+    unsigned long long bits_acc = hdr;
+    int n = hlen;
+    tile_walk_emit(dc_nonzero, emit, [&](int p, int r) {
+        uint32_t code, bits;
+        ac_code<NARROW>(vlc, r, fetch(p), code, bits, bad);
+        bits_acc = (bits_acc << bits) | code;
+        n += (int)bits;
+    });
+    acc = (bits_acc << 2) | 0x2u; // EOB "10", mpeg1_blk.c:115-117
+    tot = n + 2;
+}
+template <bool NARROW, typename Fetch, typename Sink>
+__device__ __forceinline__ void tile_walk_codes(uint32_t hdr, int hlen, bool dc_nonzero, unsigned long long emit, const uint32_t *vlc,
+                                                Fetch fetch, Sink &sink) {
+    sink(hdr, hlen);
+    uint32_t bad = 0;
+    tile_walk_emit(dc_nonzero, emit, [&](int p, int r) {
+        uint32_t code, bits;
+        ac_code<NARROW>(vlc, r, fetch(p), code, bits, bad);
+        sink(code, (int)bits);
+    });
+    sink(0x2u, 2);
+}
 
 // column pass + quantise + stage in LDS; returns the DC level, nz = the non-zero mask of the AC levels (bit 0 clear)
 template <bool STAGE8, int KEEP>
