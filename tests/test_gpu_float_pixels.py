@@ -402,7 +402,8 @@ def test_argument_errors_leave_the_layout_in_force(torch_cuda, orc, kind):
         with pytest.raises(EncoderError):
             enc.set_float_pixel_layout(lay)
     assert _encode(torch, enc, x, 0) == want
-    # the largest extent whose offsets are still 32-bit, and the smallest stride
+    # the largest extent whose offsets are still 32-bit (only set here; encoded in tests/test_gpu_address_space.py), and the
+    # smallest stride
     edge = (2 ** 32 - 1 - W * step) // (H - 1) // S * S
     assert L.m1v_set_float_pixel_layout(enc._h, C.byref(_ffi.FloatPixelLayout(**dict(good, row_pitch=edge, frame_stride=big)))) == 0
     least = (H - 1) * P + W * step

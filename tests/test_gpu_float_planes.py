@@ -405,7 +405,8 @@ def test_argument_errors_leave_the_layout_in_force(torch_cuda, orc, kind):
         with pytest.raises(EncoderError):
             enc.set_float_plane_layout(lay)
     assert _encode(torch, enc, x, 0) == want
-    # the largest extent whose offsets are still 32-bit, the smallest stride, and planes interleaved by rows
+    # the largest extent whose offsets are still 32-bit (only set here; encoded in tests/test_gpu_address_space.py), the smallest
+    # stride, and planes interleaved by rows
     edge = 2 ** 32 - (H - 1) * P - W * S - S
     assert L.m1v_set_float_plane_layout(enc._h, C.byref(_ffi.FloatPlaneLayout(**dict(good, b_offset=edge, frame_stride=big)))) == 0
     least = good["b_offset"] - good["r_offset"] + (H - 1) * P + W * S

@@ -375,7 +375,8 @@ def test_argument_errors_leave_the_layout_in_force(torch_cuda, orc):
         with pytest.raises(EncoderError):
             enc.set_rgb_plane_layout(lay)
     assert _encode(torch, enc, dev, 0) == want
-    # the largest extent whose offsets are still 32-bit, the smallest stride, and rows of the three planes interleaved with padding
+    # the largest extent whose offsets are still 32-bit (only set here; encoded in tests/test_gpu_address_space.py), the smallest
+    # stride, and rows of the three planes interleaved with padding
     assert L.m1v_set_rgb_plane_layout(enc._h, C.byref(_ffi.RgbPlaneLayout(**dict(good, b_offset=2 ** 32 - (H - 1) * P - W - 1, frame_stride=big)))) == 0
     assert L.m1v_set_rgb_plane_layout(enc._h, C.byref(_ffi.RgbPlaneLayout(**dict(good, frame_stride=good["b_offset"] + (H - 1) * P + W)))) == 0
     assert L.m1v_set_rgb_plane_layout(enc._h, C.byref(_ffi.RgbPlaneLayout(0, W + 1, 2 * W + 2, 3 * W + 3, H * (3 * W + 3)))) == 0

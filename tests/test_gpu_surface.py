@@ -474,7 +474,8 @@ def test_argument_errors(torch_cuda):
                 (row, 0, 2), (0, 0, -1), (row, H * row, 7)):                  # an unknown order
             assert L.m1v_set_input_layout(enc._h, pitch, stride, order) == _ffi.E_ARG, (pitch, stride, order)
             assert enc.input_layout == good and enc.path == "tiles"
-        # the largest window whose offsets are still 32-bit is accepted (nothing is read until a call)
+        # the largest window whose offsets are still 32-bit is accepted (only set here: tests/test_gpu_address_space.py encodes
+        # through this pitch, in a pool that holds every offset it reaches)
         assert L.m1v_set_input_layout(enc._h, (2 ** 32 - row - 1) // (H - 1), 0, 0) == 0
         enc.set_input_layout()
         assert enc.input_layout == (0, 0, "rgb")
