@@ -90,8 +90,8 @@ _u8p = C.POINTER(C.c_uint8)
 
 # every symbol include/mpeg1_hip.h declares (tests check that the library exports all of them)
 MPEG1_HIP_SYMBOLS = [
-    "m1v_device_count", "m1v_warm_up", "m1v_last_error", "m1v_create", "m1v_destroy", "m1v_strips", "m1v_mb_rows",
-    "m1v_frame_bound", "m1v_frame_bound_for", "m1v_frame_bytes_in", "m1v_file_prolog", "m1v_encode_device", "m1v_encode_host",
+    "m1v_device_count", "m1v_warm_up", "m1v_last_error", "m1v_create", "m1v_batch_limit", "m1v_destroy", "m1v_strips",
+    "m1v_mb_rows", "m1v_frame_bound", "m1v_frame_bound_for", "m1v_frame_bytes_in", "m1v_file_prolog", "m1v_encode_device", "m1v_encode_host",
     "m1v_encode_planes_host", "m1v_encode_quality_device", "m1v_frame_sizes_device", "m1v_encode_budget_device",
     "m1v_frame_size_table_device", "m1v_encode_batch_budget_device", "m1v_encode_cbr_device",
     "m1v_frame_rd_table_device", "m1v_encode_rd_device",
@@ -140,7 +140,7 @@ def lib():
     L.m1v_create.restype = C.c_int
     L.m1v_destroy.argtypes = [vp]
     L.m1v_destroy.restype = None
-    for name in ("m1v_strips", "m1v_mb_rows"):
+    for name in ("m1v_strips", "m1v_mb_rows", "m1v_batch_limit"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = C.c_int
     for name in ("m1v_frame_bound", "m1v_frame_bytes_in"):

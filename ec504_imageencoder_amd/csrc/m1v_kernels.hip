@@ -1767,6 +1767,7 @@ struct m1v_encoder {
     int device = 0;
     Geometry g = {};
     int qf = 0, mode = 0, max_frames = 0;
+    int batch_limit = 0;    // what bounds a call's frames beside max_frames: the device's smaller grid extent in y and z (m1v_create)
     bool dense = false;     // blocks per strip >= 64: k_encode_dense, else one workgroup per strip
     bool narrow = false;    // no AC level can reach +-128: one byte per staged level
     bool fast_ok = false;   // geometry allows the 4-byte-aligned 24-byte row loads
@@ -2298,6 +2299,19 @@ static int check_frame_table(const m1v_encoder *e, const uint8_t *d_rgb) {
     return fail(M1V_E_ARG, "a frame table is on (m1v_set_frame_table): d_rgb is an array of 64-bit frame addresses and must be 8-byte aligned%s");
 }
 
+// The frame count of one call, in front of everything it queues: within max_frames, and within the grid extents of the device,
+// since k_assemble takes the batch's frames as its grid's y and the run-shaped k_coefficients as its grid's z (m1v_batch_limit).
+static int check_grid_frames(const m1v_encoder *e, int n_frames) {
+    if (n_frames > e->batch_limit)
+        return fail(M1V_E_ARG, "n_frames exceeds the %s frames of one batch on this device (m1v_batch_limit: a grid's y and z extent)",
+                    std::to_string(e->batch_limit).c_str());
+    return M1V_OK;
+}
+static int check_batch_frames(const m1v_encoder *e, int n_frames) {
+    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    return check_grid_frames(e, n_frames);
+}
+
 // From its construction on, an error return leaves counters half used: the flag tells the next call to clear them first
 struct PoisonOnReturn {
     bool *flag;
@@ -2350,7 +2364,7 @@ struct EncodeOut {
 static int encode_batch(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, int first_frame_index, const Selection *sel, bool probe,
                         const EncodeOut &o, void *stream) {
     if (!e || (!d_rgb && n_frames > 0) || (!o.out && !probe)) return fail(M1V_E_ARG, "null pointer%s"); // (an empty batch reads no input)
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (const int rc = check_batch_frames(e, n_frames)) return rc;
     if (const int rc = check_frame_table(e, d_rgb)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));

@@ -420,9 +420,13 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (n <= 0) return fail(M1V_E_NODEVICE, "no HIP device%s");
     if (device < 0 || device >= n) return fail(M1V_E_ARG, "device index out of range%s");
     HIP_TRY(hipSetDevice(device));
+    int grid_y = 0, grid_z = 0;
+    HIP_TRY(hipDeviceGetAttribute(&grid_y, hipDeviceAttributeMaxGridDimY, device));
+    HIP_TRY(hipDeviceGetAttribute(&grid_z, hipDeviceAttributeMaxGridDimZ, device));
 
     m1v_encoder *e = new m1v_encoder();
     e->device = device;
+    e->batch_limit = std::min(grid_y, grid_z);
     e->qf = quality_factor;
     e->mode = mode;
     e->max_frames = max_frames;
@@ -527,6 +531,7 @@ void m1v_destroy(m1v_encoder *e) {
     delete e;
 }
 
+int m1v_batch_limit(const m1v_encoder *e) { return e ? std::min(e->max_frames, e->batch_limit) : 0; }
 int m1v_strips(const m1v_encoder *e) { return e ? e->g.n_strips : 0; }
 int m1v_mb_rows(const m1v_encoder *e) { return e ? e->g.n_mbrows : 0; }
 size_t m1v_frame_bytes_in(const m1v_encoder *e) { return e ? (size_t)e->g.frame_bytes : 0; }
@@ -1080,7 +1085,7 @@ static int check_candidate_call(const m1v_encoder *e, bool first, const uint8_t 
     for (int k = 0; k < n_q && !on_table; k++)
         if (q[k] < 1 || q[k] > encoder_quality(e) || (k > 0 && q[k] <= q[k - 1]))
             return fail(M1V_E_ARG, "candidates must increase strictly within 1 .. the encoder's quality factor%s");
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (const int rc = check_batch_frames(e, n_frames)) return rc;
     return then ? M1V_OK : fail(M1V_E_ARG, "null pointer%s");
 }
 
@@ -1438,7 +1443,7 @@ int m1v_encode_streams_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (const int rc = check_spans(d_spans, n_streams)) return rc;
     if ((!d_rgb && n_frames > 0) || !d_out) return fail(M1V_E_ARG, "null pointer%s");
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (const int rc = check_batch_frames(e, n_frames)) return rc;
     StreamsStep s = {};
     s.spans = d_spans;
     s.n_streams = n_streams;
@@ -1624,6 +1629,7 @@ int m1v_delivery_step(m1v_delivery *d, const uint8_t *d_rgb, int n_frames, int f
     if (!d || !d_rgb) return fail(M1V_E_ARG, "null pointer%s");
     if (n_frames <= 0 || n_frames > d->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
     m1v_encoder *e = d->e;
+    if (const int rc = check_batch_frames(e, n_frames)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(e->device));
     const int b = (int)(d->step_no++ & 1u);
@@ -1691,7 +1697,7 @@ long m1v_encode_planes_host(m1v_encoder *e, const uint8_t *rgb, int n_frames, in
                             uint8_t *out, size_t out_cap, uint64_t *frame_sizes, uint8_t *planes) {
     if (!e || !rgb || !out) return fail(M1V_E_ARG, "null pointer%s");
     if (const int rc = packed_only(e)) return rc;
-    if (n_frames < 0 || n_frames > e->max_frames) return fail(M1V_E_ARG, "n_frames exceeds max_frames%s");
+    if (const int rc = check_batch_frames(e, n_frames)) return rc;
     if (n_frames == 0) return 0;
     HIP_TRY(hipSetDevice(e->device));
     const size_t frame_in = (size_t)e->g.frame_bytes, frame_planes = (size_t)e->g.W * e->g.H * 3;
@@ -1807,6 +1813,9 @@ int m1v_coefficients_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, 
         HIP_TRY(hipGetLastError());
         return M1V_OK;
     }
+    // (the batch's frames are this grid's z: the long-batch rule; the tile form above has a one-dimensional grid.  The call is
+    // not bound by max_frames: it uses no scratch)
+    if (const int rc = check_grid_frames(e, n_frames)) return rc;
     int bps = e->g.n_mbrows * 6;
     dim3 grid((bps + 255) / 256, e->g.n_strips, n_frames);
     if (fast_path(e, d_rgb))

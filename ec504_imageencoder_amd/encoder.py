@@ -386,6 +386,9 @@ class Mpeg1Encoder:
         L = _ffi.lib()
         self.strips, self.mb_rows = L.m1v_strips(self._h), L.m1v_mb_rows(self._h)
         self.frame_bound = L.m1v_frame_bound(self._h)
+        # the long-batch rule (include/mpeg1_hip.h, m1v_create): min(max_frames, the device's grid extents in y and z); a call
+        # with more frames raises EncoderError (E_ARG) before anything is queued
+        self.batch_limit = L.m1v_batch_limit(self._h)
         self.frame_bytes_in = L.m1v_frame_bytes_in(self._h)
         self.blocks_per_frame = self.strips * self.mb_rows * 6
         self._refresh_input()

@@ -86,9 +86,19 @@ const char *m1v_last_error(void); /* thread-local, never NULL */
 
 /* One encoder = one device, one picture geometry, one quality factor (the finest a frame of it can have: see
  * m1v_encode_quality_device).  max_frames bounds the batch
- * a single m1v_encode_* call may carry (scratch is sized for it). */
+ * a single m1v_encode_* call may carry (scratch is sized for it).
+ *
+ * The long-batch rule.  Any positive max_frames is accepted, but one call carries at most m1v_batch_limit(enc) frames: the
+ * smaller of max_frames and of the extents the device reports for a grid's y and z axes (hipDeviceAttributeMaxGridDimY / Z; the
+ * assembly kernel takes the batch's frames as its grid's y, the run-shaped coefficient kernel as its grid's z).  Every call that
+ * takes n_frames and is bound by max_frames, and m1v_coefficients_device where the run-shaped kernel serves it (4 channels, or a
+ * path or input mode forced by a m1v_debug_set_* hook; its tile form has a one-dimensional grid and takes any n_frames), refuses
+ * a longer batch with M1V_E_ARG and a reason that names the limit, in front of everything it would queue: nothing is launched, no
+ * counter set is taken, and the next call on the encoder is an ordinary one.  A longer sequence is encoded in several calls (first_frame_index carries the position).  The
+ * two to-bytes calls, m1v_convert_device and m1v_synth_device are not bound by it: they split their grids themselves. */
 int m1v_create(m1v_encoder **out, int device, int width, int height, int channels,
                int quality_factor, int mode, int max_frames);
+int m1v_batch_limit(const m1v_encoder *enc); /* the most frames one call may carry: min(max_frames, grid y, grid z extent) */
 void m1v_destroy(m1v_encoder *enc);
 
 /* Scratch policy.  Every run of 256 blocks owns a compact slot (what the kernel's LDS image of its bits can hold: 2 KiB at
