@@ -101,7 +101,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
     "m1v_debug_set_input_mode", "m1v_reserve_scratch", "m1v_scratch_bytes", "m1v_debug_set_path", "m1v_path_in_use", "m1v_debug_fail_alloc",
-    "m1v_debug_fail_encode", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
+    "m1v_debug_fail_encode", "m1v_debug_assemble_shape", "m1v_debug_set_assemble_shape", "m1v_size_table_fused", "m1v_set_input_layout", "m1v_input_layout",
     "m1v_plane_layout_preset", "m1v_set_plane_layout", "m1v_plane_layout_in_force",
     "m1v_sample_layout_preset", "m1v_set_sample_layout", "m1v_sample_layout_in_force",
     "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
@@ -232,6 +232,10 @@ def lib():
     L.m1v_debug_set_path.restype = C.c_int
     L.m1v_path_in_use.argtypes = [vp]
     L.m1v_path_in_use.restype = C.c_int
+    L.m1v_debug_assemble_shape.argtypes = [vp, C.POINTER(C.c_int)]
+    L.m1v_debug_assemble_shape.restype = C.c_int
+    L.m1v_debug_set_assemble_shape.argtypes = [vp, C.c_int, C.c_int]
+    L.m1v_debug_set_assemble_shape.restype = C.c_int
     L.m1v_size_table_fused.argtypes = [vp]
     L.m1v_size_table_fused.restype = C.c_int
     L.m1v_set_input_layout.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]

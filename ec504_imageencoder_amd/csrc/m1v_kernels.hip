@@ -1778,6 +1778,9 @@ struct m1v_encoder {
     int forced_path = -1;       // m1v_debug_set_path: -1 = by geometry, 0 = runs, 1 = tiles
     int forced_T = 0;           // run length forced by m1v_debug_set_dense_threads (0 = default)
     bool pipelined = false;     // layout + gather of batch k on `side` while batch k+1 encodes on the caller's stream
+    // m1v_debug_set_assemble_shape: k_assemble's strips per workgroup and lanes per segment, 0 = the plan's own (one record, so
+    // that a refused or failed call leaves both as they were)
+    struct AsmShape { int group, lanes_log2; } forced_asm = {0, 0};
     // What the debug hooks force, as each place that reads them asks.  The four differ on purpose:
     // m1v_coefficients_device: its run-shaped kernel has no run length, so a forced one does not select it
     bool runs_by_path_or_mode() const { return forced_path == 0 || forced_mode >= 0; }
@@ -2103,6 +2106,9 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
     const size_t seg_words = seg_blocks * bpb / 32;
     p.asm_lanes_log2 = 1; // four words per lane: enough lanes for 1.6 x the expected words, at most one DPP row
     while (p.asm_lanes_log2 < 4 && ((size_t)4 << p.asm_lanes_log2) * 5 < seg_words * 8) p.asm_lanes_log2++;
+    // m1v_debug_set_assemble_shape (it has checked the values): any shape is correct, the plan's own is the fast one
+    if (e.forced_asm.group > 0) p.asm_group = e.forced_asm.group;
+    if (e.forced_asm.lanes_log2 > 0) p.asm_lanes_log2 = e.forced_asm.lanes_log2;
     out = p;
     return M1V_OK;
 }

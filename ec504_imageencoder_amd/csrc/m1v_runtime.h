@@ -616,6 +616,24 @@ int m1v_debug_set_path(m1v_encoder *e, int path) {
     return reconfigure(e, &m1v_encoder::forced_path, path);
 }
 
+int m1v_debug_assemble_shape(const m1v_encoder *e, int out[4]) {
+    if (!e || !out) return fail(M1V_E_ARG, "null encoder or output%s");
+    out[0] = e->plan.asm_group;
+    out[1] = e->plan.asm_lanes_log2;
+    out[2] = e->plan.segs;
+    out[3] = e->plan.producer == Producer::tiles ? 0 : (e->plan.producer == Producer::dense ? 1 : 2);
+    return M1V_OK;
+}
+
+int m1v_debug_set_assemble_shape(m1v_encoder *e, int group, int lanes_log2) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    // only what plan_for can produce: the launch and the kernel hold no other shape
+    if (group < 0 || group > kAsmMaxGroup || (group & (group - 1)) || group > e->g.n_strips)
+        return fail(M1V_E_ARG, "group must be 0 (the plan's own) or a power of two, at most 16 and at most the number of strips%s");
+    if (lanes_log2 < 0 || lanes_log2 > 4) return fail(M1V_E_ARG, "lanes_log2 must be 0 (the plan's own) or 1..4%s");
+    return reconfigure(e, &m1v_encoder::forced_asm, m1v_encoder::AsmShape{group, lanes_log2});
+}
+
 int m1v_set_input_layout(m1v_encoder *e, size_t row_pitch_bytes, size_t frame_stride_bytes, int order) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");
     if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "order must be M1V_ORDER_RGB or M1V_ORDER_BGR%s");

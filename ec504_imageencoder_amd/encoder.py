@@ -1318,6 +1318,17 @@ class Mpeg1Encoder:
     def debug_set_dense_threads(self, threads):
         _call("m1v_debug_set_dense_threads", self._h, int(threads))
 
+    def debug_assemble_shape(self):
+        """Test hook: the assembly kernel's shape under the plan in force, as (group, lanes_log2, segs, producer) with the
+        producer "tiles", "dense" or "strips" (see mpeg1_hip.h)."""
+        out = (C.c_int * 4)()
+        _call("m1v_debug_assemble_shape", self._h, out)
+        return out[0], out[1], out[2], ("tiles", "dense", "strips")[out[3]]
+
+    def debug_set_assemble_shape(self, group=0, lanes_log2=0):
+        """Test hook: force the assembly kernel's strips per workgroup and lanes per segment; 0 = the plan's own (see mpeg1_hip.h)."""
+        _call("m1v_debug_set_assemble_shape", self._h, int(group), int(lanes_log2))
+
 
 def file_prolog():
     buf = (C.c_uint8 * 27)()

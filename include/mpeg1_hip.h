@@ -982,6 +982,18 @@ int m1v_debug_set_input_mode(m1v_encoder *enc, int mode);
 /* Tuning/test hook: blocks per workgroup of the RUN kernel (multiple of 64, 64..384, not more than the blocks of one
  * strip; 0 = default).  Forcing a run length selects the run path unless m1v_debug_set_path says tiles. */
 int m1v_debug_set_dense_threads(m1v_encoder *enc, int threads);
+/* Test hook, read-only: the shape of the assembly kernel (k_assemble) under the plan in force.  out[0] = strips per workgroup
+ * (1, 2, 4, 8 or 16), out[1] = log2 of the lanes that share a segment (1..4), out[2] = segments per strip (tile rows on the tile
+ * path; the most runs a strip can touch on the run path; 1 for the strip kernel), out[3] = the producer: 0 = tiles, 1 = the run
+ * kernel (dense), 2 = the strip kernel.  Launches nothing.  M1V_E_ARG for a null argument. */
+int m1v_debug_assemble_shape(const m1v_encoder *enc, int out[4]);
+/* Test hook: force that shape; 0 = the plan's own value, for either argument.  Every shape produces the same bytes: a group
+ * whose bytes outgrow the kernel's LDS image takes several passes, one of more than 256 segments several chunks, a segment of
+ * 4 * lanes words or more an extra loop.  Only values the plan can produce are taken: group a power of two, at most 16 and at
+ * most m1v_strips(enc); lanes_log2 1..4.  Anything else returns M1V_E_ARG and changes nothing.  The forced values hold across
+ * the other hooks and setters until they are set to 0.  A reconfiguration like the other m1v_debug_set_* hooks: it waits for
+ * the device, and a failure leaves the encoder exactly as it was. */
+int m1v_debug_set_assemble_shape(m1v_encoder *enc, int group, int lanes_log2);
 
 #ifdef __cplusplus
 }

@@ -143,27 +143,57 @@ def test_colour_inside_the_encode_kernels_exhaustive_2_24(torch_cuda, orc, path)
     _check_colours_through(torch_cuda, orc, colours, lambda e: e.debug_set_path(path))
 
 
+# What each case of the test below reaches in k_assemble, as tests/assemble_space.py's model derives it from the oracle and as
+# the test asserts it (the shape through m1v_debug_assemble_shape).  Noise codes 13 to 30 bits per block at any quality (the
+# reference's walk stops at the first pair of adjacent non-zero coefficients), so no strip of noise outgrows the 14-KiB image:
+# the cases once labelled "several passes" and "three chunks" took one of each under the shape the plan chooses, and the two
+# 128 x 4368 cases now force the 8 strips per workgroup their labels assumed.  tests/test_gpu_assemble_space.py sweeps the space.
+#   key (W, H, qf, path): forced group (plan: the shape the plan chose where one is forced: 138 and 69 segments, one chunk), then the
+#   shape, passes, chunks and long-loop trips the model must find
+_ASSEMBLE_CLAIMS = {
+    (1920, 1080, 100, "tiles"): dict(force=0, shape=(1, 4, 17, "tiles"), passes={1}, chunks={1}, trips=0),
+    (1920, 1080, 90, "runs"): dict(force=0, shape=(1, 4, 3, "dense"), passes={1}, chunks={1}, trips=1),
+    (128, 4368, 12, "tiles"): dict(force=8, plan=(2, 3, 69, "tiles"), shape=(8, 3, 69, "tiles"), passes={3}, chunks={3}, trips=0),
+    (128, 4368, 75, "tiles"): dict(force=8, plan=(1, 4, 69, "tiles"), shape=(8, 4, 69, "tiles"), passes={2}, chunks={3}, trips=0),
+    (640, 480, 50, "auto"): dict(force=0, shape=(4, 4, 1, "strips"), passes={1}, chunks={1}, trips=0),
+    (4112, 160, 30, "tiles"): dict(force=0, shape=(16, 4, 3, "tiles"), passes={1}, chunks={1}, trips=0),
+    (16, 16, 12, "tiles"): dict(force=0, shape=(1, 3, 1, "tiles"), passes={1}, chunks={1}, trips=0),
+}
+
+
 @pytest.mark.parametrize("W,H,channels,mode,qf,n,path", [
-    (1920, 1080, 3, "full", 100, 2, "tiles"),    # a strip of ~20 KB: one strip per workgroup, several PASSES over the 14-KiB image
-    (1920, 1080, 3, "full", 90, 2, "runs"),      # the same through the run kernel's long segments (64 words and more per lane group)
-    (128, 4368, 3, "full", 12, 3, "tiles"),      # 69 tile rows x 8 strips = 552 segments in one group: three CHUNKS of the placement table
-    (128, 4368, 3, "full", 75, 2, "tiles"),      # ... and several passes on top
+    (1920, 1080, 3, "full", 100, 2, "tiles"),    # one strip per workgroup, 17 segments of ~12 words: one pass, no long segment
+    (1920, 1080, 3, "full", 90, 2, "runs"),      # the run kernel's long segments (64 words and more per lane group: the extra loop)
+    (128, 4368, 3, "full", 12, 3, "tiles"),      # 69 tile rows x 8 strips (forced) = 552 segments in one group: three CHUNKS, three passes
+    (128, 4368, 3, "full", 75, 2, "tiles"),      # ... with 16 lanes per segment: three chunks, two passes
     (640, 480, 4, "strict", 50, 5, "auto"),      # 4 channels, 54 blocks per strip: the strip-per-workgroup kernel, one segment per strip
-    (4112, 160, 3, "full", 30, 2, "tiles"),      # 257 strips: 33 groups, the last of one strip; start codes wrap at 256
+    (4112, 160, 3, "full", 30, 2, "tiles"),      # 257 strips: 17 groups, the last of one strip; start codes wrap at 256
     (16, 16, 3, "full", 12, 7, "tiles"),         # one macroblock per frame
 ])
 def test_assemble_kernel_passes_chunks_and_long_segments(torch_cuda, orc, W, H, channels, mode, qf, n, path):
     """k_assemble (csrc/m1v_assemble.h) outside the shape the host sizes it for: groups whose bytes outgrow the LDS image
     (passes), groups of more than 256 segments (chunks), segments longer than their lanes' first trip, the three producers of
     segment tables (tiles, runs, strips), every frame's size and the total against the oracle, and a second batch on the same
-    encoder (the counters the first batch's assembly cleared)."""
+    encoder (the counters the first batch's assembly cleared).  What each case reaches is asserted, not assumed
+    (_ASSEMBLE_CLAIMS): the shape as the library reports it, the classes as the model derives them from the oracle."""
+    import assemble_space as A
     torch = torch_cuda
+    claim = _ASSEMBLE_CLAIMS[W, H, qf, path]
     enc = _enc(W, H, qf, mode, channels=channels, max_frames=n)
     if path != "auto":
         enc.debug_set_path(path)
+    sc = A.Scene("parity", W, H, channels, qf, "runs" if path == "runs" else None, n, 0, (256,) * n, None, ((0, 0),), "", mode)
+    planned = enc.debug_assemble_shape()                   # what the plan chooses, before anything is forced
+    assert planned == A.plan_shape(sc) and (planned == claim["shape"] or planned == claim.get("plan"))
+    enc.debug_set_assemble_shape(claim["force"], 0)
+    assert enc.debug_assemble_shape() == A.plan_shape(sc, (claim["force"], 0)) == claim["shape"]
     rng = np.random.default_rng(W * 31 + H + qf)
     for first in (0, 250):
         rgb = rng.integers(0, 256, (n, H, W, channels), dtype=np.uint8)
+        if first == 0:
+            wgs, _ = A.workgroups(orc, sc, claim["shape"][:2], px=rgb)
+            got = ({w.passes for w in wgs}, {w.chunks for w in wgs}, max(max(w.trips) for w in wgs))
+            assert got == (claim["passes"], claim["chunks"], claim["trips"]), got
         want, wsizes = orc.encode_frames(rgb, n, W, H, first, qf, _omode(orc, mode), channels=channels)
         got, sizes = enc.encode_to_bytes(torch.from_numpy(rgb).cuda(), first)
         assert sizes == [int(x) for x in wsizes], (first, sizes[:3], list(wsizes[:3]))
