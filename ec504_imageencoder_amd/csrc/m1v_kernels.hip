@@ -296,6 +296,9 @@ __device__ __forceinline__ const float *frame_rq_t(const float *rq_all, const ui
 // coordinates, the results of the kernel's last integer divisions (the compiler expands those through v_rcp_iflag_f32 and a
 // float multiply: they stay in the default mode; tests/test_abi.py checks the code object for both).
 // The run kernel keeps the default mode and the integer form: measured 1 % faster there (profiles/r03_ab_history.txt).
+// The switch writes MODE bits 1:0 only (offset 0, width 2): the fp32 denormal bits 5:4 keep the kernel descriptor's value,
+// denormals enabled, which the luma waves' colour sums rely on (luma_sums_denormal: flushed, every colour byte would read
+// as 0).  No flush flag belongs in the Makefile for the same reason; tests/test_luma_denormal_cpu.py reads the descriptors.
 __device__ __forceinline__ const uint8_t *pixel_stage_rounds_down(const uint8_t *frame_base, int &u0, int &u1) {
     unsigned long long p = (unsigned long long)(uintptr_t)frame_base;
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2" : "+s"(p), "+s"(u0), "+s"(u1));
@@ -349,6 +352,92 @@ __device__ __forceinline__ void convert_row(const RowT &v, const CompCoefF &k, f
             if (t - clear_fraction(t) < kFracLow)
                 out[j] = m1vf::kPxBiasF + (float)component_fp64((int)r, (int)gg, (int)b, d.k0, d.kr, d.kg, d.kb);
         }
+    }
+}
+
+// The three FMAs of component_t for a wave whose lanes all convert LUMA from packed R,G,B bytes (waves 0, 1 of a tile,
+// m1v_tiles.h), without the twenty-four v_cvt_f32_ubyteN of a row (4.75 cycles each against 2.5 for a v_and_b32 with a literal,
+// profiles/r01_valu_rates.txt).  A colour byte is taken where it lies in its dword, position q = (3j + ch) & 3, and read as a
+// float:
+//     w & (0xff << 8q), q = 0, 1, 2  =  b * 2^(8q - 149);      w >> 24, q = 3  =  b * 2^-149 (the scale of q = 0)
+// a denormal, which v_fma_f32 takes at full rate.  Its coefficient is fl32(k_ch) * 2^(125 - 8q) (a literal: the wave's
+// component is a compile-time constant) and the sum starts from (k0 + 256 + eps) * 2^-24.  A power-of-two rescale of an fp32
+// coefficient is exact and every product is the unit-scale product * 2^-24, so every FMA rounds where component_t's does, in
+// round-to-nearest and in the wave's round-down mode: t' = t * 2^-24 bit for bit in the mantissa, in [2^-16, 2^-15), normal.
+// Needs fp32 denormals enabled (the compiler's default for gfx950; pixel_stage_rounds_down leaves MODE's denormal bits alone).
+// Proof over all 2^24 triples x the four dword phases of a pixel, both rounding modes: tools/colour_fast_proof.c denormal [down].
+__device__ __forceinline__ void luma_sums_denormal(const Row24 &v, float k0, float t[8]) {
+    constexpr float kY[3] = {0.299f, 0.587f, 0.114f};
+    constexpr float kScale[4] = {0x1p125f, 0x1p117f, 0x1p109f, 0x1p125f}; // by byte position q
+    auto chan = [&](int j, int ch) -> float {
+        const int byte = 3 * j + ch, q = byte & 3;
+        const uint32_t w = v.d[byte >> 2];
+        return __uint_as_float(q == 3 ? w >> 24 : w & (0xffu << (8 * q)));
+    };
+    auto coef = [&](int j, int ch) -> float { return kY[ch] * kScale[(3 * j + ch) & 3]; };
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        t[j] = fmaf(chan(j, 2), coef(j, 2), k0);
+        t[j] = fmaf(chan(j, 1), coef(j, 1), t[j]);
+        t[j] = fmaf(chan(j, 0), coef(j, 0), t[j]);
+    }
+}
+
+// convert_row<3, ., 0> of the tile kernels that round down (m1v_tiles.h): one wave-uniform branch around the eight sums — the
+// luma waves take luma_sums_denormal, the chroma wave component_t with its per-lane coefficients — and ONE tail for both,
+// which reads a sum's bit pattern and so does not care which of the two scales it has (the exponent is fixed at either):
+//     fraction       the low 15 mantissa bits L as an integer; t - p < kFracLow  <=>  L < 10   (t - p = L * 2^-15 exactly)
+//     raw pixel      (bits & 0x007f8000) | bits(256.0f) = clear_fraction(t)                      (ONE v_and_or_b32)
+// so the luma pixels return to unit scale without a multiply.  Only the eight sums live across the rare branch (the pixels are
+// cut from them behind it; a flagged pixel's sum is replaced by its raw pixel, which the and-or leaves as it is): eight
+// registers fewer than convert_row holds there, at no instruction more.  The rare branch is convert_row's: the same pixels
+// flagged, the reference's fp64 expression with the wave's k.d, no fp64 FMA.  It is marked unlikely (taken by about half of
+// the rows, but its code — eight pixels' fp64 expressions — is placed behind the kernel's hot path, not between the rows).
+// The two constants of the row that need a vector register (v_fmamk_f32 takes its addend, v_and_or_b32 its third operand, from
+// one), set up once in front of the rows: opaque, or the compiler moves them into a register again in every row.
+struct TileRowConst {
+    float k0;      // (256 + eps) * 2^-24: where a luma sum starts
+    uint32_t bias; // bits of kPxBiasF
+};
+__device__ __forceinline__ TileRowConst tile_row_const() {
+    TileRowConst c = {(256.0f + kEps) * 0x1p-24f, __float_as_uint(m1vf::kPxBiasF)};
+    asm("" : "+v"(c.k0), "+v"(c.bias));
+    return c;
+}
+__device__ __forceinline__ void convert_row_tile(const Row24 &v, const CompCoefF &k, const TileRowConst &c, bool luma_wave, float out[8]) {
+    float t[8];
+    if (luma_wave) {
+        luma_sums_denormal(v, c.k0, t);
+    } else {
+        auto chan = [&](int j, int ch) -> uint32_t { return (v.d[(3 * j + ch) >> 2] >> (((3 * j + ch) & 3) * 8)) & 0xffu; };
+#pragma unroll
+        for (int j = 0; j < 8; j++) t[j] = component_t(chan(j, 0), chan(j, 1), chan(j, 2), k);
+    }
+    uint32_t L[8], lowest = 0x7fffu;
+#pragma unroll
+    for (int j = 0; j < 8; j++) L[j] = __float_as_uint(t[j]) & 0x7fffu;
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) lowest = min(min(lowest, L[j]), L[j + 1]);
+    if (__builtin_expect(lowest < 10u, 0)) { // redo the row's flagged pixels in the reference's arithmetic
+        // (the bytes' origin is hidden, as convert_row's LEAN does: a byte at position 0 or 3 was masked to its own value by
+        // the luma sums, and left visible the twelve of them stay in registers across the branch)
+        Row24 w = v;
+#pragma unroll
+        for (int i = 0; i < 6; i++) asm("" : "+v"(w.d[i]));
+        const CompCoef &d = k.d;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (L[j] < 10u) {
+                auto byte_of = [&](int ch) -> int { return (int)((w.d[(3 * j + ch) >> 2] >> (((3 * j + ch) & 3) * 8)) & 0xffu); };
+                t[j] = m1vf::kPxBiasF + (float)component_fp64(byte_of(0), byte_of(1), byte_of(2), d.k0, d.kr, d.kg, d.kb);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        uint32_t p;
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(p) : "v"(t[j]), "s"(0x007f8000u), "v"(c.bias));
+        out[j] = __uint_as_float(p);
     }
 }
 

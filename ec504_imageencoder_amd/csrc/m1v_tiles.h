@@ -570,7 +570,13 @@ __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t
 
     // ---- rows out of the ring as they land, the freed slot refilled with row i + R ----
     (void)comp;
+    // packed R,G,B bytes in the kernels that round down: the luma waves take their colour sums from denormal operands
+    // (convert_row_tile, m1v_kernels.hip)
+    constexpr bool kLumaRow = DOWN && BPP == 3 && !SURFACE && ORDER == 0;
     const CompCoefF kf = comp_coef_wave(!chroma, lane);
+    TileRowConst row_const = {};
+    if constexpr (kLumaRow) row_const = tile_row_const();
+    (void)row_const;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         const int newest = (i - 1 + R < 7) ? (i - 1 + R) : 7; // newest row-step requested so far
@@ -586,7 +592,14 @@ __device__ __forceinline__ void tile_pixel_rows(const Geometry &g, const uint8_t
         } else {
             const Row24 v = ring_read24(lane_row + (uint32_t)(i % R) * kSlot);
             if (i + R < 8) issue_row(i + R);
-            convert_row<3, M1V_TILE_LEAN, ORDER>(v, kf, px);
+            if constexpr (kLumaRow) {
+                // one wave-uniform branch per row-step around the eight colour sums only: the ring read, the refill, the tie branch
+                // and the row pass exist once.  (opaque per row-step: branches on one visible condition would be threaded into
+                // two copies of the whole stage)
+                convert_row_tile(v, kf, row_const, uniform((uint32_t)wave) != 2u, px);
+            } else {
+                convert_row<3, M1V_TILE_LEAN, ORDER>(v, kf, px);
+            }
         }
         float ro[8];
         m1vf::fdct_row_f<float, DOWN>(px, ro); // DOWN: the wave rounds down, pixel_stage_rounds_down()
