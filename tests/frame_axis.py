@@ -20,8 +20,8 @@ import numpy as np
 import rd_oracle as rd
 import rd_rate_model as M
 import streams_model as sm
-from test_gpu_size_table import _mixed_frames
-from test_rate_abi import batch_rule, cbr_rule
+from gpu_calls import _mixed_frames
+from rate_rules import batch_rule, cbr_rule
 
 W = H = 32
 Q = 12

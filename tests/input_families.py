@@ -29,16 +29,12 @@ import numpy as np
 
 import float_planes as fp
 import geometry_space as gs
-from test_gpu_float_planes import _tensor
-from test_gpu_frame_table import RESIDUES, _addresses, _RgbPlanes, _Samples, _Surface
-from test_gpu_plane_table import SEPARATE, _blocks, _device_table, _Rgb, _Ycc
-from test_gpu_planes import _addressed, _buffer, _layout, _plane_encoder, _view, _write_planes
-from test_gpu_rgb_planes import _planar
-from test_gpu_sample_layout import _noise as _sample_noise
-from test_gpu_sample_layout import _scatter as _sample_scatter
-from test_gpu_sample_layout import _view as _sample_view
-from test_gpu_surface import _geometry as _surface_geometry
-from test_gpu_surface import _surface, _surface_encoder
+from layout_inputs import (RESIDUES, SEPARATE, _addressed, _addresses, _blocks, _buffer, _device_table, _layout, _planar,
+                           _plane_encoder, _Rgb, _RgbPlanes, _sample_view, _Samples, _surface, _Surface, _surface_encoder,
+                           _surface_geometry, _view, _write_planes, _Ycc)
+from layout_inputs import _float_planes_tensor as _tensor
+from layout_inputs import _noise as _sample_noise
+from layout_inputs import _scatter as _sample_scatter
 
 GUARD = 64
 SAMPLE_PRESETS = ("yuy2", "uyvy", "p010")
@@ -116,7 +112,7 @@ def float_bits(px, kind, rng, seed=0):
 
 def sample_frames(preset, W, H, Y, Cb, Cr, fill_seed=0):
     """Plane-form content in the tight sample preset -> (host image of the buffer, layout, byte offset of frame 0): noise of
-    fill_seed as a whole, the addressed bytes are the planes (tests/test_gpu_sample_layout.py's _noise and _scatter)."""
+    fill_seed as a whole, the addressed bytes are the planes (tests/layout_inputs.py's _noise and _scatter)."""
     from ec504_imageencoder_amd import sample_layout_preset
     lay = sample_layout_preset(W, H, preset)
     host = _sample_noise(Y.shape[0], lay, GUARD, seed=5000 + fill_seed)
@@ -144,7 +140,7 @@ def plane_ranges(family, W, H, mode):
 
 
 class _YccFrames(_Samples):
-    """tests/test_gpu_frame_table.py's _Samples for any layout of tests/test_gpu_planes.py: a frame is the bytes of its extent."""
+    """tests/layout_inputs.py's _Samples for any layout of tests/test_gpu_planes.py: a frame is the bytes of its extent."""
 
     def __init__(self, preset, mode):
         self.preset, self.mode = preset, mode
@@ -245,7 +241,7 @@ def place_planes(torch, fam, virtuals, W, H, reg, fill_seed=0):
 # ---- the builder ------------------------------------------------------------------------------------------------------------
 class Input:
     """What build() returns.  enc, dev, kind, kernels; keep holds the allocations alive; buf, lay, base are those of a plane
-    layout in stride mode (tests/test_gpu_planes.py's _oracle_on_buffer reads them)."""
+    layout in stride mode (tests/gpu_calls.py's _oracle_on_buffer reads them)."""
     buf = lay = base = None
 
     def __init__(self, family, enc, dev, kind, keep=()):

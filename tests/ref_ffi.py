@@ -8,6 +8,7 @@ The reference prints to stdout from most functions; `quiet()` redirects fd 1 to 
 import contextlib
 import ctypes as C
 import os
+import struct
 import subprocess
 
 import numpy as np
@@ -198,4 +199,34 @@ def dump_rgb(images_dir, prefix):
         off += 12
         frames.append(np.frombuffer(raw, np.uint8, w * h * c, off).reshape(h, w, c).copy())
         off += w * h * c
+    return names, frames
+
+
+def _make_folder(tmp, name, frames, quality=90):
+    from PIL import Image
+    d = tmp / name
+    (d / "images").mkdir(parents=True)
+    (d / "bit").mkdir()
+    for i, a in enumerate(frames):
+        Image.fromarray(a).save(str(d / "images" / f"f{i:03d}.jpg"), quality=quality)
+    return d
+
+
+def _check_folder(ref, orc, d, qf, modes=("strict", "full")):
+    names, frames = ref.dump_rgb(str(d / "images"), str(d / "dump"))
+    assert frames, "no frames decoded"
+    H, W, Cn = frames[0].shape
+    rgb = np.concatenate([f.reshape(-1) for f in frames])
+    for mode in modes:
+        video = d / "bit" / f"{mode}_{qf}.mpeg"
+        assert ref.run_encoder(str(d / "images"), str(d / "bit"), str(video), qf, mode) == 0, (
+            "run_encoder did not return 0", len(frames), W, H, qf, mode)
+        theirs = video.read_bytes()
+        mine = orc.encode_sequence(rgb, len(frames), W, H, qf, orc.MODE_STRICT if mode == "strict" else orc.MODE_FULL, Cn)
+        assert mine == theirs, (mode, qf, len(mine), len(theirs))
+    # .bit side files (written by either run; identical)
+    for i, f in enumerate(frames):
+        Y, Cb, Cr = orc.convert(f, Cn)
+        want = struct.pack("<ii", W, H) + Y.tobytes() + Cb.tobytes() + Cr.tobytes()
+        assert (d / "bit" / f"image_{i + 1}.bit").read_bytes() == want, (f"image_{i + 1}.bit", len(want))
     return names, frames

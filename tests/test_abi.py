@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+from code_object import _gfx950_disassembly
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "ec504_imageencoder_amd", "libencoder.so")
 
@@ -55,24 +57,7 @@ def test_file_prolog_bytes(built):
 
 def test_device_code_is_gfx950_and_unfused(built):
     """The colour conversion must evaluate image_processing.c:104-106 without FMA contraction."""
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    bundler = "/opt/rocm/lib/llvm/bin/clang-offload-bundler"
-    if not (os.path.exists(objdump) and os.path.exists(bundler)):
-        pytest.skip("llvm tools absent")
-    obj = os.path.join(ROOT, "ec504_imageencoder_amd", "csrc", "m1v_kernels.o")
-    if not os.path.exists(obj):
-        pytest.skip("object file absent")
-    import glob
-    import shutil
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        shutil.copy(obj, os.path.join(td, "k.o"))
-        subprocess.run([objdump, "--offloading", "k.o"], cwd=td, capture_output=True, text=True)
-        cos = glob.glob(os.path.join(td, "k.o.*gfx950*"))
-        if not cos:
-            pytest.skip("cannot extract the gfx950 code object")
-        out = subprocess.run([objdump, "-d", cos[0]], capture_output=True, text=True)
-    asm = out.stdout
+    asm, _ = _gfx950_disassembly()
     assert "v_mul_f64" in asm and "v_add_f64" in asm
     assert not re.search(r"v_fma(c)?_f64", asm), "fp64 FMA found: colour conversion would not be bit-exact"
 
@@ -80,21 +65,7 @@ def test_device_code_is_gfx950_and_unfused(built):
 def test_encode_kernels_do_not_spill(built):
     """The dominant kernel is vector-issue bound at 5 waves per SIMD: its speed hinges on fitting 96 VGPRs with no
     scratch (builds that spilled 130-200 B/lane measured 1.7x-2.4x slower).  Read the code object's metadata."""
-    readobj = "/opt/rocm/lib/llvm/bin/llvm-readobj"
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    obj = os.path.join(ROOT, "ec504_imageencoder_amd", "csrc", "m1v_kernels.o")
-    if not (os.path.exists(readobj) and os.path.exists(obj)):
-        pytest.skip("llvm tools or object absent")
-    import glob
-    import shutil
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        shutil.copy(obj, os.path.join(td, "k.o"))
-        subprocess.run([objdump, "--offloading", "k.o"], cwd=td, capture_output=True, text=True)
-        cos = glob.glob(os.path.join(td, "k.o.*gfx950*"))
-        if not cos:
-            pytest.skip("cannot extract the gfx950 code object")
-        notes = subprocess.run([readobj, "--notes", cos[0]], capture_output=True, text=True).stdout
+    _, notes = _gfx950_disassembly()
     kernels = {}
     name = None
     fields = {}
@@ -131,20 +102,7 @@ def test_hot_kernel_consumes_pixel_rows_as_they_arrive(built):
     count them: the code tables are waited for with the pixels still in flight (vmcnt(16)) and every row is converted
     as soon as ITS loads are back (vmcnt(14), (12) ... (0)).  One branch around one load silently turns all of these
     into vmcnt(0) — correct, and 9 % slower — so the disassembly is checked."""
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    obj = os.path.join(ROOT, "ec504_imageencoder_amd", "csrc", "m1v_kernels.o")
-    if not (os.path.exists(objdump) and os.path.exists(obj)):
-        pytest.skip("llvm tools or object absent")
-    import glob
-    import shutil
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        shutil.copy(obj, os.path.join(td, "k.o"))
-        subprocess.run([objdump, "--offloading", "k.o"], cwd=td, capture_output=True, text=True)
-        cos = glob.glob(os.path.join(td, "k.o.*gfx950*"))
-        if not cos:
-            pytest.skip("cannot extract the gfx950 code object")
-        asm = subprocess.run([objdump, "-d", cos[0]], capture_output=True, text=True).stdout
+    asm, _ = _gfx950_disassembly()
     for variant in ("k_encode_denseILi1ELb1", "k_encode_denseILi1ELb0"):      # the two aligned-input (mode 1) variants
         m = re.search(r"<_ZN\S*%s\S*>:\n(.*?)\n\n" % variant, asm, re.S)
         assert m, variant
@@ -163,20 +121,7 @@ def test_hot_kernel_shape_of_round_2(built):
     cost 20-45 cycles each inside a float stream, profiles/r02_stream_probe.txt; the sixteen (x * 181) >> 17 of the row
     pass use the 32-bit multiplier), the quantised levels leave as 64 LDS byte stores, and the waves of a
     workgroup meet only twice on the common path (scan, store) plus twice on the global-memory fallback (arena slot, clear)."""
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    obj = os.path.join(ROOT, "ec504_imageencoder_amd", "csrc", "m1v_kernels.o")
-    if not (os.path.exists(objdump) and os.path.exists(obj)):
-        pytest.skip("llvm tools or object absent")
-    import glob
-    import shutil
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        shutil.copy(obj, os.path.join(td, "k.o"))
-        subprocess.run([objdump, "--offloading", "k.o"], cwd=td, capture_output=True, text=True)
-        cos = glob.glob(os.path.join(td, "k.o.*gfx950*"))
-        if not cos:
-            pytest.skip("cannot extract the gfx950 code object")
-        asm = subprocess.run([objdump, "-d", cos[0]], capture_output=True, text=True).stdout
+    asm, _ = _gfx950_disassembly()
     m = re.search(r"<_ZN\S*k_encode_denseILi1ELb1\S*>:\n(.*?)\n\n", asm, re.S)
     assert m
     ops = [l.split()[0] for l in m.group(1).splitlines() if l.strip() and not l.strip().startswith(("/", ";"))]
@@ -185,24 +130,6 @@ def test_hot_kernel_shape_of_round_2(built):
     assert count("ds_write_b8") == 64
     assert count("v_floor_f32") == 112 and count("v_min3_f32") == 32
     assert count("s_barrier") <= 4, count("s_barrier")
-
-
-def _gfx950_disassembly():
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    obj = os.path.join(ROOT, "ec504_imageencoder_amd", "csrc", "m1v_kernels.o")
-    if not (os.path.exists(objdump) and os.path.exists(obj)):
-        pytest.skip("llvm tools or object absent")
-    import glob
-    import shutil
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        shutil.copy(obj, os.path.join(td, "k.o"))
-        subprocess.run([objdump, "--offloading", "k.o"], cwd=td, capture_output=True, text=True)
-        cos = glob.glob(os.path.join(td, "k.o.*gfx950*"))
-        if not cos:
-            pytest.skip("cannot extract the gfx950 code object")
-        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readobj", "--notes", cos[0]], capture_output=True, text=True).stdout
-        return subprocess.run([objdump, "-d", cos[0]], capture_output=True, text=True).stdout, notes
 
 
 def test_tile_kernel_shape_of_round_3(built):
@@ -270,7 +197,6 @@ def test_rounding_mode_of_the_pixel_stage(built):
         late = [l for l in lines[switches[0]:] if l.startswith(("v_rcp", "v_cvt_f32_u32", "v_cvt_u32_f32", "v_div_"))]
         assert not late, (name, late)
     assert sorted(n[n.index("k_"):][:18] for n in switching) == ["k_coefficient_tile", "k_encode_tilesILb0", "k_encode_tilesILb1"], switching
-
 
 
 def test_assemble_kernel_shape_of_round_4(built):

@@ -9,10 +9,7 @@ import os
 import re
 
 import float_planes as fp
-import test_float_planes_abi
-import test_rgb_planes_abi
-import test_sample_layout_abi
-from test_frame_table_abi import _code_object
+from code_object import EXISTING, RGB_PLANES_COUNTED, SAMPLE_LAYOUT_COUNTED, _code_object
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("row_pitch", "frame_stride", "pixel_step", "order", "sample", "range")
@@ -21,8 +18,7 @@ SYMBOLS = ("m1v_float_pixel_layout_preset", "m1v_set_float_pixel_layout", "m1v_f
 ROWS = ("encode", "size_table", "rd_table")
 SAMPLES = {"float16": "9F16Sample", "bfloat16": "10Bf16Sample", "float32": "9F32Sample"}
 # what the code-object tests of the other layouts count kernels by: no new mangled name may contain one
-TAKEN = ("float_planes",) + test_float_planes_abi.EXISTING + test_float_planes_abi.COUNTED + test_rgb_planes_abi.COUNTED \
-    + test_sample_layout_abi.COUNTED
+TAKEN = ("float_planes",) + EXISTING + RGB_PLANES_COUNTED + SAMPLE_LAYOUT_COUNTED
 # the completeness pattern of tests/test_input_families_cpu.py
 TILE_SHAPED = r"\d(k[tp]?_(?:encode|size_table|rd_table)_[a-z0-9_]+)"
 
@@ -156,7 +152,7 @@ def test_the_sweeps_reach_every_tile_kernel():
     """The completeness pin of the new name pattern: every (row, type, samples per pixel) of the code object is declared by
     tests/test_gpu_float_pixels_sweeps.py, and that module declares nothing the code object lacks.  (Both stagings of each are
     reached: every sweep runs narrow and wide qualities.)"""
-    import test_gpu_float_pixels_sweeps as sweeps
+    import float_pixel_sweeps as sweeps
     bodies, _ = _mine()
     found = {v[:1] + v[2:] for v in map(_variant, bodies) if v}
     assert len(found) == 18

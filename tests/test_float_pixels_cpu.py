@@ -102,7 +102,8 @@ def addressed_mask(length, base, lay, n, height, width):
 def _buffer(bits, kind, Cs, form, order, fill_seed):
     """tests/test_gpu_float_pixels.py's _tensor on the host: (uint8 image of the buffer, byte offset of the view, layout)."""
     from ec504_imageencoder_amd import float_pixel_strides
-    from test_gpu_float_pixels import GUARD, _geometry
+    from layout_inputs import GUARD
+    from layout_inputs import _float_pixels_geometry as _geometry
     n, h, w, _ = bits.shape
     S = fp.BYTES[kind]
     strides, at = _geometry(form, n, h, w, Cs)

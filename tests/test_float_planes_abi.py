@@ -9,17 +9,14 @@ import re
 
 import pytest
 
-from test_frame_table_abi import _code_object
-from test_rgb_planes_abi import COUNTED
+from code_object import EXISTING, _code_object
+from code_object import RGB_PLANES_COUNTED as COUNTED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride", "sample", "range")
 SYMBOLS = ("m1v_float_plane_layout_preset", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force",
            "m1v_float_planes_to_bytes_device")
 FAMILIES = ("k_encode_float_planes", "k_size_table_float_planes", "k_rd_table_float_planes")
-# the families whose names the issue of this layout lists: no new mangled name may contain one
-EXISTING = ("k_encode_planes", "k_size_table_planes", "k_encode_rgb_planes", "k_size_table_rgb_planes", "k_rd_table_rgb_planes",
-            "k_encode_step2", "k_encode_surface", "k_size_table_tiles")
 
 
 def test_declared_exported_and_bound():

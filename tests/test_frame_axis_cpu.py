@@ -7,7 +7,7 @@ import frame_axis as fa
 import rd_oracle as rd
 import rd_rate_model as M
 import streams_model as sm
-from test_rate_abi import batch_rule
+from rate_rules import batch_rule
 
 CHANNELS = (3, 4)
 PER_FRAME_RULES = (fa.LARGEST, rd.BEST_IN_BUDGET, rd.SMALLEST_AT_DISTORTION)

@@ -3,13 +3,12 @@ exported and bound, refuse a null encoder, and the Python mirror carries the set
 FrameTable object; the code object holds a kt_* twin of every tile-shaped kernel of a non-packed layout, of the same shape, and none
 of a packed kernel."""
 import ctypes as C
-import functools
 import os
 import re
 
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _kernels, _ops, _vgprs, _waves
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the layout families whose kernels have a frame-table twin (kt_*), and their instantiations per row: [STAGE8] x the variants
@@ -60,35 +59,6 @@ def test_python_mirror():
     keep = [object(), object()]
     ft = FrameTable(_Table(), keep)
     assert ft.shape == (5,) and len(ft) == 5 and ft.device == "cuda:0" and ft.data_ptr() == 4096 and ft.frames == tuple(keep)
-
-
-@functools.lru_cache(maxsize=1)
-def _code_object():
-    """({kernel: body}, [(kernel, scratch bytes, VGPRs)]) of the whole code object, disassembled and parsed once per run."""
-    asm, notes = _gfx950_disassembly()
-    bodies = dict(re.findall(r"<(_ZN\S*)>:\n(.*?)\n\n", asm, re.S))
-    recs = re.findall(r"\.name:\s*(_ZN\S*).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)", notes, re.S)
-    return bodies, recs
-
-
-def _kernels(family):
-    bodies, recs = _code_object()
-    mine = re.compile(r"\d+%sI" % family)
-    return {n: b for n, b in bodies.items() if mine.search(n)}, [r for r in recs if mine.search(r[0])]
-
-
-def _ops(body):
-    return [l.split("//")[0].split() for l in body.splitlines() if l.split("//")[0].strip() and not l.strip().startswith(("/", ";"))]
-
-
-def _waves(vgprs):
-    """Waves per SIMD that a VGPR count allows on gfx950: 512 registers per lane in blocks of 8, 8 waves at most."""
-    return min(8, 512 // ((vgprs + 7) // 8 * 8))
-
-
-def _vgprs(family):
-    """{mangled name: (scratch bytes, VGPRs)} of a kernel family."""
-    return {n: (int(sc), int(v)) for n, sc, v in _kernels(family)[1]}
 
 
 @pytest.mark.parametrize("row", ("encode", "size_table", "rd_table"))

@@ -191,7 +191,7 @@ def test_a_difference_is_named_by_its_slice(orc):
 def test_oracle_matches_the_reference_on_the_even_height_members(ref, orc, tmp_path):
     """Two frames of the member's quality-12 content as JPEGs through the reference's driver; JPEG decoding happens on both
     sides, so what both encode is the decoded RGB (ref.dump_rgb)."""
-    from test_oracle_vs_reference import _check_folder, _make_folder
+    from ref_ffi import _check_folder, _make_folder
     members = [t for t in gs.tile_set() if t.H % 2 == 0]
     assert len(members) == 32 and {(t.s, t.grid) for t in members} == {(s, g) for s in range(1, 9) for g in (0, 1)}
     # the formula gives even widths where it gives even heights (k even): odd widths at even heights come from these six

@@ -21,8 +21,7 @@ import pytest
 import code_space as cs
 import hard_content as hc
 import input_families as fam
-from test_gpu_size_table import _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _table
 
 pytestmark = pytest.mark.gpu
 

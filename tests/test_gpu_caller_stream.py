@@ -25,7 +25,7 @@ import launch_side as LS
 import rd_oracle as rd
 import rd_rate_model as M
 import streams_model as sm
-from test_rate_abi import batch_rule
+from rate_rules import batch_rule
 
 pytestmark = pytest.mark.gpu
 

@@ -13,13 +13,11 @@ import numpy as np
 import pytest
 
 import float_planes as fp
-from test_gpu_rd_table import _rd
-from test_gpu_size_table import _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _rd, _table
+from layout_inputs import _float_pixels_tensor as _tensor
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 # one macroblock; 3 strips in one partial tile; a 2 x 2 tile grid with one strip in the last column; 17 strips
 SIZES = ((16, 16), (48, 32), (144, 80), (272, 144))
 FORMS = ("nhwc", "nchw", "window")     # packed [n, H, W, C]; its channels-last view [n, C, H, W]; a window of a larger tensor
@@ -27,7 +25,6 @@ WIDTHS = (3, 4)                        # samples per pixel
 ORDERS = ("rgb", "bgr")
 K8 = (1, 2, 3, 5, 7, 9, 11, 12)
 K8_WIDE = (20, 40, 60, 76, 77, 80, 85, 90)
-_NP = {"float16": np.uint16, "bfloat16": np.uint16, "float32": np.uint32}
 
 
 @pytest.fixture(scope="module")
@@ -35,46 +32,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _geometry(form, n, H, W, Cs):
-    """(strides in elements of the pixel array [n, H, W, Cs], offset of pixel (0, 0) of frame 0 in elements)."""
-    if form in ("nhwc", "nchw"):
-        return (H * W * Cs, W * Cs, Cs, 1), 0
-    assert form == "window"                     # x[:, 3:3+H, 5:5+W, :3] of an [n, H + 7, W + 13, Cs] tensor: an odd x0, a pitch that
-    P, R = W + 13, H + 7                        # is no multiple of 16 bytes, rows between frames
-    return (R * P * Cs, P * Cs, Cs, 1), (3 * P + 5) * Cs
-
-
-def _tensor(torch, bits, kind, form, Cs=3, order="rgb", rng="unit", fill="noise", seed=0, fourth=None):
-    """bits: patterns [n, H, W, 3] of R, G, B -> (the strided CUDA view the encoder is given, its layout dict).  Everything else
-    of the buffer — row padding, 4th samples, the gaps between frames, GUARD bytes either side — is noise of `seed`, or all-NaN
-    patterns (every byte 0xff); fourth="nan" makes the 4th samples NaN under either fill."""
-    from ec504_imageencoder_amd import float_pixel_strides
-    n, H, W, _ = bits.shape
-    S = fp.BYTES[kind]
-    strides, at = _geometry(form, n, H, W, Cs)
-    base = GUARD // S + at
-    span = sum(s * (d - 1) for s, d in zip(strides, (n, H, W, Cs))) + 1
-    total = base + span + GUARD // S
-    if fill == "noise":
-        buf = np.random.default_rng(3000 + seed).integers(0, 1 << (8 * S), total, dtype=np.uint64).astype(_NP[kind])
-    else:
-        buf = np.full(total, (1 << (8 * S)) - 1, dtype=_NP[kind])
-    pixels = np.lib.stride_tricks.as_strided(buf[base:], (n, H, W, Cs), tuple(s * S for s in strides))
-    pixels[..., :3] = bits if order == "rgb" else bits[..., ::-1]
-    if Cs == 4 and fourth == "nan":
-        pixels[..., 3] = (1 << (8 * S)) - 1
-    signed = {2: np.int16, 4: np.int32}[S]
-    dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}[kind]
-    dev = torch.from_numpy(buf.view(signed)).cuda().view(dtype)
-    if form == "nchw":
-        shape, vstrides, dims = (n, Cs, H, W), (strides[0], 1, strides[1], strides[2]), "nchw"
-    elif form == "window":
-        shape, vstrides, dims = (n, H, W, 3), strides, "nhwc"
-    else:
-        shape, vstrides, dims = (n, H, W, Cs), strides, "nhwc"
-    return torch.as_strided(dev, shape, vstrides, base), float_pixel_strides(shape, vstrides, kind, dims, order, rng)
 
 
 def _encoder(W, H, Q, n, lay):

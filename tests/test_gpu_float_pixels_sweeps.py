@@ -6,8 +6,8 @@ pixel (input_families.float_bits, transposed to pixels), written into the window
 noise (tests/test_gpu_float_pixels.py); a 4th sample is NaN.  So the records, censuses and failure messages are the existing
 sweeps': a failure names the member, the slice and the tile column, or the block by its DC level and first (run, level).
 
-REACHED lists the (kernel row, type, samples per pixel) this module sends content through; tests/test_float_pixels_abi.py holds
-it against the code object, so a float pixel kernel added without a sweep fails there.
+REACHED (tests/float_pixel_sweeps.py) lists the (kernel row, type, samples per pixel) this module sends content through;
+tests/test_float_pixels_abi.py holds it against the code object, so a float pixel kernel added without a sweep fails there.
 
   geometry      all 64 members of geometry_space.tile_set() and the batch member at even widths, narrow staging (quality 12):
                 encode, size table, rd table; the four members of tests/test_input_families_cpu.py at wide staging (quality 90)
@@ -17,23 +17,19 @@ it against the code object, so a float pixel kernel added without a sweep fails 
 import pytest
 
 import code_space as cs
-import float_planes as fp
+import code_space_cases as code
+import geometry_cases as geo
 import geometry_space as gs
 import hard_content as hc
+import hard_content_cases as hard
 import input_families as fam
 import rd_oracle as rd
-import test_gpu_code_space as code
-import test_gpu_geometry as geo
-import test_gpu_hard_content as hard
-from test_gpu_float_pixels import _tensor
-from test_gpu_rd_table import _rd
-from test_gpu_surface import _encode
+from float_pixel_sweeps import VARIANTS
+from gpu_calls import _encode, _rd
+from layout_inputs import _float_pixels_tensor as _tensor
 
 pytestmark = pytest.mark.gpu
 
-ROWS = ("encode", "size_table", "rd_table")
-VARIANTS = [(kind, Cs) for kind in fp.KINDS for Cs in (3, 4)]
-REACHED = [(row, kind, Cs) for row in ROWS for kind, Cs in VARIANTS]     # every sweep below runs every variant through every row
 IDS = [f"{kind}-x{Cs}" for kind, Cs in VARIANTS]
 # the members of tests/test_input_families_cpu.py
 MEMBERS = [next(t for t in gs.tile_set() if (t.grid, t.s, t.m) == key) for key in ((0, 1, 1), (0, 8, 4), (1, 3, 1), (1, 7, 3))]

@@ -13,18 +13,16 @@ import numpy as np
 import pytest
 
 import float_planes as fp
-from test_gpu_size_table import _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _table
+from layout_inputs import _float_planes_tensor as _tensor
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 # the sizes of tests/test_gpu_rgb_planes.py that differ in the lane-to-block map: one macroblock; 3 strips in one partial tile;
 # a 2 x 2 tile grid with one strip in the last column; 17 strips
 SIZES = ((16, 16), (48, 32), (144, 80), (272, 144))
 LAYOUTS = ("rgb", "bgr", "window", "rgba")
 K8 = (1, 2, 3, 5, 7, 9, 11, 12)
-_NP = {"float16": np.uint16, "bfloat16": np.uint16, "float32": np.uint32}
 
 
 @pytest.fixture(scope="module")
@@ -32,42 +30,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _geometry(layout, n, H, W):
-    """(shape, strides in elements, offset of the view in elements, which component each of the first three channels holds)."""
-    if layout in ("rgb", "bgr"):                # tightly packed planes in that memory order
-        return (n, 3, H, W), (3 * H * W, H * W, W, 1), 0, (0, 1, 2) if layout == "rgb" else (2, 1, 0)
-    if layout == "rgba":                        # the first three planes of a 4-plane tensor
-        return (n, 4, H, W), (4 * H * W, H * W, W, 1), 0, (0, 1, 2)
-    assert layout == "window"                   # x[:, :, 3:3+H, 5:5+W] of a [n, 4, H + 7, W + 13] tensor: an odd x0, a pitch that
-    P, R = W + 13, H + 7                        # is no multiple of 16 bytes (W + 13 is odd), a fourth plane, rows between frames
-    return (n, 4, H, W), (4 * R * P, R * P, P, 1), 3 * P + 5, (0, 1, 2)
-
-
-def _tensor(torch, bits, kind, layout, rng="unit", fill="noise", seed=0):
-    """bits: patterns [n, 3, H, W] of R, G, B -> (the strided CUDA view [n, C, H, W] the encoder is given, its layout dict).
-    Everything else of the buffer — row padding, a fourth plane, the gaps between frames, GUARD bytes either side — is noise of
-    `seed`, or all-NaN patterns (every byte 0xff)."""
-    from ec504_imageencoder_amd import float_plane_strides
-    n, _, H, W = bits.shape
-    S = fp.BYTES[kind]
-    shape, strides, at, comp = _geometry(layout, n, H, W)
-    base = GUARD // S + at
-    span = sum(s * (d - 1) for s, d in zip(strides, shape)) + 1
-    total = base + span + GUARD // S
-    if fill == "noise":
-        buf = np.random.default_rng(3000 + seed).integers(0, 1 << (8 * S), total, dtype=np.uint64).astype(_NP[kind])
-    else:
-        buf = np.full(total, (1 << (8 * S)) - 1, dtype=_NP[kind])
-    view = np.lib.stride_tricks.as_strided(buf[base:], shape, tuple(s * S for s in strides))
-    for c in range(3):
-        view[:, c] = bits[:, comp[c]]
-    signed = {2: np.int16, 4: np.int32}[S]
-    dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}[kind]
-    dev = torch.from_numpy(buf.view(signed)).cuda().view(dtype)
-    order = "bgr" if layout == "bgr" else "rgb"
-    return torch.as_strided(dev, shape, strides, base), float_plane_strides(shape, strides, kind, order, rng)
 
 
 def _encoder(W, H, Q, n, lay):

@@ -10,9 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import sample_oracle
-from test_gpu_size_table import _frames, _mixed_frames, _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _table
+from layout_inputs import FIRST, RESIDUES, _addresses, _check, _picture_of, _RgbPlanes, _Samples, _Surface
 
 pytestmark = pytest.mark.gpu
 
@@ -20,8 +19,6 @@ GUARD = 64
 SIZES = ((16, 16), (48, 32), (144, 80))     # one macroblock; one partial tile; a 2 x 2 tile grid
 BATCHES = (1, 3, 9, 17)                     # up to 8 frames and more: both branches of the workgroup -> (frame, tile) map
 QUALITIES = (12, 100)                       # byte staging, halfword staging (noise of amplitude 64: no level reaches 256)
-RESIDUES = (1, 6, 11, 0, 7, 13, 4, 15)      # a frame base's address mod 16, slot by slot
-FIRST = 17
 
 
 @pytest.fixture(scope="module")
@@ -32,106 +29,6 @@ def torch_cuda():
 
 
 # ---- one layout of each kernel family ---------------------------------------------------------------------------------------
-class _Pixels:
-    """A layout whose frames are pictures [H, W, C]: a pitched surface, or pitched planes of R, G and B."""
-
-    def pictures(self, rng, m, W, H, amp=256):
-        px = _frames(rng, m, W, H, self.channels, amp)
-        if self.channels == 4:              # alpha is noise: a kernel that reads it as a colour gets every size wrong
-            px[..., 3] = rng.integers(0, 256, px.shape[:3], dtype=np.uint8)
-        return list(px)
-
-    def want(self, orc, pic, W, H, index, Q):
-        return orc.encode_frame(pic, W, H, index, Q, orc.MODE_FULL, channels=self.channels)
-
-
-class _Surface(_Pixels):
-    def __init__(self, channels, pad, order):
-        self.channels, self.pad, self.order = channels, pad, order
-
-    def pitch(self, W):
-        return W * self.channels + self.pad
-
-    def span(self, W, H):
-        return (H - 1) * self.pitch(W) + W * self.channels
-
-    def encoder(self, W, H, Q, n, stride=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
-        enc = Mpeg1Encoder(W, H, Q, "full", channels=self.channels, max_frames=n)
-        enc.set_input_layout(self.pitch(W), stride, self.order)
-        return enc
-
-    def view(self, torch, pool, base, W, H, n=None, stride=0):
-        """The tensor of the frame at pool[base] (n: of the n frames `stride` apart from there), as the layout's calls take it."""
-        one = (H, W, self.channels), (self.pitch(W), self.channels, 1)
-        return torch.as_strided(pool, *(one if n is None else ((n,) + one[0], (stride,) + one[1])), base)
-
-    def write(self, torch, pool, base, pic, W, H):
-        src = pic if self.order == "rgb" else np.ascontiguousarray(pic[..., [2, 1, 0] + ([3] if self.channels == 4 else [])])
-        self.view(torch, pool, base, W, H).copy_(torch.from_numpy(np.array(src)).cuda())
-
-
-class _RgbPlanes(_Pixels):
-    channels = 3
-
-    def pitch(self, W):
-        return W + 13
-
-    def span(self, W, H):
-        return 2 * H * self.pitch(W) + (H - 1) * self.pitch(W) + W
-
-    def encoder(self, W, H, Q, n, stride=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
-        P = self.pitch(W)
-        enc = Mpeg1Encoder(W, H, Q, "full", max_frames=n)
-        enc.set_rgb_plane_layout(dict(r_offset=0, g_offset=H * P, b_offset=2 * H * P, row_pitch=P, frame_stride=stride or 3 * H * P))
-        return enc
-
-    def view(self, torch, pool, base, W, H, n=None, stride=0):
-        P = self.pitch(W)
-        one = (3, H, W), (H * P, P, 1)
-        return torch.as_strided(pool, *(one if n is None else ((n,) + one[0], (stride,) + one[1])), base)
-
-    def write(self, torch, pool, base, pic, W, H):
-        self.view(torch, pool, base, W, H).copy_(torch.from_numpy(np.ascontiguousarray(pic.transpose(2, 0, 1))).cuda())
-
-
-class _Samples:
-    """A tightly packed plane or sample preset: a frame is its bytes, every one of which the definition addresses."""
-    channels = 3
-
-    def __init__(self, preset):
-        self.preset = preset
-
-    def layout(self, W, H):
-        from ec504_imageencoder_amd import plane_layout_preset, sample_layout_preset
-        if self.preset == "yuy2":
-            return sample_layout_preset(W, H, "yuy2")
-        return dict(plane_layout_preset(W, H, self.preset), y_step=1)
-
-    def span(self, W, H):
-        return self.layout(W, H)["frame_stride"]
-
-    def encoder(self, W, H, Q, n, stride=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
-        enc = Mpeg1Encoder(W, H, Q, "full", max_frames=n)
-        enc.set_sample_layout(dict(self.layout(W, H), frame_stride=stride or self.span(W, H)))
-        return enc
-
-    def view(self, torch, pool, base, W, H, n=None, stride=0):
-        L = self.span(W, H)
-        return torch.as_strided(pool, *(((L,), (1,)) if n is None else ((n, L), (stride, 1))), base)
-
-    def pictures(self, rng, m, W, H, amp=256):
-        L = self.span(W, H)
-        return [rng.integers(0, 256, L, dtype=np.uint8) if amp >= 256 else (128 - amp // 2 + rng.integers(0, amp, L)).astype(np.uint8)
-                for _ in range(m)]
-
-    def write(self, torch, pool, base, pic, W, H):
-        self.view(torch, pool, base, W, H).copy_(torch.from_numpy(np.array(pic)).cuda())
-
-    def want(self, orc, pic, W, H, index, Q):
-        return sample_oracle.encode_layout(pic, self.layout(W, H), W, H, index, Q, orc.MODE_FULL)
 
 
 FAMILIES = {"bgra": _Surface(4, 12, "bgr"),     # pitched B,G,R,A surface (k_*_surface, 4-byte pixels)
@@ -143,9 +40,6 @@ FAMILIES = {"bgra": _Surface(4, 12, "bgr"),     # pitched B,G,R,A surface (k_*_s
 
 
 # ---- scattered placement ----------------------------------------------------------------------------------------------------
-def _picture_of(f):
-    """Which picture frame f of a batch shows: frame 2 repeats frame 0's, so a batch of three or more names one address twice."""
-    return 0 if f == 2 else f
 
 
 def _scatter(torch, fam, pics, n, W, H, fill_seed=0):
@@ -171,11 +65,6 @@ def _scatter(torch, fam, pics, n, W, H, fill_seed=0):
     if n >= 3:
         assert bases[2] == bases[0] and bases != sorted(bases) and len({b % 16 for b in bases}) >= 2 and any(b % 2 for b in bases)
     return pool, bases
-
-
-def _addresses(torch, pool, bases):
-    """A caller-built table: the int64 CUDA tensor of the frames' addresses."""
-    return torch.tensor([pool.data_ptr() + b for b in bases], dtype=torch.int64).cuda()
 
 
 _cache = {}
@@ -204,22 +93,6 @@ def _table_encoder(fam, W, H, Q, n, stride=0):
     enc.set_frame_table()
     assert enc.frame_table and (enc.path, enc.size_table_fused, enc.scratch_bytes(), enc._input) == before == ("tiles", 1) + before[2:]
     return enc
-
-
-def _check(torch, enc, table, recs, first=FIRST, Q=None):
-    """encode, the size-table row and the rd-table row of the table against the oracle's records."""
-    got, sizes = _encode(torch, enc, table, first)
-    want = [len(r) for r in recs]
-    assert sizes == want, [f for f in range(len(recs)) if sizes[f] != want[f]]
-    at = np.concatenate([[0], np.cumsum(want)])
-    wrong = [f for f in range(len(recs)) if got[at[f]:at[f + 1]] != recs[f]]
-    assert not wrong and len(got) == at[-1], ("frames", wrong)
-    Q = enc.quality_factor if Q is None else Q
-    rows, status = _table(torch, enc, table, (Q,))
-    assert status == [0] and rows == [want]
-    rd_sizes, _ = enc.frame_rd_table(table, (Q,))
-    torch.cuda.synchronize()
-    assert rd_sizes.cpu().numpy().tolist() == [want]
 
 
 # ---- 1. the parity matrix ---------------------------------------------------------------------------------------------------

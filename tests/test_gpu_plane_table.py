@@ -11,10 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import sample_oracle
-from test_gpu_frame_table import _check, _picture_of
-from test_gpu_size_table import _frames, _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _table
+from layout_inputs import SEPARATE, _blocks, _check, _device_table, _picture_of, _Rgb, _Ycc
 
 pytestmark = pytest.mark.gpu
 
@@ -34,105 +32,8 @@ def torch_cuda():
 
 
 # ---- the families: the layout the encoder is given, the virtual frame the oracle reads, and how the planes are grouped ------------
-class _Ycc:
-    """Y, Cb, Cr planes.  preset: the layout of the virtual contiguous frame, which the oracle reads.  chroma_offsets: None = the
-    encoder gets the preset too (a plane's pointer then stands for the virtual frame's byte 0, and the plane's samples lie
-    p_offset behind it); or the (cb, cr) offsets the encoder gets, with y_offset 0.  groups: the planes that share an allocation,
-    each with the distance of its pointer from the allocation's first byte."""
-    rgb = False
-
-    def __init__(self, preset, groups, chroma_offsets=None):
-        self.preset, self.groups, self.chroma_offsets = preset, groups, chroma_offsets
-
-    def oracle_layout(self, W, H):
-        from ec504_imageencoder_amd import plane_layout_preset
-        return dict(plane_layout_preset(W, H, self.preset), y_step=1)
-
-    def encoder_layout(self, W, H):
-        lay = {k: v for k, v in self.oracle_layout(W, H).items() if k != "y_step"}
-        if self.chroma_offsets is not None:
-            lay.update(y_offset=0, cb_offset=self.chroma_offsets[0], cr_offset=self.chroma_offsets[1])
-        return lay
-
-    def encoder(self, W, H, Q, n, stride=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
-        enc = Mpeg1Encoder(W, H, Q, "full", max_frames=n)
-        enc.set_plane_layout(dict(self.encoder_layout(W, H), **({"frame_stride": stride} if stride else {})))
-        return enc
-
-    def pictures(self, rng, m, W, H, amp=256):
-        L = self.oracle_layout(W, H)["frame_stride"]
-        return [rng.integers(0, 256, L, dtype=np.uint8) if amp >= 256 else (128 - amp // 2 + rng.integers(0, amp, L)).astype(np.uint8)
-                for _ in range(m)]
-
-    def virtual(self, pic, W, H):
-        return pic
-
-    def want(self, orc, pic, W, H, index, Q):
-        return sample_oracle.encode_layout(pic, self.oracle_layout(W, H), W, H, index, Q, orc.MODE_FULL)
-
-    def planes(self, W, H, region=None):
-        """Per plane (v, lo, E, A): the virtual frame's index the plane's pointer stands for, the range [lo, E) of the read
-        contract relative to the pointer, and the virtual indices of the samples the definition addresses.  region: the coded
-        region (xe, ye), by default W & ~15, H & ~15: the header's E_p counts ye rows of xe bytes for Y and ye / 2 rows of
-        (xe / 2 - 1) * c_step + 1 bytes for Cb and Cr."""
-        xe, ye = (W & ~15, H & ~15) if region is None else region
-        o, e = self.oracle_layout(W, H), self.encoder_layout(W, H)
-        r, c = np.arange(ye)[:, None], np.arange(xe)[None, :]
-        out = [(o["y_offset"] - e["y_offset"], 0, e["y_offset"] + (ye - 1) * e["y_pitch"] + xe,
-                (o["y_offset"] + r * o["y_pitch"] + c).reshape(-1))]
-        r, c = np.arange(ye // 2)[:, None], np.arange(xe // 2)[None, :]
-        for k in ("cb_offset", "cr_offset"):
-            out.append((o[k] - e[k], 0, e[k] + (ye // 2 - 1) * e["c_pitch"] + (xe // 2 - 1) * e["c_step"] + 1,
-                        (o[k] + r * o["c_pitch"] + c * o["c_step"]).reshape(-1)))
-        return out
 
 
-class _Rgb:
-    """Pitched planes of R, G and B, `order` = which third of the virtual frame holds R, G and B.  A plane's range starts at its
-    offset, so its pointer may stand c_offset in front of the allocation that holds it."""
-    rgb = True
-    groups = (((0, 0),), ((1, 0),), ((2, 0),))
-
-    def __init__(self, order):
-        self.order = order
-
-    def pitch(self, W):
-        return W + 13
-
-    def encoder_layout(self, W, H):
-        P = self.pitch(W)
-        r, g, b = (self.order.index(ch) * H * P for ch in "rgb")
-        return dict(r_offset=r, g_offset=g, b_offset=b, row_pitch=P, frame_stride=3 * H * P)
-
-    def encoder(self, W, H, Q, n, stride=0):
-        from ec504_imageencoder_amd import Mpeg1Encoder
-        enc = Mpeg1Encoder(W, H, Q, "full", max_frames=n)
-        enc.set_rgb_plane_layout(dict(self.encoder_layout(W, H), **({"frame_stride": stride} if stride else {})))
-        return enc
-
-    def pictures(self, rng, m, W, H, amp=256):
-        return list(_frames(rng, m, W, H, 3, amp))
-
-    def virtual(self, pic, W, H):
-        e = self.encoder_layout(W, H)
-        v = np.zeros(e["frame_stride"], np.uint8)
-        for ch, (_, _, _, A) in enumerate(self.planes(W, H)):
-            v[A] = pic[..., ch].reshape(-1)
-        return v
-
-    def want(self, orc, pic, W, H, index, Q):
-        return orc.encode_frame(pic, W, H, index, Q, orc.MODE_FULL, channels=3)
-
-    def planes(self, W, H, region=None):
-        """(An RGB plane's range is the layout's own, of the whole picture: width bytes of height rows, whatever the region.)"""
-        e = self.encoder_layout(W, H)
-        r, c = np.arange(H)[:, None], np.arange(W)[None, :]
-        return [(0, e[k], e[k] + (H - 1) * e["row_pitch"] + W, (e[k] + r * e["row_pitch"] + c).reshape(-1))
-                for k in ("r_offset", "g_offset", "b_offset")]
-
-
-SEPARATE = (((0, 0),), ((1, 0),), ((2, 0),))
 FAMILIES = {"i420": _Ycc("i420", SEPARATE),
             "yv12": _Ycc("yv12", SEPARATE),                                      # the offsets are swapped, not the pointers
             "nv12": _Ycc("nv12", (((0, 0),), ((1, 0), (2, 0)))),                 # both chroma entries hold the UV pointer, offsets 0 and 1
@@ -143,18 +44,6 @@ FAMILIES = {"i420": _Ycc("i420", SEPARATE),
 
 
 # ---- placement --------------------------------------------------------------------------------------------------------------
-def _blocks(fam, W, H, region=None):
-    """Per group (v0, length, [(plane, distance of its pointer from the block's first byte)], virtual indices written): the bytes
-    of the virtual frame from v0 on that the block stands for."""
-    planes = fam.planes(W, H, region)
-    out = []
-    for group in fam.groups:
-        # (the group's pointers are d apart as the family says: [f][2] = [f][1] + 1 stands for virtual indices one apart)
-        assert len({planes[p][0] - d for p, d in group}) == 1, group
-        v0 = min(planes[p][0] + planes[p][1] for p, d in group)
-        end = max(planes[p][0] + planes[p][2] for p, d in group)
-        out.append((v0, end - v0, [(p, planes[p][0] - v0) for p, d in group], np.concatenate([planes[p][3] for p, d in group])))
-    return out
 
 
 def _place(torch, fam, pics, n, W, H, fill_seed=0, tight=False):
@@ -210,10 +99,6 @@ def _place(torch, fam, pics, n, W, H, fill_seed=0, tight=False):
     if G == 3 and not tight:
         assert not (table[0, 0] < table[0, 1] < table[0, 2]) and len({pool_of[t] for t in range(3)}) == 3
     return pools, table
-
-
-def _device_table(torch, table):
-    return torch.from_numpy(np.ascontiguousarray(table)).cuda()
 
 
 _cache = {}

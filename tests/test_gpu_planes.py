@@ -12,16 +12,14 @@ import numpy as np
 import pytest
 
 import plane_oracle
-from test_gpu_rate import SEQUENCE, RateMixed
-from test_gpu_size_table import _frames, _mixed_frames, _oracle, _oracle_sizes, _table
-from test_gpu_surface import MATRIX as SURFACE_MATRIX
-from test_gpu_surface import _encode, _frame_rule
-from test_gpu_size_table import CASES as RGB_CASES
-from test_rate_abi import batch_rule, cbr_rule
+from gpu_calls import _encode, _frame_rule, _frames, _mixed_frames, _oracle, _oracle_on_buffer, _oracle_sizes, _table
+from layout_inputs import PRESETS, _buffer, _layout, _plane_encoder, _planes_of, _region, _view, _write_planes
+from rate_rules import batch_rule, cbr_rule
+from table_cases import RGB_CASES, SEQUENCE, RateMixed
+from table_cases import MATRIX as SURFACE_MATRIX
 
 pytestmark = pytest.mark.gpu
 
-PRESETS = ("reference", "i420", "yv12", "nv12", "nv21")
 LAYOUTS = PRESETS + ("pitched", "odd", "window")
 # the surface matrix (3-channel side) with the odd-width case kept: a plane layout takes odd widths
 MATRIX = dict(SURFACE_MATRIX)
@@ -33,97 +31,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _region(W, H, mode):
-    return (W & ~15, H & ~15) if mode == "full" else (96, 144)
-
-
-# ---- layouts ----------------------------------------------------------------------------------------------------------------
-def _layout(name, W, H):
-    """(layout dict with no zeros, byte offset of frame 0 in the buffer)."""
-    from ec504_imageencoder_amd import plane_layout_preset
-    if name in PRESETS:
-        return plane_layout_preset(W, H, name), 0
-    hw, hh = W // 2, H // 2
-    if name == "pitched":                       # both pitches + 256 and a gap between the frames
-        yp, cp = W + 256, hw + 256
-        cb = H * yp
-        cr = cb + hh * cp
-        return dict(y_offset=0, cb_offset=cb, cr_offset=cr, y_pitch=yp, c_pitch=cp, c_step=1, frame_stride=cr + hh * cp + 4099), 0
-    if name == "odd":                           # base, offsets, pitches and stride odd
-        yp, cp = (W + 1) | 1, (hw + 1) | 1
-        cb = (3 + H * yp) | 1
-        cr = (cb + hh * cp + 2) | 1
-        return dict(y_offset=3, cb_offset=cb, cr_offset=cr, y_pitch=yp, c_pitch=cp, c_step=1, frame_stride=(cr + hh * cp + 8) | 1), 1
-    assert name == "window"                     # a window at odd (x0, y0) of planes about twice as large
-    SW, SH = 2 * W + 6, 2 * H + 2
-    cw, ch = SW // 2, SH // 2
-    x0, y0, cx0, cy0 = (W // 2) | 1, (H // 2) | 1, (W // 4) | 1, (H // 4) | 1
-    return dict(y_offset=y0 * SW + x0, cb_offset=SW * SH + cy0 * cw + cx0, cr_offset=SW * SH + cw * ch + cy0 * cw + cx0,
-                y_pitch=SW, c_pitch=cw, c_step=1, frame_stride=SW * SH + 2 * cw * ch), 0
-
-
-def _buffer(torch, n, lay, base, fill_seed):
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2000 + fill_seed)
-    return torch.randint(0, 256, (base + n * lay["frame_stride"] + 64,), dtype=torch.uint8, device="cuda", generator=gen)
-
-
-def _view(torch, buf, n, lay, base, enc):
-    """The [n, L] tensor the encoder is given: row f = frame f, L = the bytes the frame's planes span."""
-    from ec504_imageencoder_amd.encoder import plane_layout_extent
-    L = plane_layout_extent(lay, enc.strips, enc.mb_rows)
-    assert L <= lay["frame_stride"]
-    return torch.as_strided(buf, (n, L), (lay["frame_stride"], 1), base)
-
-
-def _write_planes(torch, buf, lay, base, Y, Cb, Cr):
-    """Y [n, rows, cols], Cb / Cr [n, rows / 2, cols / 2] (numpy) -> the samples the definition addresses, through the layout;
-    every other byte of buf stays what it was."""
-    n = Y.shape[0]
-    s = lay["frame_stride"]
-    torch.as_strided(buf, Y.shape, (s, lay["y_pitch"], 1), base + lay["y_offset"]).copy_(torch.from_numpy(np.ascontiguousarray(Y)).cuda())
-    for plane, off in ((Cb, lay["cb_offset"]), (Cr, lay["cr_offset"])):
-        torch.as_strided(buf, plane.shape, (s, lay["c_pitch"], lay["c_step"]), base + off).copy_(
-            torch.from_numpy(np.ascontiguousarray(plane)).cuda())
-    assert n == Cb.shape[0] == Cr.shape[0]
-
-
-def _addressed(orc, px, mode):
-    """RGB frames [n, H, W, 3] -> the samples the encoder's region addresses: Y [n, ye, xe] and Cb, Cr [n, ye / 2, xe / 2] cut
-    from the converted full-resolution planes read with stride W / 2 (encoder.h:347-348)."""
-    n, H, W, _ = px.shape
-    xe, ye = _region(W, H, mode)
-    hw = W // 2
-    Ys, Cbs, Crs = [], [], []
-    for f in range(n):
-        Y, Cb, Cr = orc.convert(px[f])
-        Ys.append(Y.reshape(H, W)[:ye, :xe])
-        Cbs.append(Cb[:(ye // 2) * hw].reshape(ye // 2, hw)[:, :xe // 2])
-        Crs.append(Cr[:(ye // 2) * hw].reshape(ye // 2, hw)[:, :xe // 2])
-    return np.stack(Ys), np.stack(Cbs), np.stack(Crs)
-
-
-def _plane_encoder(W, H, Q, mode, n, lay, pipelined=False):
-    from ec504_imageencoder_amd import Mpeg1Encoder
-    enc = Mpeg1Encoder(W, H, Q, mode, channels=3, max_frames=n)
-    enc.set_plane_layout(lay)
-    assert enc.path == "tiles" and enc.size_table_fused == 1
-    assert enc.plane_layout == lay
-    if pipelined:
-        enc.set_pipelined(True)
-        assert enc.path == "tiles" and enc.plane_layout == lay
-    return enc
-
-
-def _planes_of(torch, orc, px, mode, layout, fill_seed=0):
-    """RGB frames -> (encoder input view, layout dict) in `layout`, over a buffer of noise."""
-    n, H, W, _ = px.shape
-    lay, base = _layout(layout, W, H)
-    buf = _buffer(torch, n, lay, base, fill_seed)
-    _write_planes(torch, buf, lay, base, *_addressed(orc, px, mode))
-    return buf, lay, base
 
 
 # ---- 1. the parity matrix ---------------------------------------------------------------------------------------------------
@@ -199,12 +106,6 @@ def _independent(W, H, n, seed):
     Cb = np.stack([plane((f + 1) % 3, H // 2, W // 2) for f in range(n)])
     Cr = np.stack([plane((f + 2) % 3, H // 2, W // 2) for f in range(n)])
     return Y, Cb, Cr
-
-
-def _oracle_on_buffer(orc, buf, n, lay, base, W, H, first, qs, mode):
-    """plane_oracle's records of the frames as they lie in the device buffer (asserts that every frame is encodable)."""
-    host = buf.cpu().numpy()
-    return [plane_oracle.encode_layout(host[base + f * lay["frame_stride"]:], lay, W, H, first + f, qs[f], mode) for f in range(n)]
 
 
 @pytest.mark.parametrize("layout", PRESETS)

@@ -7,8 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_size_table import Mixed, _frames, _mixed_frames, _oracle, _oracle_sizes
-from test_rate_abi import batch_rule, cbr_rule
+from gpu_calls import _frames, _mixed_frames, _oracle
+from rate_rules import batch_rule, cbr_rule
+from table_cases import RCANDS, SEQUENCE, RateMixed, _table
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +30,6 @@ def _encoder(W, H, n, producer, pipelined=False, channels=3, quality=12):
     if pipelined:
         enc.set_pipelined(True)
     return enc
-
-
-def _table(orc, rgb, cands, channels=3):
-    return [_oracle_sizes(orc, rgb, orc.MODE_FULL, c, channels) for c in cands]
 
 
 def _stream(torch):
@@ -301,41 +298,6 @@ def test_launch_count(torch_cuda, orc, producer):
 
 
 # ---- 6. interleaved with every other kind of call -------------------------------------------------------------------------
-RCANDS = (3, 7, 12)
-
-
-class RateMixed(Mixed):
-    """Mixed (tests/test_gpu_size_table.py) with batch-budget and bitrate calls, checked at once against the rules."""
-
-    def __init__(self, torch, orc, enc, seed):
-        super().__init__(torch, orc, enc, seed)
-        self.level = torch.full((1,), 123456, dtype=torch.int64, device="cuda")
-        self.level_host = 123456
-
-    def call(self, kind, n):
-        if kind not in ("batch", "cbr"):
-            return super().call(kind, n)
-        torch, enc, orc = self.torch, self.enc, self.orc
-        rgb = _mixed_frames(self.rng, n, enc.width, enc.height, enc.channels)
-        dev = torch.from_numpy(rgb).cuda()
-        self.first += 29
-        s = _table(orc, rgb, RCANDS, enc.channels)
-        if kind == "batch":
-            B = (sum(s[0]) + sum(s[1])) // 2
-            pick, over = batch_rule(s, B)
-            got, sizes, ch, ov = enc.encode_to_batch_budget(dev, B, RCANDS, first_frame_index=self.first)
-        else:
-            r = sorted(s[1])[n // 2]
-            pick, over, self.level_host = cbr_rule(s, r, 3 * r, self.level_host)
-            got, sizes, ch, ov = enc.encode_at_bitrate(dev, r, 3 * r, RCANDS, self.level, first_frame_index=self.first)
-            assert int(self.level.cpu()[0]) == self.level_host
-        chosen = [RCANDS[k] for k in pick]
-        want, wsizes = _oracle(orc, rgb, self.first, chosen, orc.MODE_FULL, enc.channels)
-        assert (ch, ov, sizes, got) == (chosen, over, wsizes, want), (kind, n)
-
-
-SEQUENCE = (("plain", 5), ("batch", 4), ("table", 3), ("cbr", 5), ("probe", 3), ("quality", 5), ("cbr", 2), ("budget", 2),
-            ("batch", 5), ("table", 1), ("plain", 5))
 
 
 @pytest.mark.parametrize("pipelined", [False, True])

@@ -7,9 +7,8 @@ import numpy as np
 import pytest
 
 import rd_oracle as rd
-from test_gpu_hard_content import FIRST, _Case
-from test_gpu_rd_table import _case_dist
-from test_gpu_size_table import _mixed_frames
+from gpu_calls import _mixed_frames, _model, _rd_device
+from hard_content_cases import FIRST, _Case, _case_dist
 
 pytestmark = pytest.mark.gpu
 
@@ -21,41 +20,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _rd_device(torch, enc, dev, cands, rule, limit, first, limits=None, want_chosen=True, want_dist=True):
-    """One m1v_encode_rd_device call through the C entry point -> (bytes, sizes, chosen, distortion, status)."""
-    from ec504_imageencoder_amd import _ffi
-    n = dev.shape[0]
-    out = torch.empty(enc.frame_bound * max(n, 1), dtype=torch.uint8, device="cuda")
-    sizes = torch.full((max(n, 1),), -1, dtype=torch.int64, device="cuda")
-    chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda") if want_chosen else None
-    dist = torch.full((max(n, 1),), -1, dtype=torch.int64, device="cuda") if want_dist else None
-    meta = torch.zeros(2, dtype=torch.int64, device="cuda")
-    d_limits = torch.tensor(list(limits), dtype=torch.int64).cuda() if limits is not None else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    cbuf = (C.c_uint8 * len(cands))(*cands)
-    rc = _ffi.lib().m1v_encode_rd_device(enc._h, p(dev), n, first, cbuf, len(cands), rule, int(limit), p(d_limits), p(chosen), p(out),
-                                         out.numel(), p(sizes), p(dist), C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, _ffi.last_error()
-    enc.flush()
-    torch.cuda.synchronize()
-    total, status = (int(x) for x in meta.cpu())
-    return (out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:n].cpu()],
-            [int(c) for c in chosen[:n].cpu()] if want_chosen else None,
-            [int(d) for d in dist[:n].cpu()] if want_dist else None, status & 0xFFFFFFFF)
-
-
-def _model(rule, s, d, limits, out=()):
-    """The model's picks for every frame of a table s / d [k][f]: (k per frame, frames over their limit)."""
-    picks, over = [], []
-    for f in range(len(s[0])):
-        k, o = rd.pick(rule, [row[f] for row in s], [row[f] for row in d], limits[f], out)
-        picks.append(k)
-        if o:
-            over.append(f)
-    return picks, over
 
 
 # ---- 1. both rules on noise: scalar and per-frame limits, none fits / none qualifies ----------------------------------------

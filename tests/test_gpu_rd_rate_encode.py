@@ -9,9 +9,8 @@ import pytest
 
 import rd_oracle as rd
 import rd_rate_model as M
-from test_gpu_hard_content import FIRST, _Case
-from test_gpu_rd_table import _case_dist
-from test_gpu_size_table import _mixed_frames
+from gpu_calls import _mixed_frames
+from hard_content_cases import FIRST, _Case, _case_dist
 
 pytestmark = pytest.mark.gpu
 
@@ -292,7 +291,7 @@ def test_failed_call_leaves_the_encoder_correct(torch_cuda, noise, stage, call):
     Limitation: these calls need the fused table, whose pass comes first and has the hook at all three stages, so the failure
     is always the table's.  This pins the table's poison recovery inside these calls, not a failure in the encode behind it."""
     from ec504_imageencoder_amd import Mpeg1Encoder, _ffi
-    from test_gpu_rd_encode import _model, _rd_device
+    from gpu_calls import _model, _rd_device
     torch = torch_cuda
     n, first, K = 5, noise["first"], len(NOISE_CANDS)
     S, D = [row[:n] for row in noise["s"]], [row[:n] for row in noise["d"]]

@@ -7,10 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import hard_content as hc
 import rd_oracle as rd
-from test_gpu_hard_content import _Case, _content
-from test_gpu_size_table import _frames, _mixed_frames, _oracle_sizes
+from gpu_calls import _frames, _mixed_frames, _oracle_sizes, _rd
+from hard_content_cases import _Case, _case_dist
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +19,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _rd(torch, enc, dev, quals):
-    """(sizes, distortion, status) of one frame_rd_table call as lists."""
-    st = torch.full((len(quals),), 0x40, dtype=torch.int32, device="cuda")
-    s, d = enc.frame_rd_table(dev, quals, status=st)
-    enc.flush()
-    torch.cuda.synchronize()
-    return s.cpu().numpy().tolist(), d.cpu().numpy().tolist(), [int(x) for x in st.cpu()]
 
 
 def _sizes(torch, enc, dev, quals):
@@ -87,23 +77,6 @@ def test_the_gradient_of_the_design_table(torch_cuda, orc):
 
 
 # ---- 2. hard content through each kernel family -----------------------------------------------------------------------------
-_dist_cache = {}
-
-
-def _case_dist(orc, case, f, q):
-    """D of frame f of a _Case at quality q, from the oracle (cached per content frame)."""
-    key = (case.kind, case.W, case.H, case.ids[f], q)
-    if key not in _dist_cache:
-        W, H = case.W, case.H
-        if case.kind == "planes":
-            d = rd.divisors_zigzag(orc, q)
-            planes = [p[case.ids[f]] for p in _content(orc, "planes", W, H)]
-            _dist_cache[key] = int(sum(rd.block_distortion(hc.plane_coefficients(orc, p, 100), hc.plane_coefficients(orc, p, q), d).sum()
-                                       for p in planes))
-        else:
-            px = _content(orc, case.kind, W, H)[case.ids[f]]
-            _dist_cache[key] = rd.frame_distortion(orc, px, W, H, q, orc.MODE_FULL, px.shape[-1])
-    return _dist_cache[key]
 
 
 FAMILIES = ["rgb", "rgba", "surface-3-bgr-window", "surface-4-bgr-window", "planes-i420", "planes-nv12"]

@@ -13,13 +13,12 @@ import pytest
 
 import hard_content as hc
 import rd_oracle
-from test_gpu_parity import _COLOURS_PER_FRAME, _CH, _CW, _flat_cell_frames, _tie_colours
-from test_gpu_size_table import _frames, _mixed_frames, _table
-from test_gpu_surface import _encode
+from colour_content import _CH, _COLOURS_PER_FRAME, _CW, _flat_cell_frames, _tie_colours
+from gpu_calls import _encode, _frames, _mixed_frames, _table
+from layout_inputs import _planar
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 # one macroblock; 3 strips in one partial tile (a chroma unit that overhangs its half row); 9 strips x 5 macroblock rows (a 2 x 2
 # tile grid whose last column holds one strip); 11 strips (3, odd, in the last tile column); 17 strips (1 in the third tile
 # column); 22 strips (6, even, in the last tile column)
@@ -27,8 +26,6 @@ SIZES = ((16, 16), (48, 32), (144, 80), (176, 144), (272, 144), (352, 288))
 LAYOUTS = ("rgb", "bgr", "gbr", "pitched", "rgba", "rows")
 QUALITIES = (12, 76, 77, 100)       # byte staging up to 76, halfword staging from 77
 BATCHES = (1, 3, 9, 17)             # up to 8 frames and more: both branches of the workgroup -> (frame, tile) map
-# which component (0 = R) each memory plane holds
-_PLANES = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "gbr": (1, 2, 0)}
 
 
 @pytest.fixture(scope="module")
@@ -36,36 +33,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _geometry(layout, n, H, W):
-    """(shape, strides, order) of the [n, C, H, W] view of `layout`, strides in bytes."""
-    if layout in _PLANES:                       # tightly packed planes in that memory order
-        return (n, 3, H, W), (3 * H * W, H * W, W, 1), layout
-    if layout == "pitched":                     # pitch W + 13, 64 + 1 bytes between frames
-        P = W + 13
-        return (n, 3, H, W), (3 * H * P + 65, H * P, P, 1), "rgb"
-    if layout == "rgba":                        # the first three planes of a 4-plane tensor
-        return (n, 4, H, W), (4 * H * W, H * W, W, 1), "rgb"
-    assert layout == "rows"                     # planes interleaved by rows: row_pitch 3 W, offsets 0, W, 2 W
-    return (n, 3, H, W), (3 * H * W, W, 3 * W, 1), "rgb"
-
-
-def _planar(torch, px, layout, fill_seed=0, base=GUARD):
-    """px: uint8 [n, H, W, 3] in R,G,B order -> (the strided CUDA view [n, C, H, W] the encoder is given, its layout dict), over a
-    buffer whose every other byte — row padding, a fourth plane, the gaps between frames, GUARD bytes in front of the first and
-    behind the last frame — is noise of fill_seed."""
-    from ec504_imageencoder_amd import rgb_plane_strides
-    n, H, W, _ = px.shape
-    shape, strides, order = _geometry(layout, n, H, W)
-    span = sum(s * (d - 1) for s, d in zip(strides[1:], shape[1:])) + 1   # bytes from a frame's first to its last element
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2000 + fill_seed)
-    buf = torch.randint(0, 256, (base + (n - 1) * strides[0] + span + GUARD,), dtype=torch.uint8, device="cuda", generator=gen)
-    view = torch.as_strided(buf, shape, strides, base)
-    comp = _PLANES.get(layout, (0, 1, 2))
-    view[:, :3].copy_(torch.from_numpy(np.ascontiguousarray(px.transpose(0, 3, 1, 2)[:, comp])).cuda())
-    return view, rgb_plane_strides(shape, strides, order)
 
 
 def _encoder(W, H, Q, n, lay):

@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_rate import SEQUENCE, RateMixed
-from test_gpu_size_table import CASES as RGB_CASES
-from test_gpu_size_table import _frames, _mixed_frames, _oracle, _oracle_sizes, _table
-from test_rate_abi import batch_rule, cbr_rule
+from gpu_calls import _frames, _mixed_frames, _oracle, _oracle_sizes, _table
+from rate_rules import batch_rule, cbr_rule
+from table_cases import SEQUENCE, RateMixed
+from table_cases import RGBA_CASES as CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -50,11 +50,6 @@ def _rgba(rng, n, W, H, amps=(4, 40, 256, 120)):
 
 
 # ---- 1. the table against the oracle --------------------------------------------------------------------------------------
-# the cases of tests/test_gpu_size_table.py, a geometry whose encodes take the strip kernel (9 macroblock rows: 54 blocks per
-# strip), and a width whose last tile column holds an odd number of strips (11 = 8 + 3)
-CASES = dict(RGB_CASES)
-CASES["strip_kernel_352x144"] = (352, 144, 12, "full", 4, (4, 40, 256, 120), (1, 3, 8, 12))
-CASES["odd_last_column_176x208"] = (176, 208, 12, "full", 3, (4, 256, 40), (2, 7, 12))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -265,7 +260,7 @@ def test_unencodable_quality_is_flagged_like_the_probes(torch_cuda, orc):
     """The picture of tests/test_gpu_state.py::_unencodable (at quality 92 every block has |level| 308 after a zero) with an
     alpha byte: M1V_STATUS_UNENCODABLE in exactly the status words where the K-probe encoder sets it; every other row is the
     oracle's."""
-    from test_gpu_state import _unencodable
+    from gpu_calls import _unencodable
     from ec504_imageencoder_amd import _ffi
     W, H, n, quals = 352, 288, 2, (12, 50, 92)
     fused, probing = _fused(W, H, 92, "full", n), _probing(W, H, 92, "full", n)

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 import sample_oracle
-from test_gpu_size_table import _table
-from test_gpu_surface import _encode
+from gpu_calls import _encode, _table
+from layout_inputs import GUARD, _noise, _scatter
+from layout_inputs import _sample_view as _view
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,6 @@ LAYOUTS = PRESETS + ("yuy2_window", "p010_window")
 SIZES = ((16, 16), (48, 16), (136, 72), (144, 80), (176, 80), (272, 144))
 QUALITIES = (12, 76, 77, 100)       # byte staging up to 76, halfword staging from 77
 BATCHES = (1, 3, 9)                 # up to 8 frames and more: both branches of the workgroup -> (frame, tile) map
-GUARD = 64
 
 
 @pytest.fixture(scope="module")
@@ -46,22 +46,6 @@ def _layout(name, W, H):
     cb = H * yp + 32 + 8 + 1
     return dict(y_offset=6 + 1, cb_offset=cb, cr_offset=cb + 2, y_pitch=yp, c_pitch=yp, y_step=2, c_step=4,
                 frame_stride=cb + (H // 2) * yp + 200), GUARD
-
-
-def _noise(n, lay, base, seed, amp=256):
-    """The host image of a buffer of n frames: noise everywhere (amp 64: 96..159, whose AC levels stay below 256 at any quality:
-    a coefficient is at most 32 * (sum of |cos|)^2 / 4 < 32 * 6.6)."""
-    rng = np.random.default_rng(seed)
-    size = base + n * lay["frame_stride"] + GUARD
-    return rng.integers(0, 256, size, dtype=np.uint8) if amp == 256 else (96 + rng.integers(0, amp, size)).astype(np.uint8)
-
-
-def _view(torch, dev, n, lay, base, enc):
-    """The [n, L] tensor the encoder is given: row f = frame f, L = the frame's extent."""
-    from ec504_imageencoder_amd.encoder import plane_layout_extent
-    L = plane_layout_extent(lay, enc.strips, enc.mb_rows)
-    assert L <= lay["frame_stride"] and base >= GUARD and base + (n - 1) * lay["frame_stride"] + L + GUARD <= dev.numel()
-    return torch.as_strided(dev, (n, L), (lay["frame_stride"], 1), base)
 
 
 def _want(orc, host, n, lay, base, W, H, first, qs):
@@ -87,17 +71,6 @@ def _gather(host, n, lay, base, W, H):
         Cbs.append(fr[lay["cb_offset"] + r * lay["c_pitch"] + c * lay["c_step"]])
         Crs.append(fr[lay["cr_offset"] + r * lay["c_pitch"] + c * lay["c_step"]])
     return np.stack(Ys), np.stack(Cbs), np.stack(Crs)
-
-
-def _scatter(host, lay, base, Y, Cb, Cr):
-    """Y [n, H, W], Cb, Cr [n, H / 2, W / 2] into the bytes the definition addresses; every other byte stays."""
-    for f in range(Y.shape[0]):
-        fr = host[base + f * lay["frame_stride"]:]
-        r, c = np.mgrid[0:Y.shape[1], 0:Y.shape[2]]
-        fr[lay["y_offset"] + r * lay["y_pitch"] + c * lay["y_step"]] = Y[f]
-        r, c = np.mgrid[0:Cb.shape[1], 0:Cb.shape[2]]
-        fr[lay["cb_offset"] + r * lay["c_pitch"] + c * lay["c_step"]] = Cb[f]
-        fr[lay["cr_offset"] + r * lay["c_pitch"] + c * lay["c_step"]] = Cr[f]
 
 
 def _i420(torch, Y, Cb, Cr):

@@ -7,6 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_calls import _frames, _mixed_frames, _oracle, _oracle_sizes, _table
+from table_cases import CANDS, Mixed, _rule
+from table_cases import RGB_CASES as CASES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,49 +21,7 @@ def torch_cuda():
     return torch
 
 
-def _frames(rng, n, W, H, channels, amp=256):
-    """n frames of noise (amp 256) or of gentle noise around mid-grey (small amp)."""
-    shape = (n, H, W, channels)
-    if amp >= 256:
-        return rng.integers(0, 256, shape, dtype=np.uint8)
-    return (128 - amp // 2 + rng.integers(0, amp, shape)).astype(np.uint8)
-
-
-def _mixed_frames(rng, n, W, H, channels, amps=(4, 40, 256, 120)):
-    """Frames whose record sizes differ a lot: flat, gentle and full noise in turn."""
-    return np.concatenate([_frames(rng, 1, W, H, channels, amps[f % len(amps)]) for f in range(n)])
-
-
-def _oracle_sizes(orc, rgb, mode, q, channels):
-    W, H = rgb.shape[2], rgb.shape[1]
-    return [len(orc.encode_frame(rgb[f], W, H, f, int(q), mode, channels=channels)) for f in range(rgb.shape[0])]
-
-
-def _oracle(orc, rgb, first, qs, mode, channels):
-    W, H = rgb.shape[2], rgb.shape[1]
-    recs = [orc.encode_frame(rgb[f], W, H, first + f, int(qs[f]), mode, channels=channels) for f in range(rgb.shape[0])]
-    return b"".join(recs), [len(r) for r in recs]
-
-
-def _table(torch, enc, dev, quals):
-    st = torch.full((len(quals),), 0x40, dtype=torch.int32, device="cuda")
-    t = enc.frame_size_table(dev, quals, status=st)
-    enc.flush()
-    torch.cuda.synchronize()
-    return t.cpu().numpy().tolist(), [int(x) for x in st.cpu()]
-
-
 # ---- 1. the table against the oracle --------------------------------------------------------------------------------------
-CASES = {
-    # name: (W, H, Q, mode, n, amps, qualities)
-    "cif_full_k8": (352, 288, 12, "full", 4, (4, 40, 256, 120), (1, 2, 3, 5, 7, 9, 11, 12)),
-    "cif_strict_k1": (352, 288, 12, "strict", 3, (4, 40, 256), (7,)),
-    "q90_wide_staging": (352, 288, 90, "full", 3, (4, 40, 20), (1, 20, 60, 76, 77, 85, 90)),
-    "q90_narrow_only": (352, 288, 90, "full", 2, (40, 256), (10, 50, 76)),
-    "partial_tiles_366x216": (366, 216, 12, "full", 3, (4, 40, 256), (1, 6, 12)),
-    "tiny_105x49": (105, 49, 12, "full", 4, (4, 40, 256, 120), (1, 12)),
-    "uhd_one_frame": (3840, 2160, 12, "full", 1, (256,), (1, 5, 12)),
-}
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -206,75 +168,6 @@ def test_argument_errors(torch_cuda):
 
 
 # ---- 4. encoder state across calls of every kind --------------------------------------------------------------------------
-CANDS = (2, 4, 8, 12)
-
-
-def _rule(table, budgets):
-    """The largest candidate whose record fits, else the smallest: (chosen, over-budget frames)."""
-    chosen, over = [], []
-    for f, cap in enumerate(budgets):
-        fits = [c for c in CANDS if table[c][f] <= cap]
-        chosen.append(fits[-1] if fits else CANDS[0])
-        if not fits:
-            over.append(f)
-    return chosen, over
-
-
-class Mixed:
-    """Calls of every kind on one encoder, the size table among them; each call's expected output is computed from the oracle
-    at check time (the pattern of tests/test_gpu_quality.py)."""
-
-    def __init__(self, torch, orc, enc, seed):
-        self.torch, self.orc, self.enc = torch, orc, enc
-        self.rng = np.random.default_rng(seed)
-        self.pending = []
-        self.first = 200
-
-    def call(self, kind, n):
-        torch, enc, orc = self.torch, self.enc, self.orc
-        rgb = _mixed_frames(self.rng, n, enc.width, enc.height, enc.channels)
-        dev = torch.from_numpy(rgb).cuda()
-        self.first += 29
-        Q = enc.quality_factor
-        if kind == "plain":
-            self.pending.append((kind, rgb, self.first, [Q] * n, dev, enc.encode(dev, self.first)))
-        elif kind == "quality":
-            qs = [int(x) for x in self.rng.integers(1, Q + 1, n)]
-            self.pending.append((kind, rgb, self.first, qs, dev, enc.encode(dev, self.first, quality=qs)))
-        elif kind == "probe":
-            qs = [int(x) for x in self.rng.integers(1, Q + 1, n)]
-            self.pending.append((kind, rgb, self.first, qs, dev, enc.frame_sizes(dev, quality=qs)))
-        elif kind == "table":
-            k = int(self.rng.integers(1, 9))
-            quals = sorted(int(x) for x in self.rng.choice(np.arange(1, Q + 1), min(k, Q), replace=False))
-            self.pending.append((kind, rgb, self.first, quals, dev, enc.frame_size_table(dev, quals)))
-        else:                                    # synchronous: checked at once against the rule on the oracle's sizes
-            table = {c: _oracle(orc, rgb, self.first, [c] * n, orc.MODE_FULL, enc.channels)[1] for c in CANDS}
-            budget = sorted(table[8])[0]
-            chosen, over = _rule(table, [budget] * n)
-            got, sizes, ch, ov = enc.encode_to_budget(dev, budget, CANDS, first_frame_index=self.first)
-            want, wsizes = _oracle(orc, rgb, self.first, chosen, orc.MODE_FULL, enc.channels)
-            assert (ch, ov, sizes, got) == (chosen, over, wsizes, want), ("budget", n)
-
-    def check(self, what):
-        self.enc.flush()
-        self.torch.cuda.synchronize()
-        for k, (kind, rgb, first, qs, _, res) in enumerate(self.pending):
-            n = rgb.shape[0]
-            if kind == "table":
-                want = [_oracle_sizes(self.orc, rgb, self.orc.MODE_FULL, q, self.enc.channels) for q in qs]
-                assert res.cpu().numpy().tolist() == want, (what, k, kind, qs)
-                continue
-            want, wsizes = _oracle(self.orc, rgb, first, qs, self.orc.MODE_FULL, self.enc.channels)
-            if kind == "probe":
-                assert [int(s) for s in res[:n].cpu()] == wsizes, (what, k, kind)
-                continue
-            out, sizes, meta = res
-            total, status = (int(x) for x in meta.cpu())
-            assert status == 0, (what, k, kind, status)
-            assert [int(s) for s in sizes[:n].cpu()] == wsizes, (what, k, kind)
-            assert out[:total].cpu().numpy().tobytes() == want, (what, k, kind)
-        self.pending = []
 
 
 SEQUENCE = (("plain", 5), ("table", 3), ("probe", 3), ("table", 5), ("quality", 5), ("budget", 2), ("table", 1), ("plain", 5))

@@ -8,6 +8,8 @@ and would hide a status bit)."""
 import numpy as np
 import pytest
 
+from gpu_calls import _unencodable
+
 pytestmark = pytest.mark.gpu
 
 M = 6  # max_frames of the small encoders
@@ -43,13 +45,6 @@ def _frames(rng, enc, n, amp=256):
     if amp >= 256:
         return rng.integers(0, 256, shape, dtype=np.uint8)
     return (128 - amp // 2 + rng.integers(0, amp, shape)).astype(np.uint8)
-
-
-def _unencodable(enc, n):
-    """The picture of test_unencodable_level_is_reported, tiled: at quality 92 every block has |level| 308 after a zero."""
-    yy = np.mgrid[0:enc.height, 0:enc.width][0]
-    a = ((yy % 8) < 4).astype(np.uint8) * 255
-    return np.ascontiguousarray(np.broadcast_to(a[None, :, :, None], (n, enc.height, enc.width, enc.channels)))
 
 
 class Calls:

@@ -6,17 +6,16 @@ the window, np.ascontiguousarray(surface[:, y0:y0+H, x0:x0+W, :]) with bytes 0 a
 device buffer of noise into which exactly that packed copy is written through the strided view the encoder is given, so the
 packed copy is the array the test started from.  Every comparison is for equality; every status word is 0 unless a case says
 otherwise."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
-from test_gpu_parity import _COLOURS_PER_FRAME, _CH, _CW, _flat_cell_frames, _tie_colours
-from test_gpu_rate import SEQUENCE, RateMixed
-from test_gpu_rgba_table import CASES as RGBA_CASES
-from test_gpu_size_table import CASES as RGB_CASES
-from test_gpu_size_table import _frames, _mixed_frames, _oracle, _oracle_sizes, _table
-from test_rate_abi import batch_rule, cbr_rule
+from colour_content import _CH, _COLOURS_PER_FRAME, _CW, _flat_cell_frames, _tie_colours
+from gpu_calls import _encode, _frame_rule, _frames, _mixed_frames, _oracle, _oracle_sizes, _table
+from layout_inputs import _surface, _surface_encoder
+from layout_inputs import _surface_geometry as _geometry
+from rate_rules import batch_rule, cbr_rule
+from table_cases import MATRIX, RGB_CASES, SEQUENCE, RateMixed
 
 pytestmark = pytest.mark.gpu
 
@@ -29,49 +28,9 @@ def torch_cuda():
 
 
 # ---- surfaces ---------------------------------------------------------------------------------------------------------------
-def _geometry(layout, W, H, C):
-    """(row pitch, frame stride, byte offset of the window's first pixel in frame 0, bytes behind the last frame's stride)."""
-    if layout == "packed":                      # pitch exactly W * C
-        return W * C, H * W * C, 0, 0
-    if layout == "odd":                         # pitch W * C + 1, the base at an odd address
-        return W * C + 1, H * (W * C + 1), 1, 8
-    if layout == "gap":                         # pitch W * C + 256 and a gap between the frames
-        return W * C + 256, H * (W * C + 256) + 4099, 0, 0
-    assert layout == "window"                   # a window at odd (x0, y0) of a surface about twice as large
-    SW, SH, x0, y0 = 2 * W + 6, 2 * H + 2, (W // 2) | 1, (H // 2) | 1
-    return SW * C, SH * SW * C, (y0 * SW + x0) * C, 0
 
 
 LAYOUTS = ("packed", "odd", "gap", "window")
-
-
-def _surface(torch, px, layout, order, fill_seed=0):
-    """px: uint8 [n, H, W, C] in R,G,B(,A) order -> the strided CUDA view the encoder is given (bytes 0 and 2 swapped for
-    "bgr"), over a buffer whose every other byte — row padding, the gaps, the surface around a window — is noise of
-    fill_seed.  Returns (view, row pitch, frame stride)."""
-    n, H, W, C_ = px.shape
-    pitch, stride, off, tail = _geometry(layout, W, H, C_)
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(1000 + fill_seed)
-    buf = torch.randint(0, 256, (off + n * stride + tail + 16,), dtype=torch.uint8, device="cuda", generator=gen)
-    view = torch.as_strided(buf, (n, H, W, C_), (stride, pitch, C_, 1), off)
-    packed = px if order == "rgb" else np.ascontiguousarray(px[..., [2, 1, 0] + ([3] if C_ == 4 else [])])
-    view.copy_(torch.from_numpy(packed).cuda())
-    if layout == "odd":
-        assert view.data_ptr() % 2 == 1
-    return view, pitch, stride
-
-
-def _surface_encoder(W, H, Q, mode, channels, n, pitch, stride, order, pipelined=False):
-    from ec504_imageencoder_amd import Mpeg1Encoder
-    enc = Mpeg1Encoder(W, H, Q, mode, channels=channels, max_frames=n)
-    enc.set_input_layout(pitch, stride, order)
-    assert enc.path == "tiles" and enc.size_table_fused == 1
-    assert enc.input_layout == (pitch, stride, order)
-    if pipelined:
-        enc.set_pipelined(True)
-        assert enc.path == "tiles" and enc.size_table_fused == 1
-    return enc
 
 
 def _with_alpha(rng, px):
@@ -80,25 +39,7 @@ def _with_alpha(rng, px):
     return px
 
 
-def _encode(torch, enc, dev, first, quality=None):
-    """One asynchronous encode into a worst-case buffer -> (bytes, sizes); the status word must be 0."""
-    n = dev.shape[0]
-    out = torch.empty(enc.frame_bound * max(n, 1), dtype=torch.uint8, device="cuda")
-    out, sizes, meta = enc.encode(dev, first, out=out, quality=quality)
-    enc.flush()
-    torch.cuda.synchronize()
-    total, status = (int(x) for x in meta.cpu())
-    assert status & 0xFFFFFFFF == 0, status
-    return out[:total].cpu().numpy().tobytes(), [int(s) for s in sizes[:n].cpu()]
-
-
 # ---- 1. the parity matrix ---------------------------------------------------------------------------------------------------
-# geometry and content of the cases of tests/test_gpu_size_table.py and test_gpu_rgba_table.py (wide staging, partial tiles,
-# an odd last tile column, the strict region, a 4K frame), an even tiny picture in place of the odd-width one (for which every
-# surface layout is an argument error: test_odd_width_keeps_the_default_layout), and a 1080p pair
-MATRIX = {k: v for k, v in {**RGB_CASES, **RGBA_CASES}.items() if k != "tiny_105x49"}
-MATRIX["tiny_96x48"] = (96, 48, 12, "full", 4, (4, 40, 256, 120), (1, 12))
-MATRIX["hd_pair"] = (1920, 1080, 12, "full", 2, (256, 40), (3, 12))
 _oracle_cache = {}
 
 
@@ -231,15 +172,6 @@ def test_colour_inside_the_surface_kernels_ties_and_sample(torch_cuda, orc, chan
 
 # ---- 5. the rate calls ------------------------------------------------------------------------------------------------------
 CANDS5 = (2, 4, 6, 8, 12)
-
-
-def _frame_rule(s, cap):
-    """m1v_encode_budget_device's rule on a table s[k][f]: the largest candidate that fits, else the smallest."""
-    pick = []
-    for f in range(len(s[0])):
-        fits = [k for k in range(len(s)) if s[k][f] <= cap]
-        pick.append(fits[-1] if fits else 0)
-    return pick, [f for f in range(len(s[0])) if s[pick[f]][f] > cap]
 
 
 def test_rate_calls_on_a_pitched_bgra_surface(torch_cuda, orc):

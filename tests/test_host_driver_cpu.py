@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STB_DIR = "/root/reference/include"
 REF = {"strict": os.path.join(ROOT, "oracle", "_ref", "ref_encoder_strict"),
@@ -138,7 +139,7 @@ def test_output_buffer_grows_when_a_batch_exceeds_the_first_guess(builds, tmp_pa
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import oracle_ffi as orc
-    from test_gpu_parity import _heavy_picture
+    from hard_content import _heavy_picture
     exe = str(tmp_path / "raw_main")
     subprocess.run(["gcc", "-O1", "-g", "-w", "-fsanitize=address", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
                     "-I" + os.path.join(ROOT, "oracle"), *[os.path.join(ROOT, f) for f in ["tests/raw_loader_main.c"] + SOURCES[1:]],

@@ -28,7 +28,7 @@ EXCLUDED = {"k_size_table_sizes": "writes the size table out behind every k_size
 def _source_names():
     """The source names of the code object's kernels that match k[tp]?_(encode|size_table|rd_table)_\\w+, from the metadata
     notes: a mangled name carries each identifier behind its length."""
-    from test_frame_table_abi import _code_object
+    from code_object import _code_object
     out = set()
     for name, _, _ in _code_object()[1]:
         m = re.search(r"\d(k[tp]?_(?:encode|size_table|rd_table)_[a-z0-9_]+)", name)    # (up to the I or E behind the identifier)
@@ -39,7 +39,7 @@ def _source_names():
 
 
 def test_the_tile_set_reaches_every_tile_shaped_kernel():
-    import test_gpu_geometry as geo
+    import geometry_cases as geo
     found = _source_names()
     assert len(found) > 40, sorted(found)
     assert set(EXCLUDED) <= found

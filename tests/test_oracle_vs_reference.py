@@ -12,10 +12,11 @@ geometry space"), so odd heights are outside its behaviour and nothing here runs
 """
 import hashlib
 import os
-import struct
 
 import numpy as np
 import pytest
+
+from ref_ffi import _check_folder, _make_folder
 
 pytestmark = pytest.mark.reference
 
@@ -209,15 +210,6 @@ def test_slice_and_macroblock_header(ref, orc):
 # end to end through the reference driver binaries
 # ------------------------------------------------------------------------------------------------
 
-def _make_folder(tmp, name, frames, quality=90):
-    from PIL import Image
-    d = tmp / name
-    (d / "images").mkdir(parents=True)
-    (d / "bit").mkdir()
-    for i, a in enumerate(frames):
-        Image.fromarray(a).save(str(d / "images" / f"f{i:03d}.jpg"), quality=quality)
-    return d
-
 
 def _synthetic(rng, n, W, H, kind):
     out = []
@@ -231,25 +223,6 @@ def _synthetic(rng, n, W, H, kind):
             a = np.clip(a + rng.integers(-12, 13, a.shape), 0, 255).astype(np.uint8)
         out.append(a)
     return out
-
-
-def _check_folder(ref, orc, d, qf, modes=("strict", "full")):
-    names, frames = ref.dump_rgb(str(d / "images"), str(d / "dump"))
-    assert frames, "no frames decoded"
-    H, W, Cn = frames[0].shape
-    rgb = np.concatenate([f.reshape(-1) for f in frames])
-    for mode in modes:
-        video = d / "bit" / f"{mode}_{qf}.mpeg"
-        assert ref.run_encoder(str(d / "images"), str(d / "bit"), str(video), qf, mode) == 0
-        theirs = video.read_bytes()
-        mine = orc.encode_sequence(rgb, len(frames), W, H, qf, orc.MODE_STRICT if mode == "strict" else orc.MODE_FULL, Cn)
-        assert mine == theirs, (mode, qf, len(mine), len(theirs))
-    # .bit side files (written by either run; identical)
-    for i, f in enumerate(frames):
-        Y, Cb, Cr = orc.convert(f, Cn)
-        want = struct.pack("<ii", W, H) + Y.tobytes() + Cb.tobytes() + Cr.tobytes()
-        assert (d / "bit" / f"image_{i + 1}.bit").read_bytes() == want
-    return names, frames
 
 
 @pytest.mark.parametrize("W,H,kind,n", [(352, 288, "noise", 4), (352, 288, "smooth", 3), (96, 144, "noise", 2),
@@ -305,4 +278,3 @@ def test_more_than_255_strips_wraps_the_slice_byte(ref, orc, tmp_path):
     rng = np.random.default_rng(41)
     d = _make_folder(tmp_path, "wide", _synthetic(rng, 2, 4128, 32, "noise"), quality=90)
     _check_folder(ref, orc, d, 12, modes=("full",))
-

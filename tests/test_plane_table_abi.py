@@ -8,7 +8,7 @@ import re
 
 import pytest
 
-from test_frame_table_abi import _kernels, _ops, _vgprs, _waves
+from code_object import _kernels, _ops, _vgprs, _waves
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the layout families whose kernels have a plane-table twin (kp_*), and their instantiations per row: [STAGE8] x the chroma steps

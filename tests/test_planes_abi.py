@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = ("k_encode_planes", "k_size_table_planes")

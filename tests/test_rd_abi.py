@@ -9,7 +9,7 @@ import re
 
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = {"m1v_frame_rd_table_device": 9, "m1v_encode_rd_device": 17}

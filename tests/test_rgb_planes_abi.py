@@ -9,15 +9,11 @@ import re
 
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
+from code_object import RGB_PLANES_COUNTED as COUNTED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = ("k_encode_rgb_planes", "k_size_table_rgb_planes", "k_rd_table_rgb_planes")
-# what the code-object tests of the other input layouts count kernels by
-COUNTED = ("k_encode_tiles", "k_encode_dense", "k_encode_strips", "k_encode_surface", "k_encode_planes", "k_encode_step2",
-           "k_size_table_tiles", "k_size_table_rgba", "k_size_table_surface", "k_size_table_planes", "k_size_table_step2",
-           "k_rd_table_tiles", "k_rd_table_rgba", "k_rd_table_surface", "k_rd_table_planes", "k_rd_table_step2", "k_assemble",
-           "k_rate_pick")
 FIELDS = ("r_offset", "g_offset", "b_offset", "row_pitch", "frame_stride")
 ORDERS = ("rgb", "bgr", "gbr")
 

@@ -5,7 +5,7 @@ import ctypes as C
 import os
 import re
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "m1v_size_table_fused"

@@ -10,15 +10,11 @@ import re
 import numpy as np
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
+from code_object import SAMPLE_LAYOUT_COUNTED as COUNTED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = ("k_encode_step2", "k_size_table_step2", "k_rd_table_step2")
-# what the code-object tests of the other input layouts count kernels by (test_planes_abi.py, test_surface_abi.py,
-# test_rgba_table_abi.py, test_rd_abi.py)
-COUNTED = ("k_encode_tiles", "k_encode_dense", "k_encode_strips", "k_encode_surface", "k_encode_planes", "k_size_table_tiles",
-           "k_size_table_rgba", "k_size_table_surface", "k_size_table_planes", "k_rd_table_tiles", "k_rd_table_rgba",
-           "k_rd_table_surface", "k_rd_table_planes", "k_assemble", "k_rate_pick")
 FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "y_step", "c_step", "frame_stride")
 NAMES = ("yuy2", "uyvy", "yvyu", "p010")
 

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "m1v_frame_size_table_device"

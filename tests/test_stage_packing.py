@@ -199,7 +199,7 @@ def test_packed_rgb_encode(torch_cuda, orc, W, H, q, n):
 @pytest.mark.parametrize("q", QUALITIES)
 def test_pitched_bgra_surface_encode(torch_cuda, orc, q):
     torch = torch_cuda
-    from test_gpu_surface import _surface, _surface_encoder
+    from layout_inputs import _surface, _surface_encoder
     W, H, n = 136, 72, 3
     rng = np.random.default_rng(q)
 
@@ -215,7 +215,7 @@ def test_pitched_bgra_surface_encode(torch_cuda, orc, q):
 @pytest.mark.parametrize("q", QUALITIES)
 def test_nv12_plane_encode(torch_cuda, orc, q):
     torch = torch_cuda
-    from test_gpu_planes import _plane_encoder, _planes_of, _view
+    from layout_inputs import _plane_encoder, _planes_of, _view
     W, H, n = 136, 72, 3
 
     def make(px):
@@ -249,7 +249,7 @@ def test_size_table_either_side_of_the_switch(torch_cuda, orc, quals):
     picture that it encodes at all three qualities."""
     torch = torch_cuda
     from ec504_imageencoder_amd import Mpeg1Encoder
-    from test_gpu_size_table import _table
+    from gpu_calls import _table
     W, H = 136, 72
     px = _content(W, H)
     enc = Mpeg1Encoder(W, H, 100, "full", max_frames=len(px))

@@ -9,7 +9,7 @@ import re
 
 import pytest
 
-from test_abi import _gfx950_disassembly
+from code_object import _gfx950_disassembly
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = ("k_encode_surface", "k_size_table_surface")
