@@ -75,6 +75,11 @@ STATUS_STREAMS = 64
 MAX_STREAMS = 4096
 STREAMS_LARGEST_THAT_FITS, STREAMS_LEAST_DISTORTION = 0, 1
 STREAMS_RULES = {"size": STREAMS_LARGEST_THAT_FITS, "distortion": STREAMS_LEAST_DISTORTION}
+SPANS_LARGEST_THAT_FITS, SPANS_LEAST_DISTORTION, SPANS_SMALLEST_AT_DISTORTION = 0, 1, 2
+# the rule of a budget per stream: what the limit bounds and what the pick goes by -> the rule, and the bit a stream over it sets
+SPANS_RULES = {"size": SPANS_LARGEST_THAT_FITS, "distortion": SPANS_LEAST_DISTORTION, "ceiling": SPANS_SMALLEST_AT_DISTORTION}
+SPANS_OVER_BITS = {SPANS_LARGEST_THAT_FITS: STATUS_OVER_BUDGET, SPANS_LEAST_DISTORTION: STATUS_OVER_BUDGET,
+                   SPANS_SMALLEST_AT_DISTORTION: STATUS_OVER_DISTORTION}
 
 
 class StreamSpan(C.Structure):
@@ -97,6 +102,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_frame_rd_table_device", "m1v_encode_rd_device",
     "m1v_encode_rd_batch_device", "m1v_encode_rd_cbr_device", "m1v_rd_batch_pick_device", "m1v_rd_cbr_pick_device",
     "m1v_encode_streams_device", "m1v_encode_streams_cbr_device", "m1v_streams_cbr_pick_device",
+    "m1v_encode_streams_budget_device", "m1v_streams_budget_pick_device",
     "m1v_set_pipelined", "m1v_flush", "m1v_alloc_host", "m1v_free_host", "m1v_alloc_device", "m1v_free_device",
     "m1v_coefficients_device", "m1v_convert_device", "m1v_convert_host", "m1v_subsample_device", "m1v_synth_device",
     "m1v_profile_enable", "m1v_profile_read", "m1v_profile_read_times", "m1v_debug_set_lds_words", "m1v_debug_set_dense_threads",
@@ -188,6 +194,12 @@ def lib():
     L.m1v_streams_cbr_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp,
                                               vp, vp, vp, vp, vp, vp]
     L.m1v_streams_cbr_pick_device.restype = C.c_int
+    L.m1v_encode_streams_budget_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, _u8p, C.c_int, C.c_int, C.c_uint64, vp, vp,
+                                                   vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    L.m1v_encode_streams_budget_device.restype = C.c_int
+    L.m1v_streams_budget_pick_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp,
+                                                 vp, vp, vp]
+    L.m1v_streams_budget_pick_device.restype = C.c_int
     L.m1v_set_pipelined.argtypes = [vp, C.c_int]
     L.m1v_set_pipelined.restype = C.c_int
     L.m1v_flush.argtypes = [vp, vp]

@@ -1634,6 +1634,7 @@ __global__ __launch_bounds__(kPickThreads) void k_rate_pick(PickArgs a) {
 
 #include "m1v_rd_rate.h"
 #include "m1v_streams.h"
+#include "m1v_span_budget.h"
 
 // The probe's place of k_assemble (one workgroup per frame): each record's size (its strips' bytes + 48 bytes of headers and
 // trailer, what k_assemble derives) and the status word, and the same counter hand-over — the set the next call adds into is
@@ -1922,6 +1923,8 @@ struct m1v_encoder {
     uint8_t *d_chosen = nullptr;
     uint32_t *d_pick_status = nullptr; // k_rate_pick's status word (batch-budget and bitrate calls)
     RdStep *d_rd_steps = nullptr;      // k_rd_chains' step table [max_frames][kMaxCandidates] (m1v_encode_rd_batch_device, m1v_rd_batch_pick_device)
+    int32_t *d_span_chunks = nullptr;  // k_span_plan's prefix [M1V_MAX_STREAMS + 1] (m1v_span_budget.h); like the step table it lives from
+                                       // the plan to the pick, both on the caller's stream: one serves both batches of pipelined mode
     int narrow_q = 0;           // the largest quality whose levels stage in one byte (e->narrow for the encoder's own)
     // The size table's counters: the k_size_table_* / k_rd_table_* kernels add, k_size_table_sizes / k_rd_table_sizes reads and
     // clears what they added.

@@ -4,7 +4,8 @@
 // candidates share one argument check (check_candidate_call, the pick-only calls included), one table step (own_table, into the
 // encoder's own buffers), one description of the table a pick reads (PickTable, the encoder's own or the caller's) and one launch
 // site per pick kernel; what writes a batch's per-frame selection reaches encode_batch as a Selection (the select_by_* steps; a
-// batch of many streams, m1v_streams.h, is one too: select_streams in front of the encode kernel, finish_streams behind k_assemble).
+// batch of many streams, m1v_streams.h, is one too: select_streams in front of the encode kernel, finish_streams behind k_assemble;
+// with a budget per stream, m1v_span_budget.h: select_span_budget in its place).
 // The input layouts (packed, surface, plane / sample, RGB plane, float plane, float pixel): a setter, a getter and a preset each, the
 // two table modes and the two to-bytes calls; what differs per kind beyond a setter's own checks is a row of kind_facts.
 // Geometry (CodedRegion, TileGrid, wave_region), the kernel registry (kKernels), the layout record with kind_facts and float_format,
@@ -479,6 +480,7 @@ int m1v_create(m1v_encoder **out, int device, int width, int height, int channel
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_sizes, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_dist, (size_t)kMaxCandidates * max_frames * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc(&e->d_rd_steps, (size_t)kMaxCandidates * max_frames * sizeof(RdStep));
+    if (err == hipSuccess) err = hipMalloc(&e->d_span_chunks, (M1V_MAX_STREAMS + 1) * sizeof(int32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_probe_status, kMaxCandidates * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc(&e->d_chosen, (size_t)max_frames);
     if (err == hipSuccess) err = hipMalloc(&e->d_pick_status, sizeof(uint32_t));
@@ -512,6 +514,7 @@ void m1v_destroy(m1v_encoder *e) {
     (void)hipFree(e->d_probe_sizes);
     (void)hipFree(e->d_probe_dist);
     (void)hipFree(e->d_rd_steps);
+    (void)hipFree(e->d_span_chunks);
     (void)hipFree(e->d_probe_status);
     (void)hipFree(e->d_chosen);
     (void)hipFree(e->d_pick_status);
@@ -1405,8 +1408,45 @@ static int launch_streams_bitrate(const PickTable &t, int n_frames, int rule, St
     return M1V_OK;
 }
 
+static int check_spans_rule(int rule) {
+    return rule == M1V_SPANS_LARGEST_THAT_FITS || rule == M1V_SPANS_LEAST_DISTORTION || rule == M1V_SPANS_SMALLEST_AT_DISTORTION
+               ? M1V_OK
+               : fail(M1V_E_ARG, "unknown spans rule%s");
+}
+
+// The budget per stream over a table (m1v_span_budget.h; an empty batch too: it writes the streams' status): k_span_plan into the
+// encoder's prefix, k_rd_chains into its step table under the two rules that pick by distortion, then k_span_budget over
+// n_streams + ceil(n_frames / 32) workgroups.  ba comes with its outputs, spans and limits set; its status word is cleared here,
+// in front of the launches.  batch_status: an encode's status word, or null.
+static int launch_span_budget(m1v_encoder *e, const PickTable &t, int n_frames, int rule, SpanBudgetArgs ba, uint32_t *batch_status, hipStream_t st) {
+    ba.sizes = t.sizes; ba.dist = t.dist; ba.stride = t.stride; ba.n_cand = t.n_cand; ba.cand = t.cand; ba.table_status = t.status; // the table
+    ba.n_frames = n_frames;
+    ba.steps = e->d_rd_steps;
+    ba.chunk_at = e->d_span_chunks;
+    ba.batch_status = batch_status;
+    HIP_TRY(hipMemsetAsync(ba.status, 0, 4, st));
+    const SpanPlanArgs pa = {ba.spans, ba.n_streams, n_frames, e->d_span_chunks, ba.picks, ba.chosen, (uint8_t)t.cand}; // (byte 0: candidate 0)
+    hipLaunchKernelGGL(k_span_plan, dim3(1), dim3(kSpanThreads), 0, st, pa);
+    HIP_TRY(hipGetLastError());
+    if (rule != M1V_SPANS_LARGEST_THAT_FITS && n_frames > 0) {
+        const RdChainArgs ca = {t.sizes, t.dist, t.stride, t.n_cand, n_frames, t.status, e->d_rd_steps};
+        hipLaunchKernelGGL(k_rd_chains, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, st, ca);
+        HIP_TRY(hipGetLastError());
+    }
+    const dim3 grid((unsigned)(ba.n_streams + (n_frames + kSpanFrames - 1) / kSpanFrames)), block(kSpanThreads);
+    if (rule == M1V_SPANS_LARGEST_THAT_FITS)
+        hipLaunchKernelGGL(k_span_budget<M1V_SPANS_LARGEST_THAT_FITS>, grid, block, 0, st, ba);
+    else if (rule == M1V_SPANS_LEAST_DISTORTION)
+        hipLaunchKernelGGL(k_span_budget<M1V_SPANS_LEAST_DISTORTION>, grid, block, 0, st, ba);
+    else
+        hipLaunchKernelGGL(k_span_budget<M1V_SPANS_SMALLEST_AT_DISTORTION>, grid, block, 0, st, ba);
+    HIP_TRY(hipGetLastError());
+    return M1V_OK;
+}
+
 // What a streams batch hands its Selection: the spans; the per-frame qualities, if any, and what wrote them (`bitrate` with `table`
-// and `rule`: k_streams_bitrate, launched by the step, where the batch's status word is known); where the spans' bytes go.
+// and `rule`: k_streams_bitrate; `budget` with `table`, `rule` and `ba`: the budget per stream; either is launched by the step,
+// where the batch's status word is known); where the spans' bytes go.
 struct StreamsStep {
     const m1v_stream_span *spans;
     int n_streams;
@@ -1416,6 +1456,8 @@ struct StreamsStep {
     int rule;
     StreamsRateArgs ra;
     unsigned long long *stream_bytes;
+    bool budget;
+    SpanBudgetArgs ba;
 };
 
 static int select_streams(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
@@ -1428,6 +1470,17 @@ static int select_streams(m1v_encoder *e, void *args, const m1v_encoder::Counter
         if (const int rc = launch_streams_bitrate(s.table, n_frames, s.rule, s.ra, st)) return rc;
     }
     return s.qa.quality ? select_by_quality(e, &s.qa, cur, n_frames, st) : M1V_OK;
+}
+
+// The step of a batch with a budget per stream: the map, then the plan, the chains and the pick (launch_span_budget), then
+// k_frame_quality on the qualities and the status word the pick wrote
+static int select_span_budget(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, int n_frames, hipStream_t st) {
+    StreamsStep &s = *static_cast<StreamsStep *>(args);
+    const StreamsMapArgs ma = {s.spans, s.n_streams, n_frames, cur.frame_index, cur.words};
+    hipLaunchKernelGGL(k_streams_map, dim3((unsigned)((s.n_streams + 255) / 256)), dim3(256), 0, st, ma);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = launch_span_budget(e, s.table, n_frames, s.rule, s.ba, cur.words, st)) return rc;
+    return select_by_quality(e, &s.qa, cur, n_frames, st);
 }
 
 static int finish_streams(m1v_encoder *e, void *args, const m1v_encoder::Counters &cur, const EncodeOut &o, int n_frames, hipStream_t gs) {
@@ -1447,7 +1500,7 @@ static int encode_streams(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, St
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipMemsetAsync(s.stream_bytes, 0, (size_t)s.n_streams * 8, (hipStream_t)stream));
     }
-    Selection sel = {select_streams, &s};
+    Selection sel = {s.budget ? select_span_budget : select_streams, &s};
     sel.own_quality = !s.qa.quality;
     sel.finish = finish_streams;
     return encode_batch(e, d_rgb, n_frames, 0, &sel, false, o, stream);
@@ -1538,6 +1591,65 @@ int m1v_streams_cbr_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const u
     ra.pick_dist = (unsigned long long *)d_pick_distortion;
     ra.status = d_status;
     return launch_streams_bitrate(t, n_frames, rule, ra, (hipStream_t)stream);
+}
+
+int m1v_encode_streams_budget_device(m1v_encoder *e, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                                     const uint8_t *candidates, int n_candidates, int rule, uint64_t limit,
+                                     const uint64_t *d_stream_limits, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap,
+                                     uint64_t *d_frame_sizes, uint64_t *d_frame_distortion, uint64_t *d_stream_bytes,
+                                     uint32_t *d_stream_status, uint64_t *d_total, uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (const int rc = check_spans(d_spans, n_streams)) return rc;
+    if (const int rc = check_candidate_call(e, true, candidates, n_candidates, n_frames, (d_rgb || n_frames <= 0) && d_out)) return rc;
+    if (const int rc = check_spans_rule(rule)) return rc;
+    if (((uintptr_t)d_stream_limits & 7) != 0) return fail(M1V_E_ARG, "the stream limits must be 8-byte aligned%s");
+    StreamsStep s = {};
+    if (const int rc = own_table(e, d_rgb, n_frames, candidates, n_candidates, rule != M1V_SPANS_LARGEST_THAT_FITS, stream, s.table)) return rc;
+    s.spans = d_spans;
+    s.n_streams = n_streams;
+    s.budget = true;
+    s.rule = rule;
+    s.ba.spans = d_spans;
+    s.ba.n_streams = n_streams;
+    s.ba.limits = (const unsigned long long *)d_stream_limits;
+    s.ba.limit = limit;
+    s.ba.chosen = d_chosen ? d_chosen : e->d_chosen;
+    s.ba.pick_dist = (unsigned long long *)d_frame_distortion;
+    s.ba.stream_status = d_stream_status;
+    s.ba.status = e->d_pick_status;
+    s.qa.quality = s.ba.chosen;
+    s.qa.pick_status = s.ba.status;
+    s.stream_bytes = (unsigned long long *)d_stream_bytes;
+    if (n_frames == 0 && d_stream_status) { // (an empty batch has no Selection step)
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMemsetAsync(d_stream_status, 0, (size_t)n_streams * 4, (hipStream_t)stream));
+    }
+    return encode_streams(e, d_rgb, n_frames, s, {d_out, out_cap, d_frame_sizes, d_total, d_status}, stream);
+}
+
+int m1v_streams_budget_pick_device(m1v_encoder *e, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                                   int n_frames, int n_candidates, const m1v_stream_span *d_spans, int n_streams, int rule,
+                                   uint64_t limit, const uint64_t *d_stream_limits, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                                   uint32_t *d_stream_status, uint32_t *d_status, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (const int rc = check_spans(d_spans, n_streams)) return rc;
+    if (const int rc = check_spans_rule(rule)) return rc;
+    const bool by_dist = rule != M1V_SPANS_LARGEST_THAT_FITS;
+    if (const int rc = check_candidate_call(e, d_sizes && (d_distortion || !by_dist) && d_picks && d_status, nullptr, n_candidates, n_frames, true, true))
+        return rc;
+    if (((uintptr_t)d_stream_limits & 7) != 0) return fail(M1V_E_ARG, "the stream limits must be 8-byte aligned%s");
+    HIP_TRY(hipSetDevice(e->device));
+    const PickTable t = {(const unsigned long long *)d_sizes, (const unsigned long long *)d_distortion, n_frames, n_candidates, 0, d_table_status};
+    SpanBudgetArgs ba = {};
+    ba.spans = d_spans;
+    ba.n_streams = n_streams;
+    ba.limits = (const unsigned long long *)d_stream_limits;
+    ba.limit = limit;
+    ba.picks = d_picks;
+    ba.pick_dist = (unsigned long long *)d_pick_distortion;
+    ba.stream_status = d_stream_status;
+    ba.status = d_status;
+    return launch_span_budget(e, t, n_frames, rule, ba, nullptr, (hipStream_t)stream);
 }
 
 // ---- overlapped delivery to the host (include/mpeg1_hip.h) ----------------------------------------------------------

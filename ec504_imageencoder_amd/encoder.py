@@ -1197,6 +1197,92 @@ class Mpeg1Encoder:
             levels.copy_(level_out.view_as(levels))
         return ([int(k) for k in picks[:n].cpu()], [int(d) for d in pick_dist[:n].cpu()] if pick_dist is not None else None, bits)
 
+    # ---- a budget per stream (include/mpeg1_hip.h, "Streams: a budget per stream") ------------------------------------------
+    @staticmethod
+    def _stream_limits(name, limits, n_streams, device):
+        """One limit for every stream (a scalar, checked here) or one per stream (a sequence of uint64 values, or a CUDA int64
+        tensor [n_streams] that holds their bit patterns): (limit, tensor or None)."""
+        import torch
+        if isinstance(limits, torch.Tensor):
+            assert limits.is_cuda and limits.dtype == torch.int64 and limits.numel() == n_streams, "limits: CUDA int64 [n_streams]"
+            return 0, limits.contiguous()
+        if isinstance(limits, numbers.Integral):
+            return Mpeg1Encoder._uint64(limits, f"{name}: the limit"), None
+        per_stream = [Mpeg1Encoder._uint64(x, f"{name}: a limit") for x in limits]
+        assert len(per_stream) == n_streams, "limits: one per stream"
+        return 0, torch.tensor([x - 2 ** 64 if x >= 2 ** 63 else x for x in per_stream], dtype=torch.int64).to(device)
+
+    def _encode_streams_budget(self, name, rule, rgb, spans, candidates, limits):
+        """The encodes with a budget per stream: (bytes, sizes, chosen, stream_bytes, over, distortion per frame or None, the
+        status word of every stream)."""
+        import torch
+        n = rgb.shape[0]
+        self._check_input(rgb)
+        spans = self._spans(spans, n, rgb.device)
+        limit, d_limits = self._stream_limits(name, limits, len(spans), rgb.device)
+        cand_buf = self._candidates(candidates, name)
+        chosen = torch.zeros(max(n, 1), dtype=torch.uint8, device=rgb.device)
+        with_dist = rule != _ffi.SPANS_LARGEST_THAT_FITS
+        dist = torch.zeros(max(n, 1), dtype=torch.int64, device=rgb.device) if with_dist else None
+        stream_bytes = torch.zeros(len(spans), dtype=torch.int64, device=rgb.device)
+        stream_status = torch.zeros(len(spans), dtype=torch.int32, device=rgb.device)
+        data, sizes_l, status = self._encode_retrying(
+            rgb, name,
+            lambda out, sizes, meta: _call(
+                "m1v_encode_streams_budget_device", self._h, _ptr(rgb), n, _ptr(spans), len(spans), cand_buf, len(cand_buf), rule,
+                limit, _ptr(d_limits), _ptr(chosen), _ptr(out), out.numel(), _ptr(sizes), _ptr(dist), _ptr(stream_bytes),
+                _ptr(stream_status), *_meta_ptrs(meta), _stream()))
+        return (data, sizes_l, [int(c) for c in chosen[:n].cpu()], [int(b) for b in stream_bytes.cpu()],
+                bool(status & _ffi.SPANS_OVER_BITS[rule]), [int(d) for d in dist[:n].cpu()] if with_dist else None,
+                [int(w) & 0xFFFFFFFF for w in stream_status.cpu()])
+
+    def encode_streams_to_budget(self, rgb, spans, candidates, limits, by="size"):
+        """Synchronous: every stream of the batch within its own byte budget (include/mpeg1_hip.h,
+        m1v_encode_streams_budget_device): one table pass, one pick and one encode for the whole batch.  spans: as in
+        encode_streams.  limits: bytes for the sum of a stream's records; one for every stream, or one per stream (a sequence or a
+        CUDA int64 tensor [n_streams]).  by: "size" (encode_to_batch_budget's pick on each stream's frames alone) or "distortion"
+        (encode_best_in_batch_budget's).  Returns (bytes, sizes, chosen, stream_bytes, over_budget, distortion or None,
+        stream_status): over_budget says that some stream does not fit even at its smallest records, stream_status which
+        (STATUS_OVER_BUDGET per stream, or 0)."""
+        assert by in ("size", "distortion"), 'by: "size" or "distortion"'
+        return self._encode_streams_budget("encode_streams_to_budget", _ffi.SPANS_RULES[by], rgb, spans, candidates, limits)
+
+    def encode_streams_to_distortion(self, rgb, spans, candidates, ceilings):
+        """Synchronous: every stream of the batch at the fewest bytes whose distortions sum to at most the stream's ceiling
+        (encode_batch_to_distortion's pick on each stream's frames alone).  ceilings: one for every stream, or one per stream.
+        Returns (bytes, sizes, chosen, stream_bytes, over_distortion, distortion, stream_status): STATUS_OVER_DISTORTION per
+        stream whose ceiling even its least distortion misses (the output is valid)."""
+        return self._encode_streams_budget("encode_streams_to_distortion", _ffi.SPANS_SMALLEST_AT_DISTORTION, rgb, spans,
+                                           candidates, ceilings)
+
+    def streams_budget_pick(self, sizes, dist, spans, rule, limits, status=None):
+        """The pick of the two encodes above alone, on a table the caller holds (frame_size_table's or frame_rd_table's CUDA int64
+        tensors [K, n]; dist may be None under SPANS_LARGEST_THAT_FITS; status: the table's CUDA int32 status words, or None).
+        rule: a SPANS_* value.  limits: as in encode_streams_to_budget.  The spans are checked on the device.  Synchronous.
+        Returns (picks, distortion, status bits, stream_status): the candidate INDEX of every frame, the picks' distortion (None
+        without dist), the pick's status word and the status word of every stream."""
+        import torch
+        assert sizes.is_cuda and sizes.dtype == torch.int64 and sizes.dim() == 2, "sizes: CUDA int64 [K, n]"
+        K, n = sizes.shape
+        sizes = sizes.contiguous()
+        if dist is not None:
+            assert dist.is_cuda and dist.dtype == torch.int64 and dist.shape == sizes.shape, "dist: CUDA int64 [K, n]"
+            dist = dist.contiguous()
+        if status is not None:
+            assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= K, "status: CUDA int32, one per candidate"
+        if not isinstance(spans, StreamSpans):
+            spans = stream_spans(spans, sizes.device)
+        limit, d_limits = self._stream_limits("streams_budget_pick", limits, len(spans), sizes.device)
+        picks = torch.zeros(max(n, 1), dtype=torch.uint8, device=sizes.device)
+        pick_dist = torch.zeros(max(n, 1), dtype=torch.int64, device=sizes.device) if dist is not None else None
+        stream_status = torch.zeros(len(spans), dtype=torch.int32, device=sizes.device)
+        word = torch.zeros(1, dtype=torch.int32, device=sizes.device)
+        _call("m1v_streams_budget_pick_device", self._h, _ptr(sizes), _ptr(dist), _ptr(status), n, K, _ptr(spans), len(spans),
+              int(rule), limit, _ptr(d_limits), _ptr(picks), _ptr(pick_dist), _ptr(stream_status), _ptr(word), _stream())
+        bits = int(word.item()) & 0xFFFFFFFF
+        return ([int(k) for k in picks[:n].cpu()], [int(d) for d in pick_dist[:n].cpu()] if pick_dist is not None else None, bits,
+                [int(w) & 0xFFFFFFFF for w in stream_status.cpu()])
+
     def set_pipelined(self, enable=True):
         """Overlap each batch's layout + gather (internal stream) with the next batch's encode kernel.
         Outputs of a batch are complete only behind flush(); callers double-buffer `out`."""

@@ -418,8 +418,8 @@ int m1v_rd_cbr_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint
  *                             table layout, preconditions and WRITTEN, not OR'ed, status.  d_distortion may be NULL under the
  *                             byte rule (d_pick_distortion is then not written).  Bad spans set M1V_STATUS_STREAMS here too.
  *
- * Not covered: m1v_delivery_step (and the CLI) with spans; per-stream batch budgets and distortion ceilings; the host-buffer
- * entry points. */
+ * Not covered: m1v_delivery_step (and the CLI) with spans; the host-buffer entry points.  A byte budget or a distortion ceiling
+ * per stream: "Streams: a budget per stream", below. */
 typedef struct m1v_stream_span {
     uint32_t first_frame;        /* position in the batch of the span's first frame          */
     uint32_t n_frames;           /* frames of this stream in the batch; 0 is allowed         */
@@ -447,6 +447,79 @@ int m1v_streams_cbr_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const
                                 uint64_t bytes_per_frame, uint64_t buffer_bytes, const m1v_stream_rate *d_stream_rates,
                                 const int64_t *d_level_in, int64_t *d_level_out, uint8_t *d_picks, uint64_t *d_pick_distortion,
                                 uint32_t *d_status, void *stream);
+
+/* Streams: a budget per stream.  The batch rules above ("these frames in B bytes", "these frames under a distortion ceiling")
+ * with one limit per stream of a batch of many streams, in one call.
+ *
+ * The batch is the concatenation of n_streams spans.
+ *   - The spans are those of m1v_encode_streams_device: on the device, validated and clamped there, M1V_STATUS_STREAMS otherwise.
+ *   - Stream s has the limit L_s = d_stream_limits[s] (uint64[n_streams] on the device, 8-byte aligned).
+ *   - With d_stream_limits NULL, L_s = `limit` for every stream.
+ * Streams do not interact.
+ *   - The picks of the frames of span s are exactly what the single-batch rule gives on the sub-table of that span's frames
+ *     alone, with the limit L_s.
+ *   - `rule` names the single-batch rule and the bit a stream over its limit sets:
+ *       M1V_SPANS_LARGEST_THAT_FITS       m1v_encode_batch_budget_device's                               M1V_STATUS_OVER_BUDGET
+ *       M1V_SPANS_LEAST_DISTORTION        m1v_rd_batch_pick_device's, M1V_RD_BEST_IN_BUDGET             M1V_STATUS_OVER_BUDGET
+ *       M1V_SPANS_SMALLEST_AT_DISTORTION  m1v_rd_batch_pick_device's, M1V_RD_SMALLEST_AT_DISTORTION     M1V_STATUS_OVER_DISTORTION
+ *   - "Frame ascending" in every tie rule is position in the batch.  Inside one span that is position in the span.
+ *   - Candidates whose table status carries M1V_STATUS_UNENCODABLE are treated as the single-batch rule treats them.
+ *   - An empty span picks nothing and is not over.
+ * The status words.
+ *   - d_stream_status[s] (uint32[n_streams] on the device, may be NULL) receives stream s's over bit, or 0.
+ *   - The batch's status word receives the OR over the streams.
+ *   - It receives M1V_STATUS_STREAMS for spans that do not tile the batch.
+ *   - It receives whatever the single-batch call passes on (M1V_STATUS_SCRATCH of the table).
+ * Bad spans.
+ *   - The picks are unspecified, but every frame's pick is a candidate index below n_candidates.
+ *   - A frame that no clamped span covers takes candidate 0.
+ *   - Nothing outside the arrays is touched.
+ * Preconditions of the pick-only call: those of m1v_rd_batch_pick_device, every s < 2^32 and every D < 2^63.  Sums of
+ * distortions are taken in 128 bits.
+ *
+ * m1v_encode_streams_budget_device
+ *   - One table pass: the size table under M1V_SPANS_LARGEST_THAT_FITS, the rd table under the other two rules.
+ *   - One pick: k_span_plan, k_rd_chains under the two rules that pick by distortion, k_span_budget.
+ *   - One encode at the picked per-frame qualities, and k_streams_finish for the indices and d_stream_bytes.
+ *   - All of it on `stream`, with no host wait, in pipelined mode too.  Every input layout and both tables are served.
+ *   - The argument checks are m1v_encode_streams_cbr_device's, in its order, then an unknown rule and a d_stream_limits that
+ *     is not 8-byte aligned: M1V_E_ARG before anything is launched.
+ *   - On an encoder whose tables are not fused, the two rules that pick by distortion return M1V_E_ARG, as m1v_encode_rd_device
+ *     does, and M1V_SPANS_LARGEST_THAT_FITS falls back to probes, as m1v_encode_batch_budget_device does.
+ *   - d_chosen, d_frame_distortion, d_stream_bytes and d_stream_status may be NULL.  d_frame_distortion is written under the
+ *     two rules that pick by distortion.
+ *   - n_frames == 0 writes *d_total = 0, *d_status = 0 and zeros into d_stream_bytes and d_stream_status.
+ *   - m1v_debug_fail_encode reaches the table's and the encode's stages as in m1v_encode_streams_cbr_device.
+ *   - A profiled call reports 2 launches.
+ * m1v_streams_budget_pick_device
+ *   - The pick alone on a table the caller holds: the streams form of m1v_rd_batch_pick_device, with the same table layout.
+ *   - d_picks receives candidate INDICES.  d_status is WRITTEN, not OR'ed.
+ *   - d_distortion may be NULL under M1V_SPANS_LARGEST_THAT_FITS; d_pick_distortion is then not written.
+ *   - It uses the encoder's step table and span prefix: calls on one encoder are ordered by the stream.
+ *   - n_frames == 0 writes the status words (every span is empty) and no pick.
+ * Kernels (csrc/m1v_span_budget.h).
+ *   - k_span_plan, one workgroup: the exclusive prefix of max(1, ceil(n_s / 32)) over the clamped spans.
+ *   - k_span_budget, n_streams + ceil(n_frames / 32) workgroups: workgroup w finds its span and its chunk of 32 frames in that
+ *     prefix and compares its steps (its frames, under M1V_SPANS_LARGEST_THAT_FITS) with those of its own span only.
+ *   - The compares cost the sum of n_s^2 over the streams, where k_rd_batch_pick costs n^2.
+ * Cost at K = 8 (tools/streams_budget_timing.py, profiles/r33_streams_budget_timing.txt).
+ *   - 30 streams x 10 frames of 1080p take 0.51 (by size) and 0.43 (by distortion) of the time of one existing batch call per
+ *     stream; 20 x 5 frames of 4K take 0.69 and 0.59.
+ *   - Against ONE existing batch call over all the frames with a single limit: 1.039 and 0.847 at 1080p, 1.022 and 0.957 at 4K.
+ *   - The A/A range is 0.999 .. 1.027 at 1080p and 0.999 .. 1.004 at 4K: by size the call lies above it (60 and 47 us: the map,
+ *     the plan and the finish are launches the single-limit call does not make); by distortion it is cheaper than one limit.
+ *
+ * Not covered: m1v_delivery_step (and the CLI) with spans; the host-buffer entry points. */
+enum { M1V_SPANS_LARGEST_THAT_FITS = 0, M1V_SPANS_LEAST_DISTORTION = 1, M1V_SPANS_SMALLEST_AT_DISTORTION = 2 };
+int m1v_encode_streams_budget_device(m1v_encoder *enc, const uint8_t *d_rgb, int n_frames, const m1v_stream_span *d_spans, int n_streams,
+                                     const uint8_t *candidates, int n_candidates, int rule, uint64_t limit,
+                                     const uint64_t *d_stream_limits, uint8_t *d_chosen, uint8_t *d_out, size_t out_cap,
+                                     uint64_t *d_frame_sizes, uint64_t *d_frame_distortion, uint64_t *d_stream_bytes,
+                                     uint32_t *d_stream_status, uint64_t *d_total, uint32_t *d_status, void *stream);
+int m1v_streams_budget_pick_device(m1v_encoder *enc, const uint64_t *d_sizes, const uint64_t *d_distortion, const uint32_t *d_table_status,
+                                   int n_frames, int n_candidates, const m1v_stream_span *d_spans, int n_streams, int rule,
+                                   uint64_t limit, const uint64_t *d_stream_limits, uint8_t *d_picks, uint64_t *d_pick_distortion,
+                                   uint32_t *d_stream_status, uint32_t *d_status, void *stream);
 
 /* Input layout: frames that already live on the device as windows of pitched surfaces, in R,G,B(,A) or B,G,R(,A) byte order,
  * encoded where they lie (no compaction or swizzle copy in front of the encoder).
