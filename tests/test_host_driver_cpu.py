@@ -26,7 +26,7 @@ def builds(tmp_path_factory):
     if not os.path.exists(os.path.join(STB_DIR, "stb_image.h")):
         pytest.skip("reference stb_image.h not present")
     if not all(os.path.exists(p) for p in REF.values()):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref"], check=True)
     out = tmp_path_factory.mktemp("hostdrv")
     exes = {}
     for san in ("thread", "address"):
@@ -53,7 +53,7 @@ def _folder(d, n, W=352, H=288, seed=7, quality=90):
 
 
 def _run(exe, cwd, *args, env=None):
-    e = dict(os.environ, TSAN_OPTIONS="exitcode=66 halt_on_error=1", ASAN_OPTIONS="exitcode=67 detect_leaks=0")
+    e = dict(os.environ, TSAN_OPTIONS="exitcode=66 halt_on_error=1", ASAN_OPTIONS="exitcode=67 detect_leaks=1")
     e.update(env or {})
     p = subprocess.run([exe, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e)
     return p.returncode, p.stderr.decode(errors="replace")
