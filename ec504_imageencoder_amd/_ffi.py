@@ -71,6 +71,13 @@ class FloatPixelLayout(_Layout):
 
 PIXEL_ORDERS = {"rgb": ORDER_RGB, "bgr": ORDER_BGR}
 
+
+class DownscaleLayout(_Layout):
+    """m1v_downscale_layout (include/mpeg1_hip.h): where the bytes of a frame's SOURCE pixels lie (a surface of twice the encoder's
+    width and height), in bytes, which of a pixel's bytes are R, G and B (ORDER_*), and the factor (2)."""
+    _fields_ = [(name, C.c_uint64) for name in ("row_pitch", "frame_stride", "pixel_step")] + \
+               [("order", C.c_int32), ("factor", C.c_int32)]
+
 STATUS_STREAMS = 64
 MAX_STREAMS = 4096
 STREAMS_LARGEST_THAT_FITS, STREAMS_LEAST_DISTORTION = 0, 1
@@ -113,6 +120,7 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_rgb_plane_layout_preset", "m1v_set_rgb_plane_layout", "m1v_rgb_plane_layout_in_force",
     "m1v_float_plane_layout_preset", "m1v_set_float_plane_layout", "m1v_float_plane_layout_in_force", "m1v_float_planes_to_bytes_device",
     "m1v_float_pixel_layout_preset", "m1v_set_float_pixel_layout", "m1v_float_pixel_layout_in_force", "m1v_float_pixels_to_bytes_device",
+    "m1v_downscale_layout_preset", "m1v_set_downscale_layout", "m1v_downscale_layout_in_force", "m1v_downscale_to_bytes_device",
     "m1v_set_frame_table", "m1v_frame_table", "m1v_set_plane_table", "m1v_plane_table",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
@@ -256,13 +264,14 @@ def lib():
     L.m1v_input_layout.restype = C.c_int
     # per layout struct: its preset (the number of ints it takes in front of the struct), its setter and its getter
     for kind, struct, preset_ints in (("plane", PlaneLayout, 3), ("sample", SampleLayout, 3), ("rgb_plane", RgbPlaneLayout, 3),
-                                      ("float_plane", FloatPlaneLayout, 5), ("float_pixel", FloatPixelLayout, 6)):
+                                      ("float_plane", FloatPlaneLayout, 5), ("float_pixel", FloatPixelLayout, 6),
+                                      ("downscale", DownscaleLayout, 5)):
         getattr(L, f"m1v_{kind}_layout_preset").argtypes = [C.c_int] * preset_ints + [C.POINTER(struct)]
         getattr(L, f"m1v_set_{kind}_layout").argtypes = [vp, C.POINTER(struct)]
         getattr(L, f"m1v_{kind}_layout_in_force").argtypes = [vp, C.POINTER(struct)]
         for name in (f"m1v_{kind}_layout_preset", f"m1v_set_{kind}_layout", f"m1v_{kind}_layout_in_force"):
             getattr(L, name).restype = C.c_int
-    for name in ("m1v_float_planes_to_bytes_device", "m1v_float_pixels_to_bytes_device"):
+    for name in ("m1v_float_planes_to_bytes_device", "m1v_float_pixels_to_bytes_device", "m1v_downscale_to_bytes_device"):
         getattr(L, name).argtypes = [vp, vp, C.c_int, vp, vp]
         getattr(L, name).restype = C.c_int
     L.m1v_set_frame_table.argtypes = [vp, C.c_int]

@@ -335,7 +335,7 @@ static int samples_in_force(const m1v_encoder *e) {
     return answer < 0 ? ask_its_getter(e) : answer;
 }
 
-// What rows of `row` bytes that lie `pitch` apart must satisfy in the surface and float pixel setters: a pitch not below the row,
+// What rows of `row` bytes that lie `pitch` apart must satisfy in the surface, float pixel and downscale setters: a pitch not below the row,
 // the rows of a frame (`what` the refusal calls them) below 4 GiB, a frame stride not below them
 static int rows_fit(unsigned long long pitch, unsigned long long row, unsigned long long H, unsigned long long frame_stride,
                     const char *pitch_below_row, const char *what, const char *stride_below_rows) {
@@ -346,7 +346,7 @@ static int rows_fit(unsigned long long pitch, unsigned long long row, unsigned l
     return M1V_OK;
 }
 
-// The launches behind the two to-bytes calls, 65535 frames (a grid's y extent) each: `kind` must be in force (`needs`: the refusal
+// The launches behind the to-bytes calls, 65535 frames (a grid's y extent) each: `kind` must be in force (`needs`: the refusal
 // where it is not); kernels: the call's kernel per M1V_SAMPLE_* value; args(frames, bytes): its argument struct for the frames from
 // `frames` on, written from `bytes` on; grid: the launch over n frames
 template <typename MakeArgs, typename Grid>
@@ -948,6 +948,61 @@ int m1v_float_pixels_to_bytes_device(m1v_encoder *e, const void *d_frames, int n
             return FloatPixelBytesArgs{frames, bytes, f.front, e->layout.frame_stride, (uint32_t)e->g.W, (uint32_t)e->g.H, f.pixel_step};
         },
         [e](unsigned n) { return dim3(((unsigned)e->g.W * (unsigned)e->g.H + 255u) / 256u, n); }); // (pixels)
+}
+
+int m1v_downscale_layout_preset(int width, int height, int pixel_bytes, int order, int factor, m1v_downscale_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (pixel_bytes != 3 && pixel_bytes != 4) return fail(M1V_E_ARG, "a source pixel has 3 or 4 bytes%s");
+    if (order != M1V_ORDER_RGB && order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
+    if (factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+    const uint64_t pitch = 2 * (uint64_t)width * (uint64_t)pixel_bytes;
+    *out = {pitch, 2 * (uint64_t)height * pitch, (uint64_t)pixel_bytes, order, factor};
+    return M1V_OK;
+}
+
+int m1v_set_downscale_layout(m1v_encoder *e, const m1v_downscale_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a downscale layout needs an encoder created with 3 channels (the source pixel's byte count is the layout's)%s");
+        if (g.W & 1) return fail(M1V_E_ARG, "a downscale layout needs an even width (the chroma plane is addressed with stride width / 2)%s");
+        if (layout->order != M1V_ORDER_RGB && layout->order != M1V_ORDER_BGR) return fail(M1V_E_ARG, "unknown order (M1V_ORDER_RGB, M1V_ORDER_BGR)%s");
+        if (layout->factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+        const unsigned long long step = layout->pixel_step;
+        if (step != 3 && step != 4) return fail(M1V_E_ARG, "pixel step must be 3 or 4 bytes%s");
+        // (the source's rows: twice the encoder's width and height)
+        if (const int rc = rows_fit(layout->row_pitch, 2ull * (unsigned long long)g.W * step, 2ull * (unsigned long long)g.H, layout->frame_stride,
+                                    "row pitch below 2 * width * pixel step", "source frame",
+                                    "frame stride below the bytes a source frame's rows span"))
+            return rc;
+        want.kind = LayoutKind::downscale;
+        want.downscale = {{(uint32_t)layout->row_pitch, layout->order == M1V_ORDER_BGR ? 1u : 0u}, (uint32_t)step};
+        want.frame_stride = layout->frame_stride;
+    }
+    return apply_layout(e, want);
+}
+
+int m1v_downscale_layout_in_force(const m1v_encoder *e, m1v_downscale_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::downscale) return 0;
+    const m1v_encoder::Layout::Downscale &d = e->layout.downscale;
+    if (out) *out = {d.front.row_pitch, e->layout.frame_stride, d.pixel_step, (int32_t)(d.front.bgr ? M1V_ORDER_BGR : M1V_ORDER_RGB), 2};
+    return 1;
+}
+
+int m1v_downscale_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream) {
+    // (one kernel whatever the sample type: a byte layout leaves the float format's zeros)
+    static const void *const kernels[3] = {(const void *)&k_downscale_to_bytes, (const void *)&k_downscale_to_bytes, (const void *)&k_downscale_to_bytes};
+    return float_to_bytes(
+        e, LayoutKind::downscale, "m1v_downscale_to_bytes_device needs a downscale layout in force (m1v_set_downscale_layout)", kernels,
+        d_frames, n_frames, d_bytes, stream,
+        [e](const uint8_t *frames, uint8_t *bytes) {
+            const m1v_encoder::Layout::Downscale &d = e->layout.downscale;
+            return DownscaleBytesArgs{frames, bytes, d.front, e->layout.frame_stride, (uint32_t)e->g.W, (uint32_t)e->g.H, d.pixel_step};
+        },
+        [e](unsigned n) { return dim3(((unsigned)e->g.W * (unsigned)e->g.H + 255u) / 256u, n); }); // (rendition pixels)
 }
 
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued

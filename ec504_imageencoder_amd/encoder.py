@@ -203,6 +203,57 @@ def float_pixel_strides(shape, strides, dtype, dims="nhwc", order="rgb", range="
                 range=_float_range(range))
 
 
+DOWNSCALE_LAYOUT_FIELDS = ("row_pitch", "frame_stride", "pixel_step", "order", "factor")
+
+
+def downscale_layout_preset(width, height, pixel_bytes, order="rgb", factor=2):
+    """The downscale layout of a tightly packed 2 * width x 2 * height source of pixel_bytes (3 or 4) bytes per pixel, for an
+    encoder of the rendition's width x height, as a dict of DOWNSCALE_LAYOUT_FIELDS (bytes, the ORDER_* code and the factor), as
+    Mpeg1Encoder.set_downscale_layout takes it (include/mpeg1_hip.h, m1v_downscale_layout_preset, whose values these are).
+    order: "rgb" or "bgr" = bytes 0, 1, 2 of a source pixel (a 4th is skipped); factor: 2.  Pure."""
+    W, H, step = int(width), int(height), int(pixel_bytes)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if step not in (3, 4):
+        raise ValueError("a source pixel has 3 or 4 bytes")
+    code = _pixel_order(order)
+    if int(factor) != 2:
+        raise ValueError("factor must be 2 (other factors are not covered)")
+    return dict(row_pitch=2 * W * step, frame_stride=2 * H * 2 * W * step, pixel_step=step, order=code, factor=2)
+
+
+def downscale_strides(shape, strides, dims="nhwc", order="rgb"):
+    """The downscale layout (a dict of DOWNSCALE_LAYOUT_FIELDS, as Mpeg1Encoder.set_downscale_layout takes it) of a 4-D uint8
+    SOURCE array with the given strides in elements (= bytes), as torch gives them, for an encoder of half its width and height.
+    dims="nhwc": an [n, 2H, 2W, C] array — a packed tensor of 3 or 4 bytes per pixel, a window x[:, y0:y0+2H, x0:x0+2W, :3] of
+    a larger one; dims="nchw": an [n, C, 2H, 2W] array with channels-last strides.  Raises ValueError for what the layout does not
+    describe: an odd extent, fewer than 3 channels, a channel stride other than 1, a pixel stride other than 3 or 4 or below C, a
+    row pitch below 2W pixels, negative strides.  Pure: no torch."""
+    if len(shape) != 4 or len(strides) != 4:
+        raise ValueError("source frames must be 4-D: [n, 2H, 2W, C], or [n, C, 2H, 2W] with channels-last strides")
+    if dims == "nhwc":
+        (n, H2, W2, C), (frame, row, pixel, channel) = (int(x) for x in shape), (int(x) for x in strides)
+    elif dims == "nchw":
+        (n, C, H2, W2), (frame, channel, row, pixel) = (int(x) for x in shape), (int(x) for x in strides)
+    else:
+        raise ValueError(f"unknown dims {dims!r}: \"nhwc\" or \"nchw\"")
+    if H2 <= 0 or W2 <= 0 or H2 % 2 or W2 % 2:
+        raise ValueError(f"a source of odd or empty extent ({W2} x {H2}) is not covered")
+    if C < 3:
+        raise ValueError(f"a pixel needs 3 colour bytes, not {C}")
+    if channel != 1:
+        raise ValueError(f"the bytes of a pixel must be adjacent (channel stride {channel})")
+    if pixel not in (3, 4) or pixel < C:
+        raise ValueError(f"source pixels must lie 3 or 4 bytes apart and hold their {C} channels (pixel stride {pixel})")
+    if row < W2 * pixel:
+        raise ValueError(f"row pitch {row} below 2W * pixel stride = {W2 * pixel}")
+    if frame < 0:
+        raise ValueError("negative strides")
+    if n <= 1:  # (a single frame's stride is arbitrary)
+        frame = (H2 - 1) * row + W2 * pixel
+    return dict(row_pitch=row, frame_stride=frame, pixel_step=pixel, order=_pixel_order(order), factor=2)
+
+
 def distortion_to_psnr(d, blocks):
     """The distortion d of a frame of `blocks` blocks (Mpeg1Encoder.blocks_per_frame = strips * mb_rows * 6) as a PSNR in dB:
     10 * log10(255^2 * 64 * blocks / d), the coefficient-domain squared error read as a pixel-domain one (the FDCT is scaled like
@@ -285,6 +336,9 @@ def plane_layout_extent(layout, strips, mb_rows):
 _Kind = namedtuple("_Kind", "prop c struct fields name preset exact no_frames no_plane_frames")
 _NO_PLANES = "a plane table needs a plane layout or an RGB plane layout in force"
 _KINDS = (
+    _Kind("downscale_layout", "downscale", _ffi.DownscaleLayout, DOWNSCALE_LAYOUT_FIELDS, "a downscale layout", None, True,
+          "a frame table does not serve a downscale layout (set_downscale_layout)",
+          "a plane table does not serve a downscale layout (set_downscale_layout)"),
     _Kind("float_pixel_layout", "float_pixel", _ffi.FloatPixelLayout, FLOAT_PIXEL_LAYOUT_FIELDS, "a float pixel layout", None, True,
           "a frame table does not serve a float pixel layout (set_float_pixel_layout)",
           "a plane table does not serve a float pixel layout (set_float_pixel_layout)"),
@@ -367,7 +421,8 @@ class Mpeg1Encoder:
 
     Input: packed uint8 frames by default; the set_*_layout methods put surfaces, YCbCr planes, planes of R, G and B bytes, or
     planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32), or float R, G, B pixels
-    (set_float_pixel_layout: channels-last tensors) in their place.
+    (set_float_pixel_layout: channels-last tensors), or byte surfaces of twice the size, averaged 2 x 2 (set_downscale_layout),
+    in their place.
 
     mode: "strict" = the 96x144 region the unmodified reference encodes (encoder.h:238,248),
           "full"   = every macroblock (the reference with its loop bounds restored).
@@ -460,6 +515,28 @@ class Mpeg1Encoder:
             dtype, S = getattr(torch, _ffi.FLOAT_SAMPLE_DTYPES[want["sample"]]), _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
                 f"the {_KIND[kind].name[2:]} in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+        if kind == "downscale_layout":  # the SOURCE: [n, 2H, 2W, C], or [n, C, 2H, 2W] with channels-last strides
+            assert isinstance(rgb, torch.Tensor) and rgb.dtype == torch.uint8, \
+                f"the downscale layout in force takes torch.uint8 tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+            assert rgb.is_cuda and rgb.dim() == 4, "downscale sources must be a CUDA tensor [n, 2H, 2W, C] or a channels-last [n, C, 2H, 2W]"
+            size = (2 * self.height, 2 * self.width)
+            if tuple(rgb.shape[1:3]) == size and rgb.shape[3] in (3, 4):
+                frame, row, pixel, channel = rgb.stride()
+                C_ = rgb.shape[3]
+            else:
+                assert tuple(rgb.shape[2:]) == size and rgb.shape[1] in (3, 4), \
+                    f"sources must be [n, 2H, 2W, C] or a channels-last [n, C, 2H, 2W] with C = 3 or 4 and 2H x 2W = {size[0]} x {size[1]}"
+                frame, channel, row, pixel = rgb.stride()
+                C_ = rgb.shape[1]
+            assert channel == 1, f"strides {tuple(rgb.stride())}: the bytes of a pixel must be adjacent"
+            assert pixel == want["pixel_step"] and pixel >= C_ and row == want["row_pitch"], \
+                f"strides {tuple(rgb.stride())} are not the downscale layout in force (pixel step {want['pixel_step']}, row pitch {want['row_pitch']} bytes)"
+            _frames_apart(rgb, want["frame_stride"])
+            # every whole pixel of the read contract lies in the storage (a window's last pixel may lack its 4th byte)
+            last = rgb.storage_offset() + max(rgb.shape[0] - 1, 0) * frame + (size[0] - 1) * row + size[1] * pixel
+            assert rgb.shape[0] == 0 or last <= rgb.untyped_storage().nbytes(), \
+                "the tensor's storage ends inside the last pixel the encoder reads (a 4th byte beyond the view)"
+            return
         if kind == "float_pixel_layout":  # [n, H, W, C], or [n, C, H, W] with channels-last strides
             assert rgb.is_cuda and rgb.dim() == 4, "float pixel frames must be a CUDA tensor [n, H, W, C] or a channels-last [n, C, H, W]"
             size = (self.height, self.width)
@@ -589,17 +666,19 @@ class Mpeg1Encoder:
         order, what set_rgb_plane_layout("rgb") takes.  Asynchronous on torch's current stream."""
         return self._to_bytes("float_plane_layout", x, out, lambda n: (n, 3, self.height, self.width))
 
-    def _to_bytes(self, prop, x, out, shape):
-        """m1v_<c>s_to_bytes_device under the float layout that `prop` describes: the bytes of x as a uint8 tensor of shape(n)."""
+    def _to_bytes(self, prop, x, out, shape, call=None):
+        """m1v_<c>s_to_bytes_device (or m1v_<call>_device) under the layout that `prop` describes: the bytes of x as a uint8 tensor
+        of shape(n)."""
         import torch
         k = _KIND[prop]
-        assert self._input[0] == prop, f"{k.c}s_to_bytes() needs {k.name} in force (set_{k.c}_layout)"
+        call = call or f"{k.c}s_to_bytes"
+        assert self._input[0] == prop, f"{call}() needs {k.name} in force (set_{k.c}_layout)"
         self._check_input(x)
         shape = shape(x.shape[0])
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=x.device)
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape
-        _call(f"m1v_{k.c}s_to_bytes_device", self._h, _ptr(x), shape[0], _ptr(out), _stream())
+        _call(f"m1v_{call}_device", self._h, _ptr(x), shape[0], _ptr(out), _stream())
         return out
 
     def set_float_pixel_layout(self, layout):
@@ -618,6 +697,23 @@ class Mpeg1Encoder:
         m1v_float_pixels_to_bytes_device: the kernels' own conversion function): a uint8 CUDA tensor [n, H, W, 3] in R, G, B
         order, what the default packed layout takes.  Asynchronous on torch's current stream."""
         return self._to_bytes("float_pixel_layout", x, out, lambda n: (n, self.height, self.width, 3))
+
+    def set_downscale_layout(self, layout):
+        """Frames as byte surfaces of TWICE the encoder's width and height on the device — [n, 2H, 2W, 3] or [n, 2H, 2W, 4] uint8
+        tensors, windows of larger surfaces — whose 2 x 2 box average, (sum of the four source bytes + 2) >> 2 per colour, is the
+        picture that is encoded: the half-size rendition without a resampling kernel and a full-size intermediate in front
+        (include/mpeg1_hip.h, m1v_set_downscale_layout; 3-channel encoders, even widths).  layout: a dict of
+        DOWNSCALE_LAYOUT_FIELDS (downscale_layout_preset, or downscale_strides from the source tensor's shape and strides), or
+        None = back to the default layout and its kernels.  Every call then takes uint8 CUDA tensors with those strides, as
+        [n, 2H, 2W, C] or as a channels-last-strided [n, C, 2H, 2W]; a window x[:, y0:y0+2H, x0:x0+2W, :3] goes in as it is.
+        Frame and plane tables do not serve it.  A reconfiguration: call it between batches."""
+        self._set_layout("downscale_layout", layout)
+
+    def downscale_to_bytes(self, x, out=None):
+        """The bytes the encoder codes for the source tensor x under the downscale layout in force (include/mpeg1_hip.h,
+        m1v_downscale_to_bytes_device): a uint8 CUDA tensor [n, H, W, 3] in R, G, B order, what the default packed layout takes.
+        Asynchronous on torch's current stream."""
+        return self._to_bytes("downscale_layout", x, out, lambda n: (n, self.height, self.width, 3), call="downscale_to_bytes")
 
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
@@ -713,6 +809,11 @@ class Mpeg1Encoder:
         if rc < 0:
             raise EncoderError(rc, name)
         return c.as_dict() if rc == 1 else None
+
+    @property
+    def downscale_layout(self):
+        """The downscale layout in force as a dict of DOWNSCALE_LAYOUT_FIELDS (bytes of the source; order code; factor), or None."""
+        return self._in_force("downscale_layout")
 
     @property
     def float_pixel_layout(self):

@@ -851,6 +851,65 @@ int m1v_set_float_pixel_layout(m1v_encoder *enc, const m1v_float_pixel_layout *l
 int m1v_float_pixel_layout_in_force(const m1v_encoder *enc, m1v_float_pixel_layout *out); /* 1 / 0 / < 0 */
 int m1v_float_pixels_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
 
+/* Downscale layout: the 2:1 downscaled rendition of byte surfaces on the device — the 1080p stream beside the 4K one, a 540p proxy,
+ * a thumbnail stream from a decoder pool — encoded from the full-size surfaces where they lie: no resampling kernel and no
+ * full-size intermediate in front of the encoder.  width and height are the RENDITION's everywhere: the encoder is created with
+ * width x height and channels = 3, and the frames it is given are 2 * width x 2 * height surfaces of 3- or 4-byte pixels (the
+ * source pixel's byte count is the layout's, not the encoder's).
+ *
+ * Definition.  d_rgb points at byte 0 of source pixel (0, 0) of frame 0.  Frame f starts at F = d_rgb + f * frame_stride, and byte
+ * i (0, 1 or 2) of source pixel (X, Y) is at
+ *     F + Y * row_pitch + X * pixel_step + i
+ * with pixel_step 3 or 4.  order says whether bytes 0, 1, 2 are R, G, B (M1V_ORDER_RGB) or B, G, R (M1V_ORDER_BGR); a 4th byte
+ * is skipped.  The byte of colour c of rendition pixel (x, y) is
+ *     (s(2x, 2y) + s(2x+1, 2y) + s(2x, 2y+1) + s(2x+1, 2y+1) + 2) >> 2
+ * with s the source bytes of that colour: an exact integer that rounds half up.  The record of a frame is the packed calls' record
+ * for the interleaved picture [y][x] = (R, G, B) of those bytes: the same colour arithmetic, chroma quirk, headers,
+ * first_frame_index, per-frame quality, sizes and status bits.
+ *
+ *   m1v_downscale_layout_preset(width, height, pixel_bytes, order, factor, &layout)   pure host arithmetic: a tightly packed source,
+ *     pixel_step = pixel_bytes, row_pitch = 2 * width * pixel_bytes, frame_stride = 2 * height * row_pitch.  M1V_E_ARG (out
+ *     untouched): a null out, width or height <= 0, pixel_bytes other than 3 or 4, an unknown order, factor != 2.
+ *   m1v_set_downscale_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like the other layout setters:
+ *     it replaces whichever layout is in force, turns tables off, allocates first and swaps on success, and a failed call leaves
+ *     the layout and the table mode as they were.  The encoder takes the tile plan behind k_downscale_encode,
+ *     k_downscale_size_table and k_downscale_rd_table.  While it is in force m1v_input_layout, m1v_plane_layout_in_force and
+ *     m1v_sample_layout_in_force return M1V_E_ARG ("ask m1v_downscale_layout_in_force"); m1v_rgb_plane_layout_in_force,
+ *     m1v_float_plane_layout_in_force and m1v_float_pixel_layout_in_force return 0.
+ *     M1V_E_ARG with a message that names the reason, before anything is launched or reallocated: a null encoder; channels != 3;
+ *     an odd width; an unknown order; factor != 2; a pixel_step other than 3 or 4; row_pitch < 2 * width * pixel_step;
+ *     (2 * height - 1) * row_pitch + 2 * width * pixel_step >= 2^32 (offsets inside a frame are 32-bit); frame_stride below
+ *     (2 * height - 1) * row_pitch + 2 * width * pixel_step; an encoder that a hook has forced to the run kernels (those hooks
+ *     return M1V_E_ARG on an encoder with this layout).  Any byte alignment of d_rgb, row_pitch and frame_stride is accepted, as
+ *     for a surface: a window may start at any pixel of a larger surface.
+ *     Served: every call that serves the float pixel layout — m1v_encode_device, m1v_encode_quality_device,
+ *     m1v_frame_sizes_device, m1v_frame_size_table_device, m1v_frame_rd_table_device, the budget, rd, batch-budget, bitrate,
+ *     streams and streams-budget encodes, pipelined mode, m1v_delivery_step with its scratch retry, the m1v_profile_* counters and
+ *     m1v_debug_set_lds_words.  The packed-only calls refuse it as they refuse every other layout.  m1v_set_frame_table and
+ *     m1v_set_plane_table return M1V_E_ARG while it is in force.
+ *   m1v_downscale_layout_in_force(enc, &layout)   1 = a downscale layout is in force (layout filled; may be NULL), 0 = another
+ *     layout or none, < 0 = error.
+ *   m1v_downscale_to_bytes_device(enc, d_frames, n_frames, d_bytes, stream)   the bytes the encoder codes for these surfaces:
+ *     d_bytes is uint8 [n_frames][height][width][3] in R, G, B order, tightly packed — exactly what the default packed layout
+ *     encodes.  Needs this layout in force (M1V_E_ARG otherwise, and for null pointers and n_frames < 0); asynchronous on `stream`.
+ * Read contract: of frame f only bytes of the source rows [F + Y * row_pitch, F + Y * row_pitch + 2 * width * pixel_step), Y in
+ * 0 ... 2 * height - 1, are read.  A 4th byte inside a pixel may be read and never influences the output.  Row padding, gaps
+ * between frames and whatever lies around the batch are never read (the proof, per wave, heads csrc/m1v_downscale.h).
+ * Not covered: factor 4 and other factors (the field exists so that they can follow); filters other than the box; sources of odd
+ * extent; downscaled YCbCr planes, RGB planes and float layouts; the layout behind a frame table or a plane table; the host-buffer
+ * entry points and the folder CLI; several renditions in one pass. */
+typedef struct m1v_downscale_layout {
+    uint64_t row_pitch;     /* bytes between SOURCE rows; >= 2 * width * pixel_step */
+    uint64_t frame_stride;  /* bytes between source frames; >= (2 * height - 1) * row_pitch + 2 * width * pixel_step */
+    uint64_t pixel_step;    /* bytes between neighbouring source pixels of a row: 3 or 4 */
+    int32_t order;          /* M1V_ORDER_RGB or M1V_ORDER_BGR: bytes 0, 1, 2 of a source pixel; a 4th byte is skipped */
+    int32_t factor;         /* 2; anything else is M1V_E_ARG */
+} m1v_downscale_layout;     /* 32 bytes, offsets 0, 8, 16, 24, 28 */
+int m1v_downscale_layout_preset(int width, int height, int pixel_bytes /* 3 or 4 */, int order, int factor, m1v_downscale_layout *out);
+int m1v_set_downscale_layout(m1v_encoder *enc, const m1v_downscale_layout *layout);   /* NULL = the default layout */
+int m1v_downscale_layout_in_force(const m1v_encoder *enc, m1v_downscale_layout *out); /* 1 / 0 / < 0 */
+int m1v_downscale_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
+
 /* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
  * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
  * contiguous batch in front of the encoder.
