@@ -1005,6 +1005,95 @@ int m1v_downscale_to_bytes_device(m1v_encoder *e, const void *d_frames, int n_fr
         [e](unsigned n) { return dim3(((unsigned)e->g.W * (unsigned)e->g.H + 255u) / 256u, n); }); // (rendition pixels)
 }
 
+int m1v_downscale_plane_layout_preset(int width, int height, int preset, int factor, m1v_downscale_plane_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (preset == M1V_PLANES_REFERENCE) return fail(M1V_E_ARG, "the reference-style 4:4:4 planes are not a source of a downscale plane layout%s");
+    if (preset < M1V_PLANES_I420 || preset > M1V_PLANES_NV21) return fail(M1V_E_ARG, "unknown plane layout preset%s");
+    if ((width | height) & 1) return fail(M1V_E_ARG, "a downscale plane layout needs an even width and height%s");
+    if (factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+    // the plane preset of the tightly packed 2 W x 2 H source
+    const uint64_t W = (uint64_t)width, H = (uint64_t)height, luma = 4 * W * H, quarter = W * H;
+    const bool planar = preset == M1V_PLANES_I420 || preset == M1V_PLANES_YV12;
+    const bool cr_first = preset == M1V_PLANES_YV12 || preset == M1V_PLANES_NV21;
+    const uint64_t second = planar ? quarter : 1;
+    *out = {0, luma + (cr_first ? second : 0), luma + (cr_first ? 0 : second), 2 * W, planar ? W : 2 * W, planar ? 1u : 2u,
+            luma * 3 / 2, factor, 0};
+    return M1V_OK;
+}
+
+int m1v_set_downscale_plane_layout(m1v_encoder *e, const m1v_downscale_plane_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a downscale plane layout needs an encoder created with 3 channels%s");
+        if ((g.W | g.H) & 1) return fail(M1V_E_ARG, "a downscale plane layout needs an even width and height (the rendition's chroma planes are width / 2 x height / 2)%s");
+        if (layout->factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+        if (layout->reserved != 0) return fail(M1V_E_ARG, "reserved must be 0%s");
+        if (layout->c_step > 2) return fail(M1V_E_ARG, "c_step must be 1 or 2 (0 = 1)%s");
+        if (layout->frame_stride == 0) return fail(M1V_E_ARG, "a downscale plane layout needs a frame stride%s");
+        const unsigned long long W = (unsigned long long)g.W, step = layout->c_step ? layout->c_step : 1;
+        if (layout->y_pitch != 0 && layout->y_pitch < 2 * W) return fail(M1V_E_ARG, "luma pitch below 2 * width%s");
+        if (layout->c_pitch != 0 && layout->c_pitch < W * step) return fail(M1V_E_ARG, "chroma pitch below width * c_step%s");
+        const unsigned long long y_pitch = layout->y_pitch ? layout->y_pitch : 2 * W, c_pitch = layout->c_pitch ? layout->c_pitch : W * step;
+        // the source's extent: the read contract of mpeg1_hip.h (the plane layout's, taken on the source's rows)
+        const unsigned long long xe = (unsigned long long)g.n_strips * 16, ye = (unsigned long long)g.n_mbrows * 16;
+        const unsigned long long limit = 1ull << 32;
+        if (y_pitch >= limit || c_pitch >= limit || layout->y_offset >= limit || layout->cb_offset >= limit || layout->cr_offset >= limit)
+            return fail(M1V_E_ARG, "a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        const unsigned long long y_rows = (2 * ye - 1) * y_pitch + 2 * xe;          // one past the last addressed luma byte
+        const unsigned long long c_rows = (ye - 1) * c_pitch + (xe - 1) * step + 1; // one past a chroma plane's last addressed byte
+        const unsigned long long extent = std::max(layout->y_offset + y_rows,
+                                                   std::max<unsigned long long>(layout->cb_offset, layout->cr_offset) + c_rows);
+        if (extent >= limit) return fail(M1V_E_ARG, "a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a source frame's planes span%s");
+        want.kind = LayoutKind::downscale_planes;
+        // (lim: the 32-byte unit that ends with the extent is the last one a kernel may load; extent >= 1024,
+        // m1v_downscale_planes.h)
+        want.downscale_planes = {{(uint32_t)layout->y_offset, (uint32_t)layout->cb_offset, (uint32_t)layout->cr_offset, (uint32_t)y_pitch,
+                                  (uint32_t)c_pitch, (uint32_t)(extent - 32ull)}, (uint32_t)step};
+        want.frame_stride = layout->frame_stride;
+    }
+    return apply_layout(e, want);
+}
+
+int m1v_downscale_plane_layout_in_force(const m1v_encoder *e, m1v_downscale_plane_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::downscale_planes) return 0;
+    const m1v_encoder::Layout::DownscalePlanes &d = e->layout.downscale_planes;
+    if (out) *out = {d.front.y_off, d.front.cb_off, d.front.cr_off, d.front.y_pitch, d.front.c_pitch, d.c_step, e->layout.frame_stride, 2, 0};
+    return 1;
+}
+
+int m1v_downscale_planes_to_i420_device(m1v_encoder *e, const void *d_src, int n_frames, void *d_dst, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::downscale_planes)
+        return fail(M1V_E_ARG, "m1v_downscale_planes_to_i420_device needs a downscale plane layout in force (m1v_set_downscale_plane_layout)%s");
+    if (n_frames < 0 || ((!d_src || !d_dst) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
+    const m1v_encoder::Layout::DownscalePlanes &d = e->layout.downscale_planes;
+    {   // the kernel reads the whole 2 W x 2 H source, which the setter held only to the coded region's extent
+        const unsigned long long W = (unsigned long long)e->g.W, H = (unsigned long long)e->g.H;
+        const unsigned long long whole = std::max((unsigned long long)d.front.y_off + (2 * H - 1) * d.front.y_pitch + 2 * W,
+                                                  (unsigned long long)std::max(d.front.cb_off, d.front.cr_off) + (H - 1) * d.front.c_pitch + (W - 1) * d.c_step + 1);
+        if (whole >= (1ull << 32))
+            return fail(M1V_E_ARG, "m1v_downscale_planes_to_i420_device reads the whole source: a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (e->layout.frame_stride < whole)
+            return fail(M1V_E_ARG, "m1v_downscale_planes_to_i420_device reads the whole source: frame stride below the bytes the whole source frame's planes span%s");
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const unsigned long long frame_out = (unsigned long long)e->g.W * (unsigned long long)e->g.H * 3 / 2;
+    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
+        HalfPlaneBytesArgs a = {static_cast<const uint8_t *>(d_src) + (unsigned long long)done * e->layout.frame_stride,
+                                static_cast<uint8_t *>(d_dst) + (unsigned long long)done * frame_out, d.front, e->layout.frame_stride,
+                                (uint32_t)e->g.W, (uint32_t)e->g.H, d.c_step};
+        void *argv[] = {&a};
+        HIP_TRY(hipLaunchKernel((const void *)&k_half_planes_to_i420, dim3(((unsigned)frame_out + 255u) / 256u, (unsigned)std::min(n_frames - done, 65535)),
+                                dim3(256u), argv, 0, (hipStream_t)stream));
+    }
+    return M1V_OK;
+}
+
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");

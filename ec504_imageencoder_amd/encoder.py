@@ -329,6 +329,39 @@ def plane_layout_extent(layout, strips, mb_rows):
     return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
 
 
+DOWNSCALE_PLANE_LAYOUT_FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride", "factor", "reserved")
+
+
+def downscale_plane_layout_preset(width, height, name, factor=2):
+    """The downscale plane layout of a tightly packed 2 * width x 2 * height 4:2:0 source `name` ("i420", "yv12", "nv12", "nv21"),
+    for an encoder of the rendition's width x height, as a dict of DOWNSCALE_PLANE_LAYOUT_FIELDS (bytes of the SOURCE, the factor
+    and a reserved 0), as Mpeg1Encoder.set_downscale_plane_layout takes it (include/mpeg1_hip.h,
+    m1v_downscale_plane_layout_preset, whose values these are).  The reference-style planes are not a source.  Pure."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if name == "reference":
+        raise ValueError("the reference-style 4:4:4 planes are not a source of a downscale plane layout")
+    if name not in _ffi.PLANE_PRESETS:
+        raise ValueError(f"unknown plane layout preset {name!r}")
+    if W % 2 or H % 2:
+        raise ValueError("a downscale plane layout needs an even width and height")
+    if int(factor) != 2:
+        raise ValueError("factor must be 2 (other factors are not covered)")
+    return dict(plane_layout_preset(2 * W, 2 * H, name), factor=2, reserved=0)
+
+
+def downscale_plane_layout_extent(layout, strips, mb_rows):
+    """Bytes of a SOURCE frame the downscaled plane kernels may read (the read contract of include/mpeg1_hip.h): the plane
+    layout's extent taken on the source, rows = 2 * ye (luma) and ye (chroma), row bytes = 2 * xe (luma) and
+    (xe - 1) * c_step + 1 (chroma) for the strips * 16 x mb_rows * 16 region.  layout: a dict of DOWNSCALE_PLANE_LAYOUT_FIELDS
+    with no zeros (Mpeg1Encoder.downscale_plane_layout)."""
+    xe, ye = strips * 16, mb_rows * 16
+    luma = (2 * ye - 1) * layout["y_pitch"] + 2 * xe
+    chroma = (ye - 1) * layout["c_pitch"] + (xe - 1) * layout["c_step"] + 1
+    return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
+
+
 # The layout kinds: the property that describes one, its name in the C API (m1v_set_<c>_layout, m1v_<c>_layout_in_force), its
 # ctypes struct, fields, name in messages and preset function, whether a dict must hold every field, why frames() and
 # plane_frames() refuse it (None: they serve it).  In the order in which the C getters cannot fail (_refresh_input):
@@ -336,6 +369,10 @@ def plane_layout_extent(layout, strips, mb_rows):
 _Kind = namedtuple("_Kind", "prop c struct fields name preset exact no_frames no_plane_frames")
 _NO_PLANES = "a plane table needs a plane layout or an RGB plane layout in force"
 _KINDS = (
+    _Kind("downscale_plane_layout", "downscale_plane", _ffi.DownscalePlaneLayout, DOWNSCALE_PLANE_LAYOUT_FIELDS, "a downscale plane layout",
+          downscale_plane_layout_preset, False,
+          "a frame table does not serve a downscale plane layout (set_downscale_plane_layout)",
+          "a plane table does not serve a downscale plane layout (set_downscale_plane_layout)"),
     _Kind("downscale_layout", "downscale", _ffi.DownscaleLayout, DOWNSCALE_LAYOUT_FIELDS, "a downscale layout", None, True,
           "a frame table does not serve a downscale layout (set_downscale_layout)",
           "a plane table does not serve a downscale layout (set_downscale_layout)"),
@@ -422,7 +459,7 @@ class Mpeg1Encoder:
     Input: packed uint8 frames by default; the set_*_layout methods put surfaces, YCbCr planes, planes of R, G and B bytes, or
     planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32), or float R, G, B pixels
     (set_float_pixel_layout: channels-last tensors), or byte surfaces of twice the size, averaged 2 x 2 (set_downscale_layout),
-    in their place.
+    or YCbCr planes of twice the size, averaged 2 x 2 per plane (set_downscale_plane_layout), in their place.
 
     mode: "strict" = the 96x144 region the unmodified reference encodes (encoder.h:238,248),
           "full"   = every macroblock (the reference with its loop bounds restored).
@@ -515,6 +552,15 @@ class Mpeg1Encoder:
             dtype, S = getattr(torch, _ffi.FLOAT_SAMPLE_DTYPES[want["sample"]]), _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
                 f"the {_KIND[kind].name[2:]} in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+        if kind == "downscale_plane_layout":  # the SOURCE: [n, L] bytes, the plane layout's rule on the source's extent
+            assert isinstance(rgb, torch.Tensor) and rgb.dtype == torch.uint8, \
+                f"the downscale plane layout in force takes torch.uint8 tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+            assert rgb.is_cuda and rgb.dim() == 2, "downscale plane sources must be a CUDA uint8 tensor [n, L]"
+            extent = downscale_plane_layout_extent(want, self.strips, self.mb_rows)
+            assert rgb.shape[0] == 0 or (rgb.stride(1) == 1 and rgb.shape[1] >= extent), \
+                f"a frame's row must be contiguous and hold the {extent} bytes its source planes span"
+            _frames_apart(rgb, want["frame_stride"])
+            return
         if kind == "downscale_layout":  # the SOURCE: [n, 2H, 2W, C], or [n, C, 2H, 2W] with channels-last strides
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == torch.uint8, \
                 f"the downscale layout in force takes torch.uint8 tensors, not {getattr(rgb, 'dtype', type(rgb))}"
@@ -715,6 +761,33 @@ class Mpeg1Encoder:
         Asynchronous on torch's current stream."""
         return self._to_bytes("downscale_layout", x, out, lambda n: (n, self.height, self.width, 3), call="downscale_to_bytes")
 
+    def set_downscale_plane_layout(self, layout):
+        """Frames as Y, Cb, Cr planes of TWICE the encoder's width and height on the device — true 4:2:0 sources: a decoder's NV12
+        surfaces, a camera's I420 frames, pitched windows of them — whose 2 x 2 box average per plane, (sum of the four source
+        samples + 2) >> 2, is the picture that is encoded: the half-size rendition without a resampling kernel in front and
+        without a detour through RGB (include/mpeg1_hip.h, m1v_set_downscale_plane_layout; 3-channel encoders, even widths and
+        heights).  layout: a preset name ("i420", "yv12", "nv12", "nv21": the tightly packed source), a dict of
+        DOWNSCALE_PLANE_LAYOUT_FIELDS in bytes of the source (downscale_plane_layout_preset gives one to start from; missing
+        pitches and c_step default as in the header, factor is 2), or None = back to the default layout and its kernels.  Every
+        call then takes uint8 CUDA tensors [n, L] whose rows are the source frames: L >= the bytes a source frame's planes span,
+        rows frame_stride apart.  Frame and plane tables do not serve it.  A reconfiguration: call it between batches."""
+        if isinstance(layout, dict):
+            layout = {"factor": 2, **layout}
+        self._set_layout("downscale_plane_layout", layout)
+
+    def downscale_planes_to_i420(self, x, out=None):
+        """The samples the encoder codes for the source tensor x under the downscale plane layout in force (include/mpeg1_hip.h,
+        m1v_downscale_planes_to_i420_device): a uint8 CUDA tensor [n, W * H * 3 / 2] of tightly packed I420 frames, what
+        set_plane_layout("i420") takes.  Reads the whole 2W x 2H source, so a row of x holds every plane in full.  Asynchronous on
+        torch's current stream."""
+        want = self._input[1] if self._input[0] == "downscale_plane_layout" else None
+        if want is not None and x.shape[0]:  # the whole source, not only the coded region
+            W, H = self.width, self.height
+            full = max(want["y_offset"] + (2 * H - 1) * want["y_pitch"] + 2 * W,
+                       max(want["cb_offset"], want["cr_offset"]) + (H - 1) * want["c_pitch"] + (W - 1) * want["c_step"] + 1)
+            assert x.dim() == 2 and x.shape[1] >= full, f"a frame's row must hold the {full} bytes of the whole source"
+        return self._to_bytes("downscale_plane_layout", x, out, lambda n: (n, self.width * self.height * 3 // 2), call="downscale_planes_to_i420")
+
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
         method takes, in the place of `rgb`, what frames() returns or a contiguous CUDA int64 tensor [n] of the frames' base
@@ -809,6 +882,12 @@ class Mpeg1Encoder:
         if rc < 0:
             raise EncoderError(rc, name)
         return c.as_dict() if rc == 1 else None
+
+    @property
+    def downscale_plane_layout(self):
+        """The downscale plane layout in force as a dict of DOWNSCALE_PLANE_LAYOUT_FIELDS (bytes of the source, no zeros; factor;
+        reserved), or None."""
+        return self._in_force("downscale_plane_layout")
 
     @property
     def downscale_layout(self):

@@ -910,6 +910,78 @@ int m1v_set_downscale_layout(m1v_encoder *enc, const m1v_downscale_layout *layou
 int m1v_downscale_layout_in_force(const m1v_encoder *enc, m1v_downscale_layout *out); /* 1 / 0 / < 0 */
 int m1v_downscale_to_bytes_device(m1v_encoder *enc, const void *d_frames, int n_frames, uint8_t *d_bytes, void *stream);
 
+/* Downscale plane layout: the 2:1 downscaled rendition of planar and semi-planar YCbCr frames on the device — the 1080p stream of
+ * a decoder pool's 4K NV12 surfaces, the proxy of a camera's I420 frames — encoded from the full-size planes where they lie: no
+ * resampling kernel and no intermediate in front of the encoder, and no detour through RGB.  width and height are the
+ * RENDITION's everywhere: the encoder is created with width x height and channels = 3, and the frames it is given are true 4:2:0
+ * sources of 2 * width x 2 * height luma samples and width x height samples per chroma component.
+ *
+ * Definition.  Source addressing is the plane layout's: frame f starts at F = d_rgb + f * frame_stride,
+ *     source luma sample (X, Y) is at                F + y_offset + Y * y_pitch + X
+ *     source sample (U, V) of chroma plane p is at   F + p_offset + V * c_pitch + U * c_step
+ * with c_step 1 (one plane per component: I420, YV12) or 2 (interleaved pairs: NV12, NV21).  The rendition's luma sample (x, y) is
+ *     (s(2x, 2y) + s(2x+1, 2y) + s(2x, 2y+1) + s(2x+1, 2y+1) + 2) >> 2
+ * with s the source luma samples, and sample (u, v) of chroma plane p, u < width / 2, v < height / 2, is the same expression over
+ * that plane's source samples (2u, 2v) ... (2u+1, 2v+1): an exact integer that rounds half up.  This is a box filter per plane,
+ * with no chroma-siting correction.  The record of a frame is, byte for byte, the record the plane layout (m1v_set_plane_layout)
+ * gives for the tightly packed M1V_PLANES_I420 frame of those rendition samples: the same headers, first_frame_index, status bits,
+ * per-frame quality and sizes.  (The plane formula on a true 4:2:0 plane is ordinary 4:2:0 sampling: the reference's chroma quirk
+ * plays no part.)  The reference-style 4:4:4 planes (M1V_PLANES_REFERENCE) are not a source of this kind.
+ *
+ *   m1v_downscale_plane_layout_preset(width, height, preset, factor, &layout)   pure host arithmetic: the tightly packed
+ *     2 * width x 2 * height source of M1V_PLANES_I420, _YV12, _NV12 or _NV21; width and height are the rendition's.  M1V_E_ARG
+ *     (out untouched): a null out, M1V_PLANES_REFERENCE, an unknown preset, an odd or non-positive width or height, factor != 2.
+ *   m1v_set_downscale_plane_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like the other layout
+ *     setters: it replaces whichever layout is in force, turns tables off, allocates first and swaps on success, and a failed call
+ *     leaves the layout and the table mode as they were.  The encoder takes the tile plan behind k_half_planes_encode,
+ *     k_half_planes_size_table and k_half_planes_rd_table.  While it is in force m1v_input_layout, m1v_plane_layout_in_force and
+ *     m1v_sample_layout_in_force return M1V_E_ARG ("ask m1v_downscale_plane_layout_in_force"); the getters of the other kinds
+ *     return 0.
+ *     M1V_E_ARG with a message that names the reason, before anything is launched or reallocated: a null encoder; channels != 3;
+ *     an odd width or height; factor != 2; reserved != 0; c_step > 2; frame_stride == 0; 0 < y_pitch < 2 * width;
+ *     0 < c_pitch < width * c_step; a source extent E of 2^32 or more (offsets inside a frame are 32-bit); frame_stride < E; an
+ *     encoder that a hook has forced to the run kernels (those hooks return M1V_E_ARG on an encoder with this layout).
+ *     E is the plane layout's extent taken on the source: the largest offset + (rows - 1) * pitch + row bytes over the three
+ *     planes, with rows = 2 * ye for luma and ye for chroma, row bytes = 2 * xe for luma and (xe - 1) * c_step + 1 for chroma, and
+ *     xe x ye the coded region in rendition samples (16 * m1v_strips x 16 * m1v_mb_rows).  Any byte alignment of d_rgb, offsets,
+ *     pitches and stride is accepted.  Planes with c_step = 2 that are not interleaved with each other work too.
+ *     Served: every call that serves the downscale layout — m1v_encode_device, m1v_encode_quality_device,
+ *     m1v_frame_sizes_device, m1v_frame_size_table_device, m1v_frame_rd_table_device, the budget, rd, batch-budget, bitrate,
+ *     streams and streams-budget encodes, pipelined mode, m1v_delivery_step with its scratch retry, the m1v_profile_* counters and
+ *     m1v_debug_set_lds_words.  The packed-only calls refuse it as they refuse every other layout.  m1v_set_frame_table and
+ *     m1v_set_plane_table return M1V_E_ARG while it is in force.
+ *   m1v_downscale_plane_layout_in_force(enc, &layout)   1 = a downscale plane layout is in force (layout filled with the values the
+ *     kernels use, no zeros; may be NULL), 0 = another layout or none, < 0 = error.
+ *   m1v_downscale_planes_to_i420_device(enc, d_src, n_frames, d_dst, stream)   the samples the encoder codes for these frames:
+ *     d_dst is uint8 [n_frames][width * height * 3 / 2], tightly packed I420 whatever the source's form — exactly what
+ *     m1v_set_plane_layout with the M1V_PLANES_I420 preset encodes.  An elementwise kernel over the whole width x height rendition
+ *     (every addressed byte of the 2 * width x 2 * height source is read, and addressed bytes only): the reference for the bytes,
+ *     not a fast path.  Needs this layout in force (M1V_E_ARG otherwise, and for null pointers and n_frames < 0).  Because it
+ *     reads the whole source and the setter holds a layout only to the coded region's extent E, it also returns M1V_E_ARG when
+ *     the extent of the whole source (E with xe x ye = width x height) is 2^32 or more or exceeds frame_stride: an encoder in
+ *     strict mode, or of a width or height that is no multiple of 16.  Asynchronous on `stream`.
+ * Read contract: of frame f only bytes of [F, F + E) rounded up to the next 4-byte boundary are read by the encoding calls (the
+ * boundary is counted from F, whatever F's own alignment).
+ * Unaddressed bytes inside that range (row padding, gaps between planes, the other component's bytes of a c_step = 2 plane) may
+ * be read and never influence the output.  Gaps between frames and whatever lies around the batch are never read (the proof, per
+ * wave, heads csrc/m1v_downscale_planes.h).
+ * Not covered: factor 4 and other filters (the factor field exists so that they can follow); sources of odd extent; 4:4:4 and
+ * reference-style planes; 4:2:2 and P010 sources; RGB-plane and float sources; the kind behind a frame table or a plane table;
+ * the host-buffer entry points and the folder CLI; several renditions in one pass. */
+typedef struct m1v_downscale_plane_layout {
+    uint64_t y_offset, cb_offset, cr_offset;  /* of the SOURCE, bytes from the frame's base                 */
+    uint64_t y_pitch;                         /* 0 = 2 * width                                              */
+    uint64_t c_pitch;                         /* 0 = width * c_step                                         */
+    uint64_t c_step;                          /* 1 or 2; 0 = 1                                              */
+    uint64_t frame_stride;                    /* never 0                                                    */
+    int32_t  factor;                          /* 2                                                          */
+    int32_t  reserved;                        /* 0                                                          */
+} m1v_downscale_plane_layout;                 /* 64 bytes */
+int m1v_downscale_plane_layout_preset(int width, int height, int preset, int factor, m1v_downscale_plane_layout *out);
+int m1v_set_downscale_plane_layout(m1v_encoder *enc, const m1v_downscale_plane_layout *layout);  /* NULL = default layout */
+int m1v_downscale_plane_layout_in_force(const m1v_encoder *enc, m1v_downscale_plane_layout *out); /* 1 / 0 / < 0 */
+int m1v_downscale_planes_to_i420_device(m1v_encoder *enc, const void *d_src, int n_frames, void *d_dst, void *stream);
+
 /* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
  * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
  * contiguous batch in front of the encoder.

@@ -29,7 +29,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD = os.path.join(ROOT, "profiles", "r04_pmc.json")
 SOURCES = ["ec504_imageencoder_amd/csrc/" + f for f in ("m1v_kernels.hip", "m1v_tiles.h", "m1v_planes.h", "m1v_encode_tile_body.h",
-                                                        "m1v_size_table_body.h", "m1v_assemble.h", "fdct_f32.h")]
+                                                        "m1v_size_table_body.h", "m1v_assemble.h", "fdct_f32.h", "m1v_downscale_planes.h")]
 
 
 def source_sha256(sources=SOURCES):
