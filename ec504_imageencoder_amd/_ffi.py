@@ -85,6 +85,18 @@ class DownscalePlaneLayout(_Layout):
     _fields_ = [(name, C.c_uint64) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")] + \
                [("factor", C.c_int32), ("reserved", C.c_int32)]
 
+
+class DownscaleWordLayout(_Layout):
+    """m1v_downscale_word_layout (include/mpeg1_hip.h): where the Y, Cb and Cr words of a frame's SOURCE lie (4:2:0 planes of 16-bit
+    little-endian words, twice the encoder's width and height), in bytes, the factor (2) and the shift from average to sample."""
+    _fields_ = [(name, C.c_uint64) for name in ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride")] + \
+               [("factor", C.c_int32), ("shift", C.c_int32)]
+
+
+# m1v_downscale_word_layout_preset: the tightly packed sources
+WORDS_P010, WORDS_I010, WORDS_I012, WORDS_I016 = 0, 1, 2, 3
+WORD_PRESETS = {"p010": WORDS_P010, "p012": WORDS_P010, "p016": WORDS_P010, "i010": WORDS_I010, "i012": WORDS_I012, "i016": WORDS_I016}
+
 STATUS_STREAMS = 64
 MAX_STREAMS = 4096
 STREAMS_LARGEST_THAT_FITS, STREAMS_LEAST_DISTORTION = 0, 1
@@ -130,6 +142,8 @@ MPEG1_HIP_SYMBOLS = [
     "m1v_downscale_layout_preset", "m1v_set_downscale_layout", "m1v_downscale_layout_in_force", "m1v_downscale_to_bytes_device",
     "m1v_downscale_plane_layout_preset", "m1v_set_downscale_plane_layout", "m1v_downscale_plane_layout_in_force",
     "m1v_downscale_planes_to_i420_device",
+    "m1v_downscale_word_layout_preset", "m1v_set_downscale_word_layout", "m1v_downscale_word_layout_in_force",
+    "m1v_downscale_words_to_i420_device",
     "m1v_set_frame_table", "m1v_frame_table", "m1v_set_plane_table", "m1v_plane_table",
     "m1v_delivery_create", "m1v_delivery_destroy", "m1v_delivery_step", "m1v_delivery_flush", "m1v_delivery_wait", "m1v_delivery_bytes",
 ]
@@ -274,14 +288,15 @@ def lib():
     # per layout struct: its preset (the number of ints it takes in front of the struct), its setter and its getter
     for kind, struct, preset_ints in (("plane", PlaneLayout, 3), ("sample", SampleLayout, 3), ("rgb_plane", RgbPlaneLayout, 3),
                                       ("float_plane", FloatPlaneLayout, 5), ("float_pixel", FloatPixelLayout, 6),
-                                      ("downscale", DownscaleLayout, 5), ("downscale_plane", DownscalePlaneLayout, 4)):
+                                      ("downscale", DownscaleLayout, 5), ("downscale_plane", DownscalePlaneLayout, 4),
+                                      ("downscale_word", DownscaleWordLayout, 4)):
         getattr(L, f"m1v_{kind}_layout_preset").argtypes = [C.c_int] * preset_ints + [C.POINTER(struct)]
         getattr(L, f"m1v_set_{kind}_layout").argtypes = [vp, C.POINTER(struct)]
         getattr(L, f"m1v_{kind}_layout_in_force").argtypes = [vp, C.POINTER(struct)]
         for name in (f"m1v_{kind}_layout_preset", f"m1v_set_{kind}_layout", f"m1v_{kind}_layout_in_force"):
             getattr(L, name).restype = C.c_int
     for name in ("m1v_float_planes_to_bytes_device", "m1v_float_pixels_to_bytes_device", "m1v_downscale_to_bytes_device",
-                 "m1v_downscale_planes_to_i420_device"):
+                 "m1v_downscale_planes_to_i420_device", "m1v_downscale_words_to_i420_device"):
         getattr(L, name).argtypes = [vp, vp, C.c_int, vp, vp]
         getattr(L, name).restype = C.c_int
     L.m1v_set_frame_table.argtypes = [vp, C.c_int]

@@ -34,6 +34,9 @@
 //   k_half_planes_encode, k_half_planes_size_table, k_half_planes_rd_table   (m1v_downscale_planes.h, the same bodies) the tile
 //                     kernels on the 2 x 2 box average of planar and semi-planar YCbCr frames of twice the encoder's width and
 //                     height (m1v_set_downscale_plane_layout), by the same rule
+//   k_half_words_encode, k_half_words_size_table, k_half_words_rd_table   (m1v_downscale_words.h, the same bodies) the tile
+//                     kernels on the 2 x 2 box average of YCbCr frames of 16-bit words of twice the encoder's width and height
+//                     (m1v_set_downscale_word_layout): averaged at the word's precision, then shifted down to a byte
 //   k_encode_dense    the run kernel (4-channel pictures; round 2's hot kernel).  A frame's blocks, in
 //                     stream order, are cut into runs of T consecutive blocks (default 256); one
 //                     workgroup per (frame, run), one LANE per 8x8 block (Y0..Y3, Cb, Cr of each
@@ -1369,6 +1372,7 @@ constexpr int kMaxCandidates = 8; // qualities of one budget call or size table
 #include "m1v_float_pixels.h"
 #include "m1v_downscale.h"
 #include "m1v_downscale_planes.h"
+#include "m1v_downscale_words.h"
 
 // ---- per-frame quality and frame-size budgets (m1v_encode_quality_device, m1v_frame_sizes_device, m1v_encode_budget_device) ----
 struct QualityArgs {
@@ -1894,7 +1898,7 @@ struct m1v_encoder {
     // The input layout in force, no zeros: its kind, the frame stride every kind but packed has, and one member per kind.  Only the
     // member of the kind in force is set and read (kind_facts: what the host knows of each kind).
     struct Layout {
-        enum class Kind { packed, surface, samples, rgb_planes, float_planes, float_pixels, downscale, downscale_planes } kind = Kind::packed;
+        enum class Kind { packed, surface, samples, rgb_planes, float_planes, float_pixels, downscale, downscale_planes, downscale_words } kind = Kind::packed;
         unsigned long long frame_stride = 0;  // bytes from a frame's first byte to the next frame's
         // m1v_set_frame_table / m1v_set_plane_table: d_rgb is a device array of one 64-bit address per frame, or of three (one per
         // plane); frame_stride is kept and unused.  Part of the record, so every setter's fresh record turns tables off and a
@@ -1917,6 +1921,9 @@ struct m1v_encoder {
         // m1v_set_downscale_plane_layout: Y, Cb, Cr planes of twice the encoder's width and height, as their kernels take them
         // (m1v_downscale_planes.h; front.lim from the source's extent), with the chroma step in bytes
         struct DownscalePlanes { HalfPlaneFrontArgs front; uint32_t c_step; } downscale_planes = {};
+        // m1v_set_downscale_word_layout: Y, Cb, Cr planes of 16-bit words of twice the encoder's width and height, as their
+        // kernels take them (m1v_downscale_words.h; front.lim from the source's extent), with the chroma step in bytes
+        struct DownscaleWords { HalfWordFrontArgs front; uint32_t c_step; } downscale_words = {};
         bool tiles_only() const { return kind != Kind::packed; }
     } layout;
     Plan plan = {};             // the plan configure_path set up
@@ -2040,6 +2047,13 @@ static KindFacts kind_facts(LayoutKind kind) {
                 "a frame table does not serve a downscale plane layout (m1v_set_downscale_plane_layout): downscaled frames behind a "
                 "table are not covered",
                 "a plane table does not serve a downscale plane layout (m1v_set_downscale_plane_layout): downscaled planes behind "
+                "separate pointers are not covered",
+                nullptr};
+    case LayoutKind::downscale_words:
+        return {"a downscale word layout", "m1v_set_downscale_word_layout", "m1v_downscale_word_layout_in_force", M1V_E_ARG,
+                "a frame table does not serve a downscale word layout (m1v_set_downscale_word_layout): downscaled frames behind a "
+                "table are not covered",
+                "a plane table does not serve a downscale word layout (m1v_set_downscale_word_layout): downscaled planes behind "
                 "separate pointers are not covered",
                 nullptr};
     }
@@ -2241,7 +2255,7 @@ static int plan_for(const m1v_encoder &e, Plan &out) {
 //   every level wide.
 enum TileVariant { kPacked3, kPacked4, kSurfaceRgb3, kSurfaceBgr3, kSurfaceRgb4, kSurfaceBgr4, kPlanes, kPlanesPaired, kStep2, kRgbPlanes, kFloatPlanesF16, kFloatPlanesBf16,
                    kFloatPlanesF32, kFloatPixelsF16x3, kFloatPixelsF16x4, kFloatPixelsBf16x3, kFloatPixelsBf16x4, kFloatPixelsF32x3, kFloatPixelsF32x4,
-                   kDownscale3, kDownscale4, kHalfPlanes, kHalfPlanesPaired,
+                   kDownscale3, kDownscale4, kHalfPlanes, kHalfPlanesPaired, kHalfWords, kHalfWordsPaired,
                    kTileVariants };
 enum TileRow { kEncode, kSizeTable, kRdTable, kTileRows };
 //   planes[...][...]: their kp_* twins of a plane table (m1v_set_plane_table); kPlanes, kPlanesPaired and kRgbPlanes only
@@ -2270,6 +2284,10 @@ struct Kernels { const void *tile[kTileRows][kTileVariants][2], *table[kTileRows
 #define M1V_HALF_PLANE_VARIANT(V, CSTEP)                                                                                          \
     (M1V_PAIR(k.tile[kEncode][V], k_half_planes_encode, CSTEP), M1V_PAIR(k.tile[kSizeTable][V], k_half_planes_size_table, CSTEP), \
      M1V_PAIR(k.tile[kRdTable][V], k_half_planes_rd_table, CSTEP))
+// the downscaled word kernels of one chroma step (m1v_downscale_words.h): no table twins either
+#define M1V_HALF_WORD_VARIANT(V, CSTEP)                                                                                           \
+    (M1V_PAIR(k.tile[kEncode][V], k_half_words_encode, CSTEP), M1V_PAIR(k.tile[kSizeTable][V], k_half_words_size_table, CSTEP),   \
+     M1V_PAIR(k.tile[kRdTable][V], k_half_words_rd_table, CSTEP))
 // ... and its kp_* kernels of a plane table
 #define M1V_PLANE_TABLE_VARIANT(V, NAME, ...)                                                                                     \
     (M1V_PAIR(k.planes[kEncode][V], kp_encode_##NAME, ##__VA_ARGS__), M1V_PAIR(k.planes[kSizeTable][V], kp_size_table_##NAME, ##__VA_ARGS__), \
@@ -2311,8 +2329,11 @@ static const Kernels kKernels = [] {
     M1V_DOWNSCALE_VARIANT(kDownscale4, 4);
     M1V_HALF_PLANE_VARIANT(kHalfPlanes, 1);
     M1V_HALF_PLANE_VARIANT(kHalfPlanesPaired, 2);
+    M1V_HALF_WORD_VARIANT(kHalfWords, 2);
+    M1V_HALF_WORD_VARIANT(kHalfWordsPaired, 4);
     return k;
 }();
+#undef M1V_HALF_WORD_VARIANT
 #undef M1V_HALF_PLANE_VARIANT
 #undef M1V_DOWNSCALE_VARIANT
 #undef M1V_FLOAT_PIXEL_VARIANT
@@ -2347,6 +2368,7 @@ static TileVariant tile_variant(const m1v_encoder *e) {
     case LayoutKind::float_pixels: return (TileVariant)(kFloatPixelsF16x3 + 2 * l.fmt.sample + (l.float_pixels.pixel_step == 4u * l.fmt.bytes ? 1 : 0));
     case LayoutKind::downscale: return l.downscale.pixel_step == 4u ? kDownscale4 : kDownscale3;
     case LayoutKind::downscale_planes: return l.downscale_planes.c_step == 2u ? kHalfPlanesPaired : kHalfPlanes;
+    case LayoutKind::downscale_words: return l.downscale_words.c_step == 4u ? kHalfWordsPaired : kHalfWords;
     case LayoutKind::samples: return l.samples.y_step == 2 ? kStep2 : (l.samples.c_step == 2 ? kPlanesPaired : kPlanes);
     case LayoutKind::surface: return l.surface.order == M1V_ORDER_BGR ? (four ? kSurfaceBgr4 : kSurfaceBgr3) : (four ? kSurfaceRgb4 : kSurfaceRgb3);
     case LayoutKind::packed: return four ? kPacked4 : kPacked3;
@@ -2393,9 +2415,9 @@ static void fill_tile_grid(const m1v_encoder *e, const uint8_t *d_rgb, int n_fra
 
 // What a tile-shaped kernel's base arguments are wrapped in for each layout kind, and their row of Kernels::tile
 template <typename Base> struct TileFamily;
-template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; using FloatPlanes = FloatPlaneArgs; using FloatPixels = FloatPixelArgs; using Downscale = DownscaleArgs; using DownscalePlanes = HalfPlaneArgs; };
-template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; using FloatPlanes = FloatPlaneTableArgs; using FloatPixels = FloatPixelTableArgs; using Downscale = DownscaleTableArgs; using DownscalePlanes = HalfPlaneTableArgs; };
-template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; using FloatPlanes = FloatPlaneRdArgs; using FloatPixels = FloatPixelRdArgs; using Downscale = DownscaleRdArgs; using DownscalePlanes = HalfPlaneRdArgs; };
+template <> struct TileFamily<TileArgs> { static constexpr TileRow row = kEncode; using Surface = SurfaceArgs; using Samples = PlaneArgs; using RgbPlanes = RgbPlaneArgs; using FloatPlanes = FloatPlaneArgs; using FloatPixels = FloatPixelArgs; using Downscale = DownscaleArgs; using DownscalePlanes = HalfPlaneArgs; using DownscaleWords = HalfWordArgs; };
+template <> struct TileFamily<TableArgs> { static constexpr TileRow row = kSizeTable; using Surface = SurfaceTableArgs; using Samples = PlaneTableArgs; using RgbPlanes = RgbPlaneTableArgs; using FloatPlanes = FloatPlaneTableArgs; using FloatPixels = FloatPixelTableArgs; using Downscale = DownscaleTableArgs; using DownscalePlanes = HalfPlaneTableArgs; using DownscaleWords = HalfWordTableArgs; };
+template <> struct TileFamily<RdTableArgs> { static constexpr TileRow row = kRdTable; using Surface = SurfaceRdArgs; using Samples = PlaneRdArgs; using RgbPlanes = RgbPlaneRdArgs; using FloatPlanes = FloatPlaneRdArgs; using FloatPixels = FloatPixelRdArgs; using Downscale = DownscaleRdArgs; using DownscalePlanes = HalfPlaneRdArgs; using DownscaleWords = HalfWordRdArgs; };
 
 // The tile-shaped kernel of a's family over the grid a carries (fill_tile_grid), with a wrapped for the layout in force
 template <typename Args>
@@ -2428,6 +2450,7 @@ static int launch_tiles(m1v_encoder *e, bool narrow, Args &a, size_t grid, size_
     case LayoutKind::float_pixels: return launch(typename Family::FloatPixels{a, l.float_pixels.front, stride});
     case LayoutKind::downscale: return launch(typename Family::Downscale{a, l.downscale.front, stride});
     case LayoutKind::downscale_planes: return launch(typename Family::DownscalePlanes{a, l.downscale_planes.front, stride});
+    case LayoutKind::downscale_words: return launch(typename Family::DownscaleWords{a, l.downscale_words.front, stride});
     case LayoutKind::packed: return launch(a);
     }
 }

@@ -1094,6 +1094,96 @@ int m1v_downscale_planes_to_i420_device(m1v_encoder *e, const void *d_src, int n
     return M1V_OK;
 }
 
+int m1v_downscale_word_layout_preset(int width, int height, int preset, int factor, m1v_downscale_word_layout *out) {
+    if (!out) return fail(M1V_E_ARG, "null out%s");
+    if (width <= 0 || height <= 0) return fail(M1V_E_ARG, "bad geometry%s");
+    if (preset < M1V_WORDS_P010 || preset > M1V_WORDS_I016) return fail(M1V_E_ARG, "unknown word layout preset%s");
+    if ((width | height) & 1) return fail(M1V_E_ARG, "a downscale word layout needs an even width and height%s");
+    if (factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+    // the tightly packed 2 W x 2 H source: 4 W H luma words, then W H words per chroma component
+    const uint64_t W = (uint64_t)width, H = (uint64_t)height, luma = 8 * W * H, plane = 2 * W * H;
+    const bool paired = preset == M1V_WORDS_P010;
+    const int32_t shift = preset == M1V_WORDS_I010 ? 2 : preset == M1V_WORDS_I012 ? 4 : 8;
+    *out = {0, luma, luma + (paired ? 2 : plane), 4 * W, paired ? 4 * W : 2 * W, paired ? 4u : 2u, luma + 2 * plane, factor, shift};
+    return M1V_OK;
+}
+
+// One past the last addressed byte of a word source whose planes hold xe x ye rendition samples (the read contract of mpeg1_hip.h)
+static unsigned long long word_source_extent(const HalfWordFrontArgs &f, unsigned long long step, unsigned long long xe, unsigned long long ye) {
+    const unsigned long long y_rows = (2 * ye - 1) * f.y_pitch + 4 * xe;
+    const unsigned long long c_rows = (ye - 1) * f.c_pitch + (xe - 1) * step + 2;
+    return std::max(f.y_off + y_rows, (unsigned long long)std::max(f.cb_off, f.cr_off) + c_rows);
+}
+
+int m1v_set_downscale_word_layout(m1v_encoder *e, const m1v_downscale_word_layout *layout) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    m1v_encoder::Layout want;
+    if (layout) {
+        const Geometry &g = e->g;
+        if (g.C != 3) return fail(M1V_E_ARG, "a downscale word layout needs an encoder created with 3 channels%s");
+        if ((g.W | g.H) & 1) return fail(M1V_E_ARG, "a downscale word layout needs an even width and height (the rendition's chroma planes are width / 2 x height / 2)%s");
+        if (layout->factor != 2) return fail(M1V_E_ARG, "factor must be 2 (other factors are not covered)%s");
+        if (layout->shift < 0 || layout->shift > 8) return fail(M1V_E_ARG, "shift must be 0 .. 8%s");
+        if (layout->c_step != 0 && layout->c_step != 2 && layout->c_step != 4) return fail(M1V_E_ARG, "c_step must be 2 or 4 (0 = 2)%s");
+        const unsigned long long W = (unsigned long long)g.W, step = layout->c_step ? layout->c_step : 2;
+        if (step == 4 && std::max(layout->cb_offset, layout->cr_offset) - std::min(layout->cb_offset, layout->cr_offset) > 3)
+            return fail(M1V_E_ARG, "with c_step 4 the chroma offsets must lie within one 4-byte group%s");
+        if (layout->frame_stride == 0) return fail(M1V_E_ARG, "a downscale word layout needs a frame stride%s");
+        if (layout->y_pitch != 0 && layout->y_pitch < 4 * W) return fail(M1V_E_ARG, "luma pitch below 4 * width%s");
+        if (layout->c_pitch != 0 && layout->c_pitch < W * step) return fail(M1V_E_ARG, "chroma pitch below width * c_step%s");
+        const unsigned long long y_pitch = layout->y_pitch ? layout->y_pitch : 4 * W, c_pitch = layout->c_pitch ? layout->c_pitch : W * step;
+        // the source's extent: the read contract of mpeg1_hip.h (the plane layout's, taken on the source's rows and words)
+        const unsigned long long limit = 1ull << 32;
+        if (y_pitch >= limit || c_pitch >= limit || layout->y_offset >= limit || layout->cb_offset >= limit || layout->cr_offset >= limit)
+            return fail(M1V_E_ARG, "a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        HalfWordFrontArgs front = {(uint32_t)layout->y_offset, (uint32_t)layout->cb_offset, (uint32_t)layout->cr_offset, (uint32_t)y_pitch,
+                                   (uint32_t)c_pitch, 0u, (uint32_t)layout->shift};
+        const unsigned long long extent = word_source_extent(front, step, (unsigned long long)g.n_strips * 16, (unsigned long long)g.n_mbrows * 16);
+        if (extent >= limit) return fail(M1V_E_ARG, "a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (layout->frame_stride < extent) return fail(M1V_E_ARG, "frame stride below the bytes a source frame's planes span%s");
+        // (lim: the 64-byte unit that ends with the extent is the last one a kernel may load; extent >= 2048, m1v_downscale_words.h)
+        front.lim = (uint32_t)(extent - 64ull);
+        want.kind = LayoutKind::downscale_words;
+        want.downscale_words = {front, (uint32_t)step};
+        want.frame_stride = layout->frame_stride;
+    }
+    return apply_layout(e, want);
+}
+
+int m1v_downscale_word_layout_in_force(const m1v_encoder *e, m1v_downscale_word_layout *out) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::downscale_words) return 0;
+    const m1v_encoder::Layout::DownscaleWords &d = e->layout.downscale_words;
+    if (out) *out = {d.front.y_off, d.front.cb_off, d.front.cr_off, d.front.y_pitch, d.front.c_pitch, d.c_step, e->layout.frame_stride, 2, (int32_t)d.front.shift};
+    return 1;
+}
+
+int m1v_downscale_words_to_i420_device(m1v_encoder *e, const void *d_src, int n_frames, void *d_dst, void *stream) {
+    if (!e) return fail(M1V_E_ARG, "null encoder%s");
+    if (e->layout.kind != LayoutKind::downscale_words)
+        return fail(M1V_E_ARG, "m1v_downscale_words_to_i420_device needs a downscale word layout in force (m1v_set_downscale_word_layout)%s");
+    if (n_frames < 0 || ((!d_src || !d_dst) && n_frames > 0)) return fail(M1V_E_ARG, "null pointer or negative n_frames%s");
+    const m1v_encoder::Layout::DownscaleWords &d = e->layout.downscale_words;
+    {   // the kernel reads the whole 2 W x 2 H source, which the setter held only to the coded region's extent
+        const unsigned long long whole = word_source_extent(d.front, d.c_step, (unsigned long long)e->g.W, (unsigned long long)e->g.H);
+        if (whole >= (1ull << 32))
+            return fail(M1V_E_ARG, "m1v_downscale_words_to_i420_device reads the whole source: a source frame of 4 GiB or more (byte offsets inside a frame are 32-bit)%s");
+        if (e->layout.frame_stride < whole)
+            return fail(M1V_E_ARG, "m1v_downscale_words_to_i420_device reads the whole source: frame stride below the bytes the whole source frame's planes span%s");
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const unsigned long long frame_out = (unsigned long long)e->g.W * (unsigned long long)e->g.H * 3 / 2;
+    for (int done = 0; done < n_frames; done += 65535) { // (a grid's y extent)
+        HalfWordBytesArgs a = {static_cast<const uint8_t *>(d_src) + (unsigned long long)done * e->layout.frame_stride,
+                               static_cast<uint8_t *>(d_dst) + (unsigned long long)done * frame_out, d.front, e->layout.frame_stride,
+                               (uint32_t)e->g.W, (uint32_t)e->g.H, d.c_step};
+        void *argv[] = {&a};
+        HIP_TRY(hipLaunchKernel((const void *)&k_half_words_to_i420, dim3(((unsigned)frame_out + 255u) / 256u, (unsigned)std::min(n_frames - done, 65535)),
+                                dim3(256u), argv, 0, (hipStream_t)stream));
+    }
+    return M1V_OK;
+}
+
 // The table mode is a field of the layout record in force: no plan, no allocation, nothing queued
 int m1v_set_frame_table(m1v_encoder *e, int enable) {
     if (!e) return fail(M1V_E_ARG, "null encoder%s");

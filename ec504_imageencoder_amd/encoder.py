@@ -362,6 +362,42 @@ def downscale_plane_layout_extent(layout, strips, mb_rows):
     return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
 
 
+DOWNSCALE_WORD_LAYOUT_FIELDS = ("y_offset", "cb_offset", "cr_offset", "y_pitch", "c_pitch", "c_step", "frame_stride", "factor", "shift")
+
+
+def downscale_word_layout_preset(width, height, name, factor=2):
+    """The downscale word layout of a tightly packed 2 * width x 2 * height 4:2:0 source of 16-bit little-endian words, `name` one of
+    "p010", "p012", "p016" (a luma plane and a plane of Cb, Cr word pairs, the value in the high bits: shift 8), "i010", "i012"
+    (yuv420p10le, yuv420p12le: three planes, the value in the low bits: shift 2, 4) or "i016" (yuv420p16le: shift 8), for an encoder
+    of the rendition's width x height, as a dict of DOWNSCALE_WORD_LAYOUT_FIELDS (bytes of the SOURCE, the factor and the shift), as
+    Mpeg1Encoder.set_downscale_word_layout takes it (include/mpeg1_hip.h, m1v_downscale_word_layout_preset, whose values these
+    are).  Pure."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError("bad geometry")
+    if name not in _ffi.WORD_PRESETS:
+        raise ValueError(f"unknown word layout preset {name!r}")
+    if W % 2 or H % 2:
+        raise ValueError("a downscale word layout needs an even width and height")
+    if int(factor) != 2:
+        raise ValueError("factor must be 2 (other factors are not covered)")
+    paired = _ffi.WORD_PRESETS[name] == _ffi.WORDS_P010
+    shift = {_ffi.WORDS_P010: 8, _ffi.WORDS_I010: 2, _ffi.WORDS_I012: 4, _ffi.WORDS_I016: 8}[_ffi.WORD_PRESETS[name]]
+    return dict(y_offset=0, cb_offset=8 * W * H, cr_offset=8 * W * H + 2 if paired else 10 * W * H, y_pitch=4 * W,
+                c_pitch=4 * W if paired else 2 * W, c_step=4 if paired else 2, frame_stride=12 * W * H, factor=2, shift=shift)
+
+
+def downscale_word_layout_extent(layout, strips, mb_rows):
+    """Bytes of a SOURCE frame the downscaled word kernels may read (the read contract of include/mpeg1_hip.h): the plane layout's
+    extent taken on the source, rows = 2 * ye (luma) and ye (chroma), row bytes = 4 * xe (luma) and (xe - 1) * c_step + 2
+    (chroma) for the strips * 16 x mb_rows * 16 region.  layout: a dict of DOWNSCALE_WORD_LAYOUT_FIELDS with no zeros but the
+    shift (Mpeg1Encoder.downscale_word_layout)."""
+    xe, ye = strips * 16, mb_rows * 16
+    luma = (2 * ye - 1) * layout["y_pitch"] + 4 * xe
+    chroma = (ye - 1) * layout["c_pitch"] + (xe - 1) * layout["c_step"] + 2
+    return max(layout["y_offset"] + luma, max(layout["cb_offset"], layout["cr_offset"]) + chroma)
+
+
 # The layout kinds: the property that describes one, its name in the C API (m1v_set_<c>_layout, m1v_<c>_layout_in_force), its
 # ctypes struct, fields, name in messages and preset function, whether a dict must hold every field, why frames() and
 # plane_frames() refuse it (None: they serve it).  In the order in which the C getters cannot fail (_refresh_input):
@@ -369,6 +405,10 @@ def downscale_plane_layout_extent(layout, strips, mb_rows):
 _Kind = namedtuple("_Kind", "prop c struct fields name preset exact no_frames no_plane_frames")
 _NO_PLANES = "a plane table needs a plane layout or an RGB plane layout in force"
 _KINDS = (
+    _Kind("downscale_word_layout", "downscale_word", _ffi.DownscaleWordLayout, DOWNSCALE_WORD_LAYOUT_FIELDS, "a downscale word layout",
+          downscale_word_layout_preset, False,
+          "a frame table does not serve a downscale word layout (set_downscale_word_layout)",
+          "a plane table does not serve a downscale word layout (set_downscale_word_layout)"),
     _Kind("downscale_plane_layout", "downscale_plane", _ffi.DownscalePlaneLayout, DOWNSCALE_PLANE_LAYOUT_FIELDS, "a downscale plane layout",
           downscale_plane_layout_preset, False,
           "a frame table does not serve a downscale plane layout (set_downscale_plane_layout)",
@@ -459,7 +499,8 @@ class Mpeg1Encoder:
     Input: packed uint8 frames by default; the set_*_layout methods put surfaces, YCbCr planes, planes of R, G and B bytes, or
     planes of float R, G and B samples (set_float_plane_layout: float16, bfloat16, float32), or float R, G, B pixels
     (set_float_pixel_layout: channels-last tensors), or byte surfaces of twice the size, averaged 2 x 2 (set_downscale_layout),
-    or YCbCr planes of twice the size, averaged 2 x 2 per plane (set_downscale_plane_layout), in their place.
+    or YCbCr planes of twice the size, averaged 2 x 2 per plane (set_downscale_plane_layout), or such planes of 16-bit words
+    (set_downscale_word_layout), in their place.
 
     mode: "strict" = the 96x144 region the unmodified reference encodes (encoder.h:238,248),
           "full"   = every macroblock (the reference with its loop bounds restored).
@@ -552,6 +593,16 @@ class Mpeg1Encoder:
             dtype, S = getattr(torch, _ffi.FLOAT_SAMPLE_DTYPES[want["sample"]]), _ffi.FLOAT_SAMPLE_BYTES[want["sample"]]
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == dtype, \
                 f"the {_KIND[kind].name[2:]} in force takes {dtype} tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+        if kind == "downscale_word_layout":  # the SOURCE: [n, L] words or bytes, held by their byte extent and byte row stride
+            words = tuple(getattr(torch, name) for name in ("uint8", "int16", "uint16") if hasattr(torch, name))
+            assert isinstance(rgb, torch.Tensor) and rgb.dtype in words, \
+                f"the downscale word layout in force takes torch.uint8, torch.int16 or torch.uint16 tensors, not {getattr(rgb, 'dtype', type(rgb))}"
+            assert rgb.is_cuda and rgb.dim() == 2, "downscale word sources must be a CUDA tensor [n, L] of words or bytes"
+            extent, S = downscale_word_layout_extent(want, self.strips, self.mb_rows), rgb.element_size()
+            assert rgb.shape[0] == 0 or (rgb.stride(1) == 1 and rgb.shape[1] * S >= extent), \
+                f"a frame's row must be contiguous and hold the {extent} bytes its source planes span"
+            _frames_apart(rgb, want["frame_stride"], S if S > 1 else None)
+            return
         if kind == "downscale_plane_layout":  # the SOURCE: [n, L] bytes, the plane layout's rule on the source's extent
             assert isinstance(rgb, torch.Tensor) and rgb.dtype == torch.uint8, \
                 f"the downscale plane layout in force takes torch.uint8 tensors, not {getattr(rgb, 'dtype', type(rgb))}"
@@ -788,6 +839,34 @@ class Mpeg1Encoder:
             assert x.dim() == 2 and x.shape[1] >= full, f"a frame's row must hold the {full} bytes of the whole source"
         return self._to_bytes("downscale_plane_layout", x, out, lambda n: (n, self.width * self.height * 3 // 2), call="downscale_planes_to_i420")
 
+    def set_downscale_word_layout(self, layout):
+        """Frames as Y, Cb, Cr planes of 16-bit little-endian words of TWICE the encoder's width and height on the device — true
+        4:2:0 sources: a hardware decoder's P010 / P012 / P016 surfaces, a software decoder's yuv420p10le / 12le / 16le frames,
+        pitched windows of them — whose 2 x 2 box average per plane, taken on the words, (sum of the four source words + 2) >> 2,
+        then >> shift and clamped to 255, is the picture that is encoded (include/mpeg1_hip.h, m1v_set_downscale_word_layout;
+        3-channel encoders, even widths and heights).  layout: a preset name ("p010", "p012", "p016", "i010", "i012", "i016": the
+        tightly packed source), a dict of DOWNSCALE_WORD_LAYOUT_FIELDS in bytes of the source (downscale_word_layout_preset gives
+        one to start from; missing pitches and c_step default as in the header, factor is 2, a missing shift is 0), or None = back
+        to the default layout and its kernels.  Every call then takes CUDA tensors [n, L] of uint8, int16 or uint16 whose rows are
+        the source frames: a row holds at least the bytes a source frame's planes span, rows frame_stride bytes apart.  Frame and
+        plane tables do not serve it.  A reconfiguration: call it between batches."""
+        if isinstance(layout, dict):
+            layout = {"factor": 2, **layout}
+        self._set_layout("downscale_word_layout", layout)
+
+    def downscale_words_to_i420(self, x, out=None):
+        """The samples the encoder codes for the source tensor x under the downscale word layout in force (include/mpeg1_hip.h,
+        m1v_downscale_words_to_i420_device): a uint8 CUDA tensor [n, W * H * 3 / 2] of tightly packed I420 frames, what
+        set_plane_layout("i420") takes.  Reads the whole 2W x 2H source, so a row of x holds every plane in full.  Asynchronous on
+        torch's current stream."""
+        want = self._input[1] if self._input[0] == "downscale_word_layout" else None
+        if want is not None and x.shape[0]:  # the whole source, not only the coded region
+            W, H = self.width, self.height
+            full = max(want["y_offset"] + (2 * H - 1) * want["y_pitch"] + 4 * W,
+                       max(want["cb_offset"], want["cr_offset"]) + (H - 1) * want["c_pitch"] + (W - 1) * want["c_step"] + 2)
+            assert x.dim() == 2 and x.shape[1] * x.element_size() >= full, f"a frame's row must hold the {full} bytes of the whole source"
+        return self._to_bytes("downscale_word_layout", x, out, lambda n: (n, self.width * self.height * 3 // 2), call="downscale_words_to_i420")
+
     def set_frame_table(self, enable=True):
         """Batches whose frames lie at separate device addresses (include/mpeg1_hip.h, m1v_set_frame_table): while on, every
         method takes, in the place of `rgb`, what frames() returns or a contiguous CUDA int64 tensor [n] of the frames' base
@@ -882,6 +961,12 @@ class Mpeg1Encoder:
         if rc < 0:
             raise EncoderError(rc, name)
         return c.as_dict() if rc == 1 else None
+
+    @property
+    def downscale_word_layout(self):
+        """The downscale word layout in force as a dict of DOWNSCALE_WORD_LAYOUT_FIELDS (bytes of the source, no zeros but the
+        shift; factor; shift), or None."""
+        return self._in_force("downscale_word_layout")
 
     @property
     def downscale_plane_layout(self):

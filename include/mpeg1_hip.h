@@ -982,6 +982,90 @@ int m1v_set_downscale_plane_layout(m1v_encoder *enc, const m1v_downscale_plane_l
 int m1v_downscale_plane_layout_in_force(const m1v_encoder *enc, m1v_downscale_plane_layout *out); /* 1 / 0 / < 0 */
 int m1v_downscale_planes_to_i420_device(m1v_encoder *enc, const void *d_src, int n_frames, void *d_dst, void *stream);
 
+/* Downscale word layout: the 2:1 downscaled rendition of YCbCr frames with 16-bit samples on the device — the 1080p stream of a
+ * decoder's 4K 10-bit material, handed out as P010 (P012, P016) by a hardware decoder or as yuv420p10le / yuv420p12le by a
+ * software decoder — encoded from the full-size planes where they lie: no resampling kernel and no intermediate in front of the
+ * encoder, and the average is taken on the words, before any bit is dropped.  width and height are the RENDITION's everywhere:
+ * the encoder is created with width x height and channels = 3, and the frames it is given are true 4:2:0 sources of
+ * 2 * width x 2 * height luma words and width x height words per chroma component.  Every sample is a 16-bit little-endian word.
+ *
+ * Definition.  Frame f starts at F = d_rgb + f * frame_stride,
+ *     source luma word (X, Y) is at                  F + y_offset + Y * y_pitch + 2 * X
+ *     source word (U, V) of chroma plane p is at     F + p_offset + V * c_pitch + U * c_step
+ * with c_step 2 (one plane per component: yuv420p10le and its kin) or 4 (interleaved Cb, Cr word pairs: P010; as in
+ * m1v_set_sample_layout the two chroma offsets are then at most 3 bytes apart).  A rendition sample is computed in two steps over
+ * its own plane's source words w, for luma sample (x, y) and likewise for sample (u, v) of chroma plane p, u < width / 2,
+ * v < height / 2:
+ *     a = (w(2x, 2y) + w(2x+1, 2y) + w(2x, 2y+1) + w(2x+1, 2y+1) + 2) >> 2
+ *     sample = min(a >> shift, 255)
+ * a is an exact integer that rounds half up, taken at the full word precision; the >> shift truncates, as the sample layout's
+ * P010 rule does.  shift is 0 .. 8: 8 for high-aligned words (P010 / P012 / P016, yuv420p16le), 2 for low-aligned 10-bit words, 4
+ * for low-aligned 12-bit words.  The min defines what bits above the stated depth do.  This is a box filter per plane,
+ * with no chroma-siting correction.  The record of a frame is, byte for byte, the record the plane layout (m1v_set_plane_layout)
+ * gives for the tightly packed M1V_PLANES_I420 frame of those rendition samples: the same headers, first_frame_index, status
+ * bits, per-frame quality and sizes.
+ *
+ *   m1v_downscale_word_layout_preset(width, height, preset, factor, &layout)   pure host arithmetic: the tightly packed
+ *     2 * width x 2 * height source; width and height are the rendition's, W and H below.
+ *         preset                               shift  c_step  y_pitch  c_pitch  cb_offset  cr_offset  frame_stride
+ *         M1V_WORDS_P010 (also P012 and P016)  8      4       4W       4W       8WH        8WH + 2    12WH
+ *         M1V_WORDS_I010                       2      2       4W       2W       8WH        10WH       12WH
+ *         M1V_WORDS_I012                       4      2       4W       2W       8WH        10WH       12WH
+ *         M1V_WORDS_I016                       8      2       4W       2W       8WH        10WH       12WH
+ *     M1V_E_ARG (out untouched): a null out, an unknown preset, an odd or non-positive width or height, factor != 2.
+ *   m1v_set_downscale_word_layout(enc, &layout)   NULL = back to the default layout.  A reconfiguration like the other layout
+ *     setters: it replaces whichever layout is in force, turns tables off, allocates first and swaps on success, and a failed call
+ *     leaves the layout and the table mode as they were.  The encoder takes the tile plan behind k_half_words_encode,
+ *     k_half_words_size_table and k_half_words_rd_table.  While it is in force m1v_input_layout, m1v_plane_layout_in_force and
+ *     m1v_sample_layout_in_force return M1V_E_ARG ("ask m1v_downscale_word_layout_in_force"); the getters of the other kinds
+ *     return 0.
+ *     M1V_E_ARG with a message that names the reason, before anything is launched or reallocated: a null encoder; channels != 3;
+ *     an odd width or height; factor != 2; shift outside 0 .. 8; c_step other than 2 or 4 (0 = 2); with c_step 4, chroma offsets
+ *     more than 3 bytes apart; frame_stride == 0; 0 < y_pitch < 4 * width; 0 < c_pitch < width * c_step; a source extent E of
+ *     2^32 or more (offsets inside a frame are 32-bit); frame_stride < E; an encoder that a hook has forced to the run kernels
+ *     (those hooks return M1V_E_ARG on an encoder with this layout).
+ *     E is the plane layout's extent taken on the source: the largest offset + (rows - 1) * pitch + row bytes over the three
+ *     planes, with rows = 2 * ye for luma and ye for chroma, row bytes = 4 * xe for luma and (xe - 1) * c_step + 2 for chroma, and
+ *     xe x ye the coded region in rendition samples (16 * m1v_strips x 16 * m1v_mb_rows).  Any byte alignment of d_rgb, offsets,
+ *     pitches and stride is accepted.
+ *     Served: every call that serves the downscale plane layout — m1v_encode_device, m1v_encode_quality_device,
+ *     m1v_frame_sizes_device, m1v_frame_size_table_device, m1v_frame_rd_table_device, the budget, rd, batch-budget, bitrate,
+ *     streams and streams-budget encodes, pipelined mode, m1v_delivery_step with its scratch retry, the m1v_profile_* counters and
+ *     m1v_debug_set_lds_words.  The packed-only calls refuse it as they refuse every other layout.  m1v_set_frame_table and
+ *     m1v_set_plane_table return M1V_E_ARG while it is in force.
+ *   m1v_downscale_word_layout_in_force(enc, &layout)   1 = a downscale word layout is in force (layout filled with the values the
+ *     kernels use, no zeros but a shift of 0; may be NULL), 0 = another layout or none, < 0 = error.
+ *   m1v_downscale_words_to_i420_device(enc, d_src, n_frames, d_dst, stream)   the samples the encoder codes for these frames:
+ *     d_dst is uint8 [n_frames][width * height * 3 / 2], tightly packed I420 whatever the source's form — exactly what
+ *     m1v_set_plane_layout with the M1V_PLANES_I420 preset encodes.  An elementwise kernel over the whole width x height rendition
+ *     (every addressed byte of the 2 * width x 2 * height source is read, and addressed bytes only): the reference for the bytes,
+ *     not a fast path.  Needs this layout in force (M1V_E_ARG otherwise, and for null pointers and n_frames < 0).  Because it
+ *     reads the whole source and the setter holds a layout only to the coded region's extent E, it also returns M1V_E_ARG when
+ *     the extent of the whole source (E with xe x ye = width x height) is 2^32 or more or exceeds frame_stride: an encoder in
+ *     strict mode, or of a width or height that is no multiple of 16.  Asynchronous on `stream`.
+ * Read contract: of frame f only bytes of [F, F + E) rounded up to the next 4-byte boundary are read by the encoding calls (the
+ * boundary is counted from F, whatever F's own alignment).
+ * Unaddressed bytes inside that range (row padding, gaps between planes, the other component's words of a c_step = 4 plane) may
+ * be read and never influence the output.  Gaps between frames and whatever lies around the batch are never read (the proof, per
+ * wave, heads csrc/m1v_downscale_words.h).
+ * Not covered: factor 4 and other filters (the factor field exists so that they can follow); sources of odd extent; big-endian
+ * words; 4:2:2 and 4:4:4 word sources (P210, Y210, yuv422p10le); rounding instead of truncation at the shift; the kind behind a
+ * frame table or a plane table; the host-buffer entry points and the folder CLI; several renditions in one pass. */
+typedef struct m1v_downscale_word_layout {
+    uint64_t y_offset, cb_offset, cr_offset;  /* of the SOURCE, bytes from the frame's base                 */
+    uint64_t y_pitch;                         /* bytes between source luma rows; 0 = 4 * width              */
+    uint64_t c_pitch;                         /* bytes between source chroma rows; 0 = width * c_step       */
+    uint64_t c_step;                          /* 2 or 4; 0 = 2                                              */
+    uint64_t frame_stride;                    /* never 0                                                    */
+    int32_t  factor;                          /* 2                                                          */
+    int32_t  shift;                           /* 0 .. 8                                                     */
+} m1v_downscale_word_layout;                  /* 64 bytes, offsets 0, 8, ... 48, 56, 60 */
+enum { M1V_WORDS_P010 = 0, M1V_WORDS_I010 = 1, M1V_WORDS_I012 = 2, M1V_WORDS_I016 = 3 };
+int m1v_downscale_word_layout_preset(int width, int height, int preset, int factor, m1v_downscale_word_layout *out);
+int m1v_set_downscale_word_layout(m1v_encoder *enc, const m1v_downscale_word_layout *layout);  /* NULL = default layout */
+int m1v_downscale_word_layout_in_force(const m1v_encoder *enc, m1v_downscale_word_layout *out); /* 1 / 0 / < 0 */
+int m1v_downscale_words_to_i420_device(m1v_encoder *enc, const void *d_src, int n_frames, void *d_dst, void *stream);
+
 /* Frame table: a batch whose frames lie at separate device addresses — the surfaces of a decoder's pool in the order the pool
  * recycles them, a capture ring, a list of tensors, frames 5, 2, 9 of a larger buffer — encoded where they lie: no gather into a
  * contiguous batch in front of the encoder.
